@@ -5,17 +5,23 @@ A "step" = one full pass of the hot path over one batch: solve_system!(system, b
 once; the timed region runs bmo_trace_device K times (all bounce-step kernels, child spawning, node ordering, detector-hit
 compaction; results stay in HBM) and, for N > 1, the RCCL all-gather of the per-GPU detector hit buffers.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--workload c2|c2v|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rays R] [--workload c2|c2v|c3|c4|c5] [--dump-outputs DIR] [--full]
 
 N = 1 (default): BASELINE config 2 on SURVEY §8(d)'s literal bundle (`c2s`) — 2^20 geometric Rays, Fibonacci disc of 0.8 x the first
                  clear aperture along the axis + 2 mrad jitter, through the 10-element mesh+SDF miniscope scene with one beamsplitter.
-                 The same line also carries the other BASELINE configs at their per-GPU sizes (`configs`; `c2_cone` is the point-source
-                 cone bundle rounds 1-3 headlined), a vignetted C2 bundle, the PCIe-inclusive rates of the host-buffer boundary
-                 (`pcie`) and the CPU baseline (`cpu_baseline`, an object: the reference algorithm on one thread, the other two nested).
+                 With --full the same line also carries the other BASELINE configs at their per-GPU sizes (`configs`; `c2_cone` is the
+                 point-source cone bundle rounds 1-3 headlined), a vignetted C2 bundle, the PCIe-inclusive rates of the host-buffer
+                 boundary (`pcie`) and the CPU baseline (`cpu_baseline`, an object: the reference algorithm on one thread, the other two
+                 nested; `vs_baseline` is the ratio to it and null without --full).
 N > 1:           BASELINE config 5 — the 32-element scene, 2^21 Rays per GPU (weak scaling: 2^24 at 8 GPUs), contiguous shards,
                  RCCL all-gather of the detector hit lists.  Started either by the driver under torch.distributed.run, or as
                  plain `python bench.py --gpus N`: the N ranks are then started as child processes (before this process touches
-                 a GPU) and rank 0's JSON line is relayed.
+                 a GPU) and rank 0's JSON line is relayed.  With --full, rank 0 also reports the rate of its shard without the
+                 exchange step (`one_gpu_same_workload`), measured before the timed region.
+A plain run (no --full) sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line; `roofline` in it
+costs no extra run (live kernel times + the counter passes committed under profiles/).
+--dump-outputs DIR: after the timed steps, what the LAST step computed, as float64 .npy files (see dump_outputs).  The inputs are
+seeded, so two builds run with the same arguments can be compared file for file.
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -47,9 +53,15 @@ def parse_args():
     ap.add_argument("--rays", type=int, default=0, help="root beams per GPU (0 = the BASELINE size of the workload)")
     ap.add_argument("--workload", default="", help="c2s | c2 | c2v | c3 | c4 | c5 (default: c2s at N = 1, c5 at N > 1)")
     ap.add_argument("--r-max", type=int, default=100)
-    ap.add_argument("--cpu-sample", type=int, default=16384, help="rays for the CPU baseline (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the other configs and the PCIe-inclusive rates")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure the CPU baseline, the other configs, the PCIe-inclusive rates "
+                    "(N = 1) and the shard's rate without the exchange step (N > 1); off: the headline figure only")
+    ap.add_argument("--cpu-sample", type=int, default=16384, help="with --full: rays for the CPU baseline (0 = skip)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N = 1: skip the other configs and the PCIe-inclusive rates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -340,6 +352,80 @@ def pcie_rates(case, r_max, calls):
     return out
 
 
+DUMP_BUDGET = 60 << 20  # bytes of array data --dump-outputs writes at most
+DUMP_SEED = 20251015
+
+
+def _dump_rows(n, cap):
+    """Rows a dumped table keeps: all n, or a fixed seeded sample of `cap` of them in ascending order (the same rows for the same n)."""
+    import numpy as np
+
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(n, cap, replace=False))
+
+
+def _split_nonfinite(t):
+    """A dumped table as finite numbers: (t with every non-finite entry replaced by 0, codes), where codes[:, k] packs 2 bits per column
+    for columns 26k .. 26k + 25 (0 finite, 1 NaN, 2 +Inf, 3 -Inf at bit 2 * (column - 26k)): at most 52 bits, an exact float64 integer.
+    The engine itself writes one non-finite value: t = +Inf on a segment without intersection (include/bmo.h)."""
+    import numpy as np
+
+    code = np.select([np.isnan(t), np.isposinf(t), np.isneginf(t)], [1, 2, 3], 0).astype(np.int64)
+    codes = np.zeros((t.shape[0], -(-t.shape[1] // 26)), dtype=np.int64)
+    for j in range(t.shape[1]):
+        codes[:, j // 26] |= code[:, j] << (2 * (j % 26))
+    return np.where(code == 0, t, 0.0), codes.astype(np.float64)
+
+
+def dump_outputs(path, case, res, gathered=None):
+    """--dump-outputs: the solution of the last timed step as a caller of bmo_trace_device reads it back (bmo_result_view), float64:
+      counts.npy         [reference intersect3d calls, segments, beams, hits of detector 0, hits of detector 1, ...]
+      nodes.npy          one row per beam: root, parent, first_child, first_rec, nseg, status, aux[0:4]
+      segments.npy       one row per segment of the log: object id, shape id, the rec_planes record planes
+      det<s>_hits.npy    detector s in reference order: beam node, then the columns the detector keeps (2 Spotdetector, 9 PSF)
+      gathered_det<s>_hits.npy  (N > 1) the all-gathered hit table of detector s after the last exchange step: its kept columns
+    Every file holds finite numbers only: beside each table <name>.npy, <name>_nonfinite.npy (same rows) says which of its entries were
+    NaN or +-Inf, and those entries are 0 in <name>.npy (_split_nonfinite).  A table larger than its share of DUMP_BUDGET, code
+    columns included, is a seeded sample of its rows (_dump_rows)."""
+    import ctypes as C
+
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    lib, abi = case.eng.lib, case.bmo.abi
+    v = abi.ResultView()
+    abi.check(lib, lib.bmo_result_view(res, C.byref(v)), "bmo_result_view")
+    nn, nr, planes, nd = int(v.n_nodes), int(v.n_records), int(v.rec_planes), int(v.n_detectors)
+
+    def arr(ptr, n, dtype):  # the view's host arrays, not copied (they live until the result is freed)
+        return np.ctypeslib.as_array(ptr, shape=(n,)) if n else np.zeros(0, dtype)
+
+    def save(name, cols, budget):
+        idx = _dump_rows(len(cols[0]), max(budget // (8 * (len(cols) + -(-len(cols) // 26))), 1))
+        values, codes = _split_nonfinite(np.stack([np.asarray(c)[idx].astype(np.float64) for c in cols], axis=1))
+        np.save(os.path.join(path, name + ".npy"), values)
+        np.save(os.path.join(path, name + "_nonfinite.npy"), codes)
+
+    det_count = arr(v.det_count, nd, np.int64)
+    np.save(os.path.join(path, "counts.npy"), np.array([v.n_intersect_calls, nr, nn] + [int(c) for c in det_count], dtype=np.float64))
+    aux = arr(v.node_aux, nn * 4, np.float64).reshape(nn, 4)
+    save("nodes", [arr(getattr(v, f), nn, np.int32) for f in ("node_root", "node_parent", "node_first_child", "node_first_rec", "node_nseg", "node_status")]
+         + [aux[:, j] for j in range(4)], DUMP_BUDGET // 5)
+    rec = arr(v.rec, nr * planes, np.float64)
+    save("segments", [arr(v.rec_obj, nr, np.int32), arr(v.rec_shape, nr, np.int32)] + [rec[p * nr:(p + 1) * nr] for p in range(planes)],
+         DUMP_BUDGET * 3 // 5)
+    det_offset, tot = arr(v.det_offset, nd, np.int64), int(det_count.sum())
+    det_node, det_data = arr(v.det_node, tot, np.int32), arr(v.det_data, tot * 9, np.float64).reshape(tot, 9)
+    share = DUMP_BUDGET // 5 // max(nd * (2 if gathered else 1), 1)
+    for s in range(nd):
+        o, c = int(det_offset[s]), int(det_count[s])
+        save(f"det{s}_hits", [det_node[o:o + c]] + [det_data[o:o + c, j] for j in range(case.det_cols[s])], share)
+    for s, (hits, _) in enumerate(gathered or []):
+        h = hits.cpu().numpy()
+        save(f"gathered_det{s}_hits", [h[:, j] for j in range(h.shape[1])], share)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -407,15 +493,18 @@ def main():
         return res, kms, nl
 
     def sync():
+        """Completes the exchange step still in flight; returns its gathered hit tables (None at N = 1 or when none was in flight)."""
         if multi:
-            finish_exchange()
+            done = finish_exchange()
             dist.barrier()
             torch.cuda.synchronize()
+            return done[-1] if done else None
+        return None
 
-    # N > 1: this rank's rate WITHOUT the exchange step, same workload, measured before the timed region — the one-GPU reference
+    # N > 1, --full: this rank's rate WITHOUT the exchange step, same workload, measured before the timed region — the one-GPU reference
     # point of the same config, so that scaling can be read against the same work (N = 1 of the driver's curve runs config 2).
     local_only = None
-    if multi:
+    if multi and args.full:
         dt0, _, _, c0 = case.measure(args.r_max, max(2, min(args.steps, 3)), 1)
         local_only = c0["calls"] * max(2, min(args.steps, 3)) / dt0
 
@@ -431,7 +520,7 @@ def main():
         last, kms, nl = one_step(multi)
         kernel_ms += kms
         launches += nl
-    sync()
+    gathered = sync()
     dt = time.perf_counter() - t0
     if multi:
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
@@ -441,6 +530,8 @@ def main():
     # workload counters of ONE step (identical every step: the trace is deterministic)
     calls, nrec, nnodes, hits = eng.result_size(last)  # bmo_result_counts: nothing is downloaded
     det_counts = eng.result_counts(last)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, case, last, gathered)
     eng.free_result(last)
     mine = dict(calls=calls, segments=nrec, nodes=nnodes, hits=hits, det_counts=det_counts)
     if multi:
@@ -482,9 +573,9 @@ def main():
         if local_only is not None:
             out["one_gpu_same_workload"] = {"value": local_only, "unit": "intersections/s",
                                             "what": "rank 0, same shard, solves only (no exchange step), measured before the timed region"}
-        if not multi and not args.no_extras:
+        if args.full and not multi and not args.no_extras:
             out["pcie"] = pcie_rates(case, args.r_max, calls)
-        if args.cpu_sample > 0 and not multi:  # the CPU baseline is reported at N = 1 only
+        if args.full and args.cpu_sample > 0 and not multi:  # the CPU baseline is reported at N = 1 only
             cb = cpu_baseline(case, min(args.cpu_sample, n_local), args.r_max)
             out["cpu_baseline"] = cb
             # BASELINE.md holds no published number for this metric (the reference publishes none); its §3 names the baseline to time
@@ -492,7 +583,7 @@ def main():
             out["vs_baseline"] = out["value"] / cb["value"] if cb["value"] > 0 else None
             out["vs_baseline_of"] = "cpu_baseline.value (BASELINE.md §3 B1: the reference algorithm restated op for op, one host thread; nothing is published upstream)"
     case.close()
-    if rank == 0 and not multi and not args.no_extras:
+    if rank == 0 and args.full and not multi and not args.no_extras:
         # the other BASELINE configs at their per-GPU sizes, and the vignetted C2 bundle: 3 resident solves each after 1 warm-up
         cfgs = {}
         for other in ("c2s", "c2", "c2v", "c3", "c4", "c5"):

@@ -232,12 +232,17 @@ def test_bench_distributed_path_over_rccl_with_one_rank(tmp_path):
 
     env = dict(os.environ, BMO_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--rays", "65536", "--cpu-sample", "0"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--rays", "65536", "--cpu-sample", "0", "--full",
+           "--dump-outputs", str(tmp_path / "dump")]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and "RCCL all-gather" in line["config"]["parallelism"]
     assert line["config"]["name"] == "c5" and line["one_gpu_same_workload"]["value"] > 0
+    # one rank: the all-gathered hit table of every detector is this rank's own (kept columns, reference order)
+    for s in range(2):
+        own, gathered = np.load(tmp_path / "dump" / f"det{s}_hits.npy"), np.load(tmp_path / "dump" / f"gathered_det{s}_hits.npy")
+        assert len(own) > 0 and np.array_equal(gathered, own[:, 1:]), s
 
 
 def _exchange_worker(rank, world, port, out_dir):
