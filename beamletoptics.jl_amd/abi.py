@@ -214,6 +214,8 @@ def load_engine():
     lib.bmo_jl_trig.argtypes = [C.c_int32, C.c_double, C.c_double]
     lib.bmo_jl_trig.restype = C.c_double
     lib.bmo_scene_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(vp)]
+    lib.bmo_scene_mesh_bvh.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.bmo_mesh_nearest_host.argtypes = [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)]
     lib.bmo_scene_destroy.argtypes = [vp]
     lib.bmo_trace.argtypes = [vp, C.POINTER(RayBatch), C.POINTER(TraceOpts), C.POINTER(vp)]
     lib.bmo_batch_upload.argtypes = [vp, C.POINTER(RayBatch), C.c_int32, C.POINTER(vp)]

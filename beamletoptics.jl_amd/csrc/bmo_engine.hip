@@ -79,7 +79,8 @@ struct BlobHeader {
     uint32_t off_objects, off_shapes, off_children, off_tris, off_ntable, total;
     uint32_t has_splitter, off_coefs;
     uint32_t has_asphere, off_cands;
-    int32_t n_cands, has_meniscus, pad[2];
+    int32_t n_cands, has_meniscus, pad[2];  // pad[0]: has_bvh (some mesh has a BVH: the kernels of level 3)
+    uint32_t off_bvh_nodes, off_bvh_faces;  // mesh BVHs (bmo_lane.hpp BvhNode; face ids, int32)
 };
 
 // `h`: the blob's header; the kernels read it from their arguments (scalar loads the compiler may repeat instead of holding the
@@ -104,6 +105,10 @@ __host__ __device__ inline SceneView view_of(CharPtr blob, const BlobHeader* h) 
     S.mt_leps = h->mt_leps;
     S.grad_h = h->grad_h;
     S.march_iters = h->march_iters;
+    if (h->pad[0]) {
+        S.bvh_nodes = (const BMO_KONST BvhNode*)(blob + h->off_bvh_nodes);
+        S.bvh_faces = (CInt*)(blob + h->off_bvh_faces);
+    }
     return S;
 }
 
@@ -389,7 +394,7 @@ constexpr int step_waves() {
     return BMO_MIN_WAVES;
 #else
     if (KIND == BMO_BEAM_POLARIZED && EXT == 0) return 4;  // three singlets, 2^18 PolarizedRays: fresh 0.317 against 0.341 ms, retrace 0.297 against 0.327
-    if (RETR && EXT == 2) return 4;                        // asphere objective: retrace 2.60 against 3.06 ms (Ray), 2.75 against 3.21 (PolarizedRay)
+    if (RETR && EXT >= 2) return 4;                        // asphere objective: retrace 2.60 against 3.06 ms (Ray), 2.75 against 3.21 (PolarizedRay)
     return 3;
 #endif
 }
@@ -1829,9 +1834,158 @@ struct HostBuf {
 
 }  // namespace
 
+// ------------------------------------------------------------------ mesh BVH builder (host, bmo_scene_create)
+// Binned SAH (16 bins per axis over the face boxes' centres, traversal and triangle test weighted alike); leaves of at most
+// BVH_MAX_LEAF faces unless the faces cannot be told apart by their centres.  Below depth BVH_SAH_DEPTH every split is an object
+// median, so no BVH is deeper than BVH_SAH_DEPTH + 31 < BMO_BVH_MAX_DEPTH (the traversal's stack).  Face boxes are inflated as
+// bmo_lane.hpp BvhNode says (the culling argument of mesh_nearest_bvh).
+namespace {
+constexpr int BVH_BINS = 16, BVH_MAX_LEAF = 8, BVH_SAH_DEPTH = 32;
+static_assert(BVH_SAH_DEPTH + 31 <= BMO_BVH_MAX_DEPTH, "median splits below BVH_SAH_DEPTH must fit the traversal stack");
+static_assert(sizeof(BvhNode) == 64, "BvhNode layout");
+struct BvhStats {
+    int32_t n_nodes = 0, depth = 0, max_leaf = 0;
+};
+struct Box3 {
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    void grow(const Box3& b) {
+        for (int a = 0; a < 3; ++a) lo[a] = std::min(lo[a], b.lo[a]), hi[a] = std::max(hi[a], b.hi[a]);
+    }
+    double area() const {
+        const double x = hi[0] - lo[0], y = hi[1] - lo[1], z = hi[2] - lo[2];
+        return x < 0 ? 0.0 : 2 * (x * y + y * z + z * x);
+    }
+};
+// Appends the BVH of the `nf` faces at `tri` (9 doubles each) to nodes / faces (absolute indices; face ids are 0-based in the mesh) and
+// returns the index of its header node, or -1 (nothing appended) when the mesh cannot have one: a non-finite vertex, or kϵ not > 0.
+int bvh_build(const double* tri, int nf, double keps, std::vector<BvhNode>& nodes, std::vector<int32_t>& faces, BvhStats& st) {
+    if (!(keps > 0.0) || !std::isfinite(keps) || nf < 1) return -1;
+    std::vector<Box3> fb((size_t)nf);
+    std::vector<double> cen((size_t)nf * 3);
+    double g = 0.0;  // max |E1| |E2|
+    for (int f = 0; f < nf; ++f) {
+        const double* v = tri + 9 * (size_t)f;
+        double e1 = 0, e2 = 0, m = 0;
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(v[a]) || !std::isfinite(v[3 + a]) || !std::isfinite(v[6 + a])) return -1;
+            const double d1 = v[3 + a] - v[a], d2 = v[6 + a] - v[a];
+            e1 += d1 * d1, e2 += d2 * d2;
+            m = std::max(m, std::max(std::fabs(v[a]), std::max(std::fabs(v[3 + a]), std::fabs(v[6 + a]))));
+        }
+        e1 = std::sqrt(e1), e2 = std::sqrt(e2);
+        g = std::max(g, e1 * e2);
+        const double infl = 4 * keps * std::max(e1, e2) + 0x1p-46 * m;
+        Box3& b = fb[(size_t)f];
+        for (int a = 0; a < 3; ++a) {
+            b.lo[a] = std::min(v[a], std::min(v[3 + a], v[6 + a])) - infl;
+            b.hi[a] = std::max(v[a], std::max(v[3 + a], v[6 + a])) + infl;
+            cen[3 * (size_t)f + a] = 0.5 * b.lo[a] + 0.5 * b.hi[a];
+        }
+    }
+    std::vector<int32_t> idx((size_t)nf);
+    for (int f = 0; f < nf; ++f) idx[(size_t)f] = f;
+    const int32_t hdr = (int32_t)nodes.size();
+    const int32_t face0 = (int32_t)faces.size();
+    nodes.resize(nodes.size() + 2);  // header, root
+    st = BvhStats{};
+    // one node: its box, then a leaf or a split into two consecutive children
+    auto build = [&](auto&& self, int32_t ni, int begin, int end, int depth) -> void {
+        Box3 box, cb;
+        for (int i = begin; i < end; ++i) {
+            const int f = idx[(size_t)i];
+            box.grow(fb[(size_t)f]);
+            for (int a = 0; a < 3; ++a)
+                cb.lo[a] = std::min(cb.lo[a], cen[3 * (size_t)f + a]), cb.hi[a] = std::max(cb.hi[a], cen[3 * (size_t)f + a]);
+        }
+        for (int a = 0; a < 3; ++a) nodes[(size_t)ni].lo[a] = box.lo[a], nodes[(size_t)ni].hi[a] = box.hi[a];
+        st.depth = std::max(st.depth, depth);
+        const int n = end - begin;
+        int axis = 0;
+        for (int a = 1; a < 3; ++a)
+            if (cb.hi[a] - cb.lo[a] > cb.hi[axis] - cb.lo[axis]) axis = a;
+        int mid = -1;
+        if (n > 2 && depth < BVH_SAH_DEPTH) {
+            double best = (double)n * box.area();  // leaf cost
+            int best_axis = -1, best_bin = 0;
+            for (int a = 0; a < 3; ++a) {
+                const double ext = cb.hi[a] - cb.lo[a];
+                if (!(ext > 0)) continue;
+                Box3 bb[BVH_BINS];
+                int cnt[BVH_BINS] = {};
+                const double k = BVH_BINS / ext;
+                for (int i = begin; i < end; ++i) {
+                    const int f = idx[(size_t)i];
+                    const int bin = std::min(BVH_BINS - 1, (int)((cen[3 * (size_t)f + a] - cb.lo[a]) * k));
+                    cnt[bin] += 1;
+                    bb[bin].grow(fb[(size_t)f]);
+                }
+                double right_area[BVH_BINS];
+                int right_n[BVH_BINS];
+                Box3 acc;
+                int an = 0;
+                for (int b = BVH_BINS - 1; b > 0; --b) {
+                    acc.grow(bb[b]);
+                    an += cnt[b];
+                    right_area[b] = acc.area(), right_n[b] = an;
+                }
+                acc = Box3{};
+                an = 0;
+                for (int b = 0; b < BVH_BINS - 1; ++b) {  // split between bin b and b + 1
+                    acc.grow(bb[b]);
+                    an += cnt[b];
+                    if (an == 0 || right_n[b + 1] == 0) continue;
+                    const double c = box.area() + acc.area() * an + right_area[b + 1] * right_n[b + 1];
+                    if (c < best) best = c, best_axis = a, best_bin = b;
+                }
+            }
+            if (best_axis >= 0) {
+                const double k = BVH_BINS / (cb.hi[best_axis] - cb.lo[best_axis]);
+                auto it = std::partition(idx.begin() + begin, idx.begin() + end, [&](int f) {
+                    return std::min(BVH_BINS - 1, (int)((cen[3 * (size_t)f + best_axis] - cb.lo[best_axis]) * k)) <= best_bin;
+                });
+                mid = (int)(it - idx.begin());
+                axis = best_axis;
+            }
+        }
+        if (mid < 0 && (n > BVH_MAX_LEAF || (depth >= BVH_SAH_DEPTH && n > 2))) {  // object median (also for faces with equal centres)
+            mid = begin + n / 2;
+            std::nth_element(idx.begin() + begin, idx.begin() + mid, idx.begin() + end,
+                             [&](int x, int y) { return cen[3 * (size_t)x + axis] < cen[3 * (size_t)y + axis]; });
+        }
+        if (mid <= begin || mid >= end) {  // leaf
+            BvhNode& nd = nodes[(size_t)ni];
+            nd.first = face0 + begin, nd.count = n, nd.axis = 0;
+            st.max_leaf = std::max(st.max_leaf, n);
+            return;
+        }
+        const int32_t c = (int32_t)nodes.size();
+        nodes.resize(nodes.size() + 2);
+        nodes[(size_t)ni].first = c, nodes[(size_t)ni].count = 0, nodes[(size_t)ni].axis = axis;
+        self(self, c, begin, mid, depth + 1);
+        self(self, c + 1, mid, end, depth + 1);
+    };
+    build(build, hdr + 1, 0, nf, 1);
+    faces.insert(faces.end(), idx.begin(), idx.end());
+    BvhNode& H = nodes[(size_t)hdr];
+    const BvhNode& R = nodes[(size_t)hdr + 1];
+    double d2 = 0;
+    for (int a = 0; a < 3; ++a) {
+        H.lo[a] = 0.5 * R.lo[a] + 0.5 * R.hi[a];
+        d2 += (R.hi[a] - R.lo[a]) * (R.hi[a] - R.lo[a]);
+    }
+    H.hi[0] = 0.5 * std::sqrt(d2) * (1 + 0x1p-40);  // (rounded up: D must bound |pos - V|)
+    H.hi[1] = 0x1p-46 * g / keps;
+    H.hi[2] = 0;
+    H.first = hdr + 1, H.count = 0, H.axis = 0;
+    st.n_nodes = (int32_t)nodes.size() - hdr - 1;
+    return hdr;
+}
+}  // namespace
+
 struct bmo_scene {
     std::vector<char> blob;
     BlobHeader hdr;
+    std::vector<BvhStats> bvh;  // per shape (n_nodes = 0: no BVH)
     double bound[4] = {0, 0, 0, -1};  // a sphere around the bounding spheres of all candidates (centre, radius; radius < 0: none) — root_chord_kernel
     std::vector<std::pair<int, std::unique_ptr<DevBuf>>> dev;  // per-device copy of the blob
     std::mutex dev_mu;  // the handle is shared between host threads (include/bmo.h "Threading"): the lazy per-device upload is the one mutation
@@ -2184,7 +2338,8 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
     const size_t lds_bytes = (use_lds ? blob_bytes : 0) + 64 + (size_t)(BMO_CC_MAX + BMO_LANE_MEM) * BMO_BLOCK * 8;
     void (*kern)(StepParams) = nullptr, (*kern_inw)(StepParams) = nullptr;  // kern_inw: the Beam kernels' variant with in-loop beam splitters
     void (*kern_wide)(StepParams) = nullptr, (*kern_inw_wide)(StepParams) = nullptr;  // the 4-waves-per-SIMD builds of the two, for large launches (step_waves)
-    const int ext = scene->hdr.has_asphere ? 2 : (scene->hdr.has_meniscus ? 1 : 0);  // extended-shapes level of the kernels (bmo_lane.hpp sdf_leaf)
+    // extended-shapes level of the kernels (bmo_lane.hpp sdf_leaf); a scene with a mesh BVH runs level 3 (level 2 + the BVH traversal)
+    const int ext = scene->hdr.pad[0] ? 3 : (scene->hdr.has_asphere ? 2 : (scene->hdr.has_meniscus ? 1 : 0));
 #if defined(BMO_DEV_RAY_LDS_ONLY)  // developer build (kernel work on one variant): everything else is refused, nothing falls back
     if constexpr (KIND == BMO_BEAM_RAY) {
         if (!prev && ext == 0) {
@@ -2201,7 +2356,14 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
     }
     if (!kern) return fail(BMO_ERR_UNSUPPORTED, "developer build: only step_kernel_gauss<0, false> is compiled in");
 #else
-    if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
+    if (ext == 3) {  // mesh BVH: one level (a superset of 0 - 2), fresh and retrace, for every beam kind
+        if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
+            kern = prev ? &step_kernel_gauss<3, true> : &step_kernel_gauss<3, false>;
+        } else {
+            kern = prev ? &step_kernel<KIND, 3, true, false> : &step_kernel<KIND, 3, false, false>;
+            kern_inw = prev ? &step_kernel<KIND, 3, true, true> : &step_kernel<KIND, 3, false, true>;
+        }
+    } else if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
         if (prev) kern = ext == 2 ? &step_kernel_gauss<2, true> : (ext == 1 ? &step_kernel_gauss<1, true> : &step_kernel_gauss<0, true>);
         else kern = ext == 2 ? &step_kernel_gauss<2, false> : (ext == 1 ? &step_kernel_gauss<1, false> : &step_kernel_gauss<0, false>);
     } else {
@@ -2938,6 +3100,26 @@ int bmo_scene_create(const bmo_scene_desc* d, bmo_scene** out) {
     h.off_cands = (uint32_t)off;
     h.n_cands = fill_candidates(d->objects, d->n_objects, d->shapes, nullptr);
     off = al(off + sizeof(Cand) * (size_t)(std::max(1, h.n_cands) + 3));  // (+ 3 zero entries: the collection of tracing_step reads four per trip)
+    // the kernels address the blob with 32-bit offsets
+    const char* too_big = "scene blob larger than 4 GiB (32-bit table offsets): fewer triangles or smaller tables";
+    if (off > 0xffffffffull) return fail(BMO_ERR_INVALID, too_big);
+    // mesh BVHs (bvh_build above): every MESH of BMO_MESH_BVH_MIN_FACES faces or more unless its input flags say BMO_SHAPE_FLAG_NO_BVH
+    std::vector<BvhNode> bvh_nodes;
+    std::vector<int32_t> bvh_faces;
+    std::vector<int32_t> bvh_hdr((size_t)d->n_shapes, -1);
+    sc->bvh.assign((size_t)d->n_shapes, BvhStats{});
+    for (int i = 0; i < d->n_shapes; ++i) {
+        const bmo_shape& s = d->shapes[i];
+        if (s.kind != BMO_SHAPE_MESH || s.tri_count < BMO_MESH_BVH_MIN_FACES || (s.flags & BMO_SHAPE_FLAG_NO_BVH)) continue;
+        bvh_hdr[(size_t)i] = bvh_build(d->tris + 9 * (size_t)s.tri_begin, s.tri_count, d->mt_keps, bvh_nodes, bvh_faces, sc->bvh[(size_t)i]);
+        if (bvh_hdr[(size_t)i] >= 0 && sc->bvh[(size_t)i].depth > BMO_BVH_MAX_DEPTH) return fail(BMO_ERR_INTERNAL, "mesh BVH deeper than the traversal stack");
+    }
+    h.pad[0] = bvh_nodes.empty() ? 0 : 1;  // has_bvh
+    h.off_bvh_nodes = (uint32_t)off;
+    off = al(off + sizeof(BvhNode) * bvh_nodes.size());
+    h.off_bvh_faces = (uint32_t)off;
+    off = al(off + 4 * bvh_faces.size());
+    if (off > 0xffffffffull) return fail(BMO_ERR_INVALID, too_big);
     h.total = (uint32_t)off;
     sc->blob.assign(off, 0);
     std::memcpy(sc->blob.data(), &h, sizeof h);
@@ -2955,6 +3137,15 @@ int bmo_scene_create(const bmo_scene_desc* d, bmo_scene** out) {
             sh->tri_begin = d->children[sh->child_begin];
         }
     }
+    for (int i = 0; i < d->n_shapes; ++i) {  // meshes with a BVH: the flag, and child_begin (unused by meshes) -> the BVH's header node
+        bmo_shape* sh = reinterpret_cast<bmo_shape*>(sc->blob.data() + h.off_shapes) + i;
+        sh->flags &= ~BMO_SHAPE_FLAG_BVH;
+        if (bvh_hdr[(size_t)i] < 0) continue;
+        sh->flags |= BMO_SHAPE_FLAG_BVH;
+        sh->child_begin = bvh_hdr[(size_t)i];
+    }
+    if (!bvh_nodes.empty()) std::memcpy(sc->blob.data() + h.off_bvh_nodes, bvh_nodes.data(), sizeof(BvhNode) * bvh_nodes.size());
+    if (!bvh_faces.empty()) std::memcpy(sc->blob.data() + h.off_bvh_faces, bvh_faces.data(), 4 * bvh_faces.size());
     if (d->n_children) std::memcpy(sc->blob.data() + h.off_children, d->children, 4 * (size_t)d->n_children);
     if (d->n_tris) std::memcpy(sc->blob.data() + h.off_tris, d->tris, 72 * (size_t)d->n_tris);
     if (d->n_media) std::memcpy(sc->blob.data() + h.off_ntable, d->n_table, 8 * (size_t)d->n_media * (size_t)d->n_lambda);
@@ -2983,6 +3174,32 @@ int bmo_scene_create(const bmo_scene_desc* d, bmo_scene** out) {
     }
     sc->hdr = h;
     *out = sc.release();
+    return BMO_OK;
+}
+
+int bmo_scene_mesh_bvh(const bmo_scene* scene, int32_t shape, int32_t* n_nodes, int32_t* depth, int32_t* max_leaf) {
+    if (!scene) return fail(BMO_ERR_INVALID, "null argument");
+    if (shape < 0 || shape >= scene->hdr.n_shapes) return fail(BMO_ERR_INVALID, "shape id out of bounds");
+    const BvhStats& st = scene->bvh[(size_t)shape];
+    if (n_nodes) *n_nodes = st.n_nodes;
+    if (depth) *depth = st.depth;
+    if (max_leaf) *max_leaf = st.max_leaf;
+    return BMO_OK;
+}
+
+int bmo_mesh_nearest_host(const bmo_scene* scene, int32_t shape, int64_t n, const double* pos, const double* dir, double* t, int32_t* fid) {
+    if (!scene || n < 0 || (n > 0 && (!pos || !dir || !t || !fid))) return fail(BMO_ERR_INVALID, "null argument");
+    if (shape < 0 || shape >= scene->hdr.n_shapes) return fail(BMO_ERR_INVALID, "shape id out of bounds");
+    const SceneView S = view_of(scene->blob.data(), &scene->hdr);
+    const bmo_shape& sh = S.shapes[shape];
+    if (sh.kind != BMO_SHAPE_MESH) return fail(BMO_ERR_INVALID, "not a mesh shape");
+    for (int64_t i = 0; i < n; ++i) {
+        const d3 p{pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}, d{dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]};
+        int32_t f = -1;
+        t[i] = (sh.flags & BMO_SHAPE_FLAG_BVH) ? mesh_nearest_bvh(S, sh.child_begin, sh.tri_begin, sh.tri_count, p, d, kinf(), f)
+                                               : mesh_nearest(S, sh.tri_begin, sh.tri_count, p, d, f);
+        fid[i] = f;
+    }
     return BMO_OK;
 }
 

@@ -98,6 +98,10 @@ struct SceneView {
     int32_t n_objects, n_lambda, n_cands;
     double eps_srf, eps_ray, eps_ins, mt_keps, mt_leps, grad_h;
     int32_t march_iters;
+    // mesh BVHs (bmo_engine.hip bmo_scene_create; null in a scene without one — the emulator builds a SceneView without them and
+    // traces every mesh by brute force)
+    const BMO_KONST struct BvhNode* bvh_nodes = nullptr;
+    CInt* bvh_faces = nullptr;
 };
 
 struct d3 {
@@ -535,7 +539,7 @@ BMO_DN DualN<N> asph_leaf(CShape&, CDouble*, const DualN<N>& r, const DualN<N>&)
 
 // leaf SDFs; `pt` is in the parent's frame (world, or the meniscus frame)
 // EXT ("extended shapes" level of the kernel): 0 = the spherical / primitive leaves only; 1 = + MeniscusLensSDF; 2 = + the aspheric
-// and cylinder-lens leaves.  A scene runs the kernels of the lowest level that covers its shapes (less code, fewer registers: the
+// and cylinder-lens leaves; 3 = level 2 + the mesh BVH traversal (mesh_nearest_bvh).  A scene runs the kernels of the lowest level that covers its shapes (less code, fewer registers: the
 // meniscus fold keeps a second dual number and a second frame alive around the leaf, the aspheric leaves are the largest by far).
 template <class T, int EXT>
 BMO_HD T sdf_leaf(CShape& s, const int kind, const v3<T>& pt, CDouble* coefs) {
@@ -946,6 +950,121 @@ BMO_HD double mesh_nearest(const SceneView& S, int tri0, int ntri, const d3& pos
     }
     return t0;
 }
+// ------------------------------------------------------------------ mesh BVH (DESIGN.md §3 "mesh BVH")
+// Node of a mesh BVH (64 B; built by bmo_scene_create, bmo_engine.hip bvh_build).  Indices are absolute (into SceneView::bvh_nodes /
+// bvh_faces).  Node 0 of every BVH is its header (the shape's child_begin points at it): lo = centre of the root box, hi[0] = half the
+// root box's diagonal, hi[1] = the rounding gain G (mesh_nearest_bvh), first = the root node.  Interior node: count = 0, children
+// `first` and `first + 1`, split axis `axis`.  Leaf: count > 0 faces, bvh_faces[first .. first + count) (0-based face ids of the mesh).
+// Every box is the union of its faces' boxes, each inflated by 4 kϵ times its longest edge plus 2^-46 times its largest |coordinate|.
+struct BvhNode {
+    double lo[3], hi[3];
+    int32_t first, count, axis, pad;
+};
+constexpr int BMO_BVH_MAX_DEPTH = 64;  // the builder keeps every BVH at most this deep (root = depth 1)
+constexpr int BMO_BVH_STACK = BMO_BVH_MAX_DEPTH;  // depth-first: at most one pending far child per level
+
+// May the faces under node `n` hold a hit that matters?  false only if none can (the argument: mesh_nearest_bvh).  `iv` = 1 / dir per axis.
+// Axis-parallel rays: for dir[k] == 0 (or so small that 1 / dir[k] is infinite) the slab bounds would be (lo - o) * inf, which is NaN when the
+// origin lies on the slab's plane; v_min_f64 / v_max_f64 would then return the OTHER bound, +inf as the entry of a ray that lies inside the
+// slab, and skip a node it meets.  Such an axis instead only asks whether the origin lies in the slab.  The caller guarantees finite
+// inputs, so no other NaN can arise.
+BMO_HD bool bvh_visit(const BMO_KONST BvhNode& n, const double* o, const double* iv, double pad, double tmin, double tb) {
+    double tn = -kinf(), tf = kinf();
+    bool outside = false;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = n.lo[k] - pad, hi = n.hi[k] + pad;
+        if (fabs(iv[k]) == kinf()) {
+            outside = outside || o[k] < lo || o[k] > hi;
+        } else {
+            const double a = (lo - o[k]) * iv[k], b = (hi - o[k]) * iv[k];
+            tn = fmax(tn, fmin(a, b));
+            tf = fmin(tf, fmax(a, b));
+        }
+    }
+    return !(outside || tn > tf || tf < tmin || tn > tb);
+}
+
+// intersect3d(mesh, ray) through the mesh's BVH (header node `hdr`): exactly what mesh_nearest returns — the lexicographic minimum of
+// (t, face id) over the faces whose moeller_trumbore(...) is finite (the reference's strict `<` keeps the first face among equal minima);
+// +Inf and fid = -1 when no face is hit.  The faces are tested by the unchanged moeller_trumbore on the unchanged vertices, so a face
+// that is tested gives the same t bits as in the brute-force loop, and the result does not depend on the order faces are visited in.
+// `tlim`: the caller rejects a hit at t >= tlim (offer accepts only t < x_t), nodes that can only hold such hits are skipped; pass +Inf
+// for the plain query.  A face outside the skipped nodes (or a lane that did not need a leaf) may still return a hit >= tlim.
+//
+// Culling argument.  A node is skipped only if no face under it can return a finite t <= min(best so far, tlim) — `>` is strict, so a
+// face with the same t as the best and a lower id is still visited.  When moeller_trumbore returns a finite t for face (V1, E1, E2):
+//  - its computed u, v lie in [-kϵ, 1 + kϵ] with u + v <= 1 + kϵ, so the exact plane point V1 + u E1 + v E2 lies within 3 kϵ max|E| of the
+//    triangle: covered by the 4 kϵ max|E| of the face's box;
+//  - the rounding of E1, E2, Tv moves the triangle by a few ulps of its coordinates: covered by the 2^-46 max|coordinate| of the box;
+//  - u, v and t carry rounding errors of a few ulps of |Tv| |Pv| / |Det| (u, and v and t alike); times the edge that turns them into a
+//    distance that is <= c eps |Tv| |dir| |E1| |E2| / |Det| <= c eps D |dir| |E1| |E2| / kϵ (|Det| >= kϵ, |Tv| <= D), and the slab
+//    test's own rounding is a few ulps of D: the lane pads every box by pad = 2^-46 D (1 + |dir| max|E1||E2| / kϵ), 2^-46 = 64 eps,
+//    several times the c of these bounds, so the point pos + t dir the face returns lies inside the padded box with room to spare, and
+//    the slab test's entry is <= t.
+// D bounds |pos - V| over the mesh's vertices (distance to the root box centre + half its diagonal).  A lane with a non-finite
+// pos, dir or pad runs the brute-force loop instead (no NaN reaches the slab test).
+//
+// Wave-coherent traversal: one stack for the wave (its entries are wave-uniform; BMO_UNIFORM keeps the node index scalar, so node, face
+// id and vertex reads are scalar loads as in mesh_nearest).  Every lane tests its own ray against both children of the node; the wave
+// goes on into a child if any lane needs it, the nearer one first (by the first active lane's direction on the split axis), the other
+// one is pushed and tested again, with the lanes' best hits by then, when it is popped.  Leaves run moeller_trumbore over wave-uniform
+// face ids for every lane of the wave (extra faces only add candidates that lose to the true minimum).
+BMO_HD double mesh_nearest_bvh(const SceneView& S, int32_t hdr, int tri0, int ntri, const d3& pos, const d3& dir, double tlim, int32_t& fid) {
+    const BMO_KONST BvhNode& H = S.bvh_nodes[hdr];
+    const d3 oc{pos.x - H.lo[0], pos.y - H.lo[1], pos.z - H.lo[2]};
+    const double D = sqrt(dot3(oc, oc)) + H.hi[0];
+    const double pad = D * 0x1p-46 + D * sqrt(dot3(dir, dir)) * H.hi[1];
+    if (!(pad < kinf())) return mesh_nearest(S, tri0, ntri, pos, dir, fid);  // (NaN / Inf in pos or dir)
+    const double o[3] = {pos.x, pos.y, pos.z}, iv[3] = {1.0 / dir.x, 1.0 / dir.y, 1.0 / dir.z};
+    const double tmin = S.mt_leps >= 0.0 ? 0.0 : -kinf();  // hits have t >= lϵ
+    double best = kinf();
+    fid = -1;
+    int32_t stk[BMO_BVH_STACK];  // nodes still to visit, far children (wave-uniform values)
+    int sp = 0;
+    int32_t ni = H.first;
+    bool tested = false;  // ni was found needed by its parent's test with the current `best` (a popped node is tested again)
+    BMO_NOUNROLL
+    for (;;) {
+        const BMO_KONST BvhNode& nd = S.bvh_nodes[ni];
+        const double tb = best < tlim ? best : tlim;
+        if (tested || BMO_WAVE_ANY(bvh_visit(nd, o, iv, pad, tmin, tb))) {
+            const int32_t first = nd.first, count = nd.count;
+            if (count > 0) {
+                BMO_NOUNROLL
+                for (int i = 0; i < count; ++i) {
+                    const int32_t f = S.bvh_faces[first + i];
+                    const double t = moeller_trumbore(S.tris + 9 * (tri0 + f), pos, dir, S.mt_keps, S.mt_leps);
+                    if (t < best || (t == best && f < fid)) {
+                        best = t;
+                        fid = f;
+                    }
+                }
+            } else {  // both children tested here (their two records load back to back); the wave goes on into the nearer one it needs
+                const bool n0 = BMO_WAVE_ANY(bvh_visit(S.bvh_nodes[first], o, iv, pad, tmin, tb));
+                const bool n1 = BMO_WAVE_ANY(bvh_visit(S.bvh_nodes[first + 1], o, iv, pad, tmin, tb));
+                if (n0 || n1) {
+                    int32_t next = n0 ? first : first + 1;
+                    if (n0 && n1) {
+                        if (sp + 1 > BMO_BVH_STACK) return mesh_nearest(S, tri0, ntri, pos, dir, fid);  // (never: the builder bounds the depth)
+                        const int ax = nd.axis;
+                        const double da = ax == 0 ? dir.x : (ax == 1 ? dir.y : dir.z);
+                        const int32_t back = BMO_UNIFORM((int32_t)(da < 0.0));  // first active lane's direction: nearer child first
+                        next = first + (back ? 1 : 0);
+                        stk[sp++] = first + (back ? 0 : 1);
+                    }
+                    ni = next;
+                    tested = true;
+                    continue;
+                }
+            }
+        }
+        if (sp == 0) break;
+        ni = BMO_UNIFORM(stk[--sp]);
+        tested = false;
+    }
+    return best;
+}
+
 // normal3d(mesh, fID) Mesh.jl:183-192, normalised a second time by intersect3d (Mesh.jl:265)
 BMO_HD d3 mesh_normal(const SceneView& S, int tri) {
     CDouble* f = S.tris + 9 * tri;
@@ -1172,7 +1291,19 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                             lm.put3(0, mesh_normal(S, s.tri_begin + x_aux));
                         } else if (active) {
                             int32_t fid = -1;
-                            const double t = mesh_nearest(S, s.tri_begin, s.tri_count, pos, dir0, fid);
+                            double t;
+                            if constexpr (EXT >= 3) {  // (the mesh-BVH level: bmo_engine.hip dispatch)
+                                if (s_flags & BMO_SHAPE_FLAG_BVH) {
+                                    // nodes beyond the running nearest hit are skipped: offer accepts only t < x_t — except for a plate
+                                    // splitter's coating, whose t is recorded whether or not it is accepted
+                                    const double tlim = (x_shape >= 0 && !(info & CAND_PLATE_COATING)) ? x_t : kinf();
+                                    t = mesh_nearest_bvh(S, s.child_begin, s.tri_begin, s.tri_count, pos, dir0, tlim, fid);
+                                } else {
+                                    t = mesh_nearest(S, s.tri_begin, s.tri_count, pos, dir0, fid);
+                                }
+                            } else {
+                                t = mesh_nearest(S, s.tri_begin, s.tri_count, pos, dir0, fid);
+                            }
                             if (fid >= 0) offer(t, fid, d3{0, 0, 0});
                         }
                         active = false;

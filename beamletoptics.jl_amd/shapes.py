@@ -17,6 +17,8 @@ from . import linalg as la
 (K_MESH, K_SPHERE, K_PLANO, K_CONVEX, K_CONCAVE, K_UNION, K_BOX, K_CYLINDER, K_CUTSPHERE, K_RING, K_PRISM, K_MENISCUS, K_POINT, K_ASPH_CONVEX,
  K_ASPH_CONCAVE, K_CYL_CONVEX, K_CYL_CONCAVE) = range(17)
 FLAG_INEXACT = 1
+FLAG_NO_BVH = 4  # include/bmo.h BMO_SHAPE_FLAG_NO_BVH: this mesh keeps the brute-force face loop
+MESH_BVH_MIN_FACES = 64  # include/bmo.h: meshes with this many faces or more get a BVH
 
 
 class AbstractShape:

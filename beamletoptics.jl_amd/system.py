@@ -34,7 +34,9 @@ StaticSystem = System  # src/System.jl:38-45: same tracing semantics
 class CompiledScene:
     """Flat tables + the ctypes descriptor that points into them (kept alive together)."""
 
-    def __init__(self, system, lambdas, cull=True, consts=None):
+    def __init__(self, system, lambdas, cull=True, consts=None, mesh_bvh=True):
+        # mesh_bvh=False: every mesh keeps the brute-force face loop (BMO_SHAPE_FLAG_NO_BVH); True: meshes of
+        # sh.MESH_BVH_MIN_FACES faces or more are traced through a BVH with the same results, bit for bit
         objs = system.objects() if isinstance(system, System) else cp.leaves(system)
         self.leaf_objects = objs
         self.lambdas = np.array(sorted(set(float(l) for l in lambdas)), dtype=np.float64)
@@ -73,6 +75,8 @@ class CompiledScene:
                 rec.tri_begin = len(tris)
                 rec.tri_count = len(t)
                 tris.extend(t)
+                if not mesh_bvh:
+                    rec.flags |= sh.FLAG_NO_BVH
                 v = s.vertices
                 c = (v.min(axis=0) + v.max(axis=0)) / 2
                 r = float(np.sqrt(((v - c) ** 2).sum(axis=1)).max())
@@ -175,6 +179,49 @@ class CompiledScene:
         if np.any(idx >= len(self.lambdas)) or np.any(self.lambdas[np.minimum(idx, len(self.lambdas) - 1)] != lams):
             raise KeyError("wavelength not in the compiled lambda table")
         return idx.astype(np.int32)
+
+
+class _SceneHandle:
+    """bmo_scene of a CompiledScene for the host-side entries (no GPU needed)."""
+
+    def __init__(self, scene):
+        self.lib = abi.load_engine()
+        self.handle = C.c_void_p()
+        abi.check(self.lib, self.lib.bmo_scene_create(C.byref(scene.desc), C.byref(self.handle)), "bmo_scene_create")
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            self.lib.bmo_scene_destroy(self.handle)
+
+
+def mesh_bvh_stats(scene):
+    """{shape id: (n_nodes, depth, max_leaf)} of the BVHs the library builds for the mesh shapes of a CompiledScene
+    (n_nodes = 0: that mesh is traced by brute force)."""
+    h = _SceneHandle(scene)
+    out = {}
+    for sid, s in enumerate(scene.shape_list):
+        if s.kind != sh.K_MESH:
+            continue
+        n, d, m = C.c_int32(), C.c_int32(), C.c_int32()
+        abi.check(h.lib, h.lib.bmo_scene_mesh_bvh(h.handle, sid, C.byref(n), C.byref(d), C.byref(m)), "bmo_scene_mesh_bvh")
+        out[sid] = (n.value, d.value, m.value)
+    return out
+
+
+def mesh_nearest_host(scene, shape_id, pos, dir):
+    """intersect3d(mesh, ray) of one mesh shape for rays pos / dir (n x 3) as the engine's lane code computes it, on the host
+    (bmo_mesh_nearest_host): (t, face) arrays, t = +Inf and face = -1 for a miss."""
+    h = _SceneHandle(scene)
+    pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+    dir = np.ascontiguousarray(dir, dtype=np.float64).reshape(-1, 3)
+    n = len(pos)
+    assert dir.shape == pos.shape
+    t = np.empty(n, dtype=np.float64)
+    fid = np.empty(n, dtype=np.int32)
+    dp = C.POINTER(C.c_double)
+    abi.check(h.lib, h.lib.bmo_mesh_nearest_host(h.handle, int(shape_id), n, pos.ctypes.data_as(dp), dir.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                                                 fid.ctypes.data_as(C.POINTER(C.c_int32))), "bmo_mesh_nearest_host")
+    return t, fid
 
 
 def make_batch(scene, bundle):

@@ -104,6 +104,14 @@ enum bmo_shape_kind {
 /* Library-internal (set by bmo_scene_create on its own copy of the tables, ignored on input): the children of this UNION are
  * consecutive shape ids starting at tri_begin (unused by unions otherwise), so the walk over children needs no children[] read. */
 #define BMO_SHAPE_FLAG_CONSECUTIVE 2
+/* Input: keep brute force (every face, every ray) for this MESH even above BMO_MESH_BVH_MIN_FACES. */
+#define BMO_SHAPE_FLAG_NO_BVH 4
+/* Library-internal (set by bmo_scene_create on its own copy of the tables, ignored on input): this MESH is traced through a bounding
+ * volume hierarchy; child_begin (unused by meshes otherwise) holds the index of its first node.  The BVH returns the same face as the
+ * brute-force loop of Mesh.jl:244-267, bit for bit (DESIGN.md §3 "mesh BVH"). */
+#define BMO_SHAPE_FLAG_BVH 8
+/* A MESH with at least this many faces (and without BMO_SHAPE_FLAG_NO_BVH) gets a BVH. */
+#define BMO_MESH_BVH_MIN_FACES 64
 
 typedef struct bmo_shape {
     int32_t kind;
@@ -304,6 +312,13 @@ int bmo_selftest(int32_t device);
 double bmo_jl_trig(int32_t which, double x, double y);
 
 int bmo_scene_create(const bmo_scene_desc* desc, bmo_scene** out);
+/* BVH of mesh shape `shape` as bmo_scene_create built it: node count (0: the shape is traced by brute force), depth (root = 1) and the
+   largest leaf (faces).  BMO_ERR_INVALID for a bad id.  No GPU needed. */
+int bmo_scene_mesh_bvh(const bmo_scene* scene, int32_t shape, int32_t* n_nodes, int32_t* depth, int32_t* max_leaf);
+/* Check entry: intersect3d(mesh, ray) of mesh shape `shape` for n rays (pos / dir: n x 3, row-major) evaluated on the host by the
+   engine's own lane code against the scene blob the GPU reads — the BVH traversal for a shape with a BVH, the brute-force loop
+   otherwise.  t[i]: the hit's t (+Inf: none), fid[i]: the face (0-based within the mesh, -1: none).  No GPU needed. */
+int bmo_mesh_nearest_host(const bmo_scene* scene, int32_t shape, int64_t n, const double* pos, const double* dir, double* t, int32_t* fid);
 int bmo_scene_destroy(bmo_scene* scene);
 /* The engine keeps freed device blocks in a per-device pool for reuse by the next trace; this returns them to HIP. */
 int bmo_pool_release(void);
