@@ -11,5 +11,6 @@ from .shapes import *  # noqa: F401,F403
 from .components import *  # noqa: F401,F403
 from .beams import *  # noqa: F401,F403
 from .system import System, StaticSystem, CompiledScene, Engine, solve_system, make_batch, release, EngineSolution  # noqa: F401
+from .system import solve_sweep, sweep_trace, sweep_snapshots, SweepSolution  # noqa: F401
 from .system import mesh_bvh_stats, mesh_nearest_host  # noqa: F401
 from . import abi, linalg, shapes, components, beams, system  # noqa: F401

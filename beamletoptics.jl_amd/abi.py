@@ -236,6 +236,9 @@ def load_engine():
     lib.bmo_gauss_parameters.argtypes = [vp, C.c_int64, dp, C.c_int32, dp]
     lib.bmo_result_set_gauss_prefix.argtypes = [vp, C.c_int64, C.POINTER(C.c_int32), dp, dp]
     lib.bmo_psf_intensity.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp]
+    lib.bmo_scene_create_sweep.argtypes = [C.POINTER(SceneDesc), C.c_int32, C.POINTER(vp)]
+    lib.bmo_trace_sweep.argtypes = [vp, C.POINTER(RayBatch), C.POINTER(C.c_int32), C.POINTER(TraceOpts), C.POINTER(vp)]
+    lib.bmo_photodetector_field_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
     _engine = lib
     return lib
 

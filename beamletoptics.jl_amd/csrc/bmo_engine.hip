@@ -173,6 +173,7 @@ struct Counters {  // device-resident, one per trace
     unsigned long long overflow;
     unsigned long long max_level[2];  // deepest in-place level any wave of the launch reached (slots used like next_count's)
     unsigned long long inwave[2];     // reflected children pushed from inside the fused loops of the launch (slots used like next_count's)
+    unsigned long long sweep_mixed;   // sweep launches: waves whose lanes did not all belong to one configuration (must stay 0)
 };
 
 struct NodeArrays {
@@ -224,6 +225,16 @@ __device__ __forceinline__ const double* old_record(const OldSolution& O, int32_
     return c.d;
 }
 
+// Sweeps (bmo_trace_sweep, DESIGN.md §3 "Sweeps"): the scene blob holds one configuration per `stride` bytes, all with the same header.
+// Lane v of the grid works on slot map[v] of the launch's chunk (-1: idle lane); the map groups the slots by configuration and pads every
+// configuration's run to whole waves, so every wave traces records of ONE configuration and reads that configuration's tables with the
+// scalar loads of bmo_lane.hpp.  root_cfg[root]: configuration of every root beam (non-decreasing).
+struct SweepLanes {
+    const int32_t* map;
+    const int32_t* root_cfg;
+    uint64_t stride;
+};
+
 #if !defined(BMO_MAX_FUSE)
 #define BMO_MAX_FUSE 32
 #endif
@@ -242,7 +253,12 @@ struct StepParams {
     NodeArrays nodes;
     int32_t r_max;
     int32_t parity;   // step & 1: which next_count slot this launch fills
-    OldSolution old;  // RETR kernels only
+    // RETR kernels read `old`, SWEEP kernels (fresh solves only) `sweep`: the two share their room, so the kernel arguments of the other
+    // kernels keep their layout
+    union {
+        OldSolution old;
+        SweepLanes sweep;
+    };
     double* gstage;      // GaussianBeamlet kernels: [21][gstage_cap] staging planes of the reflected child's rays (GaussRecDev)
     int64_t gstage_cap;
     uint8_t* wave_last;  // [waves of the launch]: the last in-place level each wave reached (nullptr: nobody will read the log)
@@ -304,6 +320,25 @@ __device__ inline int prefix_rank(unsigned long long mask) {
     return __popcll(mask & ((1ull << lane_id()) - 1ull));
 }
 
+
+// Slot and configuration of this lane of a sweep launch (StepParams::sweep).  The configuration of the lane's record (node -> root ->
+// root_cfg) is read by every lane, the first lane's value is made wave-uniform, and the wave checks that its lanes agree: a wave that mixes
+// configurations traces nothing and is counted (Counters::sweep_mixed fails the solve with BMO_ERR_INTERNAL), never a wrong answer.
+__device__ __forceinline__ int32_t sweep_lane(const StepParams& P, int64_t gwave, int64_t& j, bool& valid) {
+    const int32_t s = P.sweep.map[(gwave << 6) + lane_id()];
+    j = s;
+    valid = s >= 0;
+    int32_t lc = -1;
+    if (valid) lc = P.sweep.root_cfg[P.nodes.root[P.cur.i[I_NODE * P.cur.cap + s]]];
+    const unsigned long long on = __ballot(valid);
+    int32_t c = __shfl(lc, on ? __ffsll((unsigned long long)on) - 1 : 0);
+    c = BMO_UNIFORM(c < 0 ? 0 : c);
+    if (!BMO_WAVE_ALL(!valid || lc == c)) {
+        if (lane_id() == 0) atomicAdd(&P.ctr->sweep_mixed, 1ull);
+        valid = false;
+    }
+    return c;
+}
 
 // Block-aggregated slot allocation.  A single address sustains only ~88 returning atomics/us (MI355X_MICROARCH.md
 // "dequeue"): one atomic per wave = 16 K per 1 M-ray launch put a ~0.3 ms floor under every launch.  Here the 4 waves
@@ -410,10 +445,11 @@ constexpr int step_waves() {
 // INW: beam splitters are handled inside the fused loop (the launches of a beam tree's tail: fewer launches, no launch waits for the
 // slowest march of every generation); without it a split ends the wave's loop and both children wait for the next launch, which costs
 // less register room — the large launches of the BASELINE configs run 2 - 7 % faster that way (profiles/r03_ab_inwave.txt).
-template <int KIND, int EXT, bool RETR, bool INW, int WAVES = step_waves<KIND, EXT, RETR>()>
+// SWEEP (bmo_trace_sweep, fresh solves only): lane -> slot through StepParams::sweep, scene tables of the wave's configuration.
+template <int KIND, int EXT, bool RETR, bool INW, int WAVES = step_waves<KIND, EXT, RETR>(), bool SWEEP = false>
 __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
+    SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
     char* scratch = lds;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         P.ctr->next_count[P.parity ^ 1] = 0;
@@ -426,9 +462,16 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
 #endif
     const int64_t gwave = ((int64_t)tile * blockDim.x + threadIdx.x) >> 6;  // wave of the grid
-    const int64_t j = (gwave << P.lane_shift) + lane_id();
+    int64_t sweep_j = 0;
+    bool sweep_valid = false;
+    if constexpr (SWEEP) {
+        static_assert(!RETR, "sweeps are fresh solves");
+        const int32_t cfg = sweep_lane(P, gwave, sweep_j, sweep_valid);
+        S = view_of((const char*)P.blob + (uint64_t)cfg * P.sweep.stride, &P.hdr);
+    }
+    const int64_t j = SWEEP ? sweep_j : (gwave << P.lane_shift) + lane_id();
     const int64_t m = P.cur.count;
-    const bool valid = j < m && lane_id() < (1 << P.lane_shift);
+    const bool valid = SWEEP ? sweep_valid : (j < m && lane_id() < (1 << P.lane_shift));
 #if defined(BMO_DEV_TIMELINE)
     if (P.tl && (threadIdx.x & 63) == 0 && (gwave << P.lane_shift) < P.cur.count) P.tl[2 * gwave] = wall_clock64();
 #endif
@@ -797,7 +840,11 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         // ---- last fused bounce of this wave (kept inside the loop so that o.next / o.refl die here instead of staying live
         //      across the march of the next iteration): note how far the wave got — the in-place levels beyond are never written and
         //      never read (Chunk::wl) —, then compact into the next launch's chunk
-        if (P.wave_last && lane_id() == 0) P.wave_last[gwave] = (uint8_t)b;
+        if constexpr (SWEEP) {  // (a wave's slots are not consecutive: the level is noted per slot, Chunk::wl_shift = 0)
+            if (P.wave_last && valid) P.wave_last[j] = (uint8_t)b;
+        } else if (P.wave_last && lane_id() == 0) {
+            P.wave_last[gwave] = (uint8_t)b;
+        }
 #if defined(BMO_DEV_TIMELINE)
         if (P.tl && (threadIdx.x & 63) == 0 && (gwave << P.lane_shift) < P.cur.count) {  // (tail waves of the grid have no slot in the timeline)
             P.tl[2 * gwave + 1] = wall_clock64();  // before the workgroup barrier of block_alloc
@@ -980,10 +1027,10 @@ struct GaussRecDevNoHint : GaussRecDev {
 // produces them (no staging copy, no compaction between the levels; P.inner has n_fuse entries here — the last one only holds the rays of
 // the last fused level until they are compacted into P.nxt).  Beam splitters are handled in the loop: the transmitted child goes on in
 // place, the reflected child's rays wait in the staging planes and are pushed to P.nxt (StepParams::inwave_cap).
-template <int EXT, bool RETR>
+template <int EXT, bool RETR, bool SWEEP = false>
 __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_gauss(StepParams P) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
+    SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
     char* scratch = lds;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         P.ctr->next_count[P.parity ^ 1] = 0;
@@ -995,9 +1042,16 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
     if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
 #endif
     const int64_t gwave = ((int64_t)tile * blockDim.x + threadIdx.x) >> 6;  // wave of the grid
-    const int64_t j = (gwave << P.lane_shift) + lane_id();
+    int64_t sweep_j = 0;
+    bool sweep_valid = false;
+    if constexpr (SWEEP) {
+        static_assert(!RETR, "sweeps are fresh solves");
+        const int32_t cfg = sweep_lane(P, gwave, sweep_j, sweep_valid);
+        S = view_of((const char*)P.blob + (uint64_t)cfg * P.sweep.stride, &P.hdr);
+    }
+    const int64_t j = SWEEP ? sweep_j : (gwave << P.lane_shift) + lane_id();
     const int64_t m = P.cur.count;
-    const bool valid = j < m && lane_id() < (1 << P.lane_shift);
+    const bool valid = SWEEP ? sweep_valid : (j < m && lane_id() < (1 << P.lane_shift));
     bool alive = valid;
     uint32_t calls = 0;
     const int64_t ncap = P.nxt.cap;
@@ -1239,7 +1293,11 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             continue;
         }
         // ---- last fused bounce of this wave
-        if (P.wave_last && lane_id() == 0) P.wave_last[gwave] = (uint8_t)b;
+        if constexpr (SWEEP) {  // (a wave's slots are not consecutive: the level is noted per slot, Chunk::wl_shift = 0)
+            if (P.wave_last && valid) P.wave_last[j] = (uint8_t)b;
+        } else if (P.wave_last && lane_id() == 0) {
+            P.wave_last[gwave] = (uint8_t)b;
+        }
         const SlotAlloc al = block_alloc<false>(survive, pend_node >= 0, calls, P, scratch, b);
         if (survive) {
             const int64_t slot = (int64_t)al.surv_base + prefix_rank(al.m_surv);
@@ -1529,6 +1587,37 @@ __global__ void iota_kernel(int32_t* a, int64_t n) {
     if (j < n) a[j] = (int32_t)j;
 }
 // flags[d*n + i] = 1 if canonical node i recorded a hit on detector d
+// ---- lane map of a sweep launch (StepParams::sweep): key = configuration of every slot of the launch's chunk (node -> root -> root_cfg),
+// a stable sort by it, the runs padded to whole waves.  beg / end: first and one-past-last sorted position of every configuration.
+__global__ void sweep_key_kernel(Chunk c, const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg, int64_t m, uint32_t* __restrict__ key,
+                                 int32_t* __restrict__ slot) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    key[j] = (uint32_t)root_cfg[root[c.i[I_NODE * c.cap + j]]];
+    slot[j] = (int32_t)j;
+}
+__global__ void sweep_bounds_kernel(const uint32_t* __restrict__ key, int64_t m, int32_t* __restrict__ beg, int32_t* __restrict__ end) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t k = key[i];
+    if (i == 0 || key[i - 1] != k) beg[k] = (int32_t)i;
+    if (i == m - 1 || key[i + 1] != k) end[k] = (int32_t)(i + 1);
+}
+__global__ void sweep_pad_kernel(const int32_t* __restrict__ beg, const int32_t* __restrict__ end, int32_t n_configs, int32_t* __restrict__ padded) {
+    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= n_configs) return;
+    padded[c] = (end[c] - beg[c] + 63) & ~63;
+}
+__global__ void sweep_scatter_kernel(const uint32_t* __restrict__ key, const int32_t* __restrict__ slot, int64_t m, const int32_t* __restrict__ beg,
+                                     const int32_t* __restrict__ pstart, int64_t lanes, int32_t* __restrict__ map, unsigned long long* __restrict__ overflow) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t k = key[i];
+    const int64_t v = (int64_t)pstart[k] + (i - beg[k]);
+    if (v < lanes) map[v] = slot[i];
+    else atomicAdd(overflow, 1ull);
+}
+
 __global__ void hit_flags_kernel(const int32_t* order, const int32_t* hit_det, int64_t n, int32_t n_det, int32_t nsub, int32_t* flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1987,6 +2076,9 @@ struct bmo_scene {
     BlobHeader hdr;
     std::vector<BvhStats> bvh;  // per shape (n_nodes = 0: no BVH)
     double bound[4] = {0, 0, 0, -1};  // a sphere around the bounding spheres of all candidates (centre, radius; radius < 0: none) — root_chord_kernel
+    // bmo_scene_create_sweep: n_configs blobs of `stride` bytes each, back to back in `blob`, all described by `hdr` (0: an ordinary scene)
+    int32_t n_configs = 0;
+    uint64_t stride = 0;
     std::vector<std::pair<int, std::unique_ptr<DevBuf>>> dev;  // per-device copy of the blob
     std::mutex dev_mu;  // the handle is shared between host threads (include/bmo.h "Threading"): the lazy per-device upload is the one mutation
     const char* device_blob(int device, int& rc) {
@@ -2047,6 +2139,10 @@ struct bmo_trace_result {
     DevBuf tile_cost;
     int64_t tile_n = 0;
     std::vector<int64_t> det_count, det_offset;
+    // bmo_trace_sweep: configurations of the sweep and the configuration of every root beam (device); 0 / empty for other solves
+    int32_t n_configs = 0;
+    std::vector<int32_t> root_cfg;
+    DevBuf d_root_cfg;
     // host views (filled by bmo_result_view / bmo_result_view_select), all page-locked; each part is materialised on first request
     bool nodes_viewed = false, hits_viewed = false;
     int rec_mode = 0;  // records on the host: 0 none, 1 last segment of every beam, 2 the whole log
@@ -2105,6 +2201,21 @@ int build_retrace_tables(bmo_trace_result* prev, hipStream_t stream) {
     }
     prev->rt_built = true;
     return BMO_OK;
+}
+
+// The SWEEP builds of the step kernels (fresh solves, every extended-shapes level): the Beam kernels without / with in-loop beam splitters.
+template <int KIND, bool INW>
+void (*sweep_step_kernel(int ext))(StepParams) {
+    if (ext == 3) return &step_kernel<KIND, 3, false, INW, step_waves<KIND, 3, false>(), true>;
+    if (ext == 2) return &step_kernel<KIND, 2, false, INW, step_waves<KIND, 2, false>(), true>;
+    if (ext == 1) return &step_kernel<KIND, 1, false, INW, step_waves<KIND, 1, false>(), true>;
+    return &step_kernel<KIND, 0, false, INW, step_waves<KIND, 0, false>(), true>;
+}
+inline void (*sweep_gauss_kernel(int ext))(StepParams) {
+    if (ext == 3) return &step_kernel_gauss<3, false, true>;
+    if (ext == 2) return &step_kernel_gauss<2, false, true>;
+    if (ext == 1) return &step_kernel_gauss<1, false, true>;
+    return &step_kernel_gauss<0, false, true>;
 }
 
 template <int KIND>
@@ -2378,6 +2489,24 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
 #endif
     }
 #endif
+    // a sweep (bmo_trace_sweep): R->n_configs configurations, R->d_root_cfg the configuration of every root; lanes find their slots through
+    // the map built before every launch (StepParams::sweep)
+    const bool sweep = R->n_configs > 0;
+    if (sweep) {
+        if (prev) return fail(BMO_ERR_UNSUPPORTED, "sweeps are fresh solves");
+#if defined(BMO_DEV_RAY_LDS_ONLY) || defined(BMO_DEV_GAUSS_ONLY)
+        return fail(BMO_ERR_UNSUPPORTED, "developer build: no sweep kernels");
+#else
+        kern_wide = kern_inw_wide = nullptr;
+        if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
+            kern = sweep_gauss_kernel(ext);
+            kern_inw = nullptr;
+        } else {
+            kern = sweep_step_kernel<KIND, false>(ext);
+            kern_inw = sweep_step_kernel<KIND, true>(ext);
+        }
+#endif
+    }
     if (lds_bytes > 48 * 1024) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
         if (kern_inw) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_inw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
@@ -2412,7 +2541,7 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
         // handled in the loop, and it costs small batches dearly (100 rays through config 2: 0.84 ms against 0.55 — every wave on a CU of
         // its own pays that CU's instruction- and scalar-cache warm-up): profiles/r03_ab_inwave.txt.
         int lane_shift = 6;
-        {
+        if (!sweep) {
             static const int64_t thin_waves = getenv("BMO_THIN_WAVES") ? atoll(getenv("BMO_THIN_WAVES")) : 0;
             while (lane_shift > 0 && ((m + (1ll << (lane_shift - 1)) - 1) >> (lane_shift - 1)) <= thin_waves) lane_shift -= 1;
         }
@@ -2425,7 +2554,10 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
         int n_fuse = tail ? fuse_max : keep_ratio >= keep_hi ? fuse_max : (keep_ratio >= keep_lo ? std::min(fuse_mid, fuse_max) : std::min(fuse_lo, fuse_max));
         // the in-place levels of a launch are allocated up front: at most 24 GB of them (2^24 beams: 8 levels)
         if (keep_log) n_fuse = (int)std::min<int64_t>(n_fuse, 1 + (int64_t)(((size_t)24 << 30) / ((size_t)std::max<int64_t>(m, 1) * rec_bytes)));
-        const int64_t n_waves = (m + (1ll << lane_shift) - 1) >> lane_shift;
+        // a sweep launch: every configuration's run of slots padded to whole waves (at most 63 idle lanes per configuration present)
+        const int64_t sweep_lanes = sweep ? ((m + 63 * std::min<int64_t>(R->n_configs, m) + 63) & ~(int64_t)63) : 0;
+        if (sweep_lanes >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "sweep launch of more than 2^31 lanes: fewer roots per call");
+        const int64_t n_waves = sweep ? sweep_lanes >> 6 : (m + (1ll << lane_shift) - 1) >> lane_shift;
         const unsigned n_blocks = (unsigned)((n_waves + BMO_BLOCK / 64 - 1) / (BMO_BLOCK / 64));
         Chunk nxt, inner[MAX_FUSE - 1];
         // the next launch's chunk first, then the in-place levels: the levels no wave reaches go back to the arena after the launch
@@ -2443,8 +2575,9 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
         uint8_t* wl = nullptr;
         if (keep_log && n_fuse > 1) {
             auto b = std::make_unique<DevBuf>();
-            // one byte per wave of the GRID, not of the batch: the tail waves of the last workgroup (no record, j >= m) note their level too
-            if ((rc = b->alloc((size_t)n_blocks * (BMO_BLOCK / 64)))) return rc;
+            // one byte per wave of the GRID, not of the batch: the tail waves of the last workgroup (no record, j >= m) note their level too.
+            // A sweep launch notes it per slot (a wave's slots are not consecutive there).
+            if ((rc = b->alloc(sweep ? (size_t)m : (size_t)n_blocks * (BMO_BLOCK / 64)))) return rc;
             wl = static_cast<uint8_t*>(b->p);
             R->wave_last.push_back(std::move(b));
         }
@@ -2467,7 +2600,7 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
             inner[q].count = m;  // same slot numbering as cur; records of beams that ended earlier are marked node = -1
             inner[q].wl = wl;
             inner[q].level = q + 1;
-            inner[q].wl_shift = lane_shift;
+            inner[q].wl_shift = sweep ? 0 : lane_shift;
             top_after[q + 1] = top;
             blocks_after[q + 1] = R->arena.size();
         }
@@ -2514,7 +2647,7 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
         P.tile_cost = nullptr;
         {
             static const bool lpt_on = !(getenv("BMO_LPT") && atoi(getenv("BMO_LPT")) == 0);
-            if (lpt_on && steps == 0 && lane_shift == 6 && n_blocks >= 64) {
+            if (lpt_on && !sweep && steps == 0 && lane_shift == 6 && n_blocks >= 64) {
                 if (batch->tile_n != (int64_t)n_blocks) {
                     PoolHold::Now at_once;
                     batch->cost_valid = false;
@@ -2552,12 +2685,43 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
 #if defined(BMO_DEV_TIMELINE)  // developer builds, BMO_TIMELINE=1: how many waves are at work over the course of every launch
         DevBuf tl_buf;
         P.tl = nullptr;
-        if (getenv("BMO_TIMELINE")) {
+        if (getenv("BMO_TIMELINE") && !sweep) {
             if ((rc = tl_buf.alloc((size_t)n_waves * 16 + 64))) return rc;
             HIP_TRY(hipMemsetAsync(tl_buf.p, 0, tl_buf.bytes, stream));
             P.tl = (unsigned long long*)tl_buf.p;
         }
 #endif
+        DevBuf sw_map;  // (P.sweep shares its room with P.old: set for sweeps only)
+        if (sweep) {
+            // lane map: key = configuration of every slot, stable sort (slot order within a configuration), runs padded to whole waves
+            const int32_t K = R->n_configs;
+            DevBuf key, key_s, slot, slot_s, beg, end, padded, pstart, tmp;
+            if ((rc = key.alloc((size_t)m * 4)) || (rc = key_s.alloc((size_t)m * 4)) || (rc = slot.alloc((size_t)m * 4)) || (rc = slot_s.alloc((size_t)m * 4)) ||
+                (rc = beg.alloc((size_t)K * 4)) || (rc = end.alloc((size_t)K * 4)) || (rc = padded.alloc((size_t)K * 4)) || (rc = pstart.alloc((size_t)K * 4)) ||
+                (rc = sw_map.alloc((size_t)sweep_lanes * 4)))
+                return rc;
+            int kbits = 1;
+            while (kbits < 32 && ((uint32_t)(K - 1) >> kbits)) ++kbits;
+            size_t tb = 0, tb2 = 0;
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t*)key.p, (uint32_t*)key_s.p, (const int32_t*)slot.p, (int32_t*)slot_s.p, (int)m, 0, kbits, stream));
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, (const int32_t*)padded.p, (int32_t*)pstart.p, (int)K, stream));
+            if ((rc = tmp.alloc(std::max(tb, tb2)))) return rc;
+            const unsigned mb = (unsigned)((m + 255) / 256);
+            hipLaunchKernelGGL(sweep_key_kernel, dim3(mb), dim3(256), 0, stream, cur, (const int32_t*)R->n_root.p, (const int32_t*)R->d_root_cfg.p, m,
+                               (uint32_t*)key.p, (int32_t*)slot.p);
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, (const uint32_t*)key.p, (uint32_t*)key_s.p, (const int32_t*)slot.p, (int32_t*)slot_s.p, (int)m, 0, kbits, stream));
+            HIP_TRY(hipMemsetAsync(beg.p, 0, (size_t)K * 4, stream));
+            HIP_TRY(hipMemsetAsync(end.p, 0, (size_t)K * 4, stream));
+            hipLaunchKernelGGL(sweep_bounds_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t*)key_s.p, m, (int32_t*)beg.p, (int32_t*)end.p);
+            hipLaunchKernelGGL(sweep_pad_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, (const int32_t*)beg.p, (const int32_t*)end.p, K, (int32_t*)padded.p);
+            size_t t2 = tmp.bytes;
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, t2, (const int32_t*)padded.p, (int32_t*)pstart.p, (int)K, stream));
+            HIP_TRY(hipMemsetAsync(sw_map.p, 0xFF, (size_t)sweep_lanes * 4, stream));
+            hipLaunchKernelGGL(sweep_scatter_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t*)key_s.p, (const int32_t*)slot_s.p, m, (const int32_t*)beg.p,
+                               (const int32_t*)pstart.p, sweep_lanes, (int32_t*)sw_map.p, &d_ctr->overflow);
+            HIP_TRY(hipGetLastError());
+            P.sweep = SweepLanes{(const int32_t*)sw_map.p, (const int32_t*)R->d_root_cfg.p, scene->stride};
+        }
         DBG("step %d launching m=%lld, %d records per wave", steps, (long long)m, 1 << lane_shift);
         // launch timing: one event pair per step out of a cached pool, read after the loop (nothing but the counter read-back
         // sits between two launches)
@@ -2627,6 +2791,7 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
         DBG("step %d done next=%llu nodes=%llu deepest in-place level %llu of %d", steps, produced, h_ctr.node_count, h_ctr.max_level[steps & 1], n_fuse);
         steps += 1;
         if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "queue overflow (internal capacity bound violated)");
+        if (h_ctr.sweep_mixed) return fail(BMO_ERR_INTERNAL, "sweep: a wave held records of more than one configuration (lane map violated)");
         if (keep_log) {
             const int used = (int)std::min<unsigned long long>(h_ctr.max_level[(steps - 1) & 1], (unsigned long long)(n_fuse - 1));  // in-place levels reached
             R->chunks.push_back(cur);
@@ -3177,6 +3342,95 @@ int bmo_scene_create(const bmo_scene_desc* d, bmo_scene** out) {
     return BMO_OK;
 }
 
+// Topology of configuration `d` against configuration 0 (bmo_scene_create_sweep): "" when they agree, else the first field that differs.
+static std::string sweep_topology_diff(const bmo_scene_desc* a, const bmo_scene_desc* d) {
+    auto ne = [](const void* x, const void* y, size_t n) { return std::memcmp(x, y, n) != 0; };
+#define BMO_CMP(f) \
+    if (a->f != d->f) return #f;
+    BMO_CMP(abi_version) BMO_CMP(n_objects) BMO_CMP(n_shapes) BMO_CMP(n_children) BMO_CMP(n_tris) BMO_CMP(n_media) BMO_CMP(n_lambda) BMO_CMP(n_detectors)
+    BMO_CMP(n_coefs) BMO_CMP(march_iters)
+#undef BMO_CMP
+    if (a->n_lambda > 0 && ne(a->lambdas, d->lambdas, 8 * (size_t)a->n_lambda)) return "lambdas";
+    const double ka[6] = {a->eps_srf, a->eps_ray, a->eps_ins, a->mt_keps, a->mt_leps, a->grad_h}, kd[6] = {d->eps_srf, d->eps_ray, d->eps_ins, d->mt_keps, d->mt_leps, d->grad_h};
+    const char* kn[6] = {"eps_srf", "eps_ray", "eps_ins", "mt_keps", "mt_leps", "grad_h"};
+    for (int q = 0; q < 6; ++q)
+        if (ne(&ka[q], &kd[q], 8)) return kn[q];
+    for (int i = 0; i < a->n_objects; ++i) {
+        const bmo_object &x = a->objects[i], &y = d->objects[i];
+        const std::string at = "objects[" + std::to_string(i) + "].";
+        if (x.kind != y.kind) return at + "kind";
+        if (ne(x.shape, y.shape, sizeof x.shape)) return at + "shape";
+        if (ne(x.medium, y.medium, sizeof x.medium)) return at + "medium";
+        if (x.detector != y.detector) return at + "detector";
+    }
+    for (int i = 0; i < a->n_shapes; ++i) {
+        const bmo_shape &x = a->shapes[i], &y = d->shapes[i];
+        const std::string at = "shapes[" + std::to_string(i) + "].";
+        if (x.kind != y.kind) return at + "kind";
+        if (x.child_begin != y.child_begin) return at + "child_begin";
+        if (x.child_count != y.child_count) return at + "child_count";
+        if (x.tri_begin != y.tri_begin) return at + "tri_begin";
+        if (x.tri_count != y.tri_count) return at + "tri_count";
+        if (x.flags != y.flags) return at + "flags";
+    }
+    if (a->n_children > 0 && ne(a->children, d->children, 4 * (size_t)a->n_children)) return "children";
+    return "";
+}
+
+int bmo_scene_create_sweep(const bmo_scene_desc* descs, int32_t n_configs, bmo_scene** out) {
+    if (!descs || !out || n_configs < 1) return fail(BMO_ERR_INVALID, "bmo_scene_create_sweep: null argument or n_configs < 1");
+    std::vector<std::unique_ptr<bmo_scene>> cfg((size_t)n_configs);
+    for (int32_t c = 0; c < n_configs; ++c) {
+        if (c > 0) {
+            const std::string diff = sweep_topology_diff(&descs[0], &descs[c]);
+            if (!diff.empty())
+                return fail(BMO_ERR_INVALID, "bmo_scene_create_sweep: configuration " + std::to_string(c) + " differs from configuration 0 in " + diff +
+                                                 " (a sweep changes numbers, not topology)");
+        }
+        bmo_scene* one = nullptr;
+        const int rc = bmo_scene_create(&descs[c], &one);
+        if (rc) return fail(rc, "bmo_scene_create_sweep: configuration " + std::to_string(c) + ": " + g_err);
+        cfg[(size_t)c].reset(one);
+    }
+    // Every region but the mesh BVHs has the same size in every configuration; the BVH node table is sized to the largest one, so that every
+    // configuration has the same offsets and the header of configuration 0 describes all of them.
+    const BlobHeader& h0 = cfg[0]->hdr;
+    size_t node_bytes = 0, face_bytes = 0;
+    for (int32_t c = 0; c < n_configs; ++c) {
+        const BlobHeader& h = cfg[(size_t)c]->hdr;
+        if (h.n_cands != h0.n_cands || h.pad[0] != h0.pad[0] || h.off_bvh_nodes != h0.off_bvh_nodes || h.has_splitter != h0.has_splitter)
+            return fail(BMO_ERR_INVALID, "bmo_scene_create_sweep: configuration " + std::to_string(c) + " differs from configuration 0 in its candidate table or BVHs");
+        node_bytes = std::max<size_t>(node_bytes, (size_t)h.off_bvh_faces - h.off_bvh_nodes);
+        face_bytes = std::max<size_t>(face_bytes, (size_t)h.total - h.off_bvh_faces);
+    }
+    BlobHeader H = h0;
+    const uint64_t faces_at = (uint64_t)H.off_bvh_nodes + node_bytes, total = faces_at + face_bytes;
+    if (total > 0xffffffffull) return fail(BMO_ERR_INVALID, "bmo_scene_create_sweep: scene blob larger than 4 GiB (32-bit table offsets)");
+    H.off_bvh_faces = (uint32_t)faces_at;
+    H.total = (uint32_t)total;
+    const uint64_t stride = (total + 255) & ~(uint64_t)255;  // configurations start on 256-byte boundaries (scalar cache lines)
+    auto sc = std::make_unique<bmo_scene>();
+    try {
+        sc->blob.assign((size_t)(stride * (uint64_t)n_configs), 0);
+    } catch (const std::bad_alloc&) {
+        return fail(BMO_ERR_OOM, "bmo_scene_create_sweep: host allocation of the configurations' blobs");
+    }
+    for (int32_t c = 0; c < n_configs; ++c) {
+        const bmo_scene& one = *cfg[(size_t)c];
+        char* dst = sc->blob.data() + stride * (uint64_t)c;
+        std::memcpy(dst, one.blob.data(), one.hdr.off_bvh_faces);  // header .. BVH nodes (shapes keep their own BVH node indices)
+        std::memcpy(dst + H.off_bvh_faces, one.blob.data() + one.hdr.off_bvh_faces, one.hdr.total - one.hdr.off_bvh_faces);
+        std::memcpy(dst, &H, sizeof H);
+    }
+    sc->hdr = H;
+    sc->bvh = cfg[0]->bvh;
+    std::memcpy(sc->bound, cfg[0]->bound, sizeof sc->bound);
+    sc->n_configs = n_configs;
+    sc->stride = stride;
+    *out = sc.release();
+    return BMO_OK;
+}
+
 int bmo_scene_mesh_bvh(const bmo_scene* scene, int32_t shape, int32_t* n_nodes, int32_t* depth, int32_t* max_leaf) {
     if (!scene) return fail(BMO_ERR_INVALID, "null argument");
     if (shape < 0 || shape >= scene->hdr.n_shapes) return fail(BMO_ERR_INVALID, "shape id out of bounds");
@@ -3213,7 +3467,10 @@ int bmo_pool_release(void) {
     return BMO_OK;
 }
 
-int bmo_batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_device_batch** out) {
+}  // extern "C"
+namespace {
+// order_roots: bin the roots by coherence key (off for sweeps: the scene bound and the candidate masks are per configuration)
+int batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_device_batch** out, bool order_roots) {
     if (!scene || !in || !out) return fail(BMO_ERR_INVALID, "null argument");
     if (in->kind != BMO_BEAM_RAY && in->kind != BMO_BEAM_POLARIZED && in->kind != BMO_BEAM_GAUSSIAN) return fail(BMO_ERR_INVALID, "bad beam kind");
     const int want = in->kind == BMO_BEAM_RAY ? BMO_PLANES_RAY : (in->kind == BMO_BEAM_POLARIZED ? BMO_PLANES_POLARIZED : BMO_PLANES_GAUSSIAN);
@@ -3242,6 +3499,7 @@ int bmo_batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, 
     // BMO_ROOT_ORDER = chord (default: root_order_key_kernel) | mask (round 3's candidate-set keys, below) | none
     const char* order_env = getenv("BMO_ROOT_ORDER");
     std::string root_order = order_env ? order_env : (getenv("BMO_NO_BINNING") ? "none" : "auto");
+    if (!order_roots) root_order = "none";
     if (in->n >= 4096 && scene->hdr.n_cands > 0 && scene->bound[3] > 0.0 && (root_order == "chord" || root_order == "auto")) {
         const int64_t n = in->n;
         DevBuf chord, lim, keys, keys_out, ids, tmp;
@@ -3319,6 +3577,13 @@ int bmo_batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, 
     *out = b.release();
     return BMO_OK;
 }
+}  // namespace
+extern "C" {
+
+int bmo_batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_device_batch** out) {
+    if (scene && scene->n_configs > 1) return fail(BMO_ERR_INVALID, "a sweep scene of several configurations is traced with bmo_trace_sweep");
+    return batch_upload(scene, in, device, out, true);
+}
 
 int bmo_batch_free(bmo_device_batch* b) {
     if (b) (void)hipSetDevice(b->device);
@@ -3328,6 +3593,8 @@ int bmo_batch_free(bmo_device_batch* b) {
 
 static int trace_or_retrace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* opts, bmo_trace_result* prev, bmo_trace_result** out) {
     if (!scene || !batch || !opts || !out) return fail(BMO_ERR_INVALID, "null argument");
+    if (scene->n_configs > 1) return fail(BMO_ERR_INVALID, "a sweep scene of several configurations is traced with bmo_trace_sweep");
+    if (prev && prev->n_configs > 0) return fail(BMO_ERR_UNSUPPORTED, "a sweep result cannot be retraced (sweeps are fresh solves of every configuration)");
     if (prev && prev->n_objects != scene->hdr.n_objects)
         return fail(BMO_ERR_INVALID, "retrace: the scene does not have the object numbering the previous solution was solved with");
     auto R = std::make_unique<bmo_trace_result>();
@@ -3353,6 +3620,7 @@ int bmo_retrace_device(bmo_scene* scene, bmo_device_batch* batch, bmo_trace_resu
 
 int bmo_retrace(bmo_scene* scene, const bmo_ray_batch* in, bmo_trace_result* prev, const bmo_trace_opts* opts, bmo_trace_result** out) {
     if (!scene || !in || !opts || !out || !prev) return fail(BMO_ERR_INVALID, "null argument");
+    if (prev->n_configs > 0) return fail(BMO_ERR_UNSUPPORTED, "a sweep result cannot be retraced (sweeps are fresh solves of every configuration)");
     bmo_device_batch* b = nullptr;
     int rc = bmo_batch_upload(scene, in, prev->device, &b);  // the stored solution pins the device
     if (rc) return rc;
@@ -3369,6 +3637,35 @@ int bmo_trace(bmo_scene* scene, const bmo_ray_batch* in, const bmo_trace_opts* o
     rc = bmo_trace_device(scene, b, opts, out);
     bmo_batch_free(b);
     return rc;
+}
+
+int bmo_trace_sweep(bmo_scene* sweep, const bmo_ray_batch* in, const int32_t* root_config, const bmo_trace_opts* opts, bmo_trace_result** out) {
+    if (!sweep || !in || !opts || !out) return fail(BMO_ERR_INVALID, "null argument");
+    if (sweep->n_configs < 1) return fail(BMO_ERR_INVALID, "bmo_trace_sweep: the scene was not made by bmo_scene_create_sweep");
+    if (in->n < 0 || (in->n > 0 && !root_config)) return fail(BMO_ERR_INVALID, "bmo_trace_sweep: root_config missing");
+    for (int64_t i = 0; i < in->n; ++i) {
+        if (root_config[i] < 0 || root_config[i] >= sweep->n_configs)
+            return fail(BMO_ERR_INVALID, "bmo_trace_sweep: root_config[" + std::to_string(i) + "] = " + std::to_string(root_config[i]) + " is not in [0, " +
+                                             std::to_string(sweep->n_configs) + ")");
+        if (i > 0 && root_config[i] < root_config[i - 1])
+            return fail(BMO_ERR_INVALID, "bmo_trace_sweep: root_config decreases at root " + std::to_string(i) + " (the roots of a configuration are consecutive)");
+    }
+    bmo_device_batch* b = nullptr;
+    int rc = batch_upload(sweep, in, opts->device, &b, false);
+    if (rc) return rc;
+    std::unique_ptr<bmo_device_batch, int (*)(bmo_device_batch*)> hold_b(b, bmo_batch_free);
+    auto R = std::make_unique<bmo_trace_result>();
+    R->n_objects = sweep->hdr.n_objects;
+    R->n_configs = sweep->n_configs;
+    R->root_cfg.assign(root_config, root_config + in->n);
+    if ((rc = R->d_root_cfg.alloc((size_t)std::max<int64_t>(in->n, 1) * 4))) return rc;
+    if (in->n) HIP_TRY(hipMemcpy(R->d_root_cfg.p, root_config, (size_t)in->n * 4, hipMemcpyHostToDevice));
+    if (b->kind == BMO_BEAM_RAY) rc = run_trace<BMO_BEAM_RAY>(sweep, b, opts, R.get());
+    else if (b->kind == BMO_BEAM_POLARIZED) rc = run_trace<BMO_BEAM_POLARIZED>(sweep, b, opts, R.get());
+    else rc = run_trace<BMO_BEAM_GAUSSIAN>(sweep, b, opts, R.get());
+    if (rc) return rc;
+    *out = R.release();
+    return BMO_OK;
 }
 
 int bmo_result_device_hits(bmo_trace_result* r, int32_t det, const double** data, int64_t* count) {

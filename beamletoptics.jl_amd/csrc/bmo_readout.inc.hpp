@@ -256,19 +256,10 @@ struct PdGeom {
     double oy[3];  // T[k,3] = orientation[3,k]
 };
 
-__global__ __launch_bounds__(256) void pd_field_kernel(int64_t n_hits, int64_t hits_per_split, const int32_t* __restrict__ seg_start,
-                                                       const int32_t* __restrict__ hit_nseg, int64_t total_segs, const double* __restrict__ segs,
-                                                       const double* __restrict__ cum, const double* __restrict__ hs, PdGeom G,
-                                                       const double* __restrict__ xs, const double* __restrict__ ys, int32_t nx, int32_t ny,
-                                                       double2* __restrict__ partial) {
-    const int64_t n_pts = (int64_t)nx * ny;
-    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (pt >= n_pts) return;
-    const int i = (int)(pt % nx), j = (int)(pt / nx);
-    const double x = xs[i], y = ys[j];
-    const d3 p1{G.ox[0] * x + G.oy[0] * y + G.p[0], G.ox[1] * x + G.oy[1] * y + G.p[1], G.ox[2] * x + G.oy[2] * y + G.p[2]};
-    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
-    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
+// The field of beamlets h0 .. h1 - 1 at detector point p1, summed in beamlet order (the blocked order of bmo_photodetector_field: one range
+// per workgroup row, the ranges summed by pd_reduce_kernel)
+__device__ __forceinline__ double2 pd_field_range(const d3& p1, int64_t h0, int64_t h1, const int32_t* __restrict__ seg_start, const int32_t* __restrict__ hit_nseg,
+                                                  int64_t total_segs, const double* __restrict__ segs, const double* __restrict__ cum, const double* __restrict__ hs) {
     double fre = 0.0, fim = 0.0;
     for (int64_t h = h0; h < h1; ++h) {  // wave-uniform: every lane walks the same beamlets (broadcast loads)
         const double* s = hs + h * PD_HS;
@@ -306,7 +297,69 @@ __global__ __launch_bounds__(256) void pd_field_kernel(int64_t n_hits, int64_t h
         fre += E.re * sp;
         fim += E.im * sp;
     }
-    partial[(int64_t)blockIdx.y * n_pts + pt] = make_double2(fre, fim);
+    return make_double2(fre, fim);
+}
+
+__global__ __launch_bounds__(256) void pd_field_kernel(int64_t n_hits, int64_t hits_per_split, const int32_t* __restrict__ seg_start,
+                                                       const int32_t* __restrict__ hit_nseg, int64_t total_segs, const double* __restrict__ segs,
+                                                       const double* __restrict__ cum, const double* __restrict__ hs, PdGeom G,
+                                                       const double* __restrict__ xs, const double* __restrict__ ys, int32_t nx, int32_t ny,
+                                                       double2* __restrict__ partial) {
+    const int64_t n_pts = (int64_t)nx * ny;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pt >= n_pts) return;
+    const int i = (int)(pt % nx), j = (int)(pt / nx);
+    const double x = xs[i], y = ys[j];
+    const d3 p1{G.ox[0] * x + G.oy[0] * y + G.p[0], G.ox[1] * x + G.oy[1] * y + G.p[1], G.ox[2] * x + G.oy[2] * y + G.p[2]};
+    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
+    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
+    partial[(int64_t)blockIdx.y * n_pts + pt] = pd_field_range(p1, h0, h1, seg_start, hit_nseg, total_segs, segs, cum, hs);
+}
+
+// Sweeps (bmo_photodetector_field_sweep): configuration c = cfg0 + blockIdx.z sums its own beamlets hit_begin .. hit_begin + n_hits - 1 at the
+// points of its own detector pose, split into ranges exactly as bmo_photodetector_field splits a solve that holds only those beamlets.
+struct PdSweepCfg {
+    int64_t hit_begin, n_hits, hits_per_split;
+    int32_t n_splits, pad;
+    PdGeom G;
+};
+__global__ __launch_bounds__(256) void pd_field_sweep_kernel(const PdSweepCfg* __restrict__ cfg, int32_t cfg0, int32_t max_splits, const int32_t* __restrict__ seg_start,
+                                                             const int32_t* __restrict__ hit_nseg, int64_t total_segs, const double* __restrict__ segs,
+                                                             const double* __restrict__ cum, const double* __restrict__ hs, const double* __restrict__ xs,
+                                                             const double* __restrict__ ys, int32_t nx, int32_t ny, double2* __restrict__ partial) {
+    const int64_t n_pts = (int64_t)nx * ny;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const PdSweepCfg& C = cfg[cfg0 + (int32_t)blockIdx.z];
+    if (pt >= n_pts || (int32_t)blockIdx.y >= C.n_splits) return;
+    const int i = (int)(pt % nx), j = (int)(pt / nx);
+    const double x = xs[i], y = ys[j];
+    const PdGeom& G = C.G;
+    const d3 p1{G.ox[0] * x + G.oy[0] * y + G.p[0], G.ox[1] * x + G.oy[1] * y + G.p[1], G.ox[2] * x + G.oy[2] * y + G.p[2]};
+    const int64_t h0 = (int64_t)blockIdx.y * C.hits_per_split;
+    const int64_t h1 = h0 + C.hits_per_split < C.n_hits ? h0 + C.hits_per_split : C.n_hits;
+    partial[((int64_t)blockIdx.z * max_splits + blockIdx.y) * n_pts + pt] =
+        pd_field_range(p1, C.hit_begin + h0, C.hit_begin + h1, seg_start, hit_nseg, total_segs, segs, cum, hs);
+}
+__global__ void pd_reduce_sweep_kernel(const PdSweepCfg* __restrict__ cfg, int32_t cfg0, int32_t max_splits, const double2* __restrict__ partial, int64_t n_pts,
+                                       double2* __restrict__ field) {
+    const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= n_pts) return;
+    const int32_t z = (int32_t)blockIdx.y, ns = cfg[cfg0 + z].n_splits;
+    double re = 0.0, im = 0.0;
+    for (int s = 0; s < ns; ++s) {
+        const double2 v = partial[((int64_t)z * max_splits + s) * n_pts + pt];
+        re += v.x;
+        im += v.y;
+    }
+    double2* f = field + (int64_t)(cfg0 + z) * n_pts + pt;
+    *f = make_double2(f->x + re, f->y + im);
+}
+// configuration of every recorded beamlet (node -> root -> root_cfg)
+__global__ void pd_hit_cfg_kernel(const int32_t* __restrict__ hit_node, int64_t n_hits, const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg,
+                                  int32_t* __restrict__ out) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n_hits) return;
+    out[h] = root_cfg[root[hit_node[h]]];
 }
 
 __global__ void pd_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pts, double2* __restrict__ field) {
@@ -421,6 +474,60 @@ extern "C" int bmo_gauss_parameters(bmo_trace_result* res, int64_t node, const d
     return BMO_OK;
 }
 
+// Steps 1 - 4 of the Photodetector pipeline for the H beamlets recorded on `detector`: the compact segment table and the per-beamlet scalars.
+struct PdTables {
+    DevBuf hit_node, hit_nseg, node_hit, seg_start, hs, tmp, segs, cum;
+    int64_t total_segs = 0;
+};
+static int pd_tables(bmo_trace_result* res, int32_t detector, int64_t H, hipStream_t st, PdTables& T) {
+    const int64_t nn = res->n_nodes;
+    int rc;
+    if ((rc = T.hit_node.alloc((size_t)H * 4)) || (rc = T.hit_nseg.alloc((size_t)H * 4)) || (rc = T.node_hit.alloc((size_t)nn * 4)) ||
+        (rc = T.seg_start.alloc((size_t)H * 4)) || (rc = T.hs.alloc((size_t)H * PD_HS * 8)))
+        return rc;
+    HIP_TRY(hipMemsetAsync(T.node_hit.p, 0xFF, (size_t)nn * 4, st));
+    HIP_TRY(hipMemsetAsync(T.hs.p, 0, (size_t)H * PD_HS * 8, st));
+    const unsigned hb = (unsigned)((H + 255) / 256);
+    hipLaunchKernelGGL(pd_hit_nodes_kernel, dim3(hb), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
+                       (const int32_t*)res->order.p, (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p, (const double*)res->n_lambda.p,
+                       (const double*)res->det_data.p, (int32_t*)T.hit_node.p, (int32_t*)T.hit_nseg.p, (int32_t*)T.node_hit.p, (double*)T.hs.p, prefix_of(res));
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
+    if ((rc = T.tmp.alloc(tmp_bytes))) return rc;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(T.tmp.p, tmp_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
+    int32_t last_start = 0, last_n = 0;
+    HIP_TRY(hipMemcpyAsync(&last_start, (const int32_t*)T.seg_start.p + H - 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_n, (const int32_t*)T.hit_nseg.p + H - 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    T.total_segs = (int64_t)last_start + last_n;
+    if ((rc = T.segs.alloc((size_t)T.total_segs * PD_SEG_PLANES * 8)) || (rc = T.cum.alloc((size_t)T.total_segs * 8))) return rc;
+    for (const Chunk& c : res->chunks)
+        if (c.count > 0)
+            hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, st, c, (const int32_t*)T.node_hit.p,
+                               (const int32_t*)T.seg_start.p, T.total_segs, (double*)T.segs.p, (double*)T.hs.p, prefix_of(res));
+    hipLaunchKernelGGL(pd_prepare_kernel, dim3(hb), dim3(256), 0, st, H, (const int32_t*)T.seg_start.p, (const int32_t*)T.hit_nseg.p, T.total_segs,
+                       (const double*)T.segs.p, (double*)T.cum.p, (double*)T.hs.p);
+    return BMO_OK;
+}
+// workgroup rows of the field sum of H beamlets on a grid of pt_blocks x 256 points: enough ranges to fill the chip when the grid is small
+static void pd_splits(int64_t H, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
+    n_splits = (2048 + pt_blocks - 1) / pt_blocks;
+    if (n_splits > H) n_splits = H;
+    if (n_splits > 65535) n_splits = 65535;
+    if (n_splits < 1) n_splits = 1;
+    hits_per_split = (H + n_splits - 1) / n_splits;
+    n_splits = (H + hits_per_split - 1) / hits_per_split;
+}
+static PdGeom pd_geom(const double position[3], const double orientation[9]) {
+    PdGeom G;
+    for (int k = 0; k < 3; ++k) {
+        G.p[k] = position[k];
+        G.ox[k] = orientation[0 * 3 + k];  // T[k,1] with T = transpose(orientation)
+        G.oy[k] = orientation[2 * 3 + k];  // T[k,3]
+    }
+    return G;
+}
+
 extern "C" int bmo_photodetector_field(bmo_trace_result* res, int32_t detector, const double position[3], const double orientation[9], const double* xs,
                                        const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms) {
     if (!res || !position || !orientation || !xs || !ys || !field_inout || nx <= 0 || ny <= 0) return fail(BMO_ERR_INVALID, "bmo_photodetector_field: bad argument");
@@ -433,60 +540,28 @@ extern "C" int bmo_photodetector_field(bmo_trace_result* res, int32_t detector, 
     if (H == 0) return BMO_OK;
     if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_photodetector_field: the solution was solved with record_segments = 0 (gauss_parameters needs the beamlets' segments)");
     HIP_TRY(hipSetDevice(res->device));
-    const int64_t nn = res->n_nodes, n_pts = (int64_t)nx * ny;
+    const int64_t n_pts = (int64_t)nx * ny;
     int rc;
-    DevBuf hit_node, hit_nseg, node_hit, seg_start, hs, tmp, segs, cum, d_xs, d_ys, partial, d_field;
-    if ((rc = hit_node.alloc((size_t)H * 4)) || (rc = hit_nseg.alloc((size_t)H * 4)) || (rc = node_hit.alloc((size_t)nn * 4)) ||
-        (rc = seg_start.alloc((size_t)H * 4)) || (rc = hs.alloc((size_t)H * PD_HS * 8)))
-        return rc;
+    PdTables T;
+    DevBuf d_xs, d_ys, partial, d_field;
     hipStream_t st = 0;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(hipMemsetAsync(node_hit.p, 0xFF, (size_t)nn * 4, st));
-    HIP_TRY(hipMemsetAsync(hs.p, 0, (size_t)H * PD_HS * 8, st));
-    const unsigned hb = (unsigned)((H + 255) / 256);
-    hipLaunchKernelGGL(pd_hit_nodes_kernel, dim3(hb), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
-                       (const int32_t*)res->order.p, (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p, (const double*)res->n_lambda.p,
-                       (const double*)res->det_data.p, (int32_t*)hit_node.p, (int32_t*)hit_nseg.p, (int32_t*)node_hit.p, (double*)hs.p, prefix_of(res));
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)hit_nseg.p, (int32_t*)seg_start.p, (int)H, st));
-    if ((rc = tmp.alloc(tmp_bytes))) return rc;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, (const int32_t*)hit_nseg.p, (int32_t*)seg_start.p, (int)H, st));
-    int32_t last_start = 0, last_n = 0;
-    HIP_TRY(hipMemcpyAsync(&last_start, (const int32_t*)seg_start.p + H - 1, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&last_n, (const int32_t*)hit_nseg.p + H - 1, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t total_segs = (int64_t)last_start + last_n;
-    // workgroups: 256 points each x beamlet ranges, enough ranges to fill the chip when the grid is small
+    if ((rc = pd_tables(res, detector, H, st, T))) return rc;
     const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    int64_t n_splits = (2048 + pt_blocks - 1) / pt_blocks;
-    if (n_splits > H) n_splits = H;
-    if (n_splits > 65535) n_splits = 65535;
-    if (n_splits < 1) n_splits = 1;
-    const int64_t hits_per_split = (H + n_splits - 1) / n_splits;
-    n_splits = (H + hits_per_split - 1) / hits_per_split;
-    if ((rc = segs.alloc((size_t)total_segs * PD_SEG_PLANES * 8)) || (rc = cum.alloc((size_t)total_segs * 8)) || (rc = d_xs.alloc((size_t)nx * 8)) ||
-        (rc = d_ys.alloc((size_t)ny * 8)) || (rc = partial.alloc((size_t)n_splits * n_pts * 16)) || (rc = d_field.alloc((size_t)n_pts * 16)))
+    int64_t n_splits, hits_per_split;
+    pd_splits(H, pt_blocks, n_splits, hits_per_split);
+    if ((rc = d_xs.alloc((size_t)nx * 8)) || (rc = d_ys.alloc((size_t)ny * 8)) || (rc = partial.alloc((size_t)n_splits * n_pts * 16)) ||
+        (rc = d_field.alloc((size_t)n_pts * 16)))
         return rc;
-    for (const Chunk& c : res->chunks)
-        if (c.count > 0)
-            hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, st, c, (const int32_t*)node_hit.p,
-                               (const int32_t*)seg_start.p, total_segs, (double*)segs.p, (double*)hs.p, prefix_of(res));
-    hipLaunchKernelGGL(pd_prepare_kernel, dim3(hb), dim3(256), 0, st, H, (const int32_t*)seg_start.p, (const int32_t*)hit_nseg.p, total_segs,
-                       (const double*)segs.p, (double*)cum.p, (double*)hs.p);
     HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)nx * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_ys.p, ys, (size_t)ny * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_field.p, field_inout, (size_t)n_pts * 16, hipMemcpyHostToDevice, st));
-    PdGeom G;
-    for (int k = 0; k < 3; ++k) {
-        G.p[k] = position[k];
-        G.ox[k] = orientation[0 * 3 + k];  // T[k,1] with T = transpose(orientation)
-        G.oy[k] = orientation[2 * 3 + k];  // T[k,3]
-    }
-    hipLaunchKernelGGL(pd_field_kernel, dim3(pt_blocks, (unsigned)n_splits), dim3(256), 0, st, H, hits_per_split, (const int32_t*)seg_start.p,
-                       (const int32_t*)hit_nseg.p, total_segs, (const double*)segs.p, (const double*)cum.p, (const double*)hs.p, G,
+    const PdGeom G = pd_geom(position, orientation);
+    hipLaunchKernelGGL(pd_field_kernel, dim3(pt_blocks, (unsigned)n_splits), dim3(256), 0, st, H, hits_per_split, (const int32_t*)T.seg_start.p,
+                       (const int32_t*)T.hit_nseg.p, T.total_segs, (const double*)T.segs.p, (const double*)T.cum.p, (const double*)T.hs.p, G,
                        (const double*)d_xs.p, (const double*)d_ys.p, nx, ny, (double2*)partial.p);
     hipLaunchKernelGGL(pd_reduce_kernel, dim3(pt_blocks), dim3(256), 0, st, (const double2*)partial.p, (int32_t)n_splits, n_pts, (double2*)d_field.p);
     HIP_TRY(hipEventRecord(e1, st));
@@ -498,5 +573,88 @@ extern "C" int bmo_photodetector_field(bmo_trace_result* res, int32_t detector, 
     (void)hipEventDestroy(e1);
     if (kernel_ms) *kernel_ms = ms;
     HIP_TRY(hipMemcpy(field_inout, d_field.p, (size_t)n_pts * 16, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* positions, const double* orientations,
+                                             const double* xs, const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms) {
+    if (!res || !positions || !orientations || !xs || !ys || !field_inout || nx <= 0 || ny <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: bad detector slot");
+    if (res->n_configs < 1 || n_configs != res->n_configs)
+        return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: n_configs must be the configuration count of the sweep result");
+    if (kernel_ms) *kernel_ms = 0.0;
+    if (res->kind != BMO_BEAM_GAUSSIAN) return BMO_OK;  // other beams leave no record (Photodetector.jl:57-60)
+    const int64_t rows = res->det_count[detector];
+    if (rows % 3) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: slot does not hold photodetector records");
+    const int64_t H = rows / 3;
+    if (H == 0) return BMO_OK;
+    if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: the solution was solved with record_segments = 0 (gauss_parameters needs the beamlets' segments)");
+    HIP_TRY(hipSetDevice(res->device));
+    const int64_t n_pts = (int64_t)nx * ny;
+    const int32_t K = n_configs;
+    int rc;
+    PdTables T;
+    DevBuf hit_cfg, d_cfg, d_xs, d_ys, partial, d_field;
+    hipStream_t st = 0;
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, st));
+    if ((rc = pd_tables(res, detector, H, st, T))) return rc;
+    // the beamlets of a configuration are consecutive (hits are in root order, roots in configuration order): their range per configuration
+    if ((rc = hit_cfg.alloc((size_t)H * 4))) return rc;
+    hipLaunchKernelGGL(pd_hit_cfg_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (const int32_t*)T.hit_node.p, H, (const int32_t*)res->n_root.p,
+                       (const int32_t*)res->d_root_cfg.p, (int32_t*)hit_cfg.p);
+    std::vector<int32_t> hc((size_t)H);
+    HIP_TRY(hipMemcpyAsync(hc.data(), hit_cfg.p, (size_t)H * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
+    std::vector<PdSweepCfg> cfg((size_t)K);
+    for (int32_t c = 0; c < K; ++c) {
+        cfg[(size_t)c] = PdSweepCfg{};
+        cfg[(size_t)c].G = pd_geom(positions + 3 * (size_t)c, orientations + 9 * (size_t)c);
+    }
+    for (int64_t h = 0; h < H; ++h) {
+        const int32_t c = hc[(size_t)h];
+        if (c < 0 || c >= K || (h > 0 && c < hc[(size_t)h - 1])) return fail(BMO_ERR_INTERNAL, "bmo_photodetector_field_sweep: beamlets out of configuration order");
+        if (cfg[(size_t)c].n_hits++ == 0) cfg[(size_t)c].hit_begin = h;
+    }
+    int64_t max_splits = 1;
+    for (auto& C : cfg) {
+        if (C.n_hits == 0) continue;
+        int64_t ns, hps;
+        pd_splits(C.n_hits, pt_blocks, ns, hps);
+        C.n_splits = (int32_t)ns;
+        C.hits_per_split = hps;
+        max_splits = std::max(max_splits, ns);
+    }
+    // configurations per launch: grid z (at most 65535) and the partial sums held at once (at most 1 GiB of them)
+    const size_t per_cfg = (size_t)max_splits * (size_t)n_pts * 16;
+    const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)K, 65535, (int64_t)(((size_t)1 << 30) / per_cfg)}));
+    if ((rc = d_cfg.alloc(sizeof(PdSweepCfg) * (size_t)K)) || (rc = d_xs.alloc((size_t)nx * 8)) || (rc = d_ys.alloc((size_t)ny * 8)) ||
+        (rc = partial.alloc(per_cfg * (size_t)batch)) || (rc = d_field.alloc((size_t)K * n_pts * 16)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_cfg.p, cfg.data(), sizeof(PdSweepCfg) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)nx * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_ys.p, ys, (size_t)ny * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_field.p, field_inout, (size_t)K * n_pts * 16, hipMemcpyHostToDevice, st));
+    for (int32_t c0 = 0; c0 < K; c0 += batch) {
+        const int32_t nz = std::min(batch, K - c0);
+        hipLaunchKernelGGL(pd_field_sweep_kernel, dim3(pt_blocks, (unsigned)max_splits, (unsigned)nz), dim3(256), 0, st, (const PdSweepCfg*)d_cfg.p, c0,
+                           (int32_t)max_splits, (const int32_t*)T.seg_start.p, (const int32_t*)T.hit_nseg.p, T.total_segs, (const double*)T.segs.p,
+                           (const double*)T.cum.p, (const double*)T.hs.p, (const double*)d_xs.p, (const double*)d_ys.p, nx, ny, (double2*)partial.p);
+        hipLaunchKernelGGL(pd_reduce_sweep_kernel, dim3(pt_blocks, (unsigned)nz), dim3(256), 0, st, (const PdSweepCfg*)d_cfg.p, c0, (int32_t)max_splits,
+                           (const double2*)partial.p, n_pts, (double2*)d_field.p);
+    }
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipGetLastError());
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (kernel_ms) *kernel_ms = ms;
+    HIP_TRY(hipMemcpy(field_inout, d_field.p, (size_t)K * n_pts * 16, hipMemcpyDeviceToHost));
     return BMO_OK;
 }

@@ -13,6 +13,7 @@ from . import abi
 from . import beams as bm
 from . import components as cp
 from . import shapes as sh
+from . import linalg as la
 
 # miss-cull inflation of bounding spheres (see DESIGN.md "miss cull")
 _BS_REL, _BS_ABS = 1e-6, 1e-6
@@ -680,3 +681,198 @@ def solve_system(system, beams, r_max=100, retrace=True, device=0):
     res, sol = _engine_solve(scene, bundle, r_max, prev, device)
     _apply(scene, res, sol, roots)
     return res
+
+
+# ---------------------------------------------------------------------------------------- sweeps
+def _fresh_head(b):
+    """A fresh (un-solved) copy of the head of root beam `b`, of the kind _fill_beams fills: its own rays come from the result."""
+    if b.kind == bm.BEAM_GAUSSIAN:
+        subs = []
+        for part in (b.chief, b.waist, b.divergence):
+            sub = bm.Beam.__new__(bm.Beam)
+            sub.rays, sub.parent, sub.children, sub.status = [part.rays[0]], None, [], 0
+            subs.append(sub)
+        h = bm.GaussianBeamlet(None, None, _parts=(subs[0], subs[1], subs[2], b.lam, b.w0, b.E0))
+    else:
+        h = bm.Beam.__new__(bm.Beam)
+        h.rays = [b.rays[0]]
+    h.parent, h.children, h.status = None, [], 0
+    return h
+
+
+def _first_rec(res, i):
+    """First segment of node i of a TraceResult in the whole log's numbering (i = n_nodes: one past the last)."""
+    if i < res.n_nodes:
+        return int(res.node_first_rec[i])
+    return int(res.node_first_rec[-1]) + int(res.node_nseg[-1]) if res.n_nodes else 0
+
+
+class _ResultSlice:
+    """The nodes, records and statuses of one configuration of a sweep's TraceResult, renumbered as a solve of that configuration alone."""
+
+    def __init__(self, res, n0, n1, r0, r1, root0):
+        # (a detector-only solve, record_segments = 0, keeps the segment numbering of the beams but no records)
+        self.beam_kind, self.n_nodes, self.n_records = res.beam_kind, n1 - n0, (r1 - r0) if res.n_records else 0
+        self.node_root = res.node_root[n0:n1] - root0
+        par = res.node_parent[n0:n1]
+        self.node_parent = np.where(par >= 0, par - n0, -1).astype(np.int32)
+        fc = res.node_first_child[n0:n1]
+        self.node_first_child = np.where(fc >= 0, fc - n0, -1).astype(np.int32)
+        self.node_first_rec = res.node_first_rec[n0:n1] - r0
+        self.node_nseg = res.node_nseg[n0:n1]
+        self.node_status = res.node_status[n0:n1]
+        self.node_aux = res.node_aux[n0:n1]
+        self.rec = res.rec[:, r0:r1]
+        self.rec_obj = res.rec_obj[r0:r1]
+        self.rec_shape = res.rec_shape[r0:r1]
+
+
+class SweepSolution:
+    """The solution of n configurations of one system (bmo.solve_sweep): configuration c is a fresh solve_system of snapshot c."""
+
+    def __init__(self, lib, handle, res, scenes, heads, poses, grids):
+        self.lib, self._handle, self.res = lib, handle, res
+        self.scenes, self._heads, self._poses, self._grids = scenes, heads, poses, grids
+        self.n = len(scenes)
+        self.n_roots = len(heads)  # roots per configuration
+        nr = self.n_roots
+        # node range of every configuration: nodes are in root order, the roots of configuration c are c * nr .. (c + 1) * nr - 1
+        self._node_start = np.searchsorted(res.node_root, np.arange(self.n + 1) * nr).astype(np.int64)
+        ns = self._node_start
+        self._rec_start = np.array([_first_rec(res, i) for i in ns], dtype=np.int64)
+
+    def close(self):
+        if self._handle:
+            self.lib.bmo_result_free(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _slot(self, det):
+        for slot, d in enumerate(self.scenes[0].detectors):
+            if d is det:
+                return slot
+        raise KeyError("detector is not part of the swept system")
+
+    def result(self, c):
+        """The nodes, records and statuses of configuration c (the layout of abi.TraceResult, numbered from 0)."""
+        n0, n1 = int(self._node_start[c]), int(self._node_start[c + 1])
+        return _ResultSlice(self.res, n0, n1, int(self._rec_start[c]), int(self._rec_start[c + 1]), c * self.n_roots)
+
+    def beams(self, c):
+        """Beam / GaussianBeamlet trees of configuration c, as solve_system would leave fresh copies of the root beams."""
+        roots = [_fresh_head(b) for b in self._heads]
+        sl = self.result(c)
+        _fill_beams(self.scenes[c], sl, roots)
+        return roots
+
+    def _hit_rows(self, slot, c):
+        nodes = self.res.detector_nodes(slot)
+        cfg = self.res.node_root[nodes] // max(1, self.n_roots)
+        return self.res.detector_hits(slot)[cfg == c]
+
+    def spot_hits(self, det, c):
+        """Rows a Spotdetector records in configuration c (x, y per hit, Spotdetector.jl:59), in the reference's order."""
+        return self._hit_rows(self._slot(det), c)[:, 0:2]
+
+    def detector_hits(self, det, c):
+        """All nine columns of the hit rows of detector `det` in configuration c (include/bmo.h det_data)."""
+        return self._hit_rows(self._slot(det), c)
+
+    def photodetector_field(self, pd):
+        """Complex field [n, nx, ny] of Photodetector `pd` in every configuration (one batched read-out, bmo_photodetector_field_sweep)."""
+        slot = self._slot(pd)
+        xs, ys = self._grids[slot]
+        nx, ny, K = len(xs), len(ys), self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([np.asarray(self._poses[c][slot][1]).reshape(9) for c in range(K)], dtype=np.float64)
+        buf = np.zeros(2 * K * nx * ny)
+        dp = C.POINTER(C.c_double)
+        ms = C.c_double()
+        x, y = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(ys, dtype=np.float64)
+        abi.check(self.lib, self.lib.bmo_photodetector_field_sweep(self._handle, int(slot), int(K), pos.ctypes.data_as(dp), ori.ctypes.data_as(dp),
+                                                                   x.ctypes.data_as(dp), y.ctypes.data_as(dp), nx, ny, buf.ctypes.data_as(dp), C.byref(ms)),
+                  "bmo_photodetector_field_sweep")
+        self.readout_ms = ms.value
+        f = (buf[0::2] + 1j * buf[1::2]).reshape(K, ny, nx)  # (i, j) at [i + nx*j]
+        return np.ascontiguousarray(f.transpose(0, 2, 1))
+
+    def optical_power(self, pd, field=None):
+        """optical_power(pd) of every configuration, [n]: the trapezoid rule of Photodetector.optical_power on each configuration's field."""
+        slot = self._slot(pd)
+        xs, ys = self._grids[slot]
+        f = self.photodetector_field(pd) if field is None else field
+        I = (f.real ** 2 + f.imag ** 2) / (2 * la.Z_vacuum)
+        inner = np.sum((I[:, 1:, :] + I[:, :-1, :]) * np.diff(xs)[None, :, None], axis=1) / 2
+        return np.sum((inner[:, 1:] + inner[:, :-1]) * np.diff(ys)[None, :], axis=1) / 2
+
+
+def sweep_snapshots(system, lambdas, n, configure):
+    """configure(c), then a CompiledScene snapshot of `system`, for c = 0 .. n - 1 in order: (scenes, detector poses per scene, detector
+    grids).  A snapshot holds copies of the numbers, so later configure calls do not change it.  A Photodetector's grid must not change."""
+    scenes, poses, grids = [], [], None
+    for c in range(n):
+        configure(c)
+        sc = CompiledScene(system, lambdas)
+        scenes.append(sc)
+        poses.append([(np.array(d.position(), dtype=np.float64), np.array(d.orientation(), dtype=np.float64)) for d in sc.detectors])
+        g = [(np.array(getattr(d, "x", ())), np.array(getattr(d, "y", ()))) for d in sc.detectors]
+        if grids is None:
+            grids = g
+        else:
+            for d, (x0, y0), (x1, y1) in zip(sc.detectors, grids, g):
+                if d.kind == cp.O_PHOTODETECTOR and not (np.array_equal(x0, x1) and np.array_equal(y0, y1)):
+                    raise ValueError(f"solve_sweep: the resolution of a Photodetector changed in configuration {c}")
+    return scenes, poses, grids
+
+
+def sweep_trace(scenes, bundle, root_config, r_max=100, device=0, record_segments=True, view=True):
+    """bmo_scene_create_sweep over the snapshots `scenes` + bmo_trace_sweep of `bundle`, root i in configuration root_config[i]
+    (non-decreasing).  Returns (abi.TraceResult or None without `view`, result handle, library); the caller frees the handle."""
+    lib = abi.load_engine()
+    n = len(scenes)
+    descs = (abi.SceneDesc * n)(*[s.desc for s in scenes])
+    handle = C.c_void_p()
+    abi.check(lib, lib.bmo_scene_create_sweep(descs, n, C.byref(handle)), "bmo_scene_create_sweep")
+    try:
+        batch, keep = make_batch(scenes[0], bundle)
+        cfg = np.ascontiguousarray(root_config, dtype=np.int32)
+        o = abi.TraceOpts()
+        o.r_max, o.device, o.record_segments, o.max_beams = int(r_max), int(device), int(bool(record_segments)), 0
+        h = C.c_void_p()
+        abi.check(lib, lib.bmo_trace_sweep(handle, C.byref(batch), cfg.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(o), C.byref(h)), "bmo_trace_sweep")
+    finally:
+        lib.bmo_scene_destroy(handle)
+    if not view:
+        return None, h, lib
+    try:
+        v = abi.ResultView()
+        abi.check(lib, lib.bmo_result_view(h, C.byref(v)), "bmo_result_view")
+        return abi.TraceResult(v), h, lib
+    except Exception:
+        lib.bmo_result_free(h)
+        raise
+
+
+def solve_sweep(system, beams, n, configure, r_max=100, device=0, record_segments=True):
+    """Solve n configurations of `system` in one trace.  configure(c) is called for c = 0 .. n - 1 in order and sets the system up for
+    configuration c (moves, parameter changes; the topology must stay: include/bmo.h "Sweeps"); a snapshot is compiled after each call.
+    Every configuration traces fresh copies of the root beams (their heads are read; `beams` is not mutated) and equals, bit for bit, a
+    fresh solve_system of its snapshot.  Detectors are not filled: read them from the returned SweepSolution.  The system is left as
+    configure(n - 1) made it."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("solve_sweep: n must be at least 1")
+    heads = _roots_of(beams)
+    if not heads:
+        raise ValueError("solve_sweep: no beams")
+    bundle = bm.RayBundle.from_beams(heads)
+    scenes, poses, grids = sweep_snapshots(system, bundle.lambdas, n, configure)
+    nr = bundle.n
+    res, h, lib = sweep_trace(scenes, bm.RayBundle(bundle.kind, np.tile(bundle.planes, (1, n))), np.repeat(np.arange(n, dtype=np.int32), nr),
+                              r_max, device, record_segments)
+    return SweepSolution(lib, h, res, scenes, heads, poses, grids)

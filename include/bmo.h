@@ -451,6 +451,38 @@ int bmo_gauss_parameters(bmo_trace_result* res, int64_t node, const double* zs, 
  * The tables are copied to the device and replace an earlier prefix of `res`.  n_roots must be the root count of `res`.        */
 int bmo_result_set_gauss_prefix(bmo_trace_result* res, int64_t n_roots, const int32_t* prefix_start, const double* prefix_segs, const double* opl_parent);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sweeps (DESIGN.md §3 "Sweeps"): many configurations of one system, solved in one call.  The reference's scans — move an element,
+ * solve_system!, read a detector, repeat (docs/src/tutorials/michelson.md "Running successive simulations", test/runtests.jl:2092-2121) —
+ * become one trace whose root beams each belong to one configuration.
+ *
+ * A configuration is a snapshot of the same system after the caller's kinematics or parameter changes.  All configurations share the
+ * topology: counts, object and shape kinds, part shape ids, media ids, detector slots, child structure, triangle ranges, shape flags,
+ * wavelengths and tracing constants.  The numbers may differ: poses, bounding spheres, shape parameters, vertices, object constants and
+ * n_table values.
+ *
+ * bmo_scene_create_sweep validates that (BMO_ERR_INVALID naming the first field that differs from configuration 0; no GPU needed) and lays
+ * the configurations out at the same offsets, one `stride` apart (the mesh BVH tables sized to the largest configuration's).  Every
+ * configuration is a full copy of the scene tables.  bmo_scene_destroy frees the handle.  bmo_trace / bmo_batch_upload / bmo_trace_device /
+ * bmo_retrace* refuse a sweep scene of more than one configuration (BMO_ERR_INVALID); bmo_scene_mesh_bvh and bmo_mesh_nearest_host describe
+ * configuration 0.
+ *
+ * bmo_trace_sweep: root i belongs to configuration root_config[i], non-decreasing, in [0, n_configs) (BMO_ERR_INVALID otherwise, checked
+ * before a device is looked for).  The result is an ordinary bmo_trace_result: nodes in reference order, so every configuration's beams and
+ * detector hits are contiguous ranges.  Semantics: the slice of configuration c equals, bit for bit, a fresh bmo_trace of configuration c
+ * on its roots — a FRESH solve of every configuration, not the reference's chain of retraces where step i re-walks step i - 1's solution
+ * (the two agree where the scan keeps every beam on its path).  A sweep result cannot be retraced (BMO_ERR_UNSUPPORTED).
+ * n_intersect_calls is the sum over all configurations.
+ *
+ * bmo_photodetector_field_sweep: the Photodetector field of every configuration in one set of launches.  positions [n_configs][3],
+ * orientations [n_configs][9] (each as in bmo_photodetector_field), one grid xs / ys for all; field_inout [n_configs][nx*ny] (re, im) pairs,
+ * contributions ADDED.  Configuration c sums only its own beamlets, in the blocked order bmo_photodetector_field uses for a solve that holds
+ * only them: its field equals that call's bit for bit.  n_configs must be the sweep's.                                                    */
+int bmo_scene_create_sweep(const bmo_scene_desc* descs, int32_t n_configs, bmo_scene** out);
+int bmo_trace_sweep(bmo_scene* sweep, const bmo_ray_batch* in, const int32_t* root_config, const bmo_trace_opts* opts, bmo_trace_result** out);
+int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* positions, const double* orientations,
+                                  const double* xs, const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
