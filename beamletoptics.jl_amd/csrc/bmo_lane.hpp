@@ -42,11 +42,17 @@
 #if !defined(BMO_DUAL_PASSES)
 #define BMO_DUAL_PASSES 1  /* evaluations per dual-number gradient: 1 (duals of three partials), 2 (two + one), 3 (one each) — see normal_of */
 #endif
+#if !defined(BMO_MARCH_FASTPATH)
+#define BMO_MARCH_FASTPATH 1  /* union fast path of tracing_step's outside march: 0 off, 1 fresh EXT = 0 kernels, 2 every kernel (tests) */
+#endif
 
 namespace bmo {
 
 #if defined(BMO_EMU_STATS)  // host-only instrumentation of the test emulator (tools/emu_stats.py)
 inline long g_emu_sdf_any = 0, g_emu_sdf_leaf = 0, g_emu_normal = 0, g_emu_normal_fd = 0;
+// union evaluations, those decided by the one `others_lb` compare, and those of them taken in tracing_step's specialised loop
+// (tools/fastpath_stats.py)
+inline long g_emu_union = 0, g_emu_union_fast = 0, g_emu_union_loop = 0;
 #endif
 
 // Scalar scene access (device builds).  The scene tables (objects, shapes, children, triangles, n(lambda), candidate table) are
@@ -541,7 +547,14 @@ BMO_DN DualN<N> asph_leaf(CShape&, CDouble*, const DualN<N>& r, const DualN<N>&)
 // EXT ("extended shapes" level of the kernel): 0 = the spherical / primitive leaves only; 1 = + MeniscusLensSDF; 2 = + the aspheric
 // and cylinder-lens leaves; 3 = level 2 + the mesh BVH traversal (mesh_nearest_bvh).  A scene runs the kernels of the lowest level that covers its shapes (less code, fewer registers: the
 // meniscus fold keeps a second dual number and a second frame alive around the leaf, the aspheric leaves are the largest by far).
-template <class T, int EXT>
+// CLS != 0: the caller knows the leaf class of `kind` (the union fast path of tracing_step): the dispatch folds to that one branch,
+// whose operations are the very ones the dispatched call performs (same function, same order: equal bits by construction).
+BMO_HD unsigned leaf_class(int kind) { return (unsigned)((0x0005041214032150ull >> (4 * (kind & 15))) & 15ull) * (kind < 16 ? 1u : 0u); }
+template <int C>
+struct LeafClass {
+    static constexpr int value = C;
+};
+template <class T, int EXT, int CLS = 0>
 BMO_HD T sdf_leaf(CShape& s, const int kind, const v3<T>& pt, CDouble* coefs) {
     // every table read of this leaf in one batch (the reads are LDS round trips of ~100 cycles each: issued one by one at their
     // points of use they, not the arithmetic, set the pace of the march); `kind` comes from the caller, who has read it already
@@ -550,7 +563,7 @@ BMO_HD T sdf_leaf(CShape& s, const int kind, const v3<T>& pt, CDouble* coefs) {
     // leaf class of the kinds 0 .. 15, four bits each (1 plano / cylinder / ring, 2 convex / cut sphere, 3 concave, 4 box / prism, 5 sphere /
     // point): two scalar instructions in front of a dense dispatch instead of a tree of compares over the sparse kind values
     // (round 4: config 2 - 4.3 %, config 5 - 4.7 %)
-    const unsigned cls = (unsigned)((0x0005041214032150ull >> (4 * (kind & 15))) & 15ull) * (kind < 16 ? 1u : 0u);
+    const unsigned cls = CLS != 0 ? (unsigned)CLS : leaf_class(kind);
     if (cls == 1) {  // PLANO | CYLINDER | RING
         // SphericalLensSDF.jl:60-65, PrimitiveSDF.jl:71-76, :151-166
         pin3(p);
@@ -614,13 +627,13 @@ BMO_HD T sdf_leaf(CShape& s, const int kind, const v3<T>& pt, CDouble* coefs) {
         T pln = (p.x + p.y) / 1.4142135623730951;  // sqrt(2)
         return jmax(box, pln);
     }
-    if constexpr (EXT >= 2) {
+    if constexpr (EXT >= 2 && CLS == 0) {  // (classes 1 - 5 hold no aspheric or cylinder-lens kind)
         if (kind == BMO_SHAPE_ASPH_CONVEX || kind == BMO_SHAPE_ASPH_CONCAVE) {  // AsphericalLensSDF.jl:309-349 (op_revolve_z)
             T r = norm2(p.x, p.z) - 0.0;
             return asph_leaf(s, coefs, r, p.y);
         }
     }
-    if constexpr (EXT >= 2) {
+    if constexpr (EXT >= 2 && CLS == 0) {
         if (kind == BMO_SHAPE_ACYL_CONVEX || kind == BMO_SHAPE_ACYL_CONCAVE) {  // AcylindricalSDF.jl:55-74, :122-141
             const double height = P2;
             T d2 = asph_distance<T>(kind == BMO_SHAPE_ACYL_CONVEX, p.z, p.y, 1 / P0, P3, P1, coefs + s.child_begin, s.child_count, s.p[4]);
@@ -728,13 +741,19 @@ BMO_HD ShapeHead shape_head(CShape& s) {
     h.tri_begin = s.tri_begin;
     return h;
 }
+// has_pre: the union fast path of tracing_step has already evaluated this lane's child cc.prev_best at `p` (value pre_v) and found the
+// trip not to be one it can finish: that child is not evaluated again.
 template <int EXT>
-BMO_HD double sdf_any(const SceneView& S, const ShapeHead& H, CShape& s, const d3& p, int32_t& best_child, ChildCache& cc, double moved) {
+BMO_HD double sdf_any(const SceneView& S, const ShapeHead& H, CShape& s, const d3& p, int32_t& best_child, ChildCache& cc, double moved,
+                      bool has_pre = false, double pre_v = 0.0) {
 #if defined(BMO_EMU_STATS)
     ++g_emu_sdf_any;
 #endif
     const v3<double> pt{p.x, p.y, p.z};
     const bool uni = H.kind == BMO_SHAPE_UNION;
+#if defined(BMO_EMU_STATS)
+    g_emu_union += uni;
+#endif
     const int nch = uni ? H.child_count : 1;
     double best = kinf();
     best_child = 0;
@@ -768,7 +787,7 @@ BMO_HD double sdf_any(const SceneView& S, const ShapeHead& H, CShape& s, const d
 #if defined(BMO_EMU_STATS)
             ++g_emu_sdf_leaf;
 #endif
-            const double v = sdf_simple<double, EXT>(S, ch, pt);
+            const double v = (has_pre && c == cc.prev_best) ? pre_v : sdf_simple<double, EXT>(S, ch, pt);
             stored = v;
             if (q == 0) {
                 best = v;
@@ -776,6 +795,9 @@ BMO_HD double sdf_any(const SceneView& S, const ShapeHead& H, CShape& s, const d
                 if (uni && first == cc.prev_best) {  // all the others out of reach?
                     const double bound = v > 0.0 ? v : 0.0;
                     if (cc.others_lb - acc > bound + 1e-12) {
+#if defined(BMO_EMU_STATS)
+                        ++g_emu_union_fast;
+#endif
                         cc.acc = acc;
                         return v;  // prev_best, others_lb and the stored values stay as they are
                     }
@@ -1326,10 +1348,79 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                         for (int round = 0; round < 2; ++round) {
                             double dist = 0.0, t0 = 0.0, t_in = 0.0;
                             int it = 1;  // iteration counter of the running march (inside, then outside)
+                            bool has_pre = false;  // the union fast path below left this trip's value of child cc.prev_best in pre_v
+                            double pre_v = 0.0;
                             child_cache_reset(cc);
                             // (a per-lane loop: lanes leave it as their marches end, the wave stays until the last one has left)
                             while ((st & (ST_ACTIVE | ST_PENDING)) == ST_ACTIVE) {
                                 const int phase = st & 3;
+                                if constexpr (BMO_MARCH_FASTPATH == 2 || (BMO_MARCH_FASTPATH == 1 && EXT == 0 && !RETR)) {
+                                    // ---- union fast path of the outside march.  The usual trip of a union march evaluates the previous
+                                    // arg-min child, finds every other child out of reach (sdf_any's one compare) and steps on.  The lanes
+                                    // whose arg-min child is the wave's first one run such trips here, in a loop of their own: the child,
+                                    // its leaf class and its table entry are wave-uniform and fixed for the loop (one instantiation of the
+                                    // leaf per class, the entry read once), none of the march's other phases is on the path.  A trip that
+                                    // is anything else — the compare fails, the march ends (hit, recede, prune, iteration limit) — is not
+                                    // committed: the lane leaves with the child's value in pre_v and the generic trip below repeats the
+                                    // trip from the same state, the step bit for bit and sdf_any without evaluating that child again.
+                                    // What a committed trip changes is what sdf_any's early return and the generic OUTSIDE branch change:
+                                    // pos, cc.acc, dist, t0, it (prev_best, others_lb, v[] and bc stay as they are).  The leaf is
+                                    // sdf_leaf itself with its class as a constant (equal bits by construction, -ffp-contract=off).
+                                    if (H.kind == BMO_SHAPE_UNION && phase == OUTSIDE) {
+                                        const int32_t fb = BMO_UNIFORM(cc.prev_best);
+                                        if (cc.prev_best == fb && fb < H.child_count) {
+                                            // (the entry through the lane's own index — the same child in every lane here: it is read by
+                                            //  vector loads into vector registers once per entry into the loop.  Through the wave-uniform
+                                            //  index the scalar loads stay inside the loop, the kernel has no scalar registers to keep 33
+                                            //  dwords in: c2s 2.84 ms against 2.80, SQ_INSTS_SMEM 4.0e7 against 3.2e7, DESIGN.md §4 "Round 5")
+                                            CShape& ch = S.shapes[(H.flags & BMO_SHAPE_FLAG_CONSECUTIVE) ? H.tri_begin + cc.prev_best
+                                                                                                         : S.children[H.child_begin + cc.prev_best]];
+                                            const int ck = ch.kind;
+                                            auto fast_march = [&](auto cls_tag) {
+                                                constexpr int CLS = decltype(cls_tag)::value;
+                                                BMO_NOUNROLL
+                                                for (;;) {
+                                                    const bool back = (st & ST_BACK) != 0;
+                                                    const d3 np = axpy3(pos, back ? -dist : dist, dir0);
+                                                    const double acc = cc.acc + (fabs(dist) * (1.0 + 1e-9) + 1e-12);
+                                                    const double v = sdf_leaf<double, EXT, CLS>(ch, ck, v3<double>{np.x, np.y, np.z}, S.coefs);
+                                                    const double bound = v > 0.0 ? v : 0.0;
+                                                    const double t1 = t0 + v;
+                                                    const int it1 = it + 1;
+                                                    bool go = (cc.others_lb - acc > bound + 1e-12) && !(v < S.eps_ray) && !(exact && !back && t1 > lim) &&
+                                                              (it1 <= S.march_iters);
+                                                    if (go && v > dist) {  // the generic branch's receding test (only when the distance grew)
+                                                        const double R = s.bs_radius;
+                                                        const d3 co{np.x - s.bs_center[0], np.y - s.bs_center[1], np.z - s.bs_center[2]};
+                                                        const double cd = dot3(co, dir0);
+                                                        go = !(R >= 0.0 && dot3(co, co) > R * R && (back ? cd < 0.0 : cd > 0.0));
+                                                    }
+                                                    if (!go) {
+                                                        has_pre = true;
+                                                        pre_v = v;
+                                                        break;
+                                                    }
+#if defined(BMO_EMU_STATS)
+                                                    ++g_emu_sdf_any, ++g_emu_sdf_leaf, ++g_emu_union, ++g_emu_union_fast, ++g_emu_union_loop;
+#endif
+                                                    pos = np;
+                                                    cc.acc = acc;
+                                                    dist = v;
+                                                    t0 = t1;
+                                                    it = it1;
+                                                }
+                                            };
+                                            switch (leaf_class(ck)) {
+                                                case 1: fast_march(LeafClass<1>{}); break;
+                                                case 2: fast_march(LeafClass<2>{}); break;
+                                                case 3: fast_march(LeafClass<3>{}); break;
+                                                case 4: fast_march(LeafClass<4>{}); break;
+                                                case 5: fast_march(LeafClass<5>{}); break;
+                                                default: break;  // meniscus, aspheric and cylinder-lens children: generic only
+                                            }
+                                        }
+                                    }
+                                }
                                 double moved = 0.0;  // how far this trip moves the evaluation point (Lipschitz memory of the union children)
                                 if (phase == INSIDE) {
                                     pos = axpy3(pos, S.eps_ins, dir0);
@@ -1339,7 +1430,8 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                     pos = axpy3(pos, (st & ST_BACK) ? -dist : dist, dir0);
                                     moved = fabs(dist);
                                 }
-                                const double d = sdf_any<EXT>(S, H, s, pos, bc, cc, moved);
+                                const double d = sdf_any<EXT>(S, H, s, pos, bc, cc, moved, has_pre, pre_v);
+                                has_pre = false;
                                 if (phase == OUTSIDE) {
                                     // (the receding test below only when the distance GREW with this step: outside the bounding ball and moving away
                                     //  from it an exact sdf grows with every step, and a march that is converging skips 16 instructions per trip;

@@ -1,0 +1,28 @@
+// Host build of the test emulator (tests/emu/emu.cpp) that also prints, after each bounce level's line of BMO_EMU_STATS, how many
+// union evaluations that level made, how many of them the one `others_lb` compare decided (sdf_any's early return), and how many
+// of those ran in tracing_step's specialised union loop.  Driven by tools/fastpath_stats.py; the emulator itself is unchanged.
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../beamletoptics.jl_amd/csrc/bmo_lane.hpp"
+
+static int fastpath_fprintf(FILE* f, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    const int r = vfprintf(f, fmt, ap);
+    va_end(ap);
+    if (strncmp(fmt, "step ", 5) == 0) {
+        static long u0 = 0, f0 = 0, l0 = 0;
+        const long u = bmo::g_emu_union - u0, q = bmo::g_emu_union_fast - f0, l = bmo::g_emu_union_loop - l0;
+        fprintf(f, "         union evals %ld  decided by one compare %ld (%.1f %%)  of them in the fast loop %ld (%.1f %%)\n", u, q,
+                100.0 * q / std::max(1L, u), l, 100.0 * l / std::max(1L, u));
+        u0 = bmo::g_emu_union, f0 = bmo::g_emu_union_fast, l0 = bmo::g_emu_union_loop;
+    }
+    return r;
+}
+#define fprintf fastpath_fprintf
+#include "../tests/emu/emu.cpp"
