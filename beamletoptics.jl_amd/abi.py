@@ -239,6 +239,7 @@ def load_engine():
     lib.bmo_scene_create_sweep.argtypes = [C.POINTER(SceneDesc), C.c_int32, C.POINTER(vp)]
     lib.bmo_trace_sweep.argtypes = [vp, C.POINTER(RayBatch), C.POINTER(C.c_int32), C.POINTER(TraceOpts), C.POINTER(vp)]
     lib.bmo_photodetector_field_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
+    lib.bmo_psf_intensity_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -275,3 +276,26 @@ def psf_intensity(hits, origin, e1, e2, xs, zs, device=0, hits_device_ptr=None, 
                                      fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_intensity")
     field = (fld[0::2] + 1j * fld[1::2]).reshape(n, n).T.copy() if want_field else None
     return out.reshape(n, n).T.copy(), field, ms.value
+
+
+def psf_intensity_sweep(res_handle, detector, n_configs, origins, e1s, e2s, xs, zs, want_field=False):
+    """bmo_psf_intensity_sweep on the result handle `res_handle`: origins / e1s / e2s [K, 3], xs / zs [K, n].  Returns (I[K, n, n] indexed
+    [c, i, j], field [K, n, n] or None, kernel_ms); configuration c equals psf_intensity on its rows at its axes and pose, bit for bit."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+
+    def arr(a, cols):
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(K, cols))
+        return a, a.ctypes.data_as(dp)
+
+    xs = np.asarray(xs, dtype=np.float64)
+    n = xs.shape[-1]
+    (o, op), (a1, e1p), (a2, e2p), (x, xp), (z, zp) = arr(origins, 3), arr(e1s, 3), arr(e2s, 3), arr(xs, n), arr(zs, n)
+    out = np.zeros(K * n * n)
+    fld = np.zeros(2 * K * n * n) if want_field else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_intensity_sweep(res_handle, int(detector), K, op, e1p, e2p, xp, zp, n, out.ctypes.data_as(dp),
+                                           fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_intensity_sweep")
+    field = np.ascontiguousarray((fld[0::2] + 1j * fld[1::2]).reshape(K, n, n).transpose(0, 2, 1)) if want_field else None
+    return np.ascontiguousarray(out.reshape(K, n, n).transpose(0, 2, 1)), field, ms.value

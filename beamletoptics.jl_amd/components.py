@@ -361,6 +361,39 @@ class Spotdetector(AbstractObject):  # Detectors/Spotdetector.jl:21-45
         self.data = np.zeros((0, 2))
 
 
+# The sampling window of a PSFDetector's read-out as a function of its rows ([H, 9], include/bmo.h det_data) and its pose, so that a sweep
+# (SweepSolution.psf_intensity) can apply it to each configuration's rows and pose.  PSFDetector's methods of the same names call these.
+def psf_local_pos(rows, position, orientation):  # PSFDetector.jl:91-101
+    loc = rows[:, 0:3] - np.asarray(position)[None, :]
+    o = np.asarray(orientation)
+    return np.stack([loc @ o[:, 0], loc @ o[:, 2]], axis=1)
+
+
+def psf_local_lims(rows, position, orientation, crop_factor=1.0, center="centroid"):  # PSFDetector.jl:116-144
+    hits = psf_local_pos(rows, position, orientation)
+    xs, zs = hits[:, 0], hits[:, 1]
+    if center == "centroid":
+        w = rows[:, 7]
+        w_sum = w.sum()
+        x0, z0 = (w * xs).sum() / w_sum, (w * zs).sum() / w_sum
+    else:
+        x0, z0 = (xs.min() + xs.max()) / 2, (zs.min() + zs.max()) / 2
+    hwx, hwy = np.abs(xs - x0).max() * crop_factor, np.abs(zs - z0).max() * crop_factor
+    return x0 - hwx, x0 + hwx, z0 - hwy, z0 + hwy
+
+
+def psf_sample_axes(rows, position, orientation, n=100, crop_factor=1.0, center="centroid", x_min=math.inf, x_max=math.inf, z_min=math.inf,
+                    z_max=math.inf, x0_shift=0.0, z0_shift=0.0):
+    """The (xs, zs) sample coordinates of intensity(psf; ...) PSFDetector.jl:205-217 for hit rows `rows` at the detector pose
+    (position, orientation)."""
+    _x_min, _x_max, _z_min, _z_max = psf_local_lims(rows, position, orientation, crop_factor=crop_factor, center=center)
+    if x_min != math.inf and x_max != math.inf:
+        _x_min, _x_max = x_min, x_max
+    if z_min != math.inf and z_max != math.inf:
+        _z_min, _z_max = z_min, z_max
+    return la.linrange(_x_min, _x_max, n) + x0_shift, la.linrange(_z_min, _z_max, n) + z0_shift
+
+
 class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
     kind = O_PSF
 
@@ -375,31 +408,16 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
 
     # ---- read-out (PSFDetector.jl:91-237); the n x n coherent sum runs on the GPU engine (bmo_psf_intensity)
     def calc_local_pos(self):  # PSFDetector.jl:91-101
-        loc = self.data[:, 0:3] - self.position()[None, :]
-        o = self.orientation()
-        return np.stack([loc @ o[:, 0], loc @ o[:, 2]], axis=1)
+        return psf_local_pos(self.data, self.position(), self.orientation())
 
     def calc_local_lims(self, crop_factor=1.0, center="centroid"):  # PSFDetector.jl:116-144
-        hits = self.calc_local_pos()
-        xs, zs = hits[:, 0], hits[:, 1]
-        if center == "centroid":
-            w = self.data[:, 7]
-            w_sum = w.sum()
-            x0, z0 = (w * xs).sum() / w_sum, (w * zs).sum() / w_sum
-        else:
-            x0, z0 = (xs.min() + xs.max()) / 2, (zs.min() + zs.max()) / 2
-        hwx, hwy = np.abs(xs - x0).max() * crop_factor, np.abs(zs - z0).max() * crop_factor
-        return x0 - hwx, x0 + hwx, z0 - hwy, z0 + hwy
+        return psf_local_lims(self.data, self.position(), self.orientation(), crop_factor=crop_factor, center=center)
 
     def sample_axes(self, n=100, crop_factor=1.0, center="centroid", x_min=math.inf, x_max=math.inf, z_min=math.inf, z_max=math.inf,
                     x0_shift=0.0, z0_shift=0.0):
         """The (xs, zs) sample coordinates of intensity(psf; ...) PSFDetector.jl:205-217."""
-        _x_min, _x_max, _z_min, _z_max = self.calc_local_lims(crop_factor=crop_factor, center=center)
-        if x_min != math.inf and x_max != math.inf:
-            _x_min, _x_max = x_min, x_max
-        if z_min != math.inf and z_max != math.inf:
-            _z_min, _z_max = z_min, z_max
-        return la.linrange(_x_min, _x_max, n) + x0_shift, la.linrange(_z_min, _z_max, n) + z0_shift
+        return psf_sample_axes(self.data, self.position(), self.orientation(), n=n, crop_factor=crop_factor, center=center, x_min=x_min,
+                               x_max=x_max, z_min=z_min, z_max=z_max, x0_shift=x0_shift, z0_shift=z0_shift)
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

@@ -2139,6 +2139,7 @@ struct bmo_trace_result {
     DevBuf tile_cost;
     int64_t tile_n = 0;
     std::vector<int64_t> det_count, det_offset;
+    std::vector<int> det_kind;  // object kind recorded into every detector slot (BMO_OBJ_*; -1: none, -2: objects of different kinds)
     // bmo_trace_sweep: configurations of the sweep and the configuration of every root beam (device); 0 / empty for other solves
     int32_t n_configs = 0;
     std::vector<int32_t> root_cfg;
@@ -2237,6 +2238,15 @@ int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* o
     R->kind = KIND;
     R->n_roots = n;
     R->n_detectors = scene->hdr.n_detectors;
+    R->det_kind.assign((size_t)R->n_detectors, -1);
+    {
+        const bmo_object* obj = reinterpret_cast<const bmo_object*>(scene->blob.data() + scene->hdr.off_objects);
+        for (int i = 0; i < scene->hdr.n_objects; ++i) {
+            const int k = obj[i].kind, d = obj[i].detector;
+            if ((k == BMO_OBJ_SPOTDETECTOR || k == BMO_OBJ_PSFDETECTOR || k == BMO_OBJ_PHOTODETECTOR) && d >= 0 && d < R->n_detectors)
+                R->det_kind[(size_t)d] = (R->det_kind[(size_t)d] == -1 || R->det_kind[(size_t)d] == k) ? k : -2;  // -2: objects of two kinds
+        }
+    }
     R->nd = L::ND;
     R->abi_planes = L::ABI;
 

@@ -13,12 +13,11 @@ namespace {
 
 constexpr int PSF_TILE = 256;
 
-__global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split, const double* __restrict__ xs,
-                                                             const double* __restrict__ zs, int32_t n, d3 origin, d3 e1, d3 e2, double2* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
-    const int64_t n_pts = (int64_t)n * n;
-    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = pt < n_pts;
+// The point-pt term of the workgroup's grid (origin + x * e1 + z * e2, left to right) summed over hits h0 .. h1 - 1 in hit order.  Every
+// lane of the workgroup calls it (it stages the hits through `tile` and syncs); a lane past the grid (`live` false) only helps to load.
+__device__ __forceinline__ double2 psf_sum_range(const double* __restrict__ hits, int64_t h0, int64_t h1, const double* __restrict__ xs,
+                                                 const double* __restrict__ zs, int32_t n, int64_t pt, bool live, const d3& origin, const d3& e1,
+                                                 const d3& e2, double* tile) {
     double px = 0, py = 0, pz = 0;
     if (live) {
         const int i = (int)(pt % n), j = (int)(pt / n);
@@ -28,8 +27,6 @@ __global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __res
         py = (origin.y + x * e1.y) + z * e2.y;
         pz = (origin.z + x * e1.z) + z * e2.z;
     }
-    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
-    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
     double re = 0.0, im = 0.0;
     for (int64_t base = h0; base < h1; base += PSF_TILE) {
         const int cnt = (int)(h1 - base < PSF_TILE ? h1 - base : PSF_TILE);
@@ -48,7 +45,19 @@ __global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __res
             }
         }
     }
-    if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = make_double2(re, im);
+    return make_double2(re, im);
+}
+
+__global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split, const double* __restrict__ xs,
+                                                             const double* __restrict__ zs, int32_t n, d3 origin, d3 e1, d3 e2, double2* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = pt < n_pts;
+    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
+    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
+    const double2 v = psf_sum_range(hits, h0, h1, xs, zs, n, pt, live, origin, e1, e2, tile);
+    if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = v;
 }
 
 __global__ void psf_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pts, double* __restrict__ intensity, double2* __restrict__ field) {
@@ -66,6 +75,20 @@ __global__ void psf_reduce_kernel(const double2* __restrict__ partial, int32_t n
 
 }  // namespace
 
+// workgroup rows of the sum of n_hits hits on a grid of pt_blocks x 256 points: enough workgroups to fill 256 CUs several times over, but
+// never splits shorter than one LDS tile
+static void psf_splits(int64_t n_hits, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
+    n_splits = (4096 + pt_blocks - 1) / pt_blocks;
+    const int64_t max_splits = (n_hits + PSF_TILE - 1) / PSF_TILE;
+    if (n_splits > max_splits) n_splits = max_splits;
+    if (n_splits < 1) n_splits = 1;
+    if (n_splits > 65535) n_splits = 65535;
+    hits_per_split = (n_hits + n_splits - 1) / n_splits;
+    hits_per_split = (hits_per_split + PSF_TILE - 1) / PSF_TILE * PSF_TILE;
+    if (hits_per_split < PSF_TILE) hits_per_split = PSF_TILE;
+    n_splits = n_hits > 0 ? (n_hits + hits_per_split - 1) / hits_per_split : 1;
+}
+
 extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
                                  const double* xs, const double* zs, int32_t n, int32_t device, double* out_intensity, double* out_field, double* kernel_ms) {
     if (!origin || !e1 || !e2 || !xs || !zs || !out_intensity || n <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
@@ -76,16 +99,8 @@ extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hit
     HIP_TRY(hipSetDevice(device));
     const int64_t n_pts = (int64_t)n * n;
     const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    // enough workgroups to fill 256 CUs several times over, but never splits shorter than one LDS tile
-    int64_t n_splits = (4096 + pt_blocks - 1) / pt_blocks;
-    const int64_t max_splits = (n_hits + PSF_TILE - 1) / PSF_TILE;
-    if (n_splits > max_splits) n_splits = max_splits;
-    if (n_splits < 1) n_splits = 1;
-    if (n_splits > 65535) n_splits = 65535;
-    int64_t hits_per_split = (n_hits + n_splits - 1) / n_splits;
-    hits_per_split = (hits_per_split + PSF_TILE - 1) / PSF_TILE * PSF_TILE;
-    if (hits_per_split < PSF_TILE) hits_per_split = PSF_TILE;
-    n_splits = n_hits > 0 ? (n_hits + hits_per_split - 1) / hits_per_split : 1;
+    int64_t n_splits, hits_per_split;
+    psf_splits(n_hits, pt_blocks, n_splits, hits_per_split);
 
     DevBuf d_hits, d_xs, d_zs, d_partial, d_int, d_field;
     const double* hits_dev = hits;
@@ -656,5 +671,172 @@ extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t dete
     (void)hipEventDestroy(e1);
     if (kernel_ms) *kernel_ms = ms;
     HIP_TRY(hipMemcpy(field_inout, d_field.p, (size_t)K * n_pts * 16, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// ====================================================================================================================
+// PSF intensity of every configuration of a sweep (bmo_psf_intensity_sweep), from the rows still resident in the result.  Configuration c
+// with H_c rows is split exactly as bmo_psf_intensity splits a call with n_hits = H_c (psf_splits) and summed by the same device code
+// (psf_sum_range, split partials reduced in split order, then abs2).  The (configuration, split) pairs form one flat work list, the second
+// grid dimension, so configurations with few or no rows launch no empty workgroups.
+namespace {
+
+struct PsfSweepCfg {
+    d3 origin, e1, e2;   // detector pose of the configuration
+    int64_t first_work;  // its first split in the work list
+    int32_t n_splits;    // 0: no rows
+    int32_t pad;
+};
+struct PsfWork {
+    int64_t h0, h1;  // rows h0 .. h1 - 1 of the slot
+    int32_t cfg, pad;
+};
+
+// configuration of every row of the slot (det_node -> node -> root -> root_cfg, as pd_hit_cfg_kernel)
+__global__ void psf_row_cfg_kernel(const int32_t* __restrict__ det_node, int64_t first_row, int64_t n_rows, const int32_t* __restrict__ order,
+                                   const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg, int32_t* __restrict__ out) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n_rows) return;
+    out[h] = root_cfg[root[order[det_node[first_row + h]]]];
+}
+
+// work item w0 + blockIdx.y: one split of one configuration, on that configuration's axes (xs, zs: [K][n]) and pose
+__global__ __launch_bounds__(256) void psf_accumulate_sweep_kernel(const double* __restrict__ hits, const PsfWork* __restrict__ work, int64_t w0,
+                                                                   const PsfSweepCfg* __restrict__ cfg, const double* __restrict__ xs,
+                                                                   const double* __restrict__ zs, int32_t n, double2* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = pt < n_pts;
+    const PsfWork W = work[w0 + blockIdx.y];
+    const PsfSweepCfg& C = cfg[W.cfg];
+    const double2 v = psf_sum_range(hits, W.h0, W.h1, xs + (int64_t)W.cfg * n, zs + (int64_t)W.cfg * n, n, pt, live, C.origin, C.e1, C.e2, tile);
+    if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = v;
+}
+
+// configuration c0 + blockIdx.y: its splits (partial rows first_work - w0 ...) summed in split order, as psf_reduce_kernel sums a call's
+__global__ void psf_reduce_sweep_kernel(const PsfSweepCfg* __restrict__ cfg, int32_t c0, int64_t w0, const double2* __restrict__ partial, int64_t n_pts,
+                                        double* __restrict__ intensity, double2* __restrict__ field) {
+    const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pt >= n_pts) return;
+    const int32_t c = c0 + (int32_t)blockIdx.y;
+    const PsfSweepCfg& C = cfg[c];
+    double re = 0.0, im = 0.0;
+    for (int s = 0; s < C.n_splits; ++s) {
+        const double2 v = partial[(C.first_work - w0 + s) * n_pts + pt];
+        re += v.x;
+        im += v.y;
+    }
+    intensity[(int64_t)c * n_pts + pt] = re * re + im * im;  // abs2
+    if (field) field[(int64_t)c * n_pts + pt] = make_double2(re, im);
+}
+
+}  // namespace
+
+extern "C" int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                                       const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
+                                       double* kernel_ms) {
+    if (!res || !origins || !e1s || !e2s || !xs || !zs || !out_intensity || n <= 0) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad detector slot");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
+        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: the slot is not a PSFDetector's");
+    if (n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int32_t K = n_configs;
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        std::fill(out_intensity, out_intensity + (size_t)K * n_pts, 0.0);
+        if (out_field) std::fill(out_field, out_field + (size_t)K * n_pts * 2, 0.0);
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    hipStream_t st = 0;
+    int rc;
+    DevBuf row_cfg, d_cfg, d_work, d_xs, d_zs, partial, d_int, d_field;
+    // rows of one configuration are consecutive (rows are in root order, roots in configuration order): their range per configuration
+    std::vector<int32_t> rcfg((size_t)H, 0);
+    if (res->n_configs > 0) {
+        if ((rc = row_cfg.alloc((size_t)H * 4))) return rc;
+        hipLaunchKernelGGL(psf_row_cfg_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
+                           (const int32_t*)res->order.p, (const int32_t*)res->n_root.p, (const int32_t*)res->d_root_cfg.p, (int32_t*)row_cfg.p);
+        HIP_TRY(hipMemcpyAsync(rcfg.data(), row_cfg.p, (size_t)H * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    std::vector<int64_t> begin((size_t)K, 0), count((size_t)K, 0);
+    for (int64_t h = 0; h < H; ++h) {
+        const int32_t c = rcfg[(size_t)h];
+        if (c < 0 || c >= K || (h > 0 && c < rcfg[(size_t)h - 1])) return fail(BMO_ERR_INTERNAL, "bmo_psf_intensity_sweep: rows out of configuration order");
+        if (count[(size_t)c]++ == 0) begin[(size_t)c] = h;
+    }
+    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
+    std::vector<PsfSweepCfg> cfg((size_t)K);
+    std::vector<PsfWork> work;
+    for (int32_t c = 0; c < K; ++c) {
+        PsfSweepCfg& C = cfg[(size_t)c];
+        C = PsfSweepCfg{};
+        const double *o = origins + 3 * (size_t)c, *a = e1s + 3 * (size_t)c, *b = e2s + 3 * (size_t)c;
+        C.origin = d3{o[0], o[1], o[2]};
+        C.e1 = d3{a[0], a[1], a[2]};
+        C.e2 = d3{b[0], b[1], b[2]};
+        C.first_work = (int64_t)work.size();
+        const int64_t nh = count[(size_t)c];
+        if (nh == 0) continue;
+        int64_t ns, hps;
+        psf_splits(nh, pt_blocks, ns, hps);
+        C.n_splits = (int32_t)ns;
+        for (int64_t s = 0; s < ns; ++s) {
+            const int64_t h0 = s * hps, h1 = h0 + hps < nh ? h0 + hps : nh;
+            work.push_back(PsfWork{begin[(size_t)c] + h0, begin[(size_t)c] + h1, c, 0});
+        }
+    }
+    // launches: consecutive configurations whose splits fit the grid's y limit and 1 GiB of partial sums (a configuration that alone needs
+    // more goes alone; its split count is at most 65535)
+    struct Batch {
+        int32_t c0, nc;
+        int64_t w0, nw;
+    };
+    const int64_t pt_bytes = n_pts * 16;
+    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)1 << 30) / pt_bytes));
+    std::vector<Batch> batches;
+    int64_t max_nw = 1;
+    for (int32_t c = 0; c < K;) {
+        Batch b{c, 0, cfg[(size_t)c].first_work, 0};
+        while (c < K && b.nc < 65535 && (b.nc == 0 || b.nw + cfg[(size_t)c].n_splits <= cap)) b.nw += cfg[(size_t)c++].n_splits, ++b.nc;
+        batches.push_back(b);
+        max_nw = std::max(max_nw, b.nw);
+    }
+    if ((rc = d_cfg.alloc(sizeof(PsfSweepCfg) * (size_t)K)) || (rc = d_work.alloc(sizeof(PsfWork) * std::max<size_t>(work.size(), 1))) ||
+        (rc = d_xs.alloc((size_t)K * n * 8)) || (rc = d_zs.alloc((size_t)K * n * 8)) || (rc = partial.alloc((size_t)max_nw * (size_t)pt_bytes)) ||
+        (rc = d_int.alloc((size_t)K * n_pts * 8)))
+        return rc;
+    if (out_field && (rc = d_field.alloc((size_t)K * n_pts * 16))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_cfg.p, cfg.data(), sizeof(PsfSweepCfg) * (size_t)K, hipMemcpyHostToDevice, st));
+    if (!work.empty()) HIP_TRY(hipMemcpyAsync(d_work.p, work.data(), sizeof(PsfWork) * work.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)K * n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_zs.p, zs, (size_t)K * n * 8, hipMemcpyHostToDevice, st));
+    const double* hits = (const double*)res->det_data.p + 9 * res->det_offset[detector];
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, st));
+    for (const Batch& b : batches) {
+        if (b.nw > 0)
+            hipLaunchKernelGGL(psf_accumulate_sweep_kernel, dim3(pt_blocks, (unsigned)b.nw), dim3(256), 0, st, hits, (const PsfWork*)d_work.p, b.w0,
+                               (const PsfSweepCfg*)d_cfg.p, (const double*)d_xs.p, (const double*)d_zs.p, n, (double2*)partial.p);
+        hipLaunchKernelGGL(psf_reduce_sweep_kernel, dim3(pt_blocks, (unsigned)b.nc), dim3(256), 0, st, (const PsfSweepCfg*)d_cfg.p, b.c0, b.w0,
+                           (const double2*)partial.p, n_pts, (double*)d_int.p, out_field ? (double2*)d_field.p : nullptr);
+    }
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipGetLastError());
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (kernel_ms) *kernel_ms = ms;
+    HIP_TRY(hipMemcpy(out_intensity, d_int.p, (size_t)K * n_pts * 8, hipMemcpyDeviceToHost));
+    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, (size_t)K * n_pts * 16, hipMemcpyDeviceToHost));
     return BMO_OK;
 }

@@ -6,6 +6,7 @@ Mirrors src/System.jl: `System(objects)` (:10-21) and
 C ABI; the beam trees are rebuilt from the engine's result tables in reference order.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -800,6 +801,37 @@ class SweepSolution:
         self.readout_ms = ms.value
         f = (buf[0::2] + 1j * buf[1::2]).reshape(K, ny, nx)  # (i, j) at [i + nx*j]
         return np.ascontiguousarray(f.transpose(0, 2, 1))
+
+    def psf_intensity(self, det, n=100, crop_factor=1, center="centroid", x_min=math.inf, x_max=math.inf, z_min=math.inf, z_max=math.inf,
+                      x0_shift=0, z0_shift=0, axes=None, want_field=False):
+        """intensity(psf; ...) of PSFDetector `det` in every configuration, in one batched read-out (bmo_psf_intensity_sweep): (xs[n_cfg, n],
+        zs[n_cfg, n], I[n_cfg, n, n]), and the complex field [n_cfg, n, n] as well with `want_field`.  Configuration c samples the axes
+        PSFDetector.sample_axes gives for its rows at its detector pose, and equals PSFDetector.intensity after a solve of its snapshot bit for
+        bit.  axes=(xs, zs) samples every configuration on that one window instead (a through-focus comparison); without it a configuration
+        whose detector recorded no hit has no window, a ValueError."""
+        slot = self._slot(det)
+        K = self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
+        if axes is not None:
+            ax, az = (np.asarray(a, dtype=np.float64) for a in axes)
+            if ax.ndim != 1 or ax.shape != az.shape:
+                raise ValueError("psf_intensity: axes must be two 1-D arrays of one length")
+            xs, zs = np.tile(ax, (K, 1)), np.tile(az, (K, 1))
+        else:
+            nodes = self.res.detector_nodes(slot)
+            cfg = self.res.node_root[nodes] // max(1, self.n_roots)
+            start = np.searchsorted(cfg, np.arange(K + 1))  # rows are in configuration order
+            rows = self.res.detector_hits(slot)
+            xs, zs = np.zeros((K, int(n))), np.zeros((K, int(n)))
+            for c in range(K):
+                if start[c] == start[c + 1]:
+                    raise ValueError(f"psf_intensity: the PSFDetector recorded no hit in configuration {c}; pass axes=(xs, zs) to read it")
+                xs[c], zs[c] = cp.psf_sample_axes(rows[start[c]:start[c + 1]], pos[c], ori[c], n=n, crop_factor=crop_factor, center=center,
+                                                  x_min=x_min, x_max=x_max, z_min=z_min, z_max=z_max, x0_shift=x0_shift, z0_shift=z0_shift)
+        I, field, ms = abi.psf_intensity_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], xs, zs, want_field=want_field)
+        self.readout_ms = ms
+        return (xs, zs, I, field) if want_field else (xs, zs, I)
 
     def optical_power(self, pd, field=None):
         """optical_power(pd) of every configuration, [n]: the trapezoid rule of Photodetector.optical_power on each configuration's field."""

@@ -477,11 +477,24 @@ int bmo_result_set_gauss_prefix(bmo_trace_result* res, int64_t n_roots, const in
  * bmo_photodetector_field_sweep: the Photodetector field of every configuration in one set of launches.  positions [n_configs][3],
  * orientations [n_configs][9] (each as in bmo_photodetector_field), one grid xs / ys for all; field_inout [n_configs][nx*ny] (re, im) pairs,
  * contributions ADDED.  Configuration c sums only its own beamlets, in the blocked order bmo_photodetector_field uses for a solve that holds
- * only them: its field equals that call's bit for bit.  n_configs must be the sweep's.                                                    */
+ * only them: its field equals that call's bit for bit.  n_configs must be the sweep's.
+ *
+ * bmo_psf_intensity_sweep: the PSF intensity (bmo_psf_intensity) of every configuration in one set of launches, from the rows of the
+ * PSFDetector slot `detector` still resident in `res`.  Configuration c samples its own axes xs[c][n], zs[c][n] at its own pose
+ * (origins, e1s, e2s: [n_configs][3], as origin / e1 / e2 of bmo_psf_intensity).  out_intensity [n_configs][n*n], element (i,j) of
+ * configuration c at [c*n*n + i + n*j]; out_field NULL or [n_configs][n*n] (re, im) pairs, same order.  Configuration c sums only its
+ * own rows, split and summed in the blocked order bmo_psf_intensity uses for a call with exactly those rows: its intensity and field
+ * equal that call's bit for bit.  A configuration without rows reads zero, as such a call with n_hits = 0 does.  n_configs must be the
+ * sweep's, or 1 for an ordinary (non-sweep) result.  BMO_ERR_INVALID for a null pointer, n <= 0, a slot out of range or not a
+ * PSFDetector's, or a wrong n_configs (all checked before a device is looked for); BMO_ERR_INTERNAL, never a wrong answer, if the rows of
+ * a configuration are not consecutive.  kernel_ms: optional, HIP-event time of the accumulation and reduction launches.          */
 int bmo_scene_create_sweep(const bmo_scene_desc* descs, int32_t n_configs, bmo_scene** out);
 int bmo_trace_sweep(bmo_scene* sweep, const bmo_ray_batch* in, const int32_t* root_config, const bmo_trace_opts* opts, bmo_trace_result** out);
 int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* positions, const double* orientations,
                                   const double* xs, const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms);
+int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                            const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
+                            double* kernel_ms);
 
 #ifdef __cplusplus
 }
