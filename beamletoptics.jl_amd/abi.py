@@ -143,43 +143,35 @@ class EngineMissing(RuntimeError):
 
 
 def _check_source_hash(lib):
-    """Refuse a library that was not built from the sources next to it (a stale, git-ignored .so pushed along with newer sources).
-    Skipped for an explicitly chosen build (BMO_ENGINE_LIB: A/B runs) and where the sources are not there to compare with."""
+    """Refuse a library that was not built from the sources next to it (a stale, git-ignored .so pushed along with newer sources), or
+    with other compiler flags (bit parity needs -ffp-contract=off & co.).  The build script next to the package says what is wanted:
+    its source list and flag list decide.  Skipped for an explicitly chosen build (BMO_ENGINE_LIB: A/B runs) and where there is no
+    build script or the sources are not there to compare with (an installed copy of the package)."""
     if os.environ.get("BMO_ENGINE_LIB"):
         return
-    root = os.path.dirname(_HERE)
-    srcs = [os.path.join(_HERE, "csrc", "bmo_engine.hip"), os.path.join(_HERE, "csrc", "bmo_lane.hpp"), os.path.join(_HERE, "csrc", "bmo_jlmath.hpp"),
-            os.path.join(_HERE, "csrc", "bmo_readout.inc.hpp"), os.path.join(root, "include", "bmo.h")]
-    if not all(os.path.exists(p) for p in srcs):
+    build = _build_script(os.path.dirname(_HERE))
+    if build is None or not all(os.path.exists(p) for p in build.engine_sources()):
         return
-    import hashlib
 
-    h = hashlib.sha256()
-    for p in srcs:
-        h.update(open(p, "rb").read())
-    try:
-        lib.bmo_source_hash.restype = C.c_char_p
-        built = lib.bmo_source_hash().decode()
-    except AttributeError:
-        built = None
-    if built != h.hexdigest():
-        raise EngineMissing(f"{ENGINE_PATH} was not built from the sources in this tree (source hash {built!r} != {h.hexdigest()[:16]}...): "
-                            "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
-    # ... nor one built with other compiler flags (bit parity needs -ffp-contract=off & co.): the build script's flag list decides
-    want = _wanted_flags_hash(root)
-    if want is not None:
+    def built(symbol):
         try:
-            lib.bmo_build_flags_hash.restype = C.c_char_p
-            got = lib.bmo_build_flags_hash().decode()
+            f = getattr(lib, symbol)
+            f.restype = C.c_char_p
+            return f().decode()
         except AttributeError:
-            got = None
-        if got != want:
-            raise EngineMissing(f"{ENGINE_PATH} was built with other compiler flags than __graft_entry__.HIP_FLAGS (flags hash {got!r} != {want!r}): "
-                                "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`")
+            return None
+
+    rebuild = "rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`"
+    got, want = built("bmo_source_hash"), build.source_hash()
+    if got != want:
+        raise EngineMissing(f"{ENGINE_PATH} was not built from the sources in this tree (source hash {got!r} != {want[:16]}...): {rebuild}")
+    got, want = built("bmo_build_flags_hash"), build.flags_hash()
+    if got != want:
+        raise EngineMissing(f"{ENGINE_PATH} was built with other compiler flags than __graft_entry__.HIP_FLAGS (flags hash {got!r} != {want!r}): {rebuild}")
 
 
-def _wanted_flags_hash(root):
-    """flags_hash() of the build script next to the package (None where there is none: an installed copy of the package)."""
+def _build_script(root):
+    """The build script next to the package as a module (None where there is none, or where it does not load)."""
     path = os.path.join(root, "__graft_entry__.py")
     if not os.path.exists(path):
         return None
@@ -189,7 +181,7 @@ def _wanted_flags_hash(root):
     mod = importlib.util.module_from_spec(spec)
     try:
         spec.loader.exec_module(mod)
-        return mod.flags_hash()
+        return mod
     except Exception:
         return None
 

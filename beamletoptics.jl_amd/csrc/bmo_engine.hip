@@ -46,11 +46,23 @@ using namespace bmo;
 namespace {
 
 thread_local std::string g_err;
-bool dbg_on() {
-    static int v = -1;
-    if (v < 0) v = getenv("BMO_DEBUG") ? 1 : 0;
-    return v == 1;
+// The switches read ONCE per process.  (Read at every launch: BMO_WIDE_MIN_WAVES; at every solve: BMO_FUSE / BMO_FUSE_GAUSS,
+// BMO_FORCE_SORT_ORDER, BMO_FORCE_DEEP_ORDER, BMO_GAPS, BMO_TIMELINE; at every upload: BMO_ROOT_ORDER / BMO_NO_BINNING — tests change those.)
+struct Knobs {
+    bool debug;          // BMO_DEBUG: phase and step log on stderr
+    bool keep_kids;      // BMO_KEEP_KIDS=0: no kept reflected children (StepParams::pend / ::gkeep)
+    int64_t thin_waves;  // BMO_THIN_WAVES=<n>: a launch of fewer than n waves spreads its records over more waves (plan_launch)
+    bool lpt;            // BMO_LPT=0: no tile-order feedback (tile_order_feedback)
+    int reverse;         // BMO_REVERSE=<0|1|2>: StepParams::reverse (-1: the default)
+};
+const Knobs& knobs() {
+    static const Knobs k = [] {
+        auto num = [](const char* name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
+        return Knobs{getenv("BMO_DEBUG") != nullptr, num("BMO_KEEP_KIDS", 1) != 0, num("BMO_THIN_WAVES", 0), num("BMO_LPT", 1) != 0, (int)num("BMO_REVERSE", -1)};
+    }();
+    return k;
 }
+bool dbg_on() { return knobs().debug; }
 #define DBG(...)                          \
     do {                                  \
         if (dbg_on()) {                   \
@@ -1921,6 +1933,50 @@ struct HostBuf {
     HostBuf& operator=(const HostBuf&) = delete;
 };
 
+// hipcub's two-call protocol, written once: f(nullptr, bytes) asks for the size of the temporary storage, scratch(bytes) provides it
+// (nullptr: out of memory, the error text is set), f(tmp, bytes) runs.  Errors map as in HIP_TRY; `what` names the call.
+// The scratch decides how long the block lives: it must not go back to the pool while work queued on it may still run.
+template <class Scratch, class F>
+int cub_run(Scratch&& scratch, const char* what, F&& f) {
+    size_t bytes = 0;
+    hipError_t e = f(nullptr, bytes);
+    if (e == hipSuccess) {
+        void* tmp = scratch(bytes);
+        if (!tmp) return BMO_ERR_OOM;
+        e = f(tmp, bytes);
+    }
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? BMO_ERR_OOM : BMO_ERR_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    return BMO_OK;
+}
+// CUB_TRY(scratch, hipcub::Algorithm(cub_tmp, cub_bytes, ...)): the call is written once, with these two names for its first two arguments
+#define CUB_TRY(scratch, call)                                                                                      \
+    do {                                                                                                            \
+        if (int rc_ = cub_run(scratch, #call, [&](void* cub_tmp, size_t& cub_bytes) { return (call); })) return rc_; \
+    } while (0)
+
+// Temporaries of a stretch of queued work: every block handed out stays alive as long as this object, which its owner lets die behind
+// a synchronisation (or under a PoolHold).  As a scratch for CUB_TRY it is ONE block shared by the calls — they run one after the
+// other on their stream —, replaced by a larger one when a call needs more.
+struct Temps {
+    std::vector<std::unique_ptr<DevBuf>> keep;
+    DevBuf* scratch = nullptr;
+    DevBuf* take(size_t bytes) {  // a block of its own; nullptr: out of memory
+        auto b = std::make_unique<DevBuf>();
+        if (b->alloc(bytes)) return nullptr;
+        keep.push_back(std::move(b));
+        return keep.back().get();
+    }
+    void* operator()(size_t bytes) {
+        if (!scratch || scratch->bytes < bytes) scratch = take(bytes);
+        return scratch ? scratch->p : nullptr;
+    }
+};
+// Scratch for CUB_TRY in a buffer that outlives the call (`b` is reused when it is large enough): only where nothing queued still uses
+// what `b` holds.
+inline auto scratch_in(DevBuf& b) {
+    return [&b](size_t bytes) -> void* { return ((b.p && b.bytes >= bytes) || !b.alloc(bytes)) ? b.p : nullptr; };
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ mesh BVH builder (host, bmo_scene_create)
@@ -2168,11 +2224,8 @@ int build_retrace_tables(bmo_trace_result* prev, hipStream_t stream) {
         return rc;
     if (prev->chunks.size() >= ((size_t)1 << (63 - OLD_LOC_SHIFT))) return fail(BMO_ERR_UNSUPPORTED, "retrace: previous solution has too many log chunks");
     if (nn > 0) {
-        DevBuf tmp;
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)prev->n_nseg.p, (int32_t*)prev->rt_rec_start.p, (int)nn, stream));
-        if ((rc = tmp.alloc(tmp_bytes))) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, (const int32_t*)prev->n_nseg.p, (int32_t*)prev->rt_rec_start.p, (int)nn, stream));
+        Temps tmp;
+        CUB_TRY(tmp, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)prev->n_nseg.p, (int32_t*)prev->rt_rec_start.p, (int)nn, stream));
         std::vector<OldChunk> oc(prev->chunks.size());
         for (size_t q = 0; q < prev->chunks.size(); ++q) oc[q] = OldChunk{prev->chunks[q].d, prev->chunks[q].cap};
         if (!oc.empty()) HIP_TRY(hipMemcpyAsync(prev->rt_chunks.p, oc.data(), oc.size() * sizeof(OldChunk), hipMemcpyHostToDevice, stream));
@@ -2204,848 +2257,7 @@ int build_retrace_tables(bmo_trace_result* prev, hipStream_t stream) {
     return BMO_OK;
 }
 
-// The SWEEP builds of the step kernels (fresh solves, every extended-shapes level): the Beam kernels without / with in-loop beam splitters.
-template <int KIND, bool INW>
-void (*sweep_step_kernel(int ext))(StepParams) {
-    if (ext == 3) return &step_kernel<KIND, 3, false, INW, step_waves<KIND, 3, false>(), true>;
-    if (ext == 2) return &step_kernel<KIND, 2, false, INW, step_waves<KIND, 2, false>(), true>;
-    if (ext == 1) return &step_kernel<KIND, 1, false, INW, step_waves<KIND, 1, false>(), true>;
-    return &step_kernel<KIND, 0, false, INW, step_waves<KIND, 0, false>(), true>;
-}
-inline void (*sweep_gauss_kernel(int ext))(StepParams) {
-    if (ext == 3) return &step_kernel_gauss<3, false, true>;
-    if (ext == 2) return &step_kernel_gauss<2, false, true>;
-    if (ext == 1) return &step_kernel_gauss<1, false, true>;
-    return &step_kernel_gauss<0, false, true>;
-}
-
-template <int KIND>
-int run_trace(bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* opts, bmo_trace_result* R, bmo_trace_result* prev = nullptr) {
-    using L = Layout<KIND>;
-    const int device = batch->device;
-    if (prev) {
-        if (prev->device != device) return fail(BMO_ERR_INVALID, "retrace: the previous solution lives on another device");
-        if (prev->kind != KIND || prev->n_roots != batch->n)
-            return fail(BMO_ERR_INVALID, "retrace: batch does not match the previous solution (root count / beam kind)");
-    }
-    HIP_TRY(hipSetDevice(device));
-    int rc = BMO_OK;
-    const char* dblob = scene->device_blob(device, rc);
-    if (rc) return rc;
-    const int64_t n = batch->n;
-    const bool has_split = scene->hdr.has_splitter != 0;
-    R->device = device;
-    R->kind = KIND;
-    R->n_roots = n;
-    R->n_detectors = scene->hdr.n_detectors;
-    R->det_kind.assign((size_t)R->n_detectors, -1);
-    {
-        const bmo_object* obj = reinterpret_cast<const bmo_object*>(scene->blob.data() + scene->hdr.off_objects);
-        for (int i = 0; i < scene->hdr.n_objects; ++i) {
-            const int k = obj[i].kind, d = obj[i].detector;
-            if ((k == BMO_OBJ_SPOTDETECTOR || k == BMO_OBJ_PSFDETECTOR || k == BMO_OBJ_PHOTODETECTOR) && d >= 0 && d < R->n_detectors)
-                R->det_kind[(size_t)d] = (R->det_kind[(size_t)d] == -1 || R->det_kind[(size_t)d] == k) ? k : -2;  // -2: objects of two kinds
-        }
-    }
-    R->nd = L::ND;
-    R->abi_planes = L::ABI;
-
-    auto wall0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!dbg_on()) return;
-        auto t = std::chrono::steady_clock::now();
-        DBG("phase %-10s %.3f ms", what, std::chrono::duration<double, std::milli>(t - wall0).count());
-        wall0 = t;
-    };
-    // one trace stream + timing events per device, created once (hipStreamCreate costs ~1 ms)
-    struct DevCtx {
-        hipStream_t stream = nullptr;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-        Counters* pinned = nullptr;
-        std::vector<hipEvent_t> step_ev;
-        std::mutex busy;  // one trace at a time per device: the stream, events and pinned counters are shared
-    };
-    static std::mutex ctx_mu;
-    static std::vector<std::pair<int, std::unique_ptr<DevCtx>>> ctxs;
-    DevCtx* ctxp = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(ctx_mu);
-        for (auto& c : ctxs)
-            if (c.first == device) ctxp = c.second.get();
-        if (!ctxp) {
-            auto nc = std::make_unique<DevCtx>();
-            // non-blocking: no implicit synchronisation with the NULL stream, so a collective or copy another library has in flight
-            // there (RCCL all-gather of the previous solve's hits) overlaps this solve
-            HIP_TRY(hipStreamCreateWithFlags(&nc->stream, hipStreamNonBlocking));
-            for (int q = 0; q < 4; ++q) HIP_TRY(hipEventCreate(&nc->ev[q]));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nc->pinned), sizeof(Counters), hipHostMallocDefault));
-            ctxp = nc.get();
-            ctxs.emplace_back(device, std::move(nc));
-        }
-    }
-    DevCtx& ctx = *ctxp;
-    std::lock_guard<std::mutex> one_trace_per_device(ctx.busy);
-    hipStream_t stream = ctx.stream;
-    hipEvent_t ev_t0 = ctx.ev[2], ev_t1 = ctx.ev[3];
-    HIP_TRY(hipEventRecord(ev_t0, stream));
-    // Every exit path — the error returns too — waits for what has been queued BEFORE the temporaries of this function go back to the
-    // shared pools: a kernel or copy still in flight must not write into a block another host thread has been handed.
-    // While `hold` lives, blocks released on this thread are parked in it; its destructor (it is declared before every temporary, so it
-    // runs after theirs) synchronises the stream and only then hands them to the pools.
-    PoolHold hold(stream);
-
-    const int nsub = KIND == BMO_BEAM_GAUSSIAN ? 3 : 1;
-    // node arrays: roots + room for children (grown on demand)
-    // Children need node slots, and every launch must have room for two per record it traces (any record may split).  One splitter per
-    // ray (3 n beams) then asks for 7 n slots before the launch that follows the split; growing the tables there costs a device copy of
-    // every node array (0.3 ms of a 6 ms solve of config C2), so moderate batches get that room up front.  Larger ones grow on demand.
-    int64_t node_cap = has_split ? (n <= ((int64_t)1 << 22) ? 7 * n + 64 : 3 * n + 64) : n;
-    auto alloc_nodes = [&](int64_t cap) -> int {
-        int r;
-        if ((r = R->n_root.alloc(cap * 4))) return r;
-        if ((r = R->n_parent.alloc(cap * 4))) return r;
-        if ((r = R->n_nseg.alloc(cap * 4))) return r;
-        if ((r = R->n_status.alloc(cap * 4))) return r;
-        if ((r = R->n_li.alloc(cap * 4))) return r;
-        if ((r = R->n_hitdet.alloc(cap * 4))) return r;
-        if ((r = R->n_key.alloc(cap * 8))) return r;
-        if ((r = R->n_lambda.alloc(cap * 8))) return r;
-        if ((r = R->n_hit.alloc(cap * 72 * nsub))) return r;
-        if ((r = R->n_aux.alloc(cap * 32))) return r;
-        if (prev && (r = R->n_old.alloc(cap * 4))) return r;
-        return BMO_OK;
-    };
-    if ((rc = alloc_nodes(node_cap))) return rc;
-    DevBuf tbits_buf;  // NodeArrays::tbits (allocated below when the scene has a splitter)
-    auto node_arrays = [&]() {
-        NodeArrays a;
-        a.root = (int32_t*)R->n_root.p;
-        a.parent = (int32_t*)R->n_parent.p;
-        a.nseg = (int32_t*)R->n_nseg.p;
-        a.status = (int32_t*)R->n_status.p;
-        a.li = (int32_t*)R->n_li.p;
-        a.hit_det = (int32_t*)R->n_hitdet.p;
-        a.key = (unsigned long long*)R->n_key.p;
-        a.lambda = (double*)R->n_lambda.p;
-        a.hit = (double*)R->n_hit.p;
-        a.aux = (double*)R->n_aux.p;
-        a.cap = node_cap;
-        a.hit_sub = nsub;
-        a.old = (int32_t*)R->n_old.p;
-        a.tbits = (unsigned long long*)tbits_buf.p;
-        return a;
-    };
-    auto grow_nodes = [&](int64_t need) -> int {
-        if (need <= node_cap) return BMO_OK;
-        int64_t ncap = std::max(need, node_cap * 2);
-        auto mv = [&](DevBuf& b, size_t elem) -> int {
-            DevBuf nb;
-            int r = nb.alloc((size_t)ncap * elem);
-            if (r) return r;
-            if (hipMemcpyAsync(nb.p, b.p, (size_t)node_cap * elem, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-                return fail(BMO_ERR_NO_DEVICE, "grow nodes");
-            (void)hipStreamSynchronize(stream);
-            std::swap(b.p, nb.p);
-            std::swap(b.bytes, nb.bytes);
-            PoolHold::Now at_once;  // the old table goes back right away (the copy above has completed)
-            nb.release();
-            return BMO_OK;
-        };
-        int r;
-        if ((r = mv(R->n_root, 4)) || (r = mv(R->n_parent, 4)) || (r = mv(R->n_nseg, 4)) || (r = mv(R->n_status, 4)) || (r = mv(R->n_li, 4)) ||
-            (r = mv(R->n_hitdet, 4)) || (r = mv(R->n_key, 8)) || (r = mv(R->n_lambda, 8)) || (r = mv(R->n_hit, 72 * (size_t)nsub)) || (r = mv(R->n_aux, 32)))
-            return r;
-        if (prev && (r = mv(R->n_old, 4))) return r;
-        node_cap = ncap;
-        return BMO_OK;
-    };
-
-    // chunk arena: bump allocation out of large blocks
-    const size_t rec_bytes = (size_t)L::ND * 8 + (size_t)NI * 4;
-    size_t block_bytes = std::max<size_t>((size_t)n * rec_bytes * 6, (size_t)1 << 20);
-    size_t top = 0;  // offset in the last block
-    // record_segments = 0: the log is not kept — every chunk gets its own pool block and goes back to the pool as soon as its level
-    // is done, so a solve holds two levels instead of all of them (beams, detector hits and counts are kept as always)
-    const bool keep_log = opts->record_segments != 0;
-    R->has_log = keep_log;
-    auto new_chunk = [&](int64_t cap, Chunk& c) -> int {
-        cap = std::max<int64_t>(cap, 1);
-        const size_t cap_al = ((size_t)cap + 1) & ~(size_t)1;  // keep int planes 8-byte aligned
-        const size_t need = cap_al * rec_bytes;
-        if (!keep_log) {
-            auto b = std::make_unique<DevBuf>();
-            int r = b->alloc(need);
-            if (r) return r;
-            char* base = static_cast<char*>(b->p);
-            c.d = reinterpret_cast<double*>(base);
-            c.i = reinterpret_cast<int32_t*>(base + cap_al * (size_t)L::ND * 8);
-            c.cap = (int64_t)cap_al;
-            c.count = 0;
-            R->arena.push_back(std::move(b));
-            return BMO_OK;
-        }
-        if (R->arena.empty() || top + need > R->arena.back()->bytes) {
-            auto b = std::make_unique<DevBuf>();
-            int r = b->alloc(std::max(block_bytes, need));
-            if (r) return r;
-            R->arena.push_back(std::move(b));
-            top = 0;
-        }
-        char* base = static_cast<char*>(R->arena.back()->p) + top;
-        c.d = reinterpret_cast<double*>(base);
-        c.i = reinterpret_cast<int32_t*>(base + cap_al * (size_t)L::ND * 8);
-        c.cap = (int64_t)cap_al;
-        c.count = 0;
-        top += need;
-        return BMO_OK;
-    };
-    auto drop_chunk = [&](const Chunk& c) {  // record_segments = 0 only; called behind the synchronisation of the chunk's launch
-        PoolHold::Now at_once;
-        for (size_t q = 0; q < R->arena.size(); ++q)
-            if (R->arena[q]->p == (void*)c.d) {
-                R->arena.erase(R->arena.begin() + (long)q);
-                return;
-            }
-    };
-    auto shrink_last = [&](Chunk& c, int64_t used) {
-        // planes are strided by cap, so the chunk keeps its footprint; nothing to return.
-        c.count = used;
-    };
-
-    DevBuf ctr_buf, shard_buf;
-    if ((rc = ctr_buf.alloc(sizeof(Counters))) || (rc = shard_buf.alloc(64 * 128))) return rc;
-    HIP_TRY(hipMemsetAsync(shard_buf.p, 0, 64 * 128, stream));
-    Counters* d_ctr = static_cast<Counters*>(ctr_buf.p);
-    Counters* h_ctr_p = ctx.pinned;  // pinned: the per-step read-back does not go through a staging copy
-    Counters& h_ctr = *h_ctr_p;
-    h_ctr = Counters{{0, 0}, (unsigned long long)n, 0, 0, {0, 0}};
-    HIP_TRY(hipMemcpyAsync(d_ctr, h_ctr_p, sizeof h_ctr, hipMemcpyHostToDevice, stream));
-
-    Chunk cur;
-    if ((rc = new_chunk(n, cur))) return rc;
-    cur.count = n;
-    OldSolution old_tab{};
-    if (prev) {
-        if ((rc = build_retrace_tables(prev, stream))) return rc;
-        old_tab.nseg = (const int32_t*)prev->n_nseg.p;
-        old_tab.status = (const int32_t*)prev->n_status.p;
-        old_tab.first_child = (const int32_t*)prev->rt_first_child.p;
-        old_tab.rec_start = (const int32_t*)prev->rt_rec_start.p;
-        old_tab.rec_obj = (const int32_t*)prev->rt_rec_obj.p;
-        old_tab.aux = (const double*)prev->n_aux.p;
-        old_tab.rec_loc = (const int64_t*)prev->rt_rec_loc.p;
-        old_tab.chunks = (const OldChunk*)prev->rt_chunks.p;
-    }
-    if (has_split && n > 0 && (rc = tbits_buf.alloc((size_t)n * 8))) return rc;
-    if (n > 0) {
-        // a retrace re-walks the stored first ray whatever r_max says (System.jl:197); root j re-walks old node j
-        hipLaunchKernelGGL((init_roots_kernel<KIND>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const double*)batch->planes.p,
-                           (const double*)(batch->perm.p ? batch->binned.p : batch->planes.p), (const int32_t*)batch->li.p, (const int32_t*)batch->perm.p, n, cur,
-                           node_arrays(), prev ? 0x7fffffff : opts->r_max, (int32_t)batch->n_planes);
-        if (prev) hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (int32_t*)R->n_old.p, n);
-    }
-    lap("setup");
-    const uint32_t blob_bytes = (uint32_t)scene->blob.size();
-    // the scene tables stay in global memory: the kernels read them with scalar loads through constant-address-space pointers
-    // (bmo_lane.hpp "scalar scene access"); LDS holds the per-lane columns only
-    const int use_lds = 0;
-    DBG("roots initialised n=%lld blob=%u use_lds=%d", (long long)n, blob_bytes, use_lds);
-    if (dbg_on()) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-        DBG("init kernel done");
-    }
-    // + block_alloc scratch + per-lane columns: child cache (BMO_CC_MAX doubles) and the lane memory of tracing_step (BMO_LANE_MEM doubles)
-    const size_t lds_bytes = (use_lds ? blob_bytes : 0) + 64 + (size_t)(BMO_CC_MAX + BMO_LANE_MEM) * BMO_BLOCK * 8;
-    void (*kern)(StepParams) = nullptr, (*kern_inw)(StepParams) = nullptr;  // kern_inw: the Beam kernels' variant with in-loop beam splitters
-    void (*kern_wide)(StepParams) = nullptr, (*kern_inw_wide)(StepParams) = nullptr;  // the 4-waves-per-SIMD builds of the two, for large launches (step_waves)
-    // extended-shapes level of the kernels (bmo_lane.hpp sdf_leaf); a scene with a mesh BVH runs level 3 (level 2 + the BVH traversal)
-    const int ext = scene->hdr.pad[0] ? 3 : (scene->hdr.has_asphere ? 2 : (scene->hdr.has_meniscus ? 1 : 0));
-#if defined(BMO_DEV_RAY_LDS_ONLY)  // developer build (kernel work on one variant): everything else is refused, nothing falls back
-    if constexpr (KIND == BMO_BEAM_RAY) {
-        if (!prev && ext == 0) {
-            kern = &step_kernel<BMO_BEAM_RAY, 0, false, false>, kern_inw = &step_kernel<BMO_BEAM_RAY, 0, false, true>;
-#if !defined(BMO_MIN_WAVES)
-            kern_wide = &step_kernel<BMO_BEAM_RAY, 0, false, false, 4>, kern_inw_wide = &step_kernel<BMO_BEAM_RAY, 0, false, true, 4>;
-#endif
-        }
-    }
-    if (!kern) return fail(BMO_ERR_UNSUPPORTED, "developer build: only step_kernel<RAY> is compiled in");
-#elif defined(BMO_DEV_GAUSS_ONLY)  // developer build: the fresh GaussianBeamlet kernel of the plain-shapes level only
-    if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
-        if (!prev && ext == 0) kern = &step_kernel_gauss<0, false>;
-    }
-    if (!kern) return fail(BMO_ERR_UNSUPPORTED, "developer build: only step_kernel_gauss<0, false> is compiled in");
-#else
-    if (ext == 3) {  // mesh BVH: one level (a superset of 0 - 2), fresh and retrace, for every beam kind
-        if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
-            kern = prev ? &step_kernel_gauss<3, true> : &step_kernel_gauss<3, false>;
-        } else {
-            kern = prev ? &step_kernel<KIND, 3, true, false> : &step_kernel<KIND, 3, false, false>;
-            kern_inw = prev ? &step_kernel<KIND, 3, true, true> : &step_kernel<KIND, 3, false, true>;
-        }
-    } else if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
-        if (prev) kern = ext == 2 ? &step_kernel_gauss<2, true> : (ext == 1 ? &step_kernel_gauss<1, true> : &step_kernel_gauss<0, true>);
-        else kern = ext == 2 ? &step_kernel_gauss<2, false> : (ext == 1 ? &step_kernel_gauss<1, false> : &step_kernel_gauss<0, false>);
-    } else {
-        if (prev) kern = ext == 2 ? &step_kernel<KIND, 2, true, false> : (ext == 1 ? &step_kernel<KIND, 1, true, false> : &step_kernel<KIND, 0, true, false>);
-        else kern = ext == 2 ? &step_kernel<KIND, 2, false, false> : (ext == 1 ? &step_kernel<KIND, 1, false, false> : &step_kernel<KIND, 0, false, false>);
-        if (prev) kern_inw = ext == 2 ? &step_kernel<KIND, 2, true, true> : (ext == 1 ? &step_kernel<KIND, 1, true, true> : &step_kernel<KIND, 0, true, true>);
-        else kern_inw = ext == 2 ? &step_kernel<KIND, 2, false, true> : (ext == 1 ? &step_kernel<KIND, 1, false, true> : &step_kernel<KIND, 0, false, true>);
-#if !defined(BMO_MIN_WAVES)
-        if constexpr (KIND == BMO_BEAM_RAY) {
-            if (!prev && ext == 0) kern_wide = &step_kernel<BMO_BEAM_RAY, 0, false, false, 4>, kern_inw_wide = &step_kernel<BMO_BEAM_RAY, 0, false, true, 4>;
-        }
-#endif
-    }
-#endif
-    // a sweep (bmo_trace_sweep): R->n_configs configurations, R->d_root_cfg the configuration of every root; lanes find their slots through
-    // the map built before every launch (StepParams::sweep)
-    const bool sweep = R->n_configs > 0;
-    if (sweep) {
-        if (prev) return fail(BMO_ERR_UNSUPPORTED, "sweeps are fresh solves");
-#if defined(BMO_DEV_RAY_LDS_ONLY) || defined(BMO_DEV_GAUSS_ONLY)
-        return fail(BMO_ERR_UNSUPPORTED, "developer build: no sweep kernels");
-#else
-        kern_wide = kern_inw_wide = nullptr;
-        if constexpr (KIND == BMO_BEAM_GAUSSIAN) {
-            kern = sweep_gauss_kernel(ext);
-            kern_inw = nullptr;
-        } else {
-            kern = sweep_step_kernel<KIND, false>(ext);
-            kern_inw = sweep_step_kernel<KIND, true>(ext);
-        }
-#endif
-    }
-    if (lds_bytes > 48 * 1024) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        if (kern_inw) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_inw), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        if (kern_wide) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        if (kern_inw_wide) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_inw_wide), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-    }
-
-    int64_t n_nodes = n;
-    double kernel_ms = 0;
-    int steps = 0;
-    // bounces per launch: fewer launches and host round trips; holes instead of compaction inside a launch.  BMO_FUSE=1 (BMO_FUSE_GAUSS=1)
-    // restores one launch per bounce level.
-    // measured on C1-C5: 8 levels per launch beat 4 by 1-4 % at 10^6 beams and by 8-10 % below 10^5; with per-wave loops 16 beat 8 by
-    // another 1-3 %, and 32 beat 16 by 1-2.5 % (config C2 reaches its splitter, level 17, in the first launch: 2 launches instead of 3).
-    // The GaussianBeamlet kernels need one in-place chunk more than they fuse levels (step_kernel_gauss): one level fewer.
-    constexpr bool GAUSS = KIND == BMO_BEAM_GAUSSIAN;
-    int fuse_max = GAUSS ? MAX_FUSE - 1 : MAX_FUSE;
-    if (const char* e = getenv(GAUSS ? "BMO_FUSE_GAUSS" : "BMO_FUSE")) fuse_max = std::max(1, std::min(fuse_max, atoi(e)));
-    DevBuf gstage;
-    int64_t gstage_cap = 0;
-    DevBuf gkeep;     // StepParams::gkeep
-    DevBuf pend_buf;  // StepParams::pend
-    int64_t pend_cap = 0;
-    static const bool keep_kids_on = !(getenv("BMO_KEEP_KIDS") && atoi(getenv("BMO_KEEP_KIDS")) == 0);
-    double keep_ratio = 1.0;  // share of the previous launch's beams that went on (the fuse-count rule of round 2: launches above BMO_INWAVE_MAX only)
-    while (cur.count > 0) {
-        const int64_t m = cur.count;
-        static const double keep_hi = getenv("BMO_KEEP_HI") ? atof(getenv("BMO_KEEP_HI")) : 0.9, keep_lo = getenv("BMO_KEEP_LO") ? atof(getenv("BMO_KEEP_LO")) : 0.6;
-        static const int fuse_mid = getenv("BMO_FUSE_MID") ? atoi(getenv("BMO_FUSE_MID")) : 2, fuse_lo = getenv("BMO_FUSE_LO") ? atoi(getenv("BMO_FUSE_LO")) : 1;
-        // records per wave (StepParams::lane_shift).  BMO_THIN_WAVES=<n>: a launch with fewer than n waves spreads its records over more waves.
-        // Off by default: it took 6 % off the vignetted bundle while launches were level-synchronous, nothing since the beam splitters are
-        // handled in the loop, and it costs small batches dearly (100 rays through config 2: 0.84 ms against 0.55 — every wave on a CU of
-        // its own pays that CU's instruction- and scalar-cache warm-up): profiles/r03_ab_inwave.txt.
-        int lane_shift = 6;
-        if (!sweep) {
-            static const int64_t thin_waves = getenv("BMO_THIN_WAVES") ? atoll(getenv("BMO_THIN_WAVES")) : 0;
-            while (lane_shift > 0 && ((m + (1ll << (lane_shift - 1)) - 1) >> (lane_shift - 1)) <= thin_waves) lane_shift -= 1;
-        }
-        // Beam kernels: every launch fuses all its levels, whatever share of its beams ends, and handles its beam splitters in the loop
-        // (step_kernel<.., INW>): holes cost lane time, launches cost the wait for the slowest march of every generation, and the second
-        // is the dearer one — the vignetted bundle takes 2 launches and 14 ms this way, 12 launches and 23 ms with the keep-ratio rule of
-        // round 2, which BMO_INWAVE_MAX (largest launch treated like this, in records) brings back for launches above it.
-        static const int64_t inwave_max = getenv("BMO_INWAVE_MAX") ? atoll(getenv("BMO_INWAVE_MAX")) : INT64_MAX;
-        const bool tail = m <= inwave_max;
-        int n_fuse = tail ? fuse_max : keep_ratio >= keep_hi ? fuse_max : (keep_ratio >= keep_lo ? std::min(fuse_mid, fuse_max) : std::min(fuse_lo, fuse_max));
-        // the in-place levels of a launch are allocated up front: at most 24 GB of them (2^24 beams: 8 levels)
-        if (keep_log) n_fuse = (int)std::min<int64_t>(n_fuse, 1 + (int64_t)(((size_t)24 << 30) / ((size_t)std::max<int64_t>(m, 1) * rec_bytes)));
-        // a sweep launch: every configuration's run of slots padded to whole waves (at most 63 idle lanes per configuration present)
-        const int64_t sweep_lanes = sweep ? ((m + 63 * std::min<int64_t>(R->n_configs, m) + 63) & ~(int64_t)63) : 0;
-        if (sweep_lanes >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "sweep launch of more than 2^31 lanes: fewer roots per call");
-        const int64_t n_waves = sweep ? sweep_lanes >> 6 : (m + (1ll << lane_shift) - 1) >> lane_shift;
-        const unsigned n_blocks = (unsigned)((n_waves + BMO_BLOCK / 64 - 1) / (BMO_BLOCK / 64));
-        Chunk nxt, inner[MAX_FUSE - 1];
-        // the next launch's chunk first, then the in-place levels: the levels no wave reaches go back to the arena after the launch
-        // (in-loop beam splitters of the Beam kernels: room for up to m reflected children more, StepParams::inwave_cap)
-        const int64_t inwave_cap = (has_split && (kern_inw || GAUSS) && n_fuse > 1 && tail) ? m : 0;
-        // (kept reflected children, StepParams::pend: a lane can end its wave's loop with a kept child AND two fresh ones — one record more per lane)
-        const bool keep_kids = inwave_cap > 0 && keep_kids_on;
-        if ((rc = new_chunk((has_split ? 2 * m : m) + inwave_cap + (keep_kids ? m : 0), nxt))) return rc;
-        if (keep_kids && !GAUSS && m > pend_cap) {  // one buffer for the whole solve (the previous launch has completed: its block goes back at once)
-            PoolHold::Now at_once;
-            pend_buf.release();
-            pend_cap = (m + 1) & ~(int64_t)1;
-            if ((rc = pend_buf.alloc((size_t)pend_cap * rec_bytes))) return rc;
-        }
-        uint8_t* wl = nullptr;
-        if (keep_log && n_fuse > 1) {
-            auto b = std::make_unique<DevBuf>();
-            // one byte per wave of the GRID, not of the batch: the tail waves of the last workgroup (no record, j >= m) note their level too.
-            // A sweep launch notes it per slot (a wave's slots are not consecutive there).
-            if ((rc = b->alloc(sweep ? (size_t)m : (size_t)n_blocks * (BMO_BLOCK / 64)))) return rc;
-            wl = static_cast<uint8_t*>(b->p);
-            R->wave_last.push_back(std::move(b));
-        }
-        size_t top_after[MAX_FUSE], blocks_after[MAX_FUSE];  // arena state behind nxt [0] and behind every in-place level [q + 1]
-        top_after[0] = top;
-        blocks_after[0] = R->arena.size();
-        for (int q = 0; q < (GAUSS ? n_fuse : n_fuse - 1); ++q) {
-            if (!keep_log && q > (GAUSS ? 1 : 0)) {
-                // nobody reads the log: a lane's in-place record is dead once it has been read back, one chunk serves all levels (a beamlet's
-                // step writes its next rays while the hits of the level it reads are still being filled in: two chunks, taken in turns)
-                inner[q] = inner[GAUSS ? (q & 1) : 0];
-                continue;
-            }
-            if ((rc = new_chunk(m, inner[q]))) {
-                if (rc != BMO_ERR_OOM || q == 0) return rc;
-                n_fuse = GAUSS ? q : q + 1;  // no room for this many in-place levels: fuse the ones that fit (the launch before fused fewer, too)
-                rc = BMO_OK;
-                break;
-            }
-            inner[q].count = m;  // same slot numbering as cur; records of beams that ended earlier are marked node = -1
-            inner[q].wl = wl;
-            inner[q].level = q + 1;
-            inner[q].wl_shift = sweep ? 0 : lane_shift;
-            top_after[q + 1] = top;
-            blocks_after[q + 1] = R->arena.size();
-        }
-        if (has_split && (rc = grow_nodes(n_nodes + 2 * m + 2 * inwave_cap))) return rc;
-        // (Gaussian) staging planes for the reflected children's rays of this launch: one buffer for the whole solve, grown when a launch has more records
-        // than any before it (the previous launch has completed by then: its block goes back to the pool at once)
-        if (KIND == BMO_BEAM_GAUSSIAN && m > gstage_cap) {
-            PoolHold::Now at_once;
-            gstage.release();
-            gkeep.release();
-            gstage_cap = ((m + m / 8 + 1) & ~(int64_t)1);
-            if ((rc = gstage.alloc((size_t)gstage_cap * 21 * 8)) || (rc = gkeep.alloc((size_t)gstage_cap * 24 * 8))) return rc;
-        }
-        StepParams P;
-        P.gstage = (double*)gstage.p;
-        P.gstage_cap = gstage_cap;
-        P.hdr = scene->hdr;
-        P.blob = dblob;
-        P.blob_bytes = blob_bytes;
-        P.use_lds = use_lds;
-        P.cur = cur;
-        P.nxt = nxt;
-        for (int q = 0; q < MAX_FUSE - 1; ++q) P.inner[q] = q < (GAUSS ? n_fuse : n_fuse - 1) ? inner[q] : Chunk{nullptr, nullptr, 0, 0};
-        P.n_fuse = n_fuse;
-        P.ctr = d_ctr;
-        P.call_shards = static_cast<unsigned long long*>(shard_buf.p);
-        P.nodes = node_arrays();
-        P.r_max = opts->r_max;
-        P.parity = steps & 1;
-        P.old = old_tab;
-        P.wave_last = wl;
-        P.lane_shift = lane_shift;
-        P.inwave_cap = inwave_cap;
-        P.nodes0 = n_nodes;
-        P.pend = Chunk{nullptr, nullptr, 0, 0};
-        P.gkeep = (GAUSS && keep_kids) ? (double*)gkeep.p : nullptr;
-        if (keep_kids && !GAUSS) {
-            P.pend.d = static_cast<double*>(pend_buf.p);
-            P.pend.i = reinterpret_cast<int32_t*>(static_cast<char*>(pend_buf.p) + (size_t)pend_cap * (size_t)L::ND * 8);
-            P.pend.cap = pend_cap;
-            P.pend.count = m;
-        }
-        P.tile_order = nullptr;
-        P.tile_cost = nullptr;
-        {
-            static const bool lpt_on = !(getenv("BMO_LPT") && atoi(getenv("BMO_LPT")) == 0);
-            if (lpt_on && !sweep && steps == 0 && lane_shift == 6 && n_blocks >= 64) {
-                if (batch->tile_n != (int64_t)n_blocks) {
-                    PoolHold::Now at_once;
-                    batch->cost_valid = false;
-                    batch->tile_n = 0;
-                    batch->tile_cost.release(), batch->tile_order.release(), batch->lpt_ids.release(), batch->lpt_keys.release(), batch->lpt_tmp.release();
-                    size_t tb = 0;
-                    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tb, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                                                         (int)n_blocks, 0, 32, stream));
-                    if ((rc = batch->tile_cost.alloc((size_t)n_blocks * 4)) || (rc = batch->tile_order.alloc((size_t)n_blocks * 4)) ||
-                        (rc = batch->lpt_ids.alloc((size_t)n_blocks * 4)) || (rc = batch->lpt_keys.alloc((size_t)n_blocks * 4)) || (rc = batch->lpt_tmp.alloc(std::max<size_t>(tb, 16))))
-                        return rc;
-                    hipLaunchKernelGGL(iota_kernel, dim3((n_blocks + 255) / 256), dim3(256), 0, stream, (int32_t*)batch->lpt_ids.p, (int64_t)n_blocks);
-                    batch->tile_n = (int64_t)n_blocks;
-                }
-                if (!batch->cost_valid && prev && prev->tile_n == (int64_t)n_blocks && prev->tile_cost.p) {  // feedback from the solution that is retraced
-                    HIP_TRY(hipMemcpyAsync(batch->tile_cost.p, prev->tile_cost.p, (size_t)n_blocks * 4, hipMemcpyDeviceToDevice, stream));
-                    batch->cost_valid = true;
-                }
-                if (batch->cost_valid) {
-                    size_t tb = batch->lpt_tmp.bytes;
-                    HIP_TRY(hipcub::DeviceRadixSort::SortPairsDescending(batch->lpt_tmp.p, tb, (const uint32_t*)batch->tile_cost.p, (uint32_t*)batch->lpt_keys.p,
-                                                                         (const int32_t*)batch->lpt_ids.p, (int32_t*)batch->tile_order.p, (int)n_blocks, 0, 32, stream));
-                    P.tile_order = (const int32_t*)batch->tile_order.p;
-                }
-                P.tile_cost = (uint32_t*)batch->tile_cost.p;
-                batch->cost_valid = true;  // (after this launch)
-            }
-        }
-        {
-            // without feedback (StepParams::tile_order) a launch starts from the END of its chunk: a disc source has its marginal rays there,
-            // children and survivors are queued in the order their parents got there — the slow ones last (StepParams::reverse)
-            static const int reverse_order = getenv("BMO_REVERSE") ? atoi(getenv("BMO_REVERSE")) : -1;
-            P.reverse = reverse_order >= 0 ? reverse_order : 1;
-        }
-#if defined(BMO_DEV_TIMELINE)  // developer builds, BMO_TIMELINE=1: how many waves are at work over the course of every launch
-        DevBuf tl_buf;
-        P.tl = nullptr;
-        if (getenv("BMO_TIMELINE") && !sweep) {
-            if ((rc = tl_buf.alloc((size_t)n_waves * 16 + 64))) return rc;
-            HIP_TRY(hipMemsetAsync(tl_buf.p, 0, tl_buf.bytes, stream));
-            P.tl = (unsigned long long*)tl_buf.p;
-        }
-#endif
-        DevBuf sw_map;  // (P.sweep shares its room with P.old: set for sweeps only)
-        if (sweep) {
-            // lane map: key = configuration of every slot, stable sort (slot order within a configuration), runs padded to whole waves
-            const int32_t K = R->n_configs;
-            DevBuf key, key_s, slot, slot_s, beg, end, padded, pstart, tmp;
-            if ((rc = key.alloc((size_t)m * 4)) || (rc = key_s.alloc((size_t)m * 4)) || (rc = slot.alloc((size_t)m * 4)) || (rc = slot_s.alloc((size_t)m * 4)) ||
-                (rc = beg.alloc((size_t)K * 4)) || (rc = end.alloc((size_t)K * 4)) || (rc = padded.alloc((size_t)K * 4)) || (rc = pstart.alloc((size_t)K * 4)) ||
-                (rc = sw_map.alloc((size_t)sweep_lanes * 4)))
-                return rc;
-            int kbits = 1;
-            while (kbits < 32 && ((uint32_t)(K - 1) >> kbits)) ++kbits;
-            size_t tb = 0, tb2 = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t*)key.p, (uint32_t*)key_s.p, (const int32_t*)slot.p, (int32_t*)slot_s.p, (int)m, 0, kbits, stream));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, (const int32_t*)padded.p, (int32_t*)pstart.p, (int)K, stream));
-            if ((rc = tmp.alloc(std::max(tb, tb2)))) return rc;
-            const unsigned mb = (unsigned)((m + 255) / 256);
-            hipLaunchKernelGGL(sweep_key_kernel, dim3(mb), dim3(256), 0, stream, cur, (const int32_t*)R->n_root.p, (const int32_t*)R->d_root_cfg.p, m,
-                               (uint32_t*)key.p, (int32_t*)slot.p);
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, (const uint32_t*)key.p, (uint32_t*)key_s.p, (const int32_t*)slot.p, (int32_t*)slot_s.p, (int)m, 0, kbits, stream));
-            HIP_TRY(hipMemsetAsync(beg.p, 0, (size_t)K * 4, stream));
-            HIP_TRY(hipMemsetAsync(end.p, 0, (size_t)K * 4, stream));
-            hipLaunchKernelGGL(sweep_bounds_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t*)key_s.p, m, (int32_t*)beg.p, (int32_t*)end.p);
-            hipLaunchKernelGGL(sweep_pad_kernel, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, stream, (const int32_t*)beg.p, (const int32_t*)end.p, K, (int32_t*)padded.p);
-            size_t t2 = tmp.bytes;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, t2, (const int32_t*)padded.p, (int32_t*)pstart.p, (int)K, stream));
-            HIP_TRY(hipMemsetAsync(sw_map.p, 0xFF, (size_t)sweep_lanes * 4, stream));
-            hipLaunchKernelGGL(sweep_scatter_kernel, dim3(mb), dim3(256), 0, stream, (const uint32_t*)key_s.p, (const int32_t*)slot_s.p, m, (const int32_t*)beg.p,
-                               (const int32_t*)pstart.p, sweep_lanes, (int32_t*)sw_map.p, &d_ctr->overflow);
-            HIP_TRY(hipGetLastError());
-            P.sweep = SweepLanes{(const int32_t*)sw_map.p, (const int32_t*)R->d_root_cfg.p, scene->stride};
-        }
-        DBG("step %d launching m=%lld, %d records per wave", steps, (long long)m, 1 << lane_shift);
-        // launch timing: one event pair per step out of a cached pool, read after the loop (nothing but the counter read-back
-        // sits between two launches)
-        while ((int)ctxp->step_ev.size() < 2 * (steps + 1)) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            ctxp->step_ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(ctxp->step_ev[2 * steps], stream));
-        // (step_kernel_gauss handles P.inwave_cap itself: the GaussianBeamlet branch above assigns no kern_inw)
-        // (the 4-waves-per-SIMD build for a launch that fills the device at that occupancy — 256 CUs x 16 waves —, the 3-waves one below: step_waves.
-        //  Between 4 096 and ~10 000 waves the two scenes measured disagree — config 5 - 13 % / - 6 %, config 2 + 2 % / + 3 % — and the larger effect decides.)
-        const char* const wide_env = getenv("BMO_WIDE_MIN_WAVES");  // (read per launch: the tests switch it between solves)
-        const int64_t wide_min_waves = wide_env ? atoll(wide_env) : 4096;
-        const bool wide = kern_wide && n_waves >= wide_min_waves;
-        void (*const launch_kern)(StepParams) = (inwave_cap > 0 && kern_inw) ? (wide ? kern_inw_wide : kern_inw) : (wide ? kern_wide : kern);
-        if (!launch_kern) return fail(BMO_ERR_INTERNAL, "no step kernel selected for this beam kind / scene level");
-        hipLaunchKernelGGL(launch_kern, dim3(n_blocks), dim3(BMO_BLOCK), lds_bytes, stream, P);
-        HIP_TRY(hipEventRecord(ctxp->step_ev[2 * steps + 1], stream));
-        HIP_TRY(hipMemcpyAsync(h_ctr_p, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-#if defined(BMO_DEV_TIMELINE)
-        if (P.tl) {
-            const size_t nw = (size_t)n_waves;
-            std::vector<unsigned long long> t(2 * nw + 3);
-            HIP_TRY(hipMemcpy(t.data(), P.tl, nw * 16 + 24, hipMemcpyDeviceToHost));
-            {
-                const double a = (double)t[2 * nw], b2 = (double)t[2 * nw + 1], c2 = (double)t[2 * nw + 2], sum = a + b2 + c2;
-                // (finer timers inside the lane code — per sdf_any / normal_any / object — measure mostly their own s_memrealtime latency)
-                fprintf(stderr, "[bmo] timeline step %d: wave time before / in / after tracing_step: %.1f %% / %.1f %% / %.1f %%  (%.1f us per wave in all)\n", steps,
-                        100 * a / sum, 100 * b2 / sum, 100 * c2 / sum, sum / nw / 100.0);
-            }
-            unsigned long long t0 = ~0ull, t1 = 0;
-            for (size_t w = 0; w < nw; ++w) {
-                t0 = std::min(t0, t[2 * w]);
-                t1 = std::max(t1, t[2 * w + 1]);
-            }
-            const double span = (double)(t1 - t0);
-            const int NB = 40;
-            std::vector<double> busy(NB, 0.0);  // wave residency integrated per bin
-            for (size_t w = 0; w < nw; ++w) {
-                const double a = (double)(t[2 * w] - t0) / span * NB, b2 = (double)(t[2 * w + 1] - t0) / span * NB;
-                for (int q = (int)a; q < NB && q <= (int)b2; ++q) busy[q] += std::min(b2, (double)q + 1) - std::max(a, (double)q);
-            }
-            fprintf(stderr, "[bmo] timeline step %d: %zu waves, span %.3f ms; mean waves at work per 1/%d of the span:\n ", steps, nw, span / 1e5, NB);
-            for (int q = 0; q < NB; ++q) fprintf(stderr, " %.0f", busy[q]);
-            fprintf(stderr, "\n");
-            {  // the waves that end last: where in the grid they sit, when they started
-                std::vector<size_t> idx(nw);
-                for (size_t w = 0; w < nw; ++w) idx[w] = w;
-                const size_t top = std::min<size_t>(nw, 12);
-                std::partial_sort(idx.begin(), idx.begin() + (long)top, idx.end(), [&](size_t a, size_t b2) { return t[2 * a + 1] > t[2 * b2 + 1]; });
-                fprintf(stderr, "[bmo] timeline step %d: last waves to end (wave of the grid: start .. end in ms):", steps);
-                for (size_t q = 0; q < top; ++q) fprintf(stderr, "  %zu: %.3f .. %.3f", idx[q], (double)(t[2 * idx[q]] - t0) / 1e5, (double)(t[2 * idx[q] + 1] - t0) / 1e5);
-                fprintf(stderr, "\n");
-                std::vector<double> dur(nw);
-                for (size_t w = 0; w < nw; ++w) dur[w] = (double)(t[2 * w + 1] - t[2 * w]) / 1e5;
-                std::vector<double> srt = dur;
-                std::sort(srt.begin(), srt.end());
-                fprintf(stderr, "[bmo] timeline step %d: wave durations ms p50 %.3f p90 %.3f p99 %.3f p99.9 %.3f max %.3f\n", steps, srt[nw / 2], srt[nw * 9 / 10], srt[nw * 99 / 100],
-                        srt[std::min(nw - 1, nw * 999 / 1000)], srt[nw - 1]);
-            }
-        }
-#endif
-        const unsigned long long produced = h_ctr.next_count[steps & 1];
-        DBG("step %d done next=%llu nodes=%llu deepest in-place level %llu of %d", steps, produced, h_ctr.node_count, h_ctr.max_level[steps & 1], n_fuse);
-        steps += 1;
-        if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "queue overflow (internal capacity bound violated)");
-        if (h_ctr.sweep_mixed) return fail(BMO_ERR_INTERNAL, "sweep: a wave held records of more than one configuration (lane map violated)");
-        if (keep_log) {
-            const int used = (int)std::min<unsigned long long>(h_ctr.max_level[(steps - 1) & 1], (unsigned long long)(n_fuse - 1));  // in-place levels reached
-            R->chunks.push_back(cur);
-            for (int q = 0; q < used; ++q) R->chunks.push_back(inner[q]);
-            // the levels behind them were never touched: their room goes back to the arena (allocation is a bump, so everything
-            // allocated after the last level in use belongs to them)
-            if (used < (GAUSS ? n_fuse : n_fuse - 1)) {  // (the GaussianBeamlet kernels' extra level is always given back)
-                PoolHold::Now at_once;  // (the launch has completed: nothing in flight touches these blocks)
-                while (R->arena.size() > blocks_after[used]) R->arena.pop_back();
-                top = top_after[used];
-            }
-        } else {  // the launch above has completed (counter read-back): its input and in-place levels are dead
-            drop_chunk(cur);
-            if (GAUSS || n_fuse > 1) drop_chunk(inner[0]);
-            if (GAUSS && n_fuse > 1) drop_chunk(inner[1]);
-        }
-        shrink_last(nxt, (int64_t)produced);
-        keep_ratio = (double)std::min<unsigned long long>(produced, (unsigned long long)m) / (double)m;
-        n_nodes = (int64_t)h_ctr.node_count;
-        if (opts->max_beams > 0 && n_nodes > (int64_t)opts->max_beams)
-            return fail(BMO_ERR_LIMIT, "beam tree exceeds bmo_trace_opts.max_beams (" + std::to_string(n_nodes) + " beams after " + std::to_string(steps) +
-                                           " launches): a splitter facing a mirror?");
-        cur = nxt;
-    }
-    for (int q = 0; q < steps; ++q) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctxp->step_ev[2 * q], ctxp->step_ev[2 * q + 1]));
-        kernel_ms += ms;
-        DBG("step %d kernel %.3f ms", q, ms);
-        if (q + 1 < steps && getenv("BMO_GAPS")) {  // diagnosis: device idle time between two step launches (host round trip)
-            float gap = 0;
-            (void)hipEventElapsedTime(&gap, ctxp->step_ev[2 * q + 1], ctxp->step_ev[2 * q + 2]);
-            fprintf(stderr, "[bmo] step %d kernel %.3f ms, gap to the next launch %.3f ms\n", q, ms, gap);
-        }
-    }
-    lap("steps");
-    R->n_nodes = n_nodes;
-    R->n_steps = steps;
-    R->kernel_ms = kernel_ms;
-    if (batch->cost_valid && batch->tile_n > 0 && batch->tile_cost.p && !R->tile_cost.alloc((size_t)batch->tile_n * 4)) {  // (best effort)
-        if (hipMemcpyAsync(R->tile_cost.p, batch->tile_cost.p, (size_t)batch->tile_n * 4, hipMemcpyDeviceToDevice, stream) == hipSuccess) R->tile_n = batch->tile_n;
-    }
-    // Everything below is queued behind ONE synchronisation at the end: temporaries stay alive until then (`keep`: a block that went
-    // back to the pool could be handed to a view running on another stream), counts are read back last.
-    std::vector<std::unique_ptr<DevBuf>> keep;
-    auto temp = [&](size_t bytes) -> DevBuf* {
-        auto b = std::make_unique<DevBuf>();
-        if (b->alloc(bytes)) return nullptr;
-        keep.push_back(std::move(b));
-        return keep.back().get();
-    };
-    // pinned read-back area: [0..1023] call-counter shards (64 x 16 words), [1024] segment count, [1025..] hit offsets
-    static_assert(sizeof(unsigned long long) == 8, "");
-    HostBuf h_tail;
-    if ((rc = h_tail.alloc((1024 + 1 + 1025) * 8))) return rc;
-    unsigned long long* const h_sh = static_cast<unsigned long long*>(h_tail.p);
-    long long* const h_sum = reinterpret_cast<long long*>(h_sh + 1024);
-    int32_t* const h_off = reinterpret_cast<int32_t*>(h_sh + 1025);
-    *h_sum = 0;
-    HIP_TRY(hipMemcpyAsync(h_sh, shard_buf.p, 64 * 128, hipMemcpyDeviceToHost, stream));
-    if (n_nodes > 0) {  // segments = sum of the beams' segment counts (chunk counts include the holes of fused levels)
-        DevBuf* d_sum = temp(8);
-        if (!d_sum) return BMO_ERR_OOM;
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, tmp_bytes, (const int32_t*)R->n_nseg.p, (long long*)d_sum->p, (int)n_nodes, stream));
-        DevBuf* tmp = temp(tmp_bytes);
-        if (!tmp) return BMO_ERR_OOM;
-        HIP_TRY(hipcub::DeviceReduce::Sum(tmp->p, tmp_bytes, (const int32_t*)R->n_nseg.p, (long long*)d_sum->p, (int)n_nodes, stream));
-        HIP_TRY(hipMemcpyAsync(h_sum, d_sum->p, 8, hipMemcpyDeviceToHost, stream));
-    }
-
-    // ---- canonical node order (bundle order x BFS order): sort by (root, depth, path)
-    if ((rc = R->order.alloc((size_t)std::max<int64_t>(n_nodes, 1) * 4))) return rc;
-    const unsigned nb = (unsigned)((n_nodes + 255) / 256);
-    // test hooks: BMO_FORCE_SORT_ORDER / BMO_FORCE_DEEP_ORDER take the radix-sort / level-by-level path for any tree
-    const bool heap_order = n_nodes > n && h_ctr.max_depth <= (unsigned long long)MAX_HEAP_LEVELS && !std::getenv("BMO_FORCE_SORT_ORDER") &&
-                            !std::getenv("BMO_FORCE_DEEP_ORDER");
-    if (heap_order) {
-        DevBuf *bits = temp((size_t)n * 8), *cnt = temp((size_t)n * 4), *base = temp((size_t)n * 4);
-        if (!bits || !cnt || !base) return BMO_ERR_OOM;
-        const unsigned rb = (unsigned)((n + 255) / 256);
-        if (tbits_buf.p) {  // collected while the nodes were made
-            bits = &tbits_buf;
-        } else {
-            HIP_TRY(hipMemsetAsync(bits->p, 0, (size_t)n * 8, stream));
-            hipLaunchKernelGGL(tree_bits_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->n_root.p, (const unsigned long long*)R->n_key.p, n_nodes,
-                               (unsigned long long*)bits->p);
-        }
-        hipLaunchKernelGGL(tree_count_kernel, dim3(rb), dim3(256), 0, stream, (const unsigned long long*)bits->p, n, (int32_t*)cnt->p);
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)cnt->p, (int32_t*)base->p, (int)n, stream));
-        DevBuf* st = temp(tmp_bytes);
-        if (!st) return BMO_ERR_OOM;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(st->p, tmp_bytes, (const int32_t*)cnt->p, (int32_t*)base->p, (int)n, stream));
-        hipLaunchKernelGGL(tree_rank_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->n_root.p, (const unsigned long long*)R->n_key.p, n_nodes,
-                           (const unsigned long long*)bits->p, (const int32_t*)base->p, (int32_t*)R->order.p);
-    } else if (n_nodes > 0) {
-        hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, stream, (int32_t*)R->order.p, n_nodes);
-    }
-    if (n_nodes > n && !heap_order) {
-        auto bits_for = [](unsigned long long v) {  // bits needed to hold values 0..v
-            int b = 0;
-            while (b < 64 && (v >> b)) ++b;
-            return b;
-        };
-        const int bits_depth = bits_for(h_ctr.max_depth), bits_root = bits_for((unsigned long long)std::max<int64_t>(n - 1, 0));
-        DevBuf keys_in, keys_out, vals_out, tmp;
-        const bool force_deep = std::getenv("BMO_FORCE_DEEP_ORDER") != nullptr;
-        if (h_ctr.max_depth <= (unsigned long long)MAX_PATH_LEVELS && !force_deep) {
-            const int bits_path = (int)h_ctr.max_depth;  // one bit per level
-            const int bits = bits_root + bits_depth + bits_path;
-            const bool narrow = bits <= 32;
-            DevBuf *k_in = temp((size_t)n_nodes * (narrow ? 4 : 8)), *k_out = temp((size_t)n_nodes * (narrow ? 4 : 8)), *v_out = temp((size_t)n_nodes * 4);
-            if (!k_in || !k_out || !v_out) return BMO_ERR_OOM;
-            hipLaunchKernelGGL(pack_keys_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->n_root.p, (const unsigned long long*)R->n_key.p, n_nodes, bits_depth,
-                               bits_path, narrow ? (uint32_t*)k_in->p : nullptr, narrow ? nullptr : (unsigned long long*)k_in->p);
-            size_t tmp_bytes = 0;
-            if (narrow) {
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const uint32_t*)k_in->p, (uint32_t*)k_out->p, (const int32_t*)R->order.p,
-                                                           (int32_t*)v_out->p, (int)n_nodes, 0, bits, stream));
-                DevBuf* st = temp(tmp_bytes);
-                if (!st) return BMO_ERR_OOM;
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(st->p, tmp_bytes, (const uint32_t*)k_in->p, (uint32_t*)k_out->p, (const int32_t*)R->order.p,
-                                                           (int32_t*)v_out->p, (int)n_nodes, 0, bits, stream));
-            } else {
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (const unsigned long long*)k_in->p, (unsigned long long*)k_out->p,
-                                                           (const int32_t*)R->order.p, (int32_t*)v_out->p, (int)n_nodes, 0, bits, stream));
-                DevBuf* st = temp(tmp_bytes);
-                if (!st) return BMO_ERR_OOM;
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(st->p, tmp_bytes, (const unsigned long long*)k_in->p, (unsigned long long*)k_out->p,
-                                                           (const int32_t*)R->order.p, (int32_t*)v_out->p, (int)n_nodes, 0, bits, stream));
-            }
-            std::swap(R->order.p, v_out->p);  // the sorted ids are the order; the iota goes to `keep`
-            std::swap(R->order.bytes, v_out->bytes);
-        } else {
-            // deep trees: ranks within each tree level, level by level, then sort by (root, depth, rank)
-            const int64_t md = (int64_t)h_ctr.max_depth;
-            const int32_t* parent = (const int32_t*)R->n_parent.p;
-            const unsigned long long* key = (const unsigned long long*)R->n_key.p;
-            DevBuf depth, depth_sorted, by_depth, starts, rank, flag, scan, k64, k64_out, ids2;
-            if ((rc = depth.alloc((size_t)n_nodes * 4)) || (rc = depth_sorted.alloc((size_t)n_nodes * 4)) || (rc = by_depth.alloc((size_t)n_nodes * 4)) ||
-                (rc = starts.alloc((size_t)(md + 2) * 4)) || (rc = rank.alloc((size_t)n_nodes * 4)) || (rc = flag.alloc((size_t)n_nodes * 4)) ||
-                (rc = scan.alloc((size_t)n_nodes * 4)) || (rc = k64.alloc((size_t)n_nodes * 8)) || (rc = k64_out.alloc((size_t)n_nodes * 8)) ||
-                (rc = ids2.alloc((size_t)n_nodes * 4)) || (rc = vals_out.alloc((size_t)n_nodes * 4)) || (rc = keys_in.alloc((size_t)n_nodes * 4)) ||
-                (rc = keys_out.alloc((size_t)n_nodes * 4)))
-                return rc;
-            hipLaunchKernelGGL(node_depth_kernel, dim3(nb), dim3(256), 0, stream, key, n_nodes, (uint32_t*)depth.p);
-            size_t tb = 0, tb2 = 0, tb3 = 0, tb4 = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t*)depth.p, (uint32_t*)depth_sorted.p, (const int32_t*)R->order.p,
-                                                       (int32_t*)by_depth.p, (int)n_nodes, 0, bits_depth, stream));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, (const int32_t*)flag.p, (int32_t*)scan.p, (int)n_nodes, stream));
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb3, (const uint32_t*)keys_in.p, (uint32_t*)keys_out.p, (const int32_t*)R->order.p,
-                                                       (int32_t*)ids2.p, (int)n_nodes, 0, 32, stream));
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb4, (const unsigned long long*)k64.p, (unsigned long long*)k64_out.p, (const int32_t*)ids2.p,
-                                                       (int32_t*)vals_out.p, (int)n_nodes, 0, 64, stream));
-            if ((rc = tmp.alloc(std::max(std::max(tb, tb2), std::max(tb3, tb4))))) return rc;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, (const uint32_t*)depth.p, (uint32_t*)depth_sorted.p, (const int32_t*)R->order.p,
-                                                       (int32_t*)by_depth.p, (int)n_nodes, 0, bits_depth, stream));
-            hipLaunchKernelGGL(level_starts_kernel, dim3(nb), dim3(256), 0, stream, (const uint32_t*)depth_sorted.p, n_nodes, md, (int32_t*)starts.p);
-            std::vector<int32_t> h_start((size_t)md + 2);
-            HIP_TRY(hipMemcpyAsync(h_start.data(), starts.p, (size_t)(md + 2) * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            const int32_t* ids = (const int32_t*)by_depth.p;
-            hipLaunchKernelGGL(level_root_rank_kernel, dim3((unsigned)((h_start[1] + 255) / 256)), dim3(256), 0, stream, ids, h_start[1], (int32_t*)rank.p);
-            int32_t max_level = h_start[1];
-            for (int64_t d = 1; d <= md; ++d) {
-                const int32_t cnt_prev = h_start[d] - h_start[d - 1], cnt = h_start[d + 1] - h_start[d];
-                if (cnt <= 0 || cnt_prev <= 0) continue;
-                max_level = std::max(max_level, cnt);
-                const unsigned lb = (unsigned)((cnt + 255) / 256);
-                HIP_TRY(hipMemsetAsync(flag.p, 0, (size_t)cnt_prev * 4, stream));
-                hipLaunchKernelGGL(level_flag_kernel, dim3(lb), dim3(256), 0, stream, ids + h_start[d], cnt, parent, key, (const int32_t*)rank.p, (int32_t*)flag.p);
-                size_t t = tmp.bytes;
-                HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, t, (const int32_t*)flag.p, (int32_t*)scan.p, (int)cnt_prev, stream));
-                hipLaunchKernelGGL(level_rank_kernel, dim3(lb), dim3(256), 0, stream, ids + h_start[d], cnt, parent, key, (const int32_t*)scan.p, (int32_t*)rank.p);
-            }
-            // LSD: by rank within the level, then (stable) by (root, depth)
-            hipLaunchKernelGGL(gather_u32_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)rank.p, n_nodes, (uint32_t*)keys_in.p);
-            size_t t3 = tmp.bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, t3, (const uint32_t*)keys_in.p, (uint32_t*)keys_out.p, (const int32_t*)R->order.p, (int32_t*)ids2.p,
-                                                       (int)n_nodes, 0, bits_for((unsigned long long)max_level), stream));
-            hipLaunchKernelGGL(root_depth_key_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)ids2.p, (const int32_t*)R->n_root.p, key, n_nodes, bits_depth,
-                               (unsigned long long*)k64.p);
-            size_t t4 = tmp.bytes;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, t4, (const unsigned long long*)k64.p, (unsigned long long*)k64_out.p, (const int32_t*)ids2.p,
-                                                       (int32_t*)vals_out.p, (int)n_nodes, 0, bits_root + bits_depth, stream));
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(stream));  // the level tables go back to the pool
-            std::swap(R->order.p, vals_out.p);
-            std::swap(R->order.bytes, vals_out.bytes);
-        }
-    }
-    lap("order");
-    // ---- detector hits in reference push! order: flags -> exclusive scan -> gather
-    const int nd = R->n_detectors;
-    R->det_count.assign(nd, 0);
-    R->det_offset.assign(nd, 0);
-    const bool with_hits = nd > 0 && n_nodes > 0;
-    if (with_hits) {
-        const int64_t tot = (int64_t)nd * n_nodes;
-        if (tot >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "detectors x beams exceeds 2^31: split the batch");
-        if (nd + 1 > 1024) return fail(BMO_ERR_UNSUPPORTED, "more than 1023 detectors");
-        DevBuf *flags = temp((size_t)tot * 4), *offs = temp((size_t)tot * 4), *d_off = temp((size_t)(nd + 1) * 4);
-        if (!flags || !offs || !d_off) return BMO_ERR_OOM;
-        hipLaunchKernelGGL(hit_flags_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, n_nodes, nd,
-                           nsub, (int32_t*)flags->p);
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)flags->p, (int32_t*)offs->p, (int)tot, stream));
-        DevBuf* st = temp(tmp_bytes);
-        if (!st) return BMO_ERR_OOM;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(st->p, tmp_bytes, (const int32_t*)flags->p, (int32_t*)offs->p, (int)tot, stream));
-        // per-detector offsets = scan value at the start of each detector's segment; total = last offs + last flag
-        hipLaunchKernelGGL(hit_offsets_kernel, dim3(1), dim3(1024), 0, stream, (const int32_t*)offs->p, (const int32_t*)flags->p, n_nodes, nd, (int32_t*)d_off->p);
-        HIP_TRY(hipMemcpyAsync(h_off, d_off->p, (size_t)(nd + 1) * 4, hipMemcpyDeviceToHost, stream));
-        // the hit table is sized before the counts are back on the host: a beam with a hit has ended and every splitting beam has two
-        // children, so there are at most (beams + roots) / 2 of them
-        const int64_t bound = (n_nodes + n) / 2 * nsub + nsub;
-        if ((rc = R->det_data.alloc((size_t)std::max<int64_t>(bound, 1) * 72)) || (rc = R->det_node.alloc((size_t)std::max<int64_t>(bound, 1) * 4))) return rc;
-        hipLaunchKernelGGL(hit_gather_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p,
-                           (const double*)R->n_hit.p, n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p,
-                           &d_ctr->overflow);
-    }
-    HIP_TRY(hipMemcpyAsync(h_ctr_p, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(ev_t1, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipGetLastError());
-    lap("hits");
-    if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
-    {
-        unsigned long long tot = 0;
-        for (int q = 0; q < 64; ++q) tot += h_sh[(size_t)q * 16];
-        R->calls = tot;
-        R->n_records = (int64_t)*h_sum;
-    }
-    if (with_hits)
-        for (int d = 0; d < nd; ++d) {
-            R->det_offset[d] = h_off[d];
-            R->det_count[d] = h_off[d + 1] - h_off[d];
-        }
-    float tms = 0;
-    HIP_TRY(hipEventElapsedTime(&tms, ev_t0, ev_t1));
-    R->total_ms = tms;
-    return BMO_OK;
-}
+#include "bmo_trace_host.inc.hpp"
 
 // bmo_selftest: the branch-free forms of bmo_lane.hpp against the rules they stand for, bitwise
 __global__ void selftest_minmax_kernel(const double* __restrict__ v, int n, int32_t* __restrict__ bad) {
@@ -3512,23 +2724,17 @@ int batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_
     if (!order_roots) root_order = "none";
     if (in->n >= 4096 && scene->hdr.n_cands > 0 && scene->bound[3] > 0.0 && (root_order == "chord" || root_order == "auto")) {
         const int64_t n = in->n;
-        DevBuf chord, lim, keys, keys_out, ids, tmp;
+        DevBuf chord, lim, keys, keys_out, ids;
+        Temps tmp;  // (the reductions and the sort share its scratch block)
         if ((rc = chord.alloc((size_t)n * 6 * 8)) || (rc = lim.alloc(13 * 8)) || (rc = keys.alloc((size_t)n * 8)) || (rc = keys_out.alloc((size_t)n * 8)) ||
             (rc = ids.alloc((size_t)n * 4)) || (rc = b->perm.alloc((size_t)n * 4)))
             return rc;
         const unsigned nb = (unsigned)((n + 255) / 256);
         hipLaunchKernelGGL(root_chord_kernel, dim3(nb), dim3(256), 0, nullptr, (const double*)b->planes.p, n, scene->bound[0], scene->bound[1], scene->bound[2],
                            scene->bound[3], (double*)chord.p);
-        size_t tb = 0, tb2 = 0;
-        HIP_TRY(hipcub::DeviceReduce::Min(nullptr, tb, (const double*)chord.p, (double*)lim.p, (int)n, nullptr));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb2, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
-                                                   (int32_t*)b->perm.p, (int)n, 0, 64, nullptr));
-        if ((rc = tmp.alloc(std::max(tb, tb2)))) return rc;
         for (int q = 0; q < 6; ++q) {
-            size_t t1 = tmp.bytes;
-            HIP_TRY(hipcub::DeviceReduce::Min(tmp.p, t1, (const double*)chord.p + (size_t)q * n, (double*)lim.p + q, (int)n, nullptr));
-            t1 = tmp.bytes;
-            HIP_TRY(hipcub::DeviceReduce::Max(tmp.p, t1, (const double*)chord.p + (size_t)q * n, (double*)lim.p + 6 + q, (int)n, nullptr));
+            CUB_TRY(tmp, hipcub::DeviceReduce::Min(cub_tmp, cub_bytes, (const double*)chord.p + (size_t)q * n, (double*)lim.p + q, (int)n, nullptr));
+            CUB_TRY(tmp, hipcub::DeviceReduce::Max(cub_tmp, cub_bytes, (const double*)chord.p + (size_t)q * n, (double*)lim.p + 6 + q, (int)n, nullptr));
         }
         bool own_order = false;  // keep the bundle's own numbering (+ the candidate-set bins below)
         if (root_order == "auto") {
@@ -3546,9 +2752,8 @@ int batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_
         root_order = "chord";
         hipLaunchKernelGGL(root_order_key_kernel, dim3(nb), dim3(256), 0, nullptr, (const double*)chord.p, n, (const double*)lim.p, (unsigned long long*)keys.p,
                            (int32_t*)ids.p);
-        size_t t2 = tmp.bytes;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, t2, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
-                                                   (int32_t*)b->perm.p, (int)n, 0, 64, nullptr));
+        CUB_TRY(tmp, hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
+                                                        (int32_t*)b->perm.p, (int)n, 0, 64, nullptr));
         if ((rc = b->binned.alloc((size_t)n * in->n_planes * 8))) return rc;
         hipLaunchKernelGGL(bin_planes_kernel, dim3(nb), dim3(256), 0, nullptr, (const double*)b->planes.p, (const int32_t*)b->perm.p, n, (int)in->n_planes,
                            (double*)b->binned.p);
@@ -3561,17 +2766,14 @@ int batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_
         const char* dblob = scene->device_blob(device, rc);
         if (rc) return rc;
         const int64_t n = in->n;
-        DevBuf keys, keys_out, ids, tmp;
+        DevBuf keys, keys_out, ids;
+        Temps tmp;
         if ((rc = keys.alloc((size_t)n * 8)) || (rc = keys_out.alloc((size_t)n * 8)) || (rc = ids.alloc((size_t)n * 4)) || (rc = b->perm.alloc((size_t)n * 4))) return rc;
         hipLaunchKernelGGL(root_key_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dblob, scene->hdr, (const double*)b->planes.p, n,
                            (unsigned long long*)keys.p, (int32_t*)ids.p);
         const int bits = std::min(64, std::max(1, scene->hdr.n_cands));
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
-                                                   (int32_t*)b->perm.p, (int)n, 0, bits, nullptr));
-        if ((rc = tmp.alloc(tb))) return rc;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
-                                                   (int32_t*)b->perm.p, (int)n, 0, bits, nullptr));
+        CUB_TRY(tmp, hipcub::DeviceRadixSort::SortPairs(cub_tmp, cub_bytes, (const unsigned long long*)keys.p, (unsigned long long*)keys_out.p, (const int32_t*)ids.p,
+                                                        (int32_t*)b->perm.p, (int)n, 0, bits, nullptr));
         unsigned long long k0 = 0, k1 = 0;
         HIP_TRY(hipMemcpy(&k0, keys_out.p, 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(&k1, (const char*)keys_out.p + (size_t)(n - 1) * 8, 8, hipMemcpyDeviceToHost));
@@ -3609,12 +2811,7 @@ static int trace_or_retrace(bmo_scene* scene, bmo_device_batch* batch, const bmo
         return fail(BMO_ERR_INVALID, "retrace: the scene does not have the object numbering the previous solution was solved with");
     auto R = std::make_unique<bmo_trace_result>();
     R->n_objects = scene->hdr.n_objects;
-    int rc;
-    if (batch->kind == BMO_BEAM_RAY) rc = run_trace<BMO_BEAM_RAY>(scene, batch, opts, R.get(), prev);
-    else if (batch->kind == BMO_BEAM_POLARIZED) rc = run_trace<BMO_BEAM_POLARIZED>(scene, batch, opts, R.get(), prev);
-    else if (batch->kind == BMO_BEAM_GAUSSIAN) rc = run_trace<BMO_BEAM_GAUSSIAN>(scene, batch, opts, R.get(), prev);
-    else return fail(BMO_ERR_UNSUPPORTED, "beam kind not built yet");
-    if (rc) return rc;
+    if (int rc = trace_by_kind(scene, batch, opts, R.get(), prev)) return rc;
     *out = R.release();
     return BMO_OK;
 }
@@ -3670,10 +2867,7 @@ int bmo_trace_sweep(bmo_scene* sweep, const bmo_ray_batch* in, const int32_t* ro
     R->root_cfg.assign(root_config, root_config + in->n);
     if ((rc = R->d_root_cfg.alloc((size_t)std::max<int64_t>(in->n, 1) * 4))) return rc;
     if (in->n) HIP_TRY(hipMemcpy(R->d_root_cfg.p, root_config, (size_t)in->n * 4, hipMemcpyHostToDevice));
-    if (b->kind == BMO_BEAM_RAY) rc = run_trace<BMO_BEAM_RAY>(sweep, b, opts, R.get());
-    else if (b->kind == BMO_BEAM_POLARIZED) rc = run_trace<BMO_BEAM_POLARIZED>(sweep, b, opts, R.get());
-    else rc = run_trace<BMO_BEAM_GAUSSIAN>(sweep, b, opts, R.get());
-    if (rc) return rc;
+    if ((rc = trace_by_kind(sweep, b, opts, R.get(), nullptr))) return rc;
     *out = R.release();
     return BMO_OK;
 }
@@ -3726,7 +2920,8 @@ int bmo_result_view_select(bmo_trace_result* r, uint32_t what, bmo_trace_result_
     if (!r->nodes_viewed) {
         // canonical node tables on the device, one pinned copy each
         const size_t n1 = (size_t)std::max<int64_t>(nn, 1);
-        DevBuf d_root, d_parent, d_fc, d_nseg, d_status, d_aux, d_last, tmp;
+        DevBuf d_root, d_parent, d_fc, d_nseg, d_status, d_aux, d_last;
+        Temps tmp;
         if ((rc = r->c_rank.alloc(n1 * 4)) || (rc = r->c_first_rec.alloc(n1 * 4)) || (rc = d_root.alloc(n1 * 4)) || (rc = d_parent.alloc(n1 * 4)) ||
             (rc = d_fc.alloc(n1 * 4)) || (rc = d_nseg.alloc(n1 * 4)) || (rc = d_status.alloc(n1 * 4)) || (rc = d_aux.alloc(n1 * 32)) ||
             (rc = r->h_root.alloc(n1 * 4)) || (rc = r->h_parent.alloc(n1 * 4)) || (rc = r->h_first_child.alloc(n1 * 4)) || (rc = r->h_first_rec.alloc(n1 * 4)) ||
@@ -3739,10 +2934,7 @@ int bmo_result_view_select(bmo_trace_result* r, uint32_t what, bmo_trace_result_
                                r->kind == BMO_BEAM_GAUSSIAN ? 1 : 0, (const int32_t*)r->n_root.p, (const int32_t*)r->n_parent.p, (const int32_t*)r->n_nseg.p,
                                (const int32_t*)r->n_status.p, (const unsigned long long*)r->n_key.p, (const double*)r->n_lambda.p, (const double*)r->n_aux.p,
                                (int32_t*)d_root.p, (int32_t*)d_parent.p, (int32_t*)d_fc.p, (int32_t*)d_nseg.p, (int32_t*)d_status.p, (double*)d_aux.p);
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int32_t*)d_nseg.p, (int32_t*)r->c_first_rec.p, (int)nn, (hipStream_t)0));
-            if ((rc = tmp.alloc(tb))) return rc;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, (const int32_t*)d_nseg.p, (int32_t*)r->c_first_rec.p, (int)nn, (hipStream_t)0));
+            CUB_TRY(tmp, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)d_nseg.p, (int32_t*)r->c_first_rec.p, (int)nn, (hipStream_t)0));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(r->h_root.p, d_root.p, (size_t)nn * 4, hipMemcpyDeviceToHost, 0));
             HIP_TRY(hipMemcpyAsync(r->h_parent.p, d_parent.p, (size_t)nn * 4, hipMemcpyDeviceToHost, 0));

@@ -506,10 +506,7 @@ static int pd_tables(bmo_trace_result* res, int32_t detector, int64_t H, hipStre
     hipLaunchKernelGGL(pd_hit_nodes_kernel, dim3(hb), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
                        (const int32_t*)res->order.p, (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p, (const double*)res->n_lambda.p,
                        (const double*)res->det_data.p, (int32_t*)T.hit_node.p, (int32_t*)T.hit_nseg.p, (int32_t*)T.node_hit.p, (double*)T.hs.p, prefix_of(res));
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
-    if ((rc = T.tmp.alloc(tmp_bytes))) return rc;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(T.tmp.p, tmp_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
+    CUB_TRY(scratch_in(T.tmp), hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
     int32_t last_start = 0, last_n = 0;
     HIP_TRY(hipMemcpyAsync(&last_start, (const int32_t*)T.seg_start.p + H - 1, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last_n, (const int32_t*)T.hit_nseg.p + H - 1, 4, hipMemcpyDeviceToHost, st));
