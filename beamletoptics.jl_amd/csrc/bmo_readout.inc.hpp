@@ -77,6 +77,8 @@ __global__ void psf_reduce_kernel(const double2* __restrict__ partial, int32_t n
 
 // workgroup rows of the sum of n_hits hits on a grid of pt_blocks x 256 points: enough workgroups to fill 256 CUs several times over, but
 // never splits shorter than one LDS tile
+// (tests/readout_ref.py restates this function and pd_splits below, to assert which path a test shape takes; tests/test_readout_reference.py
+// reads PSF_TILE and the two workgroup targets, 4096 and 2048, from this text: keep them in step)
 static void psf_splits(int64_t n_hits, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
     n_splits = (4096 + pt_blocks - 1) / pt_blocks;
     const int64_t max_splits = (n_hits + PSF_TILE - 1) / PSF_TILE;

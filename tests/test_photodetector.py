@@ -246,6 +246,133 @@ def test_gpu_photodetector_field_matches_oracle(oracle, n):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("nx,ny", [(48, 17), (1, 33), (300, 1)])
+def test_gpu_photodetector_field_on_a_non_square_grid(oracle, nx, ny):
+    """nx != ny with unequal axes: the kernel's pt % nx, pt / nx split and the [i + nx*j] layout (Photodetector(l, n) is always square)."""
+    system, pd, bundle = pd_scene(7)
+    scene = bmo.CompiledScene(system, bundle.lambdas)
+    a, osol = oracle.trace(scene, bundle, 20, threads=16, keep=True)
+    g, gsol = bmo.system._engine_solve(scene, bundle, 20, None)
+    try:
+        compare(g, a, 0.0, "pd scene")
+        xs = bmo.linalg.linrange(-0.30 * mm, 0.45 * mm, nx)  # the spots of the bundle are inside, off the centre of both axes
+        ys = bmo.linalg.linrange(-0.25 * mm, 0.40 * mm, ny)
+        fa = np.zeros((nx, ny), dtype=np.complex128)
+        fg = fa.copy()
+        osol.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, fa)
+        gsol.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, fg)
+        assert fg.shape == (nx, ny) and fg.dtype == np.complex128
+        peak = np.abs(fa).max()
+        assert peak > 0
+        assert np.abs(fg - fa).max() <= 1e-9 * peak
+        # [i, j] is the point (xs[i], ys[j]): the oracle on that single point, for the peak and three more points
+        i0, j0 = np.unravel_index(np.abs(fa).argmax(), fa.shape)
+        for i, j in {(int(i0), int(j0)), (0, 0), (nx - 1, 0), (0, ny - 1), (nx // 3, ny // 2)}:
+            one = np.zeros((1, 1), dtype=np.complex128)
+            osol.photodetector_field(0, pd.position(), pd.orientation(), xs[i:i + 1], ys[j:j + 1], one)
+            assert abs(fg[i, j] - one[0, 0]) <= 1e-9 * peak, (i, j)
+        # the call adds to the caller's field
+        fg2 = fg.copy()
+        gsol.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, fg2)
+        assert np.abs(fg2 - 2 * fg).max() <= 1e-12 * peak
+    finally:
+        gsol.free()
+        osol.free()
+
+
+# Pointwise bound of the tail checks.  Oracle and kernel run the same expression sequence on bit-identical records, so z, r, w, R, psi, ph and
+# ref_phi are the same doubles on both sides and only the library functions differ: exp(-r^2 / w^2), sincos(ph) and sincos(ref_phi).  OpenCL's
+# FP64 bound on the device is 4 ulp for exp and for each component of sincos, glibc's on the host is 1 ulp: 5 ulp per factor, three
+# factors, 15 ulp; the two complex products and the scalings after them are about ten correctly rounded operations, half an ulp each on
+# each side: 10 ulp more, and sqrt(2) for the modulus of a complex error: roughly 30 ulp.  Doubled: 64 ulp of 2^-52, relative to |f| at the point
+# itself, so the Gaussian tail is checked as strictly as the peak.
+TAIL_ULPS = 64
+TAIL_FLOOR = 1e-290  # below it the field runs into subnormal numbers, where an ulp is no longer relative
+
+
+def _tail_scene():
+    """One root GaussianBeamlet (w0 = 0.1 mm, 0.334 mm radius after 100 mm of free space), slightly oblique, on a tilted, decentred
+    Photodetector 10.6 mm wide: more than 30 beam radii."""
+    pd = bmo.Photodetector(10.6 * mm, 65)
+    bmo.xrotate3d(pd, math.radians(7))
+    bmo.zrotate3d(pd, math.radians(4))
+    bmo.translate3d(pd, [0.3 * mm, 0.1, -0.2 * mm])
+    beam = bmo.GaussianBeamlet([0, 0, 0], [0.002, 1, -0.003], 1e-6, 0.1 * mm, P0=1e-3)
+    return bmo.System([pd]), pd, bmo.RayBundle.from_beams([beam])
+
+
+def _tail_check(fg, fa, scale):
+    """fg against fa within TAIL_ULPS ulp of `scale` (the modulus of the field, or the sum of the beamlets' moduli) at every point."""
+    peak = np.abs(fa).max()
+    assert peak > 0 and np.isfinite(fa.view(np.float64)).all() and np.isfinite(fg.view(np.float64)).all()
+    assert np.abs(fa).min() < 1e-100 * peak  # the grid reaches the far tail ...
+    live = scale > TAIL_FLOOR
+    assert live.mean() >= 0.9, live.mean()  # ... and nearly all of it is above the subnormal range, so it is checked
+    rel = np.abs(fg - fa)[live] / scale[live]
+    print("tail check: %d points, %.1f %% checked, min |f| / peak %.3g, max error %.2f ulp" % (fa.size, 100 * live.mean(), np.abs(fa).min() / peak, rel.max() * 2.0 ** 52))
+    assert rel.max() <= TAIL_ULPS * 2.0 ** -52, (rel.max() * 2.0 ** 52, np.unravel_index(rel.argmax(), rel.shape))
+    assert np.abs(fg - fa).max() <= 1e-9 * peak
+
+
+@pytest.mark.gpu
+def test_gpu_photodetector_field_tail_of_one_beamlet(oracle):
+    system, pd, bundle = _tail_scene()
+    scene = bmo.CompiledScene(system, bundle.lambdas)
+    a, osol = oracle.trace(scene, bundle, 20, keep=True)
+    g, gsol = bmo.system._engine_solve(scene, bundle, 20, None)
+    try:
+        compare(g, a, 0.0, "tail scene")
+        assert a.det_count[0] == 3  # one beamlet: three rows
+        o = np.array(pd.orientation())
+        assert np.count_nonzero(np.abs(o) > 1e-3) >= 8  # tilted: the x and y steps of the grid have (almost) no zero component
+        fa = np.zeros((len(pd.x), len(pd.y)), dtype=np.complex128)
+        fg = fa.copy()
+        osol.photodetector_field(0, pd.position(), pd.orientation(), pd.x, pd.y, fa)
+        gsol.photodetector_field(0, pd.position(), pd.orientation(), pd.x, pd.y, fg)
+        _tail_check(fg, fa, np.abs(fa))
+    finally:
+        gsol.free()
+        osol.free()
+
+
+@pytest.mark.gpu
+def test_gpu_photodetector_field_tail_of_three_beamlets(oracle):
+    """Three beamlets of pd_scene's bundle, which reach the detector through the train and the splitter (H = 3; a single root of that bundle
+    records one beamlet, three ROWS).  Their spots (22 um radius) are apart, so the error is measured against sum_h |E_h| at the point, the
+    moduli read out of the oracle one beamlet at a time."""
+    system, pd, bundle = pd_scene(3)
+    scene = bmo.CompiledScene(system, bundle.lambdas)
+    xs = bmo.linalg.linrange(-0.33 * mm, 0.33 * mm, 67)
+    ys = bmo.linalg.linrange(-0.40 * mm, 0.60 * mm, 53)
+    a, osol = oracle.trace(scene, bundle, 20, keep=True)
+    g, gsol = bmo.system._engine_solve(scene, bundle, 20, None)
+    try:
+        compare(g, a, 0.0, "pd scene")
+        assert a.det_count[0] == 9
+        fa = np.zeros((len(xs), len(ys)), dtype=np.complex128)
+        fg = fa.copy()
+        osol.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, fa)
+        gsol.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, fg)
+        scale = np.zeros(fa.shape)
+        total = np.zeros_like(fa)
+        for h in range(3):
+            one = bmo.RayBundle(bundle.kind, bundle.planes[:, h:h + 1].copy())
+            a1, osol1 = oracle.trace(scene, one, 20, keep=True)
+            assert a1.det_count[0] == 3
+            f1 = np.zeros_like(fa)
+            osol1.photodetector_field(0, pd.position(), pd.orientation(), xs, ys, f1)
+            osol1.free()
+            scale += np.abs(f1)
+            total += f1
+        assert np.abs(total - fa).max() <= 4 * 2.0 ** -52 * scale.max()  # the three read-outs are the terms of the sum
+        assert (np.abs(total - fa) <= 4 * 2.0 ** -52 * scale).all()
+        _tail_check(fg, fa, scale)
+    finally:
+        gsol.free()
+        osol.free()
+
+
+@pytest.mark.gpu
 def test_gpu_kat_michelson_sweep_with_retracing():
     beam = michelson_equal_arm_sweep(bmo.solve_system, 24)
     bmo.release(beam)
