@@ -1,12 +1,22 @@
 // bmo_readout.inc.hpp — detector read-out kernels (included by bmo_engine.hip; shares its pool / error helpers).
 //
+// Every read-out is one split-and-reduce pipeline: a grid of points times the recorded rows of a detector slot, summed per configuration.
+//   * The rows of configuration c are the consecutive range begin[c] .. begin[c] + count[c] - 1 of the slot (slot_ranges).  A single call is
+//     the K = 1 case: one configuration that owns every row.
+//   * SplitPlan cuts each range into splits (psf_splits / pd_splits: enough workgroups to fill the chip) and lists them as flat work items
+//     {h0, h1, cfg}; a configuration without rows has none.  Consecutive configurations whose items fit the grid's y limit and 1 GiB of
+//     partial sums form one launch.
+//   * An accumulate kernel (psf_accumulate_list_kernel / pd_field_kernel) runs one workgroup per (256 grid points, work item) and writes the
+//     item's partial sum to row `item - w0` of a [item][point] plane; reduce_splits_kernel sums each configuration's rows in split order
+//     and finishes (PSF: abs2, and the field when asked; Photodetector: added to the caller's field).  The result is deterministic for given
+//     (grid, counts); it re-associates the reference's sequential sum at split boundaries only.
+//   * The plan, the poses and the axes go up in one copy (Packed); one pair of events times the launches (EventTimer).
+//   * One exception: a PSF launch of one configuration runs psf_accumulate_kernel, the same sum with the split and the pose in the kernel
+//     arguments instead of the lists (see there).
+//
 // PSF intensity (PSFDetector.jl:190-237): an n x n grid of sample points times H recorded hits, one cis() per pair.
-//   * a workgroup owns 256 consecutive grid points (point index = i + n*j, i fastest like the reference's Matrix) and a
-//     contiguous range of hits ("split"); hits are staged through LDS in tiles of 256 x 9 doubles so every lane reads each
-//     hit from LDS (broadcast reads) instead of HBM;
-//   * each lane accumulates its point's complex sum over the split in hit order; the per-split partial sums are written to
-//     a [split][point] plane and reduced in split order by a second kernel, which also takes abs2.  The result is
-//     deterministic for a given (n, H); it re-associates the reference's sequential sum at split boundaries only.
+//   * a workgroup owns 256 consecutive grid points (point index = i + n*j, i fastest like the reference's Matrix); the hits of its split
+//     are staged through LDS in tiles of 256 x 9 doubles so every lane reads each hit from LDS (broadcast reads) instead of HBM;
 //   * arithmetic follows the reference expression by expression (p = origin + x*e1 + z*e2; l = dot(p - hit, dir);
 //     phase = k*(opl + l); acc += proj*cis(phase)), FP64, no contraction.
 namespace {
@@ -48,6 +58,22 @@ __device__ __forceinline__ double2 psf_sum_range(const double* __restrict__ hits
     return make_double2(re, im);
 }
 
+// One split of one configuration: rows h0 .. h1 - 1 of the slot.  Configuration c owns items first_work .. first_work + n_splits - 1.
+struct SplitWork {
+    int64_t h0, h1;
+    int32_t cfg, pad;
+};
+struct SplitCfg {
+    int64_t first_work;
+    int32_t n_splits, pad;  // 0: no rows
+};
+struct PsfPose {
+    d3 origin, e1, e2;
+};
+
+// A launch of one configuration, which every single call is: split blockIdx.y of its n_hits rows, the pose in the kernel arguments.  It does
+// what the list kernel below does for such a launch; it stays because its code is the faster one where a call has few workgroups and waits
+// on latency (the loop of 1 024-row calls of tools/psf_sweep_bench.py: 2.5 % less kernel time, profiles/readout_refactor_ab.txt).
 __global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split, const double* __restrict__ xs,
                                                              const double* __restrict__ zs, int32_t n, d3 origin, d3 e1, d3 e2, double2* __restrict__ partial) {
     __shared__ double tile[PSF_TILE * 9];
@@ -60,25 +86,67 @@ __global__ __launch_bounds__(256) void psf_accumulate_kernel(const double* __res
     if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = v;
 }
 
-__global__ void psf_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pts, double* __restrict__ intensity, double2* __restrict__ field) {
+// work item w0 + blockIdx.y, on its configuration's axes (xs, zs: [K][n]) and pose
+__global__ __launch_bounds__(256) void psf_accumulate_list_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, int64_t w0,
+                                                                  const PsfPose* __restrict__ pose, const double* __restrict__ xs,
+                                                                  const double* __restrict__ zs, int32_t n, double2* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = pt < n_pts;
+    const SplitWork W = work[w0 + blockIdx.y];
+    const PsfPose& C = pose[W.cfg];
+    const double2 v = psf_sum_range(hits, W.h0, W.h1, xs + (int64_t)W.cfg * n, zs + (int64_t)W.cfg * n, n, pt, live, C.origin, C.e1, C.e2, tile);
+    if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = v;
+}
+
+// what becomes of the sum (re, im) of point i = c * n_pts + pt
+struct PsfFinish {
+    double* intensity;
+    double2* field;  // nullptr: not asked for
+    __device__ void operator()(int64_t i, double re, double im) const {
+        intensity[i] = re * re + im * im;  // abs2
+        if (field) field[i] = make_double2(re, im);
+    }
+};
+struct PdFinish {
+    double2* field;  // the caller's: added to
+    __device__ void operator()(int64_t i, double re, double im) const {
+        double2* f = field + i;
+        *f = make_double2(f->x + re, f->y + im);
+    }
+};
+
+// configuration c0 + blockIdx.y: its splits (partial rows first_work - w0 ...) summed in split order; none: the sum is +0
+template <class Finish>
+__global__ void reduce_splits_kernel(const SplitCfg* __restrict__ cfg, int32_t c0, int64_t w0, const double2* __restrict__ partial, int64_t n_pts, Finish finish) {
     const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (pt >= n_pts) return;
+    const int32_t c = c0 + (int32_t)blockIdx.y;
+    const SplitCfg& C = cfg[c];
     double re = 0.0, im = 0.0;
-    for (int s = 0; s < n_splits; ++s) {
-        const double2 v = partial[(int64_t)s * n_pts + pt];
+    for (int s = 0; s < C.n_splits; ++s) {
+        const double2 v = partial[(C.first_work - w0 + s) * n_pts + pt];
         re += v.x;
         im += v.y;
     }
-    intensity[pt] = re * re + im * im;  // abs2
-    if (field) field[pt] = make_double2(re, im);
+    finish((int64_t)c * n_pts + pt, re, im);
+}
+
+// configuration of rows first_row + stride * h of the slot (det_node -> node -> root -> root_cfg)
+__global__ void row_cfg_kernel(const int32_t* __restrict__ det_node, int64_t first_row, int64_t stride, int64_t n, const int32_t* __restrict__ order,
+                               const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg, int32_t* __restrict__ out) {
+    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n) return;
+    out[h] = root_cfg[root[order[det_node[first_row + stride * h]]]];
 }
 
 }  // namespace
 
 // workgroup rows of the sum of n_hits hits on a grid of pt_blocks x 256 points: enough workgroups to fill 256 CUs several times over, but
 // never splits shorter than one LDS tile
-// (tests/readout_ref.py restates this function and pd_splits below, to assert which path a test shape takes; tests/test_readout_reference.py
-// reads PSF_TILE and the two workgroup targets, 4096 and 2048, from this text: keep them in step)
+// (tests/readout_ref.py restates this function, pd_splits below and SplitPlan's launches, to assert which path a test shape takes;
+// tests/test_readout_reference.py reads PSF_TILE and the two workgroup targets, 4096 and 2048, from this text: keep them in step)
 static void psf_splits(int64_t n_hits, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
     n_splits = (4096 + pt_blocks - 1) / pt_blocks;
     const int64_t max_splits = (n_hits + PSF_TILE - 1) / PSF_TILE;
@@ -90,6 +158,187 @@ static void psf_splits(int64_t n_hits, unsigned pt_blocks, int64_t& n_splits, in
     if (hits_per_split < PSF_TILE) hits_per_split = PSF_TILE;
     n_splits = n_hits > 0 ? (n_hits + hits_per_split - 1) / hits_per_split : 1;
 }
+// workgroup rows of the field sum of H beamlets on a grid of pt_blocks x 256 points: enough ranges to fill the chip when the grid is small
+static void pd_splits(int64_t H, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
+    n_splits = (2048 + pt_blocks - 1) / pt_blocks;
+    if (n_splits > H) n_splits = H;
+    if (n_splits > 65535) n_splits = 65535;
+    if (n_splits < 1) n_splits = 1;
+    hits_per_split = (H + n_splits - 1) / n_splits;
+    n_splits = (H + hits_per_split - 1) / hits_per_split;
+}
+
+// A pair of events around the launches of a read-out; destroyed on every path.
+struct EventTimer {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipStream_t st = 0;
+    int start(hipStream_t stream) {
+        st = stream;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        return BMO_OK;
+    }
+    // waits for everything queued so far; ms: nullptr if not asked for
+    int stop(double* ms) {
+        HIP_TRY(hipEventRecord(e1, st));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipGetLastError());
+        float f = 0;
+        HIP_TRY(hipEventElapsedTime(&f, e0, e1));
+        if (ms) *ms = f;
+        return BMO_OK;
+    }
+    ~EventTimer() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    EventTimer() = default;
+    EventTimer(const EventTimer&) = delete;
+    EventTimer& operator=(const EventTimer&) = delete;
+};
+
+// Small host arrays that go to the device in one buffer and one copy (a single call pays one upload for its plan, pose and axes).
+struct Packed {
+    std::vector<char> host;
+    DevBuf dev;
+    template <class T>
+    size_t add(const T* v, size_t count) {  // its offset, for at()
+        const size_t off = host.size(), bytes = count * sizeof(T);
+        host.resize(off + (bytes + 7) / 8 * 8);
+        if (bytes) memcpy(host.data() + off, v, bytes);
+        return off;
+    }
+    template <class T>
+    size_t add(const std::vector<T>& v) { return add(v.data(), v.size()); }
+    int upload(hipStream_t st) {
+        if (int rc = dev.alloc(host.size())) return rc;
+        if (!host.empty()) HIP_TRY(hipMemcpyAsync(dev.p, host.data(), host.size(), hipMemcpyHostToDevice, st));
+        return BMO_OK;
+    }
+    template <class T>
+    const T* at(size_t off) const { return (const T*)((const char*)dev.p + off); }
+};
+
+// rows begin[c] .. begin[c] + count[c] - 1 (units of `stride` rows, relative to the slot's first) belong to configuration c
+struct Ranges {
+    std::vector<int64_t> begin, count;
+};
+// The ranges of the H units of slot `detector`.  per_config: the result is a sweep's and each unit goes to its root's configuration (units
+// of one configuration are consecutive: rows are in root order, roots in configuration order); otherwise one configuration owns them all.
+static int slot_ranges(bmo_trace_result* res, int32_t detector, int64_t stride, int64_t H, int32_t K, bool per_config, const char* refusal, hipStream_t st, Ranges& R) {
+    R.begin.assign((size_t)K, 0);
+    R.count.assign((size_t)K, 0);
+    if (!per_config) {
+        R.count[0] = H;
+        return BMO_OK;
+    }
+    DevBuf row_cfg;
+    if (int rc = row_cfg.alloc((size_t)H * 4)) return rc;
+    hipLaunchKernelGGL(row_cfg_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], stride, H,
+                       (const int32_t*)res->order.p, (const int32_t*)res->n_root.p, (const int32_t*)res->d_root_cfg.p, (int32_t*)row_cfg.p);
+    std::vector<int32_t> rcfg((size_t)H);
+    HIP_TRY(hipMemcpyAsync(rcfg.data(), row_cfg.p, (size_t)H * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int64_t h = 0; h < H; ++h) {
+        const int32_t c = rcfg[(size_t)h];
+        if (c < 0 || c >= K || (h > 0 && c < rcfg[(size_t)h - 1])) return fail(BMO_ERR_INTERNAL, refusal);
+        if (R.count[(size_t)c]++ == 0) R.begin[(size_t)c] = h;
+    }
+    return BMO_OK;
+}
+
+// The splits of every configuration as one flat work list, and the launches that run it.
+struct SplitPlan {
+    struct Launch {
+        int32_t c0, nc;  // configurations c0 .. c0 + nc - 1
+        int64_t w0, nw;  // their work items
+    };
+    std::vector<int64_t> per_split;  // rows per split of every configuration
+    std::vector<SplitCfg> cfg;
+    std::vector<SplitWork> work;
+    std::vector<Launch> launches;
+    int64_t max_nw = 1;  // partial rows the largest launch writes
+
+    // configuration c is split exactly as a single call with R.count[c] rows splits them
+    SplitPlan(const Ranges& R, unsigned pt_blocks, int64_t n_pts, void (*splits)(int64_t, unsigned, int64_t&, int64_t&)) {
+        const int32_t K = (int32_t)R.count.size();
+        cfg.resize((size_t)K);
+        per_split.assign((size_t)K, 0);
+        for (int32_t c = 0; c < K; ++c) {
+            cfg[(size_t)c] = SplitCfg{(int64_t)work.size(), 0, 0};
+            const int64_t nh = R.count[(size_t)c];
+            if (nh == 0) continue;
+            int64_t ns, hps;
+            splits(nh, pt_blocks, ns, hps);
+            cfg[(size_t)c].n_splits = (int32_t)ns;
+            per_split[(size_t)c] = hps;
+            for (int64_t s = 0; s < ns; ++s) {
+                const int64_t h0 = s * hps, h1 = h0 + hps < nh ? h0 + hps : nh;
+                work.push_back(SplitWork{R.begin[(size_t)c] + h0, R.begin[(size_t)c] + h1, c, 0});
+            }
+        }
+        // launches: consecutive configurations whose splits fit the grid's y limit and 1 GiB of partial sums (a configuration that alone
+        // needs more goes alone; its split count is at most 65535)
+        const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)1 << 30) / (n_pts * 16)));
+        for (int32_t c = 0; c < K;) {
+            Launch b{c, 0, cfg[(size_t)c].first_work, 0};
+            while (c < K && b.nc < 65535 && (b.nc == 0 || b.nw + cfg[(size_t)c].n_splits <= cap)) b.nw += cfg[(size_t)c++].n_splits, ++b.nc;
+            launches.push_back(b);
+            max_nw = std::max(max_nw, b.nw);
+        }
+    }
+};
+
+// Runs the plan: accumulate(grid, launch, partial) queues the accumulate kernel of one launch, the reduction follows it.  `timer` is started
+// here unless the caller's timing began earlier; kernel_ms is read from it once everything has run.
+template <class Accumulate, class Finish>
+static int split_reduce(const SplitPlan& plan, const SplitCfg* d_cfg, int64_t n_pts, hipStream_t st, EventTimer& timer, double* kernel_ms, Accumulate&& accumulate,
+                        Finish finish) {
+    DevBuf partial;
+    if (int rc = partial.alloc((size_t)plan.max_nw * (size_t)n_pts * sizeof(double2))) return rc;
+    if (!timer.e0)
+        if (int rc = timer.start(st)) return rc;
+    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
+    for (const SplitPlan::Launch& b : plan.launches) {
+        if (b.nw > 0) accumulate(dim3(pt_blocks, (unsigned)b.nw), b, (double2*)partial.p);
+        hipLaunchKernelGGL(reduce_splits_kernel<Finish>, dim3(pt_blocks, (unsigned)b.nc), dim3(256), 0, st, d_cfg, b.c0, b.w0, (const double2*)partial.p, n_pts, finish);
+    }
+    return timer.stop(kernel_ms);
+}
+
+// The PSF of the K = R.count.size() configurations from the device rows `hits`: poses [K][3], axes [K][n], outputs [K][n * n].
+static int psf_read(const double* hits, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* xs, const double* zs, int32_t n,
+                    double* out_intensity, double* out_field, double* kernel_ms) {
+    const size_t K = R.count.size();
+    const int64_t n_pts = (int64_t)n * n;
+    hipStream_t st = 0;
+    const SplitPlan plan(R, (unsigned)((n_pts + 255) / 256), n_pts, psf_splits);
+    std::vector<PsfPose> pose(K);
+    for (size_t c = 0; c < K; ++c) {
+        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
+        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
+    }
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_pose = up.add(pose), o_xs = up.add(xs, K * n), o_zs = up.add(zs, K * n);
+    DevBuf d_int, d_field;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_int.alloc(K * n_pts * sizeof(double))) || (out_field && (rc = d_field.alloc(K * n_pts * sizeof(double2))))) return rc;
+    EventTimer timer;
+    auto accumulate = [&](dim3 grid, const SplitPlan::Launch& L, double2* partial) {
+        const size_t c = (size_t)L.c0;
+        if (L.nc == 1)
+            hipLaunchKernelGGL(psf_accumulate_kernel, grid, dim3(256), 0, st, hits + 9 * R.begin[c], R.count[c], plan.per_split[c], up.at<double>(o_xs) + c * n,
+                               up.at<double>(o_zs) + c * n, n, pose[c].origin, pose[c].e1, pose[c].e2, partial);
+        else
+            hipLaunchKernelGGL(psf_accumulate_list_kernel, grid, dim3(256), 0, st, hits, up.at<SplitWork>(o_work), L.w0, up.at<PsfPose>(o_pose),
+                               up.at<double>(o_xs), up.at<double>(o_zs), n, partial);
+    };
+    if ((rc = split_reduce(plan, up.at<SplitCfg>(o_cfg), n_pts, st, timer, kernel_ms, accumulate, PsfFinish{(double*)d_int.p, (double2*)d_field.p}))) return rc;
+    HIP_TRY(hipMemcpy(out_intensity, d_int.p, K * n_pts * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, K * n_pts * sizeof(double2), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
 
 extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
                                  const double* xs, const double* zs, int32_t n, int32_t device, double* out_intensity, double* out_field, double* kernel_ms) {
@@ -99,44 +348,37 @@ extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hit
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BMO_ERR_NO_DEVICE, "bmo_psf_intensity: no HIP device (there is no CPU fallback)");
     if (device < 0 || device >= ndev) return fail(BMO_ERR_INVALID, "bmo_psf_intensity: bad device ordinal");
     HIP_TRY(hipSetDevice(device));
-    const int64_t n_pts = (int64_t)n * n;
-    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    int64_t n_splits, hits_per_split;
-    psf_splits(n_hits, pt_blocks, n_splits, hits_per_split);
-
-    DevBuf d_hits, d_xs, d_zs, d_partial, d_int, d_field;
-    const double* hits_dev = hits;
-    int rc;
+    DevBuf d_hits;
     if (!hits_on_device && n_hits > 0) {
-        if ((rc = d_hits.alloc((size_t)n_hits * 9 * sizeof(double)))) return rc;
+        if (int rc = d_hits.alloc((size_t)n_hits * 9 * sizeof(double))) return rc;
         HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t)n_hits * 9 * sizeof(double), hipMemcpyHostToDevice));
-        hits_dev = (const double*)d_hits.p;
+        hits = (const double*)d_hits.p;
     }
-    if ((rc = d_xs.alloc((size_t)n * sizeof(double))) || (rc = d_zs.alloc((size_t)n * sizeof(double))) ||
-        (rc = d_partial.alloc((size_t)n_splits * n_pts * sizeof(double2))) || (rc = d_int.alloc((size_t)n_pts * sizeof(double))))
-        return rc;
-    if (out_field && (rc = d_field.alloc((size_t)n_pts * sizeof(double2)))) return rc;
-    HIP_TRY(hipMemcpy(d_xs.p, xs, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_zs.p, zs, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    hipEvent_t e0, e1v;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1v));
-    HIP_TRY(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(psf_accumulate_kernel, dim3(pt_blocks, (unsigned)n_splits), dim3(256), 0, 0, hits_dev, n_hits, hits_per_split, (const double*)d_xs.p,
-                       (const double*)d_zs.p, n, d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, (double2*)d_partial.p);
-    hipLaunchKernelGGL(psf_reduce_kernel, dim3(pt_blocks), dim3(256), 0, 0, (const double2*)d_partial.p, (int32_t)n_splits, n_pts, (double*)d_int.p,
-                       out_field ? (double2*)d_field.p : nullptr);
-    HIP_TRY(hipEventRecord(e1v, 0));
-    HIP_TRY(hipEventSynchronize(e1v));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1v));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1v);
-    if (kernel_ms) *kernel_ms = ms;
-    HIP_TRY(hipMemcpy(out_intensity, d_int.p, (size_t)n_pts * sizeof(double), hipMemcpyDeviceToHost));
-    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, (size_t)n_pts * sizeof(double2), hipMemcpyDeviceToHost));
-    return BMO_OK;
+    return psf_read(hits, Ranges{{0}, {n_hits}}, origin, e1, e2, xs, zs, n, out_intensity, out_field, kernel_ms);
+}
+
+// PSF intensity of every configuration of a sweep, from the rows still resident in the result (an ordinary result is one configuration)
+extern "C" int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                                       const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
+                                       double* kernel_ms) {
+    if (!res || !origins || !e1s || !e2s || !xs || !zs || !out_intensity || n <= 0) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad detector slot");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
+        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: the slot is not a PSFDetector's");
+    if (n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        std::fill(out_intensity, out_intensity + (size_t)n_configs * n_pts, 0.0);
+        if (out_field) std::fill(out_field, out_field + (size_t)n_configs * n_pts * 2, 0.0);
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    Ranges R;
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_intensity_sweep: rows out of configuration order", 0, R)) return rc;
+    return psf_read((const double*)res->det_data.p + 9 * res->det_offset[detector], R, origins, e1s, e2s, xs, zs, n, out_intensity, out_field, kernel_ms);
 }
 
 // ====================================================================================================================
@@ -150,7 +392,8 @@ extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hit
 //   5. pd_field_kernel       : 256 grid points per workgroup x a contiguous range of beamlets; per pair the reference's
 //                              expression sequence (point on the detector, projection on the beamlet axis, point_on_beam,
 //                              gauss_parameters, electric_field); partial sums per beamlet range
-//   6. pd_reduce_kernel      : sums the ranges in order and adds the result to the caller's field
+//   6. reduce_splits_kernel  : sums the ranges in order and adds the result to the caller's field
+// Steps 1 - 4 are pd_tables (bmo_gauss_parameters runs them for one beamlet), steps 5 - 6 the split-and-reduce pipeline above.
 namespace {
 
 enum { PD_SEG_PLANES = 24, PD_HS = 12 };
@@ -166,15 +409,17 @@ struct PdPrefix {
     __device__ int len(int32_t nd) const { return (start && nd < n_roots) ? start[nd + 1] - start[nd] : 0; }
 };
 
-__global__ void pd_hit_nodes_kernel(const int32_t* __restrict__ det_node, int64_t first_row, int64_t n_hits, const int32_t* __restrict__ order,
+
+// Beamlet h of the tables is the one recorded on slot rows first_row + 3 h .. + 2 (row 0 = {proj, 0, ...}), or, with canon >= 0, the one
+// beamlet is canonical node `canon` and proj = 1 (bmo_gauss_parameters).
+__global__ void pd_hit_nodes_kernel(const int32_t* __restrict__ det_node, int64_t first_row, int64_t canon, int64_t n_hits, const int32_t* __restrict__ order,
                                     const int32_t* __restrict__ nseg, const double* __restrict__ aux, const double* __restrict__ lambda,
-                                    const double* __restrict__ det_data, int32_t* __restrict__ hit_node, int32_t* __restrict__ hit_nseg,
-                                    int32_t* __restrict__ node_hit, double* __restrict__ hs, PdPrefix pre) {
+                                    const double* __restrict__ det_data, int32_t* __restrict__ hit_nseg, int32_t* __restrict__ node_hit,
+                                    double* __restrict__ hs, PdPrefix pre) {
     const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (h >= n_hits) return;
-    const int64_t row = first_row + 3 * h;  // three hit rows per beamlet, row 0 = {proj, 0, ...}
-    const int32_t nd = order[det_node[row]];
-    hit_node[h] = nd;
+    const int64_t row = first_row + 3 * h;
+    const int32_t nd = order[canon < 0 ? det_node[row] : canon];
     hit_nseg[h] = nseg[nd] + pre.len(nd);
     node_hit[nd] = (int32_t)h;
     double* s = hs + h * PD_HS;
@@ -183,7 +428,7 @@ __global__ void pd_hit_nodes_kernel(const int32_t* __restrict__ det_node, int64_
     s[2] = aux[(int64_t)nd * 4 + 2];
     s[3] = aux[(int64_t)nd * 4 + 3];
     s[4] = lambda[nd];
-    s[5] = det_data[row * 9 + 0];
+    s[5] = canon < 0 ? det_data[row * 9 + 0] : 1.0;
 }
 
 __global__ void pd_gather_kernel(Chunk c, const int32_t* __restrict__ node_hit, const int32_t* __restrict__ seg_start, int64_t total_segs,
@@ -274,7 +519,7 @@ struct PdGeom {
 };
 
 // The field of beamlets h0 .. h1 - 1 at detector point p1, summed in beamlet order (the blocked order of bmo_photodetector_field: one range
-// per workgroup row, the ranges summed by pd_reduce_kernel)
+// per workgroup row, the ranges summed by reduce_splits_kernel)
 __device__ __forceinline__ double2 pd_field_range(const d3& p1, int64_t h0, int64_t h1, const int32_t* __restrict__ seg_start, const int32_t* __restrict__ hit_nseg,
                                                   int64_t total_segs, const double* __restrict__ segs, const double* __restrict__ cum, const double* __restrict__ hs) {
     double fre = 0.0, fim = 0.0;
@@ -317,95 +562,25 @@ __device__ __forceinline__ double2 pd_field_range(const d3& p1, int64_t h0, int6
     return make_double2(fre, fim);
 }
 
-__global__ __launch_bounds__(256) void pd_field_kernel(int64_t n_hits, int64_t hits_per_split, const int32_t* __restrict__ seg_start,
-                                                       const int32_t* __restrict__ hit_nseg, int64_t total_segs, const double* __restrict__ segs,
-                                                       const double* __restrict__ cum, const double* __restrict__ hs, PdGeom G,
+// work item w0 + blockIdx.y at the points of its configuration's detector pose
+__global__ __launch_bounds__(256) void pd_field_kernel(const SplitWork* __restrict__ work, int64_t w0, const PdGeom* __restrict__ geom,
+                                                       const int32_t* __restrict__ seg_start, const int32_t* __restrict__ hit_nseg, int64_t total_segs,
+                                                       const double* __restrict__ segs, const double* __restrict__ cum, const double* __restrict__ hs,
                                                        const double* __restrict__ xs, const double* __restrict__ ys, int32_t nx, int32_t ny,
                                                        double2* __restrict__ partial) {
     const int64_t n_pts = (int64_t)nx * ny;
     const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (pt >= n_pts) return;
+    const SplitWork W = work[w0 + blockIdx.y];
+    const PdGeom& G = geom[W.cfg];
     const int i = (int)(pt % nx), j = (int)(pt / nx);
     const double x = xs[i], y = ys[j];
     const d3 p1{G.ox[0] * x + G.oy[0] * y + G.p[0], G.ox[1] * x + G.oy[1] * y + G.p[1], G.ox[2] * x + G.oy[2] * y + G.p[2]};
-    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
-    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
-    partial[(int64_t)blockIdx.y * n_pts + pt] = pd_field_range(p1, h0, h1, seg_start, hit_nseg, total_segs, segs, cum, hs);
+    partial[(int64_t)blockIdx.y * n_pts + pt] = pd_field_range(p1, W.h0, W.h1, seg_start, hit_nseg, total_segs, segs, cum, hs);
 }
 
-// Sweeps (bmo_photodetector_field_sweep): configuration c = cfg0 + blockIdx.z sums its own beamlets hit_begin .. hit_begin + n_hits - 1 at the
-// points of its own detector pose, split into ranges exactly as bmo_photodetector_field splits a solve that holds only those beamlets.
-struct PdSweepCfg {
-    int64_t hit_begin, n_hits, hits_per_split;
-    int32_t n_splits, pad;
-    PdGeom G;
-};
-__global__ __launch_bounds__(256) void pd_field_sweep_kernel(const PdSweepCfg* __restrict__ cfg, int32_t cfg0, int32_t max_splits, const int32_t* __restrict__ seg_start,
-                                                             const int32_t* __restrict__ hit_nseg, int64_t total_segs, const double* __restrict__ segs,
-                                                             const double* __restrict__ cum, const double* __restrict__ hs, const double* __restrict__ xs,
-                                                             const double* __restrict__ ys, int32_t nx, int32_t ny, double2* __restrict__ partial) {
-    const int64_t n_pts = (int64_t)nx * ny;
-    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const PdSweepCfg& C = cfg[cfg0 + (int32_t)blockIdx.z];
-    if (pt >= n_pts || (int32_t)blockIdx.y >= C.n_splits) return;
-    const int i = (int)(pt % nx), j = (int)(pt / nx);
-    const double x = xs[i], y = ys[j];
-    const PdGeom& G = C.G;
-    const d3 p1{G.ox[0] * x + G.oy[0] * y + G.p[0], G.ox[1] * x + G.oy[1] * y + G.p[1], G.ox[2] * x + G.oy[2] * y + G.p[2]};
-    const int64_t h0 = (int64_t)blockIdx.y * C.hits_per_split;
-    const int64_t h1 = h0 + C.hits_per_split < C.n_hits ? h0 + C.hits_per_split : C.n_hits;
-    partial[((int64_t)blockIdx.z * max_splits + blockIdx.y) * n_pts + pt] =
-        pd_field_range(p1, C.hit_begin + h0, C.hit_begin + h1, seg_start, hit_nseg, total_segs, segs, cum, hs);
-}
-__global__ void pd_reduce_sweep_kernel(const PdSweepCfg* __restrict__ cfg, int32_t cfg0, int32_t max_splits, const double2* __restrict__ partial, int64_t n_pts,
-                                       double2* __restrict__ field) {
-    const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pt >= n_pts) return;
-    const int32_t z = (int32_t)blockIdx.y, ns = cfg[cfg0 + z].n_splits;
-    double re = 0.0, im = 0.0;
-    for (int s = 0; s < ns; ++s) {
-        const double2 v = partial[((int64_t)z * max_splits + s) * n_pts + pt];
-        re += v.x;
-        im += v.y;
-    }
-    double2* f = field + (int64_t)(cfg0 + z) * n_pts + pt;
-    *f = make_double2(f->x + re, f->y + im);
-}
-// configuration of every recorded beamlet (node -> root -> root_cfg)
-__global__ void pd_hit_cfg_kernel(const int32_t* __restrict__ hit_node, int64_t n_hits, const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg,
-                                  int32_t* __restrict__ out) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= n_hits) return;
-    out[h] = root_cfg[root[hit_node[h]]];
-}
-
-__global__ void pd_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pts, double2* __restrict__ field) {
-    const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pt >= n_pts) return;
-    double re = 0.0, im = 0.0;
-    for (int s = 0; s < n_splits; ++s) {
-        const double2 v = partial[(int64_t)s * n_pts + pt];
-        re += v.x;
-        im += v.y;
-    }
-    field[pt] = make_double2(field[pt].x + re, field[pt].y + im);
-}
-
-// gauss_parameters(gauss, z) for one beamlet (slot 0 of the per-hit tables) at n values of z: the same gather / prepare / locate /
-// gauss_parameters_at sequence the Photodetector field runs per grid point
-__global__ void gp_pick_kernel(int64_t canon, const int32_t* __restrict__ order, const int32_t* __restrict__ nseg, const double* __restrict__ aux,
-                               const double* __restrict__ lambda, int32_t* __restrict__ hit_nseg, int32_t* __restrict__ node_hit, double* __restrict__ hs,
-                               PdPrefix pre) {
-    const int32_t nd = order[canon];
-    hit_nseg[0] = nseg[nd] + pre.len(nd);
-    node_hit[nd] = 0;
-    hs[0] = aux[(int64_t)nd * 4 + 0];
-    hs[1] = aux[(int64_t)nd * 4 + 1];
-    hs[2] = aux[(int64_t)nd * 4 + 2];
-    hs[3] = aux[(int64_t)nd * 4 + 3];
-    hs[4] = lambda[nd];
-    hs[5] = 1.0;
-}
+// gauss_parameters(gauss, z) for the one beamlet of the tables at n values of z: the same locate / gauss_parameters_at sequence the
+// Photodetector field runs per grid point
 __global__ void gp_eval_kernel(int32_t n, const double* __restrict__ zs, int ns, int64_t total_segs, const double* __restrict__ segs, const double* __restrict__ cum,
                                const double* __restrict__ hs, double* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -455,65 +630,31 @@ extern "C" int bmo_result_set_gauss_prefix(bmo_trace_result* res, int64_t n_root
     return BMO_OK;
 }
 
-extern "C" int bmo_gauss_parameters(bmo_trace_result* res, int64_t node, const double* zs, int32_t n, double* out) {
-    if (!res || !zs || !out || n <= 0) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: bad argument");
-    if (res->kind != BMO_BEAM_GAUSSIAN) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: not a GaussianBeamlet solution");
-    if (node < 0 || node >= res->n_nodes) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: bad beamlet index");
-    if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: the solution was solved with record_segments = 0 (no segments to evaluate)");
-    HIP_TRY(hipSetDevice(res->device));
-    int rc;
-    DevBuf hit_nseg, node_hit, seg_start, hs, segs, cum, d_z, d_out;
-    if ((rc = hit_nseg.alloc(4)) || (rc = node_hit.alloc((size_t)res->n_nodes * 4)) || (rc = seg_start.alloc(4)) || (rc = hs.alloc(PD_HS * 8)) ||
-        (rc = d_z.alloc((size_t)n * 8)) || (rc = d_out.alloc((size_t)n * 32)))
-        return rc;
-    hipStream_t st = 0;
-    HIP_TRY(hipMemsetAsync(node_hit.p, 0xFF, (size_t)res->n_nodes * 4, st));
-    HIP_TRY(hipMemsetAsync(hs.p, 0, PD_HS * 8, st));
-    HIP_TRY(hipMemsetAsync(seg_start.p, 0, 4, st));
-    hipLaunchKernelGGL(gp_pick_kernel, dim3(1), dim3(1), 0, st, node, (const int32_t*)res->order.p, (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p,
-                       (const double*)res->n_lambda.p, (int32_t*)hit_nseg.p, (int32_t*)node_hit.p, (double*)hs.p, prefix_of(res));
-    int32_t ns = 0;
-    HIP_TRY(hipMemcpyAsync(&ns, hit_nseg.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ns <= 0) return fail(BMO_ERR_INTERNAL, "bmo_gauss_parameters: beamlet without segments");
-    if ((rc = segs.alloc((size_t)ns * PD_SEG_PLANES * 8)) || (rc = cum.alloc((size_t)ns * 8))) return rc;
-    for (const Chunk& c : res->chunks)
-        if (c.count > 0)
-            hipLaunchKernelGGL(pd_gather_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, st, c, (const int32_t*)node_hit.p,
-                               (const int32_t*)seg_start.p, (int64_t)ns, (double*)segs.p, (double*)hs.p, prefix_of(res));
-    hipLaunchKernelGGL(pd_prepare_kernel, dim3(1), dim3(256), 0, st, (int64_t)1, (const int32_t*)seg_start.p, (const int32_t*)hit_nseg.p, (int64_t)ns,
-                       (const double*)segs.p, (double*)cum.p, (double*)hs.p);
-    HIP_TRY(hipMemcpyAsync(d_z.p, zs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gp_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const double*)d_z.p, (int)ns, (int64_t)ns, (const double*)segs.p,
-                       (const double*)cum.p, (const double*)hs.p, (double*)d_out.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return BMO_OK;
-}
-
-// Steps 1 - 4 of the Photodetector pipeline for the H beamlets recorded on `detector`: the compact segment table and the per-beamlet scalars.
+// Steps 1 - 4 of the Photodetector pipeline for H beamlets (pd_hit_nodes_kernel: slot rows from first_row, or node `canon`): the compact
+// segment table and the per-beamlet scalars.
 struct PdTables {
-    DevBuf hit_node, hit_nseg, node_hit, seg_start, hs, tmp, segs, cum;
+    DevBuf hit_nseg, node_hit, seg_start, hs, tmp, segs, cum;
     int64_t total_segs = 0;
 };
-static int pd_tables(bmo_trace_result* res, int32_t detector, int64_t H, hipStream_t st, PdTables& T) {
+static int pd_tables(bmo_trace_result* res, int64_t first_row, int64_t canon, int64_t H, hipStream_t st, const char* who, PdTables& T) {
     const int64_t nn = res->n_nodes;
     int rc;
-    if ((rc = T.hit_node.alloc((size_t)H * 4)) || (rc = T.hit_nseg.alloc((size_t)H * 4)) || (rc = T.node_hit.alloc((size_t)nn * 4)) ||
-        (rc = T.seg_start.alloc((size_t)H * 4)) || (rc = T.hs.alloc((size_t)H * PD_HS * 8)))
+    if ((rc = T.hit_nseg.alloc((size_t)H * 4)) || (rc = T.node_hit.alloc((size_t)nn * 4)) || (rc = T.seg_start.alloc((size_t)H * 4)) ||
+        (rc = T.hs.alloc((size_t)H * PD_HS * 8)))
         return rc;
     HIP_TRY(hipMemsetAsync(T.node_hit.p, 0xFF, (size_t)nn * 4, st));
     HIP_TRY(hipMemsetAsync(T.hs.p, 0, (size_t)H * PD_HS * 8, st));
     const unsigned hb = (unsigned)((H + 255) / 256);
-    hipLaunchKernelGGL(pd_hit_nodes_kernel, dim3(hb), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
-                       (const int32_t*)res->order.p, (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p, (const double*)res->n_lambda.p,
-                       (const double*)res->det_data.p, (int32_t*)T.hit_node.p, (int32_t*)T.hit_nseg.p, (int32_t*)T.node_hit.p, (double*)T.hs.p, prefix_of(res));
+    hipLaunchKernelGGL(pd_hit_nodes_kernel, dim3(hb), dim3(256), 0, st, (const int32_t*)res->det_node.p, first_row, canon, H, (const int32_t*)res->order.p,
+                       (const int32_t*)res->n_nseg.p, (const double*)res->n_aux.p, (const double*)res->n_lambda.p, (const double*)res->det_data.p,
+                       (int32_t*)T.hit_nseg.p, (int32_t*)T.node_hit.p, (double*)T.hs.p, prefix_of(res));
     CUB_TRY(scratch_in(T.tmp), hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)T.hit_nseg.p, (int32_t*)T.seg_start.p, (int)H, st));
     int32_t last_start = 0, last_n = 0;
     HIP_TRY(hipMemcpyAsync(&last_start, (const int32_t*)T.seg_start.p + H - 1, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last_n, (const int32_t*)T.hit_nseg.p + H - 1, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     T.total_segs = (int64_t)last_start + last_n;
+    if (T.total_segs <= 0) return fail(BMO_ERR_INTERNAL, std::string(who) + ": beamlet without segments");
     if ((rc = T.segs.alloc((size_t)T.total_segs * PD_SEG_PLANES * 8)) || (rc = T.cum.alloc((size_t)T.total_segs * 8))) return rc;
     for (const Chunk& c : res->chunks)
         if (c.count > 0)
@@ -523,15 +664,26 @@ static int pd_tables(bmo_trace_result* res, int32_t detector, int64_t H, hipStre
                        (const double*)T.segs.p, (double*)T.cum.p, (double*)T.hs.p);
     return BMO_OK;
 }
-// workgroup rows of the field sum of H beamlets on a grid of pt_blocks x 256 points: enough ranges to fill the chip when the grid is small
-static void pd_splits(int64_t H, unsigned pt_blocks, int64_t& n_splits, int64_t& hits_per_split) {
-    n_splits = (2048 + pt_blocks - 1) / pt_blocks;
-    if (n_splits > H) n_splits = H;
-    if (n_splits > 65535) n_splits = 65535;
-    if (n_splits < 1) n_splits = 1;
-    hits_per_split = (H + n_splits - 1) / n_splits;
-    n_splits = (H + hits_per_split - 1) / hits_per_split;
+
+extern "C" int bmo_gauss_parameters(bmo_trace_result* res, int64_t node, const double* zs, int32_t n, double* out) {
+    if (!res || !zs || !out || n <= 0) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: bad argument");
+    if (res->kind != BMO_BEAM_GAUSSIAN) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: not a GaussianBeamlet solution");
+    if (node < 0 || node >= res->n_nodes) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: bad beamlet index");
+    if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_gauss_parameters: the solution was solved with record_segments = 0 (no segments to evaluate)");
+    HIP_TRY(hipSetDevice(res->device));
+    int rc;
+    PdTables T;
+    DevBuf d_z, d_out;
+    hipStream_t st = 0;
+    if ((rc = pd_tables(res, 0, node, 1, st, "bmo_gauss_parameters", T)) || (rc = d_z.alloc((size_t)n * 8)) || (rc = d_out.alloc((size_t)n * 32))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_z.p, zs, (size_t)n * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(gp_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, (const double*)d_z.p, (int)T.total_segs, T.total_segs,
+                       (const double*)T.segs.p, (const double*)T.cum.p, (const double*)T.hs.p, (double*)d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    return BMO_OK;
 }
+
 static PdGeom pd_geom(const double position[3], const double orientation[9]) {
     PdGeom G;
     for (int k = 0; k < 3; ++k) {
@@ -542,6 +694,40 @@ static PdGeom pd_geom(const double position[3], const double orientation[9]) {
     return G;
 }
 
+// The field of the H beamlets of the slot added to field_inout [K][nx * ny], configuration c at pose c (positions [K][3], orientations
+// [K][9]).  order_refusal: the result is a sweep's and every beamlet counts for its own configuration; nullptr: one configuration has all.
+// kernel_ms covers everything on the device, the tables included.
+static int pd_read(bmo_trace_result* res, int32_t detector, int64_t H, int32_t K, const char* who, const char* order_refusal, const double* positions,
+                   const double* orientations, const double* xs, const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms) {
+    HIP_TRY(hipSetDevice(res->device));
+    const int64_t n_pts = (int64_t)nx * ny;
+    const size_t field_bytes = (size_t)K * n_pts * sizeof(double2);
+    hipStream_t st = 0;
+    int rc;
+    PdTables T;
+    Ranges R;
+    EventTimer timer;
+    if ((rc = timer.start(st)) || (rc = pd_tables(res, res->det_offset[detector], -1, H, st, who, T)) ||
+        (rc = slot_ranges(res, detector, 3, H, K, order_refusal != nullptr, order_refusal, st, R)))
+        return rc;
+    const SplitPlan plan(R, (unsigned)((n_pts + 255) / 256), n_pts, pd_splits);
+    std::vector<PdGeom> geom((size_t)K);
+    for (size_t c = 0; c < (size_t)K; ++c) geom[c] = pd_geom(positions + 3 * c, orientations + 9 * c);
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_geom = up.add(geom), o_xs = up.add(xs, (size_t)nx), o_ys = up.add(ys, (size_t)ny);
+    DevBuf d_field;
+    if ((rc = up.upload(st)) || (rc = d_field.alloc(field_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_field.p, field_inout, field_bytes, hipMemcpyHostToDevice, st));
+    auto accumulate = [&](dim3 grid, const SplitPlan::Launch& L, double2* partial) {
+        hipLaunchKernelGGL(pd_field_kernel, grid, dim3(256), 0, st, up.at<SplitWork>(o_work), L.w0, up.at<PdGeom>(o_geom), (const int32_t*)T.seg_start.p,
+                           (const int32_t*)T.hit_nseg.p, T.total_segs, (const double*)T.segs.p, (const double*)T.cum.p, (const double*)T.hs.p,
+                           up.at<double>(o_xs), up.at<double>(o_ys), nx, ny, partial);
+    };
+    if ((rc = split_reduce(plan, up.at<SplitCfg>(o_cfg), n_pts, st, timer, kernel_ms, accumulate, PdFinish{(double2*)d_field.p}))) return rc;
+    HIP_TRY(hipMemcpy(field_inout, d_field.p, field_bytes, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
 extern "C" int bmo_photodetector_field(bmo_trace_result* res, int32_t detector, const double position[3], const double orientation[9], const double* xs,
                                        const double* ys, int32_t nx, int32_t ny, double* field_inout, double* kernel_ms) {
     if (!res || !position || !orientation || !xs || !ys || !field_inout || nx <= 0 || ny <= 0) return fail(BMO_ERR_INVALID, "bmo_photodetector_field: bad argument");
@@ -550,44 +736,9 @@ extern "C" int bmo_photodetector_field(bmo_trace_result* res, int32_t detector, 
     if (res->kind != BMO_BEAM_GAUSSIAN) return BMO_OK;  // other beams leave no record (Photodetector.jl:57-60)
     const int64_t rows = res->det_count[detector];
     if (rows % 3) return fail(BMO_ERR_INVALID, "bmo_photodetector_field: slot does not hold photodetector records");
-    const int64_t H = rows / 3;
-    if (H == 0) return BMO_OK;
+    if (rows == 0) return BMO_OK;
     if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_photodetector_field: the solution was solved with record_segments = 0 (gauss_parameters needs the beamlets' segments)");
-    HIP_TRY(hipSetDevice(res->device));
-    const int64_t n_pts = (int64_t)nx * ny;
-    int rc;
-    PdTables T;
-    DevBuf d_xs, d_ys, partial, d_field;
-    hipStream_t st = 0;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, st));
-    if ((rc = pd_tables(res, detector, H, st, T))) return rc;
-    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    int64_t n_splits, hits_per_split;
-    pd_splits(H, pt_blocks, n_splits, hits_per_split);
-    if ((rc = d_xs.alloc((size_t)nx * 8)) || (rc = d_ys.alloc((size_t)ny * 8)) || (rc = partial.alloc((size_t)n_splits * n_pts * 16)) ||
-        (rc = d_field.alloc((size_t)n_pts * 16)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)nx * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ys.p, ys, (size_t)ny * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_field.p, field_inout, (size_t)n_pts * 16, hipMemcpyHostToDevice, st));
-    const PdGeom G = pd_geom(position, orientation);
-    hipLaunchKernelGGL(pd_field_kernel, dim3(pt_blocks, (unsigned)n_splits), dim3(256), 0, st, H, hits_per_split, (const int32_t*)T.seg_start.p,
-                       (const int32_t*)T.hit_nseg.p, T.total_segs, (const double*)T.segs.p, (const double*)T.cum.p, (const double*)T.hs.p, G,
-                       (const double*)d_xs.p, (const double*)d_ys.p, nx, ny, (double2*)partial.p);
-    hipLaunchKernelGGL(pd_reduce_kernel, dim3(pt_blocks), dim3(256), 0, st, (const double2*)partial.p, (int32_t)n_splits, n_pts, (double2*)d_field.p);
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (kernel_ms) *kernel_ms = ms;
-    HIP_TRY(hipMemcpy(field_inout, d_field.p, (size_t)n_pts * 16, hipMemcpyDeviceToHost));
-    return BMO_OK;
+    return pd_read(res, detector, rows / 3, 1, "bmo_photodetector_field", nullptr, position, orientation, xs, ys, nx, ny, field_inout, kernel_ms);
 }
 
 extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* positions, const double* orientations,
@@ -601,241 +752,8 @@ extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t dete
     if (res->kind != BMO_BEAM_GAUSSIAN) return BMO_OK;  // other beams leave no record (Photodetector.jl:57-60)
     const int64_t rows = res->det_count[detector];
     if (rows % 3) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: slot does not hold photodetector records");
-    const int64_t H = rows / 3;
-    if (H == 0) return BMO_OK;
+    if (rows == 0) return BMO_OK;
     if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: the solution was solved with record_segments = 0 (gauss_parameters needs the beamlets' segments)");
-    HIP_TRY(hipSetDevice(res->device));
-    const int64_t n_pts = (int64_t)nx * ny;
-    const int32_t K = n_configs;
-    int rc;
-    PdTables T;
-    DevBuf hit_cfg, d_cfg, d_xs, d_ys, partial, d_field;
-    hipStream_t st = 0;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, st));
-    if ((rc = pd_tables(res, detector, H, st, T))) return rc;
-    // the beamlets of a configuration are consecutive (hits are in root order, roots in configuration order): their range per configuration
-    if ((rc = hit_cfg.alloc((size_t)H * 4))) return rc;
-    hipLaunchKernelGGL(pd_hit_cfg_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (const int32_t*)T.hit_node.p, H, (const int32_t*)res->n_root.p,
-                       (const int32_t*)res->d_root_cfg.p, (int32_t*)hit_cfg.p);
-    std::vector<int32_t> hc((size_t)H);
-    HIP_TRY(hipMemcpyAsync(hc.data(), hit_cfg.p, (size_t)H * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    std::vector<PdSweepCfg> cfg((size_t)K);
-    for (int32_t c = 0; c < K; ++c) {
-        cfg[(size_t)c] = PdSweepCfg{};
-        cfg[(size_t)c].G = pd_geom(positions + 3 * (size_t)c, orientations + 9 * (size_t)c);
-    }
-    for (int64_t h = 0; h < H; ++h) {
-        const int32_t c = hc[(size_t)h];
-        if (c < 0 || c >= K || (h > 0 && c < hc[(size_t)h - 1])) return fail(BMO_ERR_INTERNAL, "bmo_photodetector_field_sweep: beamlets out of configuration order");
-        if (cfg[(size_t)c].n_hits++ == 0) cfg[(size_t)c].hit_begin = h;
-    }
-    int64_t max_splits = 1;
-    for (auto& C : cfg) {
-        if (C.n_hits == 0) continue;
-        int64_t ns, hps;
-        pd_splits(C.n_hits, pt_blocks, ns, hps);
-        C.n_splits = (int32_t)ns;
-        C.hits_per_split = hps;
-        max_splits = std::max(max_splits, ns);
-    }
-    // configurations per launch: grid z (at most 65535) and the partial sums held at once (at most 1 GiB of them)
-    const size_t per_cfg = (size_t)max_splits * (size_t)n_pts * 16;
-    const int32_t batch = (int32_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)K, 65535, (int64_t)(((size_t)1 << 30) / per_cfg)}));
-    if ((rc = d_cfg.alloc(sizeof(PdSweepCfg) * (size_t)K)) || (rc = d_xs.alloc((size_t)nx * 8)) || (rc = d_ys.alloc((size_t)ny * 8)) ||
-        (rc = partial.alloc(per_cfg * (size_t)batch)) || (rc = d_field.alloc((size_t)K * n_pts * 16)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(d_cfg.p, cfg.data(), sizeof(PdSweepCfg) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)nx * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_ys.p, ys, (size_t)ny * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_field.p, field_inout, (size_t)K * n_pts * 16, hipMemcpyHostToDevice, st));
-    for (int32_t c0 = 0; c0 < K; c0 += batch) {
-        const int32_t nz = std::min(batch, K - c0);
-        hipLaunchKernelGGL(pd_field_sweep_kernel, dim3(pt_blocks, (unsigned)max_splits, (unsigned)nz), dim3(256), 0, st, (const PdSweepCfg*)d_cfg.p, c0,
-                           (int32_t)max_splits, (const int32_t*)T.seg_start.p, (const int32_t*)T.hit_nseg.p, T.total_segs, (const double*)T.segs.p,
-                           (const double*)T.cum.p, (const double*)T.hs.p, (const double*)d_xs.p, (const double*)d_ys.p, nx, ny, (double2*)partial.p);
-        hipLaunchKernelGGL(pd_reduce_sweep_kernel, dim3(pt_blocks, (unsigned)nz), dim3(256), 0, st, (const PdSweepCfg*)d_cfg.p, c0, (int32_t)max_splits,
-                           (const double2*)partial.p, n_pts, (double2*)d_field.p);
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (kernel_ms) *kernel_ms = ms;
-    HIP_TRY(hipMemcpy(field_inout, d_field.p, (size_t)K * n_pts * 16, hipMemcpyDeviceToHost));
-    return BMO_OK;
-}
-
-// ====================================================================================================================
-// PSF intensity of every configuration of a sweep (bmo_psf_intensity_sweep), from the rows still resident in the result.  Configuration c
-// with H_c rows is split exactly as bmo_psf_intensity splits a call with n_hits = H_c (psf_splits) and summed by the same device code
-// (psf_sum_range, split partials reduced in split order, then abs2).  The (configuration, split) pairs form one flat work list, the second
-// grid dimension, so configurations with few or no rows launch no empty workgroups.
-namespace {
-
-struct PsfSweepCfg {
-    d3 origin, e1, e2;   // detector pose of the configuration
-    int64_t first_work;  // its first split in the work list
-    int32_t n_splits;    // 0: no rows
-    int32_t pad;
-};
-struct PsfWork {
-    int64_t h0, h1;  // rows h0 .. h1 - 1 of the slot
-    int32_t cfg, pad;
-};
-
-// configuration of every row of the slot (det_node -> node -> root -> root_cfg, as pd_hit_cfg_kernel)
-__global__ void psf_row_cfg_kernel(const int32_t* __restrict__ det_node, int64_t first_row, int64_t n_rows, const int32_t* __restrict__ order,
-                                   const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg, int32_t* __restrict__ out) {
-    const int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= n_rows) return;
-    out[h] = root_cfg[root[order[det_node[first_row + h]]]];
-}
-
-// work item w0 + blockIdx.y: one split of one configuration, on that configuration's axes (xs, zs: [K][n]) and pose
-__global__ __launch_bounds__(256) void psf_accumulate_sweep_kernel(const double* __restrict__ hits, const PsfWork* __restrict__ work, int64_t w0,
-                                                                   const PsfSweepCfg* __restrict__ cfg, const double* __restrict__ xs,
-                                                                   const double* __restrict__ zs, int32_t n, double2* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
-    const int64_t n_pts = (int64_t)n * n;
-    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool live = pt < n_pts;
-    const PsfWork W = work[w0 + blockIdx.y];
-    const PsfSweepCfg& C = cfg[W.cfg];
-    const double2 v = psf_sum_range(hits, W.h0, W.h1, xs + (int64_t)W.cfg * n, zs + (int64_t)W.cfg * n, n, pt, live, C.origin, C.e1, C.e2, tile);
-    if (live) partial[(int64_t)blockIdx.y * n_pts + pt] = v;
-}
-
-// configuration c0 + blockIdx.y: its splits (partial rows first_work - w0 ...) summed in split order, as psf_reduce_kernel sums a call's
-__global__ void psf_reduce_sweep_kernel(const PsfSweepCfg* __restrict__ cfg, int32_t c0, int64_t w0, const double2* __restrict__ partial, int64_t n_pts,
-                                        double* __restrict__ intensity, double2* __restrict__ field) {
-    const int64_t pt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (pt >= n_pts) return;
-    const int32_t c = c0 + (int32_t)blockIdx.y;
-    const PsfSweepCfg& C = cfg[c];
-    double re = 0.0, im = 0.0;
-    for (int s = 0; s < C.n_splits; ++s) {
-        const double2 v = partial[(C.first_work - w0 + s) * n_pts + pt];
-        re += v.x;
-        im += v.y;
-    }
-    intensity[(int64_t)c * n_pts + pt] = re * re + im * im;  // abs2
-    if (field) field[(int64_t)c * n_pts + pt] = make_double2(re, im);
-}
-
-}  // namespace
-
-extern "C" int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
-                                       const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
-                                       double* kernel_ms) {
-    if (!res || !origins || !e1s || !e2s || !xs || !zs || !out_intensity || n <= 0) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad argument");
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad detector slot");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
-        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: the slot is not a PSFDetector's");
-    if (n_configs != std::max<int32_t>(res->n_configs, 1))
-        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
-    if (kernel_ms) *kernel_ms = 0.0;
-    const int32_t K = n_configs;
-    const int64_t n_pts = (int64_t)n * n;
-    const int64_t H = res->det_count[detector];
-    if (H == 0) {  // every configuration reads like a call with n_hits = 0
-        std::fill(out_intensity, out_intensity + (size_t)K * n_pts, 0.0);
-        if (out_field) std::fill(out_field, out_field + (size_t)K * n_pts * 2, 0.0);
-        return BMO_OK;
-    }
-    HIP_TRY(hipSetDevice(res->device));
-    hipStream_t st = 0;
-    int rc;
-    DevBuf row_cfg, d_cfg, d_work, d_xs, d_zs, partial, d_int, d_field;
-    // rows of one configuration are consecutive (rows are in root order, roots in configuration order): their range per configuration
-    std::vector<int32_t> rcfg((size_t)H, 0);
-    if (res->n_configs > 0) {
-        if ((rc = row_cfg.alloc((size_t)H * 4))) return rc;
-        hipLaunchKernelGGL(psf_row_cfg_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, st, (const int32_t*)res->det_node.p, res->det_offset[detector], H,
-                           (const int32_t*)res->order.p, (const int32_t*)res->n_root.p, (const int32_t*)res->d_root_cfg.p, (int32_t*)row_cfg.p);
-        HIP_TRY(hipMemcpyAsync(rcfg.data(), row_cfg.p, (size_t)H * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    std::vector<int64_t> begin((size_t)K, 0), count((size_t)K, 0);
-    for (int64_t h = 0; h < H; ++h) {
-        const int32_t c = rcfg[(size_t)h];
-        if (c < 0 || c >= K || (h > 0 && c < rcfg[(size_t)h - 1])) return fail(BMO_ERR_INTERNAL, "bmo_psf_intensity_sweep: rows out of configuration order");
-        if (count[(size_t)c]++ == 0) begin[(size_t)c] = h;
-    }
-    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
-    std::vector<PsfSweepCfg> cfg((size_t)K);
-    std::vector<PsfWork> work;
-    for (int32_t c = 0; c < K; ++c) {
-        PsfSweepCfg& C = cfg[(size_t)c];
-        C = PsfSweepCfg{};
-        const double *o = origins + 3 * (size_t)c, *a = e1s + 3 * (size_t)c, *b = e2s + 3 * (size_t)c;
-        C.origin = d3{o[0], o[1], o[2]};
-        C.e1 = d3{a[0], a[1], a[2]};
-        C.e2 = d3{b[0], b[1], b[2]};
-        C.first_work = (int64_t)work.size();
-        const int64_t nh = count[(size_t)c];
-        if (nh == 0) continue;
-        int64_t ns, hps;
-        psf_splits(nh, pt_blocks, ns, hps);
-        C.n_splits = (int32_t)ns;
-        for (int64_t s = 0; s < ns; ++s) {
-            const int64_t h0 = s * hps, h1 = h0 + hps < nh ? h0 + hps : nh;
-            work.push_back(PsfWork{begin[(size_t)c] + h0, begin[(size_t)c] + h1, c, 0});
-        }
-    }
-    // launches: consecutive configurations whose splits fit the grid's y limit and 1 GiB of partial sums (a configuration that alone needs
-    // more goes alone; its split count is at most 65535)
-    struct Batch {
-        int32_t c0, nc;
-        int64_t w0, nw;
-    };
-    const int64_t pt_bytes = n_pts * 16;
-    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)1 << 30) / pt_bytes));
-    std::vector<Batch> batches;
-    int64_t max_nw = 1;
-    for (int32_t c = 0; c < K;) {
-        Batch b{c, 0, cfg[(size_t)c].first_work, 0};
-        while (c < K && b.nc < 65535 && (b.nc == 0 || b.nw + cfg[(size_t)c].n_splits <= cap)) b.nw += cfg[(size_t)c++].n_splits, ++b.nc;
-        batches.push_back(b);
-        max_nw = std::max(max_nw, b.nw);
-    }
-    if ((rc = d_cfg.alloc(sizeof(PsfSweepCfg) * (size_t)K)) || (rc = d_work.alloc(sizeof(PsfWork) * std::max<size_t>(work.size(), 1))) ||
-        (rc = d_xs.alloc((size_t)K * n * 8)) || (rc = d_zs.alloc((size_t)K * n * 8)) || (rc = partial.alloc((size_t)max_nw * (size_t)pt_bytes)) ||
-        (rc = d_int.alloc((size_t)K * n_pts * 8)))
-        return rc;
-    if (out_field && (rc = d_field.alloc((size_t)K * n_pts * 16))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_cfg.p, cfg.data(), sizeof(PsfSweepCfg) * (size_t)K, hipMemcpyHostToDevice, st));
-    if (!work.empty()) HIP_TRY(hipMemcpyAsync(d_work.p, work.data(), sizeof(PsfWork) * work.size(), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_xs.p, xs, (size_t)K * n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_zs.p, zs, (size_t)K * n * 8, hipMemcpyHostToDevice, st));
-    const double* hits = (const double*)res->det_data.p + 9 * res->det_offset[detector];
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    HIP_TRY(hipEventRecord(e0, st));
-    for (const Batch& b : batches) {
-        if (b.nw > 0)
-            hipLaunchKernelGGL(psf_accumulate_sweep_kernel, dim3(pt_blocks, (unsigned)b.nw), dim3(256), 0, st, hits, (const PsfWork*)d_work.p, b.w0,
-                               (const PsfSweepCfg*)d_cfg.p, (const double*)d_xs.p, (const double*)d_zs.p, n, (double2*)partial.p);
-        hipLaunchKernelGGL(psf_reduce_sweep_kernel, dim3(pt_blocks, (unsigned)b.nc), dim3(256), 0, st, (const PsfSweepCfg*)d_cfg.p, b.c0, b.w0,
-                           (const double2*)partial.p, n_pts, (double*)d_int.p, out_field ? (double2*)d_field.p : nullptr);
-    }
-    HIP_TRY(hipEventRecord(e1, st));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (kernel_ms) *kernel_ms = ms;
-    HIP_TRY(hipMemcpy(out_intensity, d_int.p, (size_t)K * n_pts * 8, hipMemcpyDeviceToHost));
-    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, (size_t)K * n_pts * 16, hipMemcpyDeviceToHost));
-    return BMO_OK;
+    return pd_read(res, detector, rows / 3, n_configs, "bmo_photodetector_field_sweep", "bmo_photodetector_field_sweep: beamlets out of configuration order", positions,
+                   orientations, xs, ys, nx, ny, field_inout, kernel_ms);
 }

@@ -18,8 +18,8 @@
          host: 5 ulp = 10 u per component, sqrt(2) of it for the modulus and the rounding of proj * c on both sides stay below 12 u proj
          per term; the sequential-sum worst case is (H - 1) u S per side, and the engine's blocked sum is inside it.
 
-3. Restatements of the engine's work splitting (psf_splits, pd_splits of csrc/bmo_readout.inc.hpp).  The tests use them ONLY to assert that a
-   chosen shape reaches the code path it was chosen for, never to compute an expected value.
+3. Restatements of the engine's work splitting (psf_splits, pd_splits and the launches of SplitPlan in csrc/bmo_readout.inc.hpp).  The tests use
+   them ONLY to assert that a chosen shape reaches the code path it was chosen for, never to compute an expected value.
 """
 import math
 import os
@@ -113,10 +113,19 @@ def pd_splits(n_hits, n_pts):
     return _cdiv(n_hits, hps), hps
 
 
-def pd_sweep_batch(counts, n_pts):
-    """Configurations per launch of bmo_photodetector_field_sweep for the per-configuration beamlet counts `counts` (1 GiB of partial sums)."""
-    max_splits = max([1] + [pd_splits(h, n_pts)[0] for h in counts if h > 0])
-    return max(1, min(len(counts), 65535, (1 << 30) // (max_splits * n_pts * 16)))
+def sweep_launches(splits_per_cfg, n_pts):
+    """[(c0, nc), ...]: the launches of a sweep read-out (SplitPlan) whose configuration c has splits_per_cfg[c] splits (0: no rows).  A launch
+    takes consecutive configurations while their splits fit min(65535, 1 GiB of 16-byte partial sums per point) rows, at most 65535 of
+    them; a configuration that alone has more goes alone."""
+    cap = max(1, min(65535, (1 << 30) // (n_pts * 16)))
+    out, c, K = [], 0, len(splits_per_cfg)
+    while c < K:
+        c0, rows = c, 0
+        while c < K and c - c0 < 65535 and (c == c0 or rows + splits_per_cfg[c] <= cap):
+            rows += splits_per_cfg[c]
+            c += 1
+        out.append((c0, c - c0))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the tilted PSF scene

@@ -1,7 +1,8 @@
 """Photodetector read-out of sweeps on the GPU: configuration c of bmo_photodetector_field_sweep equals, bit for bit, a fresh solve of snapshot c
 followed by bmo_photodetector_field at that snapshot's detector pose; a few configurations per test are also held to the oracle.  The cases
 are the ones tests/test_sweep_gpu.py's Michelson KAT leaves out: a detector pose per configuration, unequal and empty configurations, several
-beamlets per range, more configurations than one launch holds, accumulation into the caller's field, a non-square grid, and the refusals."""
+beamlets per range, more configurations than one launch holds, ragged counts across a launch boundary, accumulation into the caller's field,
+a non-square grid, and the refusals.  The sweep and the single call share their device code: the independent check is the oracle's."""
 import ctypes as C
 import math
 
@@ -180,17 +181,18 @@ def test_accumulation_into_the_callers_field():
 
 def test_more_configurations_than_one_launch_holds(oracle):
     """260 configurations x 228 beamlets on pd_scene's 48 x 48 grid: 228 ranges and 8.4 MB of partial sums per configuration, so the 1 GiB cap
-    of one launch makes it three (cfg0 = 0, 127, 254)."""
+    of one launch makes it three (first configurations 0, 127, 254)."""
     K, n = 260, 228
     sw, pd = _moving_sweep(n, K, step=0.01)
     try:
         n_pts = len(pd.x) * len(pd.y)
         assert sw.counts == [n] * K and sum(sw.counts) <= 1e5
-        batch = rr.pd_sweep_batch(sw.counts, n_pts)
-        assert batch < K and -(-K // batch) == 3, batch
+        launches = rr.sweep_launches([rr.pd_splits(h, n_pts)[0] for h in sw.counts], n_pts)
+        assert len(launches) == 3 and [c0 for c0, _ in launches] == [0, 127, 254], launches
+        batch = launches[1][0]
         f = sw.fields(pd.x, pd.y)
         check = {0, 1, K - 2, K - 1}
-        for b in range(batch, K, batch):
+        for b, _ in launches[1:]:
             check |= {b - 1, b, b + 1}
         assert len(check) >= 10
         for c in sorted(check):
@@ -200,6 +202,51 @@ def test_more_configurations_than_one_launch_holds(oracle):
             assert np.abs(f[c] - fa).max() <= 1e-9 * np.abs(fa).max(), c
         # neighbours across a launch boundary are different configurations
         assert not _same_bits(f[batch - 1], f[batch]) and not _same_bits(f[2 * batch - 1], f[2 * batch])
+    finally:
+        sw.close()
+
+
+def test_ragged_counts_across_a_launch_boundary(oracle):
+    """_ragged_sweep's detector with 48 x 48 points, stepped through a bundle of 1 200 beamlets 280 times: inside the bundle it records about
+    two hundred beamlets, towards the rim fewer, every tenth configuration none.  A launch holds 2^30 // (2304 * 16) = 29 127 ranges whichever
+    configurations they belong to: two launches, where one sized by the largest configuration (the rule before) took three."""
+    K = 280
+    bundle = scenes.gaussian_bundle(1200, center=[0, 0, 0], direction=[0, 1, 0], diameter=12 * mm, lam=1e-6, w0=0.2 * mm, jitter=1e-3)
+    pd = bmo.Photodetector(4.5 * mm, 48)
+    bmo.translate3d(pd, [0, 50 * mm, 0])
+    xoff = [0.0, 5.0 * mm, 2.0 * mm, 40 * mm, 1.0 * mm, 6.5 * mm, 3.0 * mm, -1.5 * mm, 7.6 * mm, -2.5 * mm]
+
+    def configure(c):
+        bmo.translate_to3d(pd, [xoff[c % 10] + 0.0005 * mm * c, 50 * mm, 0.005 * mm * c])
+
+    sw = _Sweep(bmo.System([pd]), pd, bundle, K, configure)
+    try:
+        n_pts = len(pd.x) * len(pd.y)
+        counts = sw.counts
+        assert n_pts == 48 * 48 and sum(counts) <= 1e5
+        empty = [c for c in range(K) if counts[c] == 0]
+        assert empty == list(range(3, K, 10)) and len(set(counts)) >= 20, counts
+        splits = [rr.pd_splits(h, n_pts)[0] if h else 0 for h in counts]
+        launches = rr.sweep_launches(splits, n_pts)
+        old_batch = max(1, min(K, 65535, (1 << 30) // (max(splits) * n_pts * 16)))  # the rule before: every configuration as many rows as the largest
+        old_starts = list(range(old_batch, K, old_batch))
+        assert len(launches) == 2 and len(old_starts) + 1 == 3, (launches, old_batch)
+        new_starts = [c0 for c0, _ in launches[1:]]
+        assert not set(new_starts) & set(old_starts)
+        f = sw.fields(pd.x, pd.y)
+        check = {0, K - 1}
+        for b in new_starts + old_starts:
+            check |= {b - 1, b}
+        near = min(empty, key=lambda c: abs(c - new_starts[0]))  # the empty configuration next to the new boundary
+        check |= {near - 1, near, near + 1}
+        assert len(check) >= 10
+        for c in sorted(check):
+            assert _same_bits(f[c], sw.single(c, pd.x, pd.y)), c
+        assert not f[near].real.any() and not f[near].imag.any()
+        assert not _same_bits(f[new_starts[0] - 1], f[new_starts[0]])
+        c = new_starts[0] if counts[new_starts[0]] else new_starts[0] - 1
+        fa = sw.oracle_field(oracle, c, pd.x, pd.y)
+        assert np.abs(fa).max() > 0 and np.abs(f[c] - fa).max() <= 1e-9 * np.abs(fa).max(), c
     finally:
         sw.close()
 

@@ -98,4 +98,22 @@ def test_psf_splits_restatement_agrees_with_the_header():
     # pd_splits: ranges of beamlets, no tile
     assert rr.pd_splits(1, 2304) == (1, 1) and rr.pd_splits(228, 2304) == (228, 1) and rr.pd_splits(300, 2304) == (150, 2)
     assert rr.pd_splits(358, 4096) == (120, 3) and rr.pd_splits(3, 1) == (3, 1)
-    assert rr.pd_sweep_batch([228] * 260, 2304) == 127
+
+
+def test_sweep_launches_restatement_on_the_shapes_the_gpu_tests_use():
+    """readout_ref.sweep_launches restates SplitPlan's launch rule; the two sweeps the GPU tests split into three launches, by hand."""
+    src = open(rr.READOUT_SOURCE).read()
+    assert src.count("((int64_t)1 << 30) / (n_pts * 16)") == 1 and "std::min<int64_t>(65535, ((int64_t)1 << 30)" in src  # the one limit
+    # Photodetector (test_more_configurations_than_one_launch_holds): 260 configurations x 228 beamlets on 48 x 48 points.  9 point blocks ask
+    # for cdiv(2048, 9) = 228 ranges: one beamlet each.  2^30 // (2304 * 16) = 29127 rows, 29127 // 228 = 127 configurations per launch.
+    assert rr.pd_splits(228, 48 * 48) == (228, 1) and (1 << 30) // (48 * 48 * 16) == 29127 and 29127 // 228 == 127
+    assert rr.sweep_launches([228] * 260, 48 * 48) == [(0, 127), (127, 127), (254, 6)]
+    # PSF (test_psf_sweep_gpu's three-launch sweep): 150 configurations of 16 splits on 256 x 256 points.  2^30 / 2^20 = 1024 rows, 64 per launch.
+    assert (1 << 30) // (256 * 256 * 16) == 1024
+    assert rr.sweep_launches([16] * 150, 256 * 256) == [(0, 64), (64, 64), (128, 22)]
+    # unequal counts pack by rows, not by the largest configuration; empty configurations take no row; an oversized one goes alone
+    assert rr.sweep_launches([600, 0, 400, 24, 1, 1000, 24], 256 * 256) == [(0, 4), (4, 2), (6, 1)]
+    assert rr.sweep_launches([5, 2000, 5], 256 * 256) == [(0, 1), (1, 1), (2, 1)]
+    assert rr.sweep_launches([0, 0, 0], 49) == [(0, 3)] and rr.sweep_launches([], 49) == []
+    assert rr.sweep_launches([0] * 70000, 49) == [(0, 65535), (65535, 4465)]  # at most 65535 configurations (grid y of the reduction)
+    assert rr.sweep_launches([1] * 70000, 16) == [(0, 65535), (65535, 4465)]  # ... and 65535 rows (grid y of the accumulation)
