@@ -16,6 +16,10 @@ VIEW_HITS, VIEW_LAST_SEGMENT, VIEW_SEGMENTS = 1, 2, 4  # bmo_result_view_select 
 PLANES_IN = {0: 8, 1: 14, 2: 25}
 PLANES_REC = {0: 11, 1: 17, 2: 33}
 
+# BMO_SPOT_STAT_*: columns of the spot statistics (bmo_spot_stats)
+SPOT_STAT_N = 12
+(SPOT_N, SPOT_CX, SPOT_CZ, SPOT_X_MIN, SPOT_X_MAX, SPOT_Z_MIN, SPOT_Z_MAX, SPOT_MXX, SPOT_MZZ, SPOT_MXZ, SPOT_RMS_R, SPOT_GEO_R) = range(SPOT_STAT_N)
+
 NODE_MISS, NODE_STOPPED, NODE_RMAX, NODE_SPLIT, NODE_DETECTED, NODE_ERR_UNIT, NODE_GAUSS_DIVERGED, NODE_BLOCKED, NODE_ERR_ORTHO = (
     1, 2, 4, 8, 16, 32, 64, 128, 256)
 
@@ -232,6 +236,11 @@ def load_engine():
     lib.bmo_trace_sweep.argtypes = [vp, C.POINTER(RayBatch), C.POINTER(C.c_int32), C.POINTER(TraceOpts), C.POINTER(vp)]
     lib.bmo_photodetector_field_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
     lib.bmo_psf_intensity_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp, dp]
+    ip = C.POINTER(C.c_int64)
+    lib.bmo_spot_image.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, C.c_int32, ip, ip, dp]
+    lib.bmo_spot_image_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, ip, ip, dp]
+    lib.bmo_spot_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    lib.bmo_spot_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
     _engine = lib
     return lib
 
@@ -291,3 +300,66 @@ def psf_intensity_sweep(res_handle, detector, n_configs, origins, e1s, e2s, xs, 
                                            fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_intensity_sweep")
     field = np.ascontiguousarray((fld[0::2] + 1j * fld[1::2]).reshape(K, n, n).transpose(0, 2, 1)) if want_field else None
     return np.ascontiguousarray(out.reshape(K, n, n).transpose(0, 2, 1)), field, ms.value
+
+
+def _spot_rows(rows, rows_device_ptr, n_rows, row_cols):
+    """(pointer, row count, columns, on_device, keep-alive) of the rows of a single spot read-out."""
+    if rows_device_ptr is not None:
+        return C.c_void_p(int(rows_device_ptr)), int(n_rows), int(row_cols), 1, None
+    r = np.asarray(rows, dtype=np.float64)
+    r = np.ascontiguousarray(r if r.ndim == 2 else r.reshape(-1, 2))
+    return r.ctypes.data_as(C.c_void_p), r.shape[0], r.shape[1], 0, r
+
+
+def spot_image(rows, window, nx, nz=None, device=0, rows_device_ptr=None, n_rows=None, row_cols=9):
+    """bmo_spot_image: the rows [n, 2..9] (x in column 0, z in column 1) binned on window (x0, x1, z0, z1) by the floor rule of include/bmo.h.
+    Returns (counts int64 [nx, nz] indexed [i, j], outside, kernel_ms).  `rows` is a host array, or pass `rows_device_ptr` + `n_rows` +
+    `row_cols` for rows already resident on `device` (bmo_result_device_hits: 9 columns)."""
+    lib = load_engine()
+    nz = nx if nz is None else nz
+    rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
+    w = np.ascontiguousarray(window, dtype=np.float64).reshape(4)
+    img = np.zeros(max(int(nx) * int(nz), 0), dtype=np.int64)
+    out = C.c_int64()
+    ms = C.c_double()
+    check(lib, lib.bmo_spot_image(rp, n, cols, on_dev, w.ctypes.data_as(C.POINTER(C.c_double)), int(nx), int(nz), int(device),
+                                  img.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(out), C.byref(ms)), "bmo_spot_image")
+    return img.reshape(nz, nx).T.copy(), out.value, ms.value
+
+
+def spot_image_sweep(res_handle, detector, n_configs, windows, nx, nz=None):
+    """bmo_spot_image_sweep on the result handle `res_handle`: windows [K, 4] (or one window for all).  Returns (counts int64 [K, nx, nz]
+    indexed [c, i, j], outside int64 [K], kernel_ms); configuration c equals spot_image on its rows."""
+    lib = load_engine()
+    K = int(n_configs)
+    nz = nx if nz is None else nz
+    w = np.asarray(windows, dtype=np.float64)
+    w = np.ascontiguousarray(np.tile(w, (max(K, 1), 1)) if w.ndim == 1 else w.reshape(max(K, 1), 4))
+    img = np.zeros(max(K, 1) * max(int(nx) * int(nz), 0), dtype=np.int64)
+    out = np.zeros(max(K, 1), dtype=np.int64)
+    ms = C.c_double()
+    ip = C.POINTER(C.c_int64)
+    check(lib, lib.bmo_spot_image_sweep(res_handle, int(detector), K, w.ctypes.data_as(C.POINTER(C.c_double)), int(nx), int(nz), img.ctypes.data_as(ip),
+                                        out.ctypes.data_as(ip), C.byref(ms)), "bmo_spot_image_sweep")
+    return np.ascontiguousarray(img.reshape(K, nz, nx).transpose(0, 2, 1)), out, ms.value
+
+
+def spot_stats(rows, device=0, rows_device_ptr=None, n_rows=None, row_cols=9):
+    """bmo_spot_stats: the twelve statistics (SPOT_* columns) of the rows, two passes on the device.  Returns (stats [12], kernel_ms)."""
+    lib = load_engine()
+    rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
+    st = np.zeros(SPOT_STAT_N)
+    ms = C.c_double()
+    check(lib, lib.bmo_spot_stats(rp, n, cols, on_dev, int(device), st.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ms)), "bmo_spot_stats")
+    return st, ms.value
+
+
+def spot_stats_sweep(res_handle, detector, n_configs):
+    """bmo_spot_stats_sweep on the result handle `res_handle`.  Returns (stats [K, 12], kernel_ms); row c equals spot_stats on the rows of
+    configuration c bit for bit."""
+    lib = load_engine()
+    K = int(n_configs)
+    st = np.zeros((max(K, 1), SPOT_STAT_N))
+    ms = C.c_double()
+    check(lib, lib.bmo_spot_stats_sweep(res_handle, int(detector), K, st.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ms)), "bmo_spot_stats_sweep")
+    return st[:K], ms.value

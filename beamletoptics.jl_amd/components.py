@@ -360,6 +360,42 @@ class Spotdetector(AbstractObject):  # Detectors/Spotdetector.jl:21-45
     def empty(self):
         self.data = np.zeros((0, 2))
 
+    # ---- read-out on the GPU engine (bmo_spot_image / bmo_spot_stats; the reference leaves `data` to its users)
+    def stats(self, device=0):
+        """The twelve spot statistics (abi.SPOT_* columns: N, centroid, extrema, central moments, RMS and geometric radius) of all rows
+        accumulated so far (the detector is not reset between solves, like the reference)."""
+        from . import abi
+
+        return abi.spot_stats(self.data, device=device)[0]
+
+    def image(self, nx, nz=None, window=None, device=0):
+        """The spot diagram of all rows accumulated so far as an image: (x_edges [nx + 1], z_edges [nz + 1], counts int64 [nx, nz], outside).
+        window: (x0, x1, z0, z1); None is the detector face (-hw, hw, -hw, hw); "extent" the extrema of the rows (ValueError without rows
+        or with a zero extent).  Membership is the floor rule of include/bmo.h, not a search in the edges: a row is inside iff
+        x0 <= x <= x1 and z0 <= z <= z1 and counts in bin i = min(floor((x - x0) * (nx / (x1 - x0))), nx - 1), j likewise; `outside`
+        counts the other rows.  The edges are linrange(x0, x1, nx + 1), for plotting."""
+        from . import abi
+
+        nz = nx if nz is None else nz
+        if window is None:
+            window = (-self.hw, self.hw, -self.hw, self.hw)
+        elif isinstance(window, str):
+            if window != "extent":
+                raise ValueError('Spotdetector.image: window must be (x0, x1, z0, z1), None or "extent"')
+            window = spot_extent_window(self.stats(device), "Spotdetector.image")
+        counts, outside, _ = abi.spot_image(self.data, window, nx, nz, device=device)
+        return la.linrange(window[0], window[1], nx + 1), la.linrange(window[2], window[3], nz + 1), counts, outside
+
+
+def spot_extent_window(stats, who):
+    """The window X_MIN .. Z_MAX of spot statistics [12]; ValueError (starting with `who`) without rows or with a zero extent."""
+    if stats[0] == 0:
+        raise ValueError(f"{who}: no row, so no extent")
+    x0, x1, z0, z1 = (float(v) for v in stats[3:7])
+    if not (x1 > x0 and z1 > z0):
+        raise ValueError(f"{who}: the rows have a zero extent")
+    return x0, x1, z0, z1
+
 
 # The sampling window of a PSFDetector's read-out as a function of its rows ([H, 9], include/bmo.h det_data) and its pose, so that a sweep
 # (SweepSolution.psf_intensity) can apply it to each configuration's rows and pose.  PSFDetector's methods of the same names call these.

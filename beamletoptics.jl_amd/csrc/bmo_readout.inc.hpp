@@ -260,8 +260,9 @@ struct SplitPlan {
     std::vector<Launch> launches;
     int64_t max_nw = 1;  // partial rows the largest launch writes
 
-    // configuration c is split exactly as a single call with R.count[c] rows splits them
-    SplitPlan(const Ranges& R, unsigned pt_blocks, int64_t n_pts, void (*splits)(int64_t, unsigned, int64_t&, int64_t&)) {
+    // configuration c is split exactly as a single call with R.count[c] rows splits them; no launches (the spot read-outs run every item
+    // in one launch)
+    SplitPlan(const Ranges& R, unsigned pt_blocks, void (*splits)(int64_t, unsigned, int64_t&, int64_t&)) {
         const int32_t K = (int32_t)R.count.size();
         cfg.resize((size_t)K);
         per_split.assign((size_t)K, 0);
@@ -278,6 +279,10 @@ struct SplitPlan {
                 work.push_back(SplitWork{R.begin[(size_t)c] + h0, R.begin[(size_t)c] + h1, c, 0});
             }
         }
+    }
+    // the same with the launches of a read-out that writes n_pts partial sums per work item
+    SplitPlan(const Ranges& R, unsigned pt_blocks, int64_t n_pts, void (*splits)(int64_t, unsigned, int64_t&, int64_t&)) : SplitPlan(R, pt_blocks, splits) {
+        const int32_t K = (int32_t)R.count.size();
         // launches: consecutive configurations whose splits fit the grid's y limit and 1 GiB of partial sums (a configuration that alone
         // needs more goes alone; its split count is at most 65535)
         const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(65535, ((int64_t)1 << 30) / (n_pts * 16)));
@@ -756,4 +761,417 @@ extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t dete
     if (!res->has_log) return fail(BMO_ERR_INVALID, "bmo_photodetector_field_sweep: the solution was solved with record_segments = 0 (gauss_parameters needs the beamlets' segments)");
     return pd_read(res, detector, rows / 3, n_configs, "bmo_photodetector_field_sweep", "bmo_photodetector_field_sweep: beamlets out of configuration order", positions,
                    orientations, xs, ys, nx, ny, field_inout, kernel_ms);
+}
+
+// ====================================================================================================================
+// Spot read-out: the binned image and the moment statistics of a Spotdetector's rows (include/bmo.h "Spot read-out").  The rows are
+// [n][cols] doubles with x in column 0 and z in column 1: the packed columns of bmo_result_copy_hit_columns, or the resident 9-column rows
+// of a slot (a 72-byte stride of which 16 bytes are used; every lane reads its own row with vector loads).  The same plumbing as above:
+//   * slot_ranges gives the rows of every configuration, SplitPlan cuts each into splits (spot_splits: multiples of 256 rows) and lists
+//     them as flat work items.  The items lie on the grid's x dimension (limit 2^31 - 1), so one launch runs them all (SplitPlan's
+//     constructor without launches).  A single call is the K = 1 case, and configuration c is split exactly as a single call with its rows.
+//   * image: one workgroup per item bins its rows into a privatised uint32 histogram in LDS (images of up to SPOT_LDS_BINS bins), then adds
+//     the non-zero bins to image[c] with 64-bit global atomics; larger images are added to global memory directly.  Counts are integers:
+//     the result does not depend on the order of the adds.  Lanes of a wave that hit the same bin are counted by one of them (spot_add).
+//   * statistics: two accumulate kernels with a per-configuration reduce each, queued behind one synchronisation; the centroid stays on
+//     the device for the second pass.  Lane l of a workgroup sums rows h0 + l, h0 + l + 256, ... sequentially, a fixed tree runs over the
+//     lanes of a wave and the four waves, the splits are summed in split order: deterministic for a given row count.
+namespace {
+
+constexpr int SPOT_MIN_SPLIT = 2048;   // rows: shorter splits would spend their time on the histogram, not on rows
+constexpr int SPOT_MAX_SPLITS = 2048;  // per configuration: eight workgroups per CU
+constexpr int SPOT_LDS_BINS = 16384;   // uint32 counters in 64 KB of LDS
+constexpr int SPOT_AGG_ITERS = 4;      // distinct bins a wave counts by ballot before the remaining lanes add one by one (0: plain atomics)
+
+struct SpotWindow {
+    double x0, x1, z0, z1, sx, sz;  // sx = nx / (x1 - x0), sz = nz / (z1 - z0)
+};
+
+// the binning rule: bin i + nx * j of (x, z), -1 outside (plain compares: a NaN is outside, the upper edge is closed)
+__device__ __forceinline__ int32_t spot_bin(double x, double z, const SpotWindow& W, int32_t nx, int32_t nz) {
+    if (!(x >= W.x0 && x <= W.x1 && z >= W.z0 && z <= W.z1)) return -1;
+    int64_t i = (int64_t)floor((x - W.x0) * W.sx), j = (int64_t)floor((z - W.z0) * W.sz);
+    if (i > nx - 1) i = nx - 1;
+    if (j > nz - 1) j = nz - 1;
+    return (int32_t)(i + (int64_t)nx * j);
+}
+
+// hist[key] += 1 for every lane with `live`.  A focused spot puts all 64 lanes on one bin: the first live lane takes its bin, the lanes
+// that share it are counted by ballot and it adds their number; after SPOT_AGG_ITERS such bins the lanes left add one each.  Called by
+// whole waves (a lane without a row passes live = false).
+template <class Counter>
+__device__ __forceinline__ void spot_add(Counter* hist, int32_t key, bool live) {
+    const int lane = (int)(threadIdx.x & 63);
+    for (int it = 0; it < SPOT_AGG_ITERS; ++it) {
+        if (live) {
+            const int32_t k = __builtin_amdgcn_readfirstlane(key);
+            const unsigned long long m = __ballot(key == k);
+            if (lane == __ffsll((long long)m) - 1) atomicAdd(&hist[k], (Counter)__popcll(m));
+            if (key == k) live = false;
+        }
+    }
+    if (live) atomicAdd(&hist[key], (Counter)1);
+}
+
+// work item blockIdx.x: its rows binned into image[cfg], the rows outside the window counted in outside[cfg]
+template <bool LDS>
+__global__ __launch_bounds__(256) void spot_image_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
+                                                         const SpotWindow* __restrict__ win, int32_t nx, int32_t nz, unsigned long long* __restrict__ image,
+                                                         unsigned long long* __restrict__ outside) {
+    extern __shared__ uint32_t spot_hist[];  // LDS: nx * nz counters
+    const SplitWork W = work[blockIdx.x];
+    const SpotWindow B = win[W.cfg];
+    const int32_t n_bins = nx * nz;
+    unsigned long long* img = image + (int64_t)W.cfg * n_bins;
+    if (LDS) {
+        for (int32_t b = threadIdx.x; b < n_bins; b += 256) spot_hist[b] = 0;
+        __syncthreads();
+    }
+    uint32_t n_out = 0;
+    for (int64_t base = W.h0; base < W.h1; base += 256) {  // workgroup-uniform trips: spot_add needs whole waves
+        const int64_t h = base + threadIdx.x;
+        int32_t key = -1;
+        if (h < W.h1) {
+            const double* r = rows + h * cols;
+            key = spot_bin(r[0], r[1], B, nx, nz);
+            n_out += key < 0;
+        }
+        if (LDS) spot_add(spot_hist, key, key >= 0);
+        else spot_add(img, key, key >= 0);
+    }
+    for (int off = 32; off > 0; off >>= 1) n_out += __shfl_down(n_out, off);
+    if ((threadIdx.x & 63) == 0 && n_out) atomicAdd(&outside[W.cfg], (unsigned long long)n_out);
+    if (LDS) {
+        __syncthreads();
+        for (int32_t b = threadIdx.x; b < n_bins; b += 256) {
+            const uint32_t v = spot_hist[b];
+            if (v) atomicAdd(&img[b], (unsigned long long)v);
+        }
+    }
+}
+
+// The sums of the workgroup's lanes by a fixed tree: over the lanes of a wave, then (w0 + w1) + (w2 + w3).  Thread 0 returns the result.
+struct SpotAdd {
+    __device__ double operator()(double a, double b) const { return a + b; }
+};
+struct SpotMin {
+    __device__ double operator()(double a, double b) const { return b < a ? b : a; }
+};
+struct SpotMax {
+    __device__ double operator()(double a, double b) const { return b > a ? b : a; }
+};
+template <class Op>
+__device__ __forceinline__ double spot_wg_reduce(double v, Op op, double* sh) {
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_down(v, off));
+    __syncthreads();  // sh is free again
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(sh[0], sh[1]), op(sh[2], sh[3]));
+}
+
+struct SpotSum1 {
+    double sx, sz, x_min, x_max, z_min, z_max;
+};
+struct SpotSum2 {
+    double xx, zz, xz, r2;
+};
+
+// first pass of work item blockIdx.x: sums and extrema of its rows
+__global__ __launch_bounds__(256) void spot_centroid_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
+                                                            SpotSum1* __restrict__ partial) {
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    double sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
+    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+        const double* r = rows + h * cols;
+        const double x = r[0], z = r[1];
+        sx += x;
+        sz += z;
+        x_min = x < x_min ? x : x_min;
+        x_max = x > x_max ? x : x_max;
+        z_min = z < z_min ? z : z_min;
+        z_max = z > z_max ? z : z_max;
+    }
+    SpotSum1 s;
+    s.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
+    s.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
+    s.x_min = spot_wg_reduce(x_min, SpotMin{}, sh);
+    s.x_max = spot_wg_reduce(x_max, SpotMax{}, sh);
+    s.z_min = spot_wg_reduce(z_min, SpotMin{}, sh);
+    s.z_max = spot_wg_reduce(z_max, SpotMax{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// configuration c: its splits summed in split order; N, the centroid and the extrema go to stats[c], the centroid to cent[c] for the second pass
+__global__ void spot_centroid_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, int32_t K, const SpotSum1* __restrict__ partial,
+                                            double* __restrict__ stats, double2* __restrict__ cent) {
+    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= K) return;
+    double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
+    const int64_t n = count[c];
+    out[BMO_SPOT_STAT_N_ROWS] = (double)n;
+    if (n == 0) {
+        for (int q = 1; q < BMO_SPOT_STAT_N; ++q) out[q] = knan();
+        cent[c] = make_double2(0.0, 0.0);
+        return;
+    }
+    const SplitCfg C = cfg[c];
+    double sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
+    for (int s = 0; s < C.n_splits; ++s) {
+        const SpotSum1 p = partial[C.first_work + s];
+        sx += p.sx;
+        sz += p.sz;
+        x_min = p.x_min < x_min ? p.x_min : x_min;
+        x_max = p.x_max > x_max ? p.x_max : x_max;
+        z_min = p.z_min < z_min ? p.z_min : z_min;
+        z_max = p.z_max > z_max ? p.z_max : z_max;
+    }
+    const double cx = sx / (double)n, cz = sz / (double)n;
+    out[BMO_SPOT_STAT_CX] = cx;
+    out[BMO_SPOT_STAT_CZ] = cz;
+    out[BMO_SPOT_STAT_X_MIN] = x_min;
+    out[BMO_SPOT_STAT_X_MAX] = x_max;
+    out[BMO_SPOT_STAT_Z_MIN] = z_min;
+    out[BMO_SPOT_STAT_Z_MAX] = z_max;
+    cent[c] = make_double2(cx, cz);
+}
+
+// second pass of work item blockIdx.x: central moments of its rows about the computed centroid of its configuration
+__global__ __launch_bounds__(256) void spot_moments_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
+                                                           const double2* __restrict__ cent, SpotSum2* __restrict__ partial) {
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const double2 c = cent[W.cfg];
+    double xx = 0.0, zz = 0.0, xz = 0.0, r2 = 0.0;
+    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+        const double* r = rows + h * cols;
+        const double dx = r[0] - c.x, dz = r[1] - c.y;
+        const double a = dx * dx, b = dz * dz;
+        xx += a;
+        zz += b;
+        xz += dx * dz;
+        const double q = a + b;
+        r2 = q > r2 ? q : r2;
+    }
+    SpotSum2 s;
+    s.xx = spot_wg_reduce(xx, SpotAdd{}, sh);
+    s.zz = spot_wg_reduce(zz, SpotAdd{}, sh);
+    s.xz = spot_wg_reduce(xz, SpotAdd{}, sh);
+    s.r2 = spot_wg_reduce(r2, SpotMax{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void spot_moments_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, int32_t K, const SpotSum2* __restrict__ partial,
+                                           double* __restrict__ stats) {
+    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= K) return;
+    const int64_t n = count[c];
+    if (n == 0) return;  // NaN already
+    const SplitCfg C = cfg[c];
+    double xx = 0.0, zz = 0.0, xz = 0.0, r2 = 0.0;
+    for (int s = 0; s < C.n_splits; ++s) {
+        const SpotSum2 p = partial[C.first_work + s];
+        xx += p.xx;
+        zz += p.zz;
+        xz += p.xz;
+        r2 = p.r2 > r2 ? p.r2 : r2;
+    }
+    double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
+    const double mxx = xx / (double)n, mzz = zz / (double)n;
+    out[BMO_SPOT_STAT_MXX] = mxx;
+    out[BMO_SPOT_STAT_MZZ] = mzz;
+    out[BMO_SPOT_STAT_MXZ] = xz / (double)n;
+    out[BMO_SPOT_STAT_RMS_R] = sqrt(mxx + mzz);
+    out[BMO_SPOT_STAT_GEO_R] = sqrt(r2);
+}
+
+}  // namespace
+
+// splits of the n_rows rows of one configuration: at least SPOT_MIN_SPLIT rows each and at most SPOT_MAX_SPLITS of them, every split a
+// multiple of 256 rows
+// (tests/spot_ref.py restates this function and reads the three constants from this text: keep them in step)
+static void spot_splits(int64_t n_rows, int64_t& n_splits, int64_t& rows_per_split) {
+    n_splits = (n_rows + SPOT_MIN_SPLIT - 1) / SPOT_MIN_SPLIT;
+    if (n_splits > SPOT_MAX_SPLITS) n_splits = SPOT_MAX_SPLITS;
+    if (n_splits < 1) n_splits = 1;
+    rows_per_split = (n_rows + n_splits - 1) / n_splits;
+    rows_per_split = (rows_per_split + 255) / 256 * 256;
+    if (rows_per_split < 256) rows_per_split = 256;
+    n_splits = n_rows > 0 ? (n_rows + rows_per_split - 1) / rows_per_split : 1;
+}
+
+// the plan of a spot read-out: splits by spot_splits (which knows no point blocks), no launch batching
+static SplitPlan spot_plan(const Ranges& R) {
+    return SplitPlan(R, 1, [](int64_t n_rows, unsigned, int64_t& n_splits, int64_t& rows_per_split) { spot_splits(n_rows, n_splits, rows_per_split); });
+}
+
+// the work items of a spot read-out on the grid's x dimension
+static int spot_items(const SplitPlan& plan, const char* who, unsigned& n_items) {
+    if (plan.work.size() > (size_t)0x7fffffff) return fail(BMO_ERR_LIMIT, std::string(who) + ": more work items than one launch holds");
+    for (int64_t per : plan.per_split)
+        if (per > (int64_t)0xffffffff) return fail(BMO_ERR_LIMIT, std::string(who) + ": more rows per split than a 32-bit counter holds");
+    n_items = (unsigned)plan.work.size();
+    return BMO_OK;
+}
+
+// window c as the kernels read it, or why it is refused
+static bool spot_window(const double* w, int32_t nx, int32_t nz, SpotWindow& W) {
+    for (int q = 0; q < 4; ++q)
+        if (!std::isfinite(w[q])) return false;
+    if (!(w[1] > w[0] && w[3] > w[2])) return false;
+    W = SpotWindow{w[0], w[1], w[2], w[3], (double)nx / (w[1] - w[0]), (double)nz / (w[3] - w[2])};
+    return std::isfinite(W.sx) && std::isfinite(W.sz) && W.sx > 0 && W.sz > 0;  // an extent that overflows or underflows has no bin width
+}
+
+// The images of the K = R.count.size() configurations from the device rows `rows` [..][cols]: win [K], image [K][nx * nz], outside [K].
+static int spot_image_read(const double* rows, int32_t cols, const Ranges& R, const std::vector<SpotWindow>& win, int32_t nx, int32_t nz, int64_t* image,
+                           int64_t* outside, double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    const int64_t n_bins = (int64_t)nx * nz;
+    hipStream_t st = 0;
+    const SplitPlan plan = spot_plan(R);
+    unsigned n_items = 0;
+    if (int rc = spot_items(plan, who, n_items)) return rc;
+    Packed up;
+    const size_t o_work = up.add(plan.work), o_win = up.add(win);
+    DevBuf d_img, d_out;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_img.alloc(K * (size_t)n_bins * 8)) || (rc = d_out.alloc(K * 8))) return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    HIP_TRY(hipMemsetAsync(d_img.p, 0, K * (size_t)n_bins * 8, st));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, K * 8, st));
+    if (n_items > 0) {
+        if (n_bins <= SPOT_LDS_BINS)
+            hipLaunchKernelGGL(spot_image_kernel<true>, dim3(n_items), dim3(256), (size_t)n_bins * 4, st, rows, cols, up.at<SplitWork>(o_work), up.at<SpotWindow>(o_win), nx,
+                               nz, (unsigned long long*)d_img.p, (unsigned long long*)d_out.p);
+        else
+            hipLaunchKernelGGL(spot_image_kernel<false>, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), up.at<SpotWindow>(o_win), nx, nz,
+                               (unsigned long long*)d_img.p, (unsigned long long*)d_out.p);
+    }
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(image, d_img.p, K * (size_t)n_bins * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(outside, d_out.p, K * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// The statistics [K][BMO_SPOT_STAT_N] of the K configurations from the device rows `rows` [..][cols].
+static int spot_stats_read(const double* rows, int32_t cols, const Ranges& R, double* stats, double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    hipStream_t st = 0;
+    const SplitPlan plan = spot_plan(R);
+    unsigned n_items = 0;
+    if (int rc = spot_items(plan, who, n_items)) return rc;
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count);
+    DevBuf p1, p2, d_stats, d_cent;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = p1.alloc((size_t)n_items * sizeof(SpotSum1))) || (rc = p2.alloc((size_t)n_items * sizeof(SpotSum2))) ||
+        (rc = d_stats.alloc(K * BMO_SPOT_STAT_N * 8)) || (rc = d_cent.alloc(K * sizeof(double2))))
+        return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    const dim3 kb((unsigned)((K + 255) / 256));
+    if (n_items > 0)
+        hipLaunchKernelGGL(spot_centroid_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (SpotSum1*)p1.p);
+    hipLaunchKernelGGL(spot_centroid_reduce_kernel, kb, dim3(256), 0, st, up.at<SplitCfg>(o_cfg), up.at<int64_t>(o_count), (int32_t)K, (const SpotSum1*)p1.p,
+                       (double*)d_stats.p, (double2*)d_cent.p);
+    if (n_items > 0)
+        hipLaunchKernelGGL(spot_moments_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (const double2*)d_cent.p, (SpotSum2*)p2.p);
+    hipLaunchKernelGGL(spot_moments_reduce_kernel, kb, dim3(256), 0, st, up.at<SplitCfg>(o_cfg), up.at<int64_t>(o_count), (int32_t)K, (const SpotSum2*)p2.p,
+                       (double*)d_stats.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_SPOT_STAT_N * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// the device and the device copy of the rows of a single call (d_rows holds an upload of host rows)
+static int spot_single_rows(const char* who, const double*& rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, DevBuf& d_rows) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BMO_ERR_NO_DEVICE, std::string(who) + ": no HIP device (there is no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(BMO_ERR_INVALID, std::string(who) + ": bad device ordinal");
+    HIP_TRY(hipSetDevice(device));
+    if (!rows_on_device && n_rows > 0) {
+        const size_t bytes = (size_t)n_rows * (size_t)row_cols * sizeof(double);
+        if (int rc = d_rows.alloc(bytes)) return rc;
+        HIP_TRY(hipMemcpy(d_rows.p, rows, bytes, hipMemcpyHostToDevice));
+        rows = (const double*)d_rows.p;
+    }
+    return BMO_OK;
+}
+
+// what the _sweep forms check of their result and slot before a device is touched
+static int spot_slot_check(const char* who, const bmo_trace_result* res, int32_t detector, int32_t n_configs) {
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, std::string(who) + ": bad detector slot");
+    if (res->kind == BMO_BEAM_GAUSSIAN)
+        return fail(BMO_ERR_UNSUPPORTED, std::string(who) + ": a GaussianBeamlet solution has no Spotdetector rows (Spotdetector.jl:50 has no method for beamlets)");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_SPOTDETECTOR)
+        return fail(BMO_ERR_INVALID, std::string(who) + ": the slot is not a Spotdetector's");
+    if (n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, std::string(who) + ": n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    return BMO_OK;
+}
+
+static bool spot_image_shape_ok(int32_t nx, int32_t nz) { return nx > 0 && nz > 0 && (int64_t)nx * nz <= (int64_t)0x7fffffff; }
+
+extern "C" int bmo_spot_image(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, const double window[4], int32_t nx, int32_t nz,
+                              int32_t device, int64_t* image, int64_t* outside, double* kernel_ms) {
+    if (!window || !image || !outside || n_rows < 0 || (n_rows > 0 && !rows) || row_cols < 2 || row_cols > 9 || !spot_image_shape_ok(nx, nz))
+        return fail(BMO_ERR_INVALID, "bmo_spot_image: bad argument (null pointer, nx or nz <= 0 or nx * nz >= 2^31, row_cols outside 2..9)");
+    std::vector<SpotWindow> win(1);
+    if (!spot_window(window, nx, nz, win[0])) return fail(BMO_ERR_INVALID, "bmo_spot_image: the window must be finite with x1 > x0 and z1 > z0");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_rows;
+    if (int rc = spot_single_rows("bmo_spot_image", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
+    return spot_image_read(rows, row_cols, Ranges{{0}, {n_rows}}, win, nx, nz, image, outside, kernel_ms, "bmo_spot_image");
+}
+
+extern "C" int bmo_spot_image_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* windows, int32_t nx, int32_t nz, int64_t* image,
+                                    int64_t* outside, double* kernel_ms) {
+    if (!res || !windows || !image || !outside || !spot_image_shape_ok(nx, nz))
+        return fail(BMO_ERR_INVALID, "bmo_spot_image_sweep: bad argument (null pointer, nx or nz <= 0 or nx * nz >= 2^31)");
+    if (int rc = spot_slot_check("bmo_spot_image_sweep", res, detector, n_configs)) return rc;
+    std::vector<SpotWindow> win((size_t)n_configs);
+    for (int32_t c = 0; c < n_configs; ++c)
+        if (!spot_window(windows + 4 * c, nx, nz, win[(size_t)c]))
+            return fail(BMO_ERR_INVALID, "bmo_spot_image_sweep: the window of configuration " + std::to_string(c) + " must be finite with x1 > x0 and z1 > z0");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_rows = 0
+        std::fill(image, image + (size_t)n_configs * (size_t)nx * (size_t)nz, (int64_t)0);
+        std::fill(outside, outside + n_configs, (int64_t)0);
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    Ranges R;
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_spot_image_sweep: rows out of configuration order", 0, R)) return rc;
+    return spot_image_read((const double*)res->det_data.p + 9 * res->det_offset[detector], 9, R, win, nx, nz, image, outside, kernel_ms, "bmo_spot_image_sweep");
+}
+
+extern "C" int bmo_spot_stats(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, double* stats, double* kernel_ms) {
+    if (!stats || n_rows < 0 || (n_rows > 0 && !rows) || row_cols < 2 || row_cols > 9)
+        return fail(BMO_ERR_INVALID, "bmo_spot_stats: bad argument (null pointer, row_cols outside 2..9)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_rows;
+    if (int rc = spot_single_rows("bmo_spot_stats", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
+    return spot_stats_read(rows, row_cols, Ranges{{0}, {n_rows}}, stats, kernel_ms, "bmo_spot_stats");
+}
+
+extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, double* stats, double* kernel_ms) {
+    if (!res || !stats) return fail(BMO_ERR_INVALID, "bmo_spot_stats_sweep: bad argument");
+    if (int rc = spot_slot_check("bmo_spot_stats_sweep", res, detector, n_configs)) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_rows = 0
+        for (int32_t c = 0; c < n_configs; ++c) {
+            double* out = stats + (size_t)c * BMO_SPOT_STAT_N;
+            std::fill(out, out + BMO_SPOT_STAT_N, std::nan(""));
+            out[BMO_SPOT_STAT_N_ROWS] = 0.0;
+        }
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    Ranges R;
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_spot_stats_sweep: rows out of configuration order", 0, R)) return rc;
+    return spot_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], 9, R, stats, kernel_ms, "bmo_spot_stats_sweep");
 }

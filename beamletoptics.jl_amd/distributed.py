@@ -203,3 +203,13 @@ def all_reduce_field(field, group=None):
     buf = torch.view_as_real(field)
     dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
     return field
+
+
+def all_reduce_image(image, group=None):
+    """Sum of the per-rank Spotdetector images: every rank bins the rows of ITS shard of the bundle (bmo_spot_image on one window that all
+    ranks share) and the detector's image is their sum, one all-reduce of the int64 counts.  Integer adds: the result equals the image of
+    the un-sharded solve exactly.  `image`: int64 tensor [nx, nz] (or [n_cfg, nx, nz]); reduced in place and returned."""
+    if image.dtype != torch.int64:
+        raise TypeError("all_reduce_image: the image must be an int64 tensor")
+    dist.all_reduce(image, op=dist.ReduceOp.SUM, group=group)
+    return image

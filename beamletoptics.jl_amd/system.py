@@ -462,6 +462,17 @@ class EngineSolution:
         field[...] = (buf[0::2] + 1j * buf[1::2]).reshape(ny, nx).T
         return ms.value
 
+    def spot_image(self, slot, window, nx, nz=None):
+        """bmo_spot_image_sweep on the resident rows of Spotdetector slot `slot`: (counts int64 [nx, nz] indexed [i, j], outside), binned on
+        window (x0, x1, z0, z1) by the floor rule of include/bmo.h."""
+        img, outside, self.readout_ms = abi.spot_image_sweep(self.handle, slot, 1, window, nx, nz)
+        return img[0], int(outside[0])
+
+    def spot_stats(self, slot):
+        """bmo_spot_stats_sweep on the resident rows of Spotdetector slot `slot`: the twelve statistics (abi.SPOT_* columns)."""
+        st, self.readout_ms = abi.spot_stats_sweep(self.handle, slot, 1)
+        return st[0]
+
 
 def _engine_solve(scene, bundle, r_max, prev, device=0, max_beams=0):
     """One solve on the HIP engine: bmo_trace, or bmo_retrace when `prev` (an EngineSolution) is given."""
@@ -832,6 +843,32 @@ class SweepSolution:
         I, field, ms = abi.psf_intensity_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], xs, zs, want_field=want_field)
         self.readout_ms = ms
         return (xs, zs, I, field) if want_field else (xs, zs, I)
+
+    def spot_stats(self, det):
+        """The spot statistics [n_cfg, 12] (abi.SPOT_* columns) of Spotdetector `det` in every configuration, in one batched read-out
+        (bmo_spot_stats_sweep); row c equals abi.spot_stats on spot_hits(det, c) bit for bit, a configuration without rows reads N = 0 and NaN."""
+        st, self.readout_ms = abi.spot_stats_sweep(self._handle, self._slot(det), self.n)
+        return st
+
+    def spot_image(self, det, nx, nz=None, window=None):
+        """The spot diagram of Spotdetector `det` in every configuration as images, in one batched read-out (bmo_spot_image_sweep):
+        (windows [n_cfg, 4], counts int64 [n_cfg, nx, nz] indexed [c, i, j], outside [n_cfg]).  window: one (x0, x1, z0, z1) for all
+        configurations, None for the detector face, an array [n_cfg, 4], or "extent" for the extrema of each configuration's rows (ValueError
+        naming the first configuration without rows or with a zero extent).  Binning is the floor rule of Spotdetector.image."""
+        slot = self._slot(det)
+        K = self.n
+        if window is None:
+            window = (-det.hw, det.hw, -det.hw, det.hw)
+        if isinstance(window, str):
+            if window != "extent":
+                raise ValueError('spot_image: window must be (x0, x1, z0, z1), [n_cfg, 4], None or "extent"')
+            st = self.spot_stats(det)
+            w = np.array([cp.spot_extent_window(st[c], f"spot_image: configuration {c}") for c in range(K)], dtype=np.float64)
+        else:
+            w = np.asarray(window, dtype=np.float64)
+            w = np.tile(w, (K, 1)) if w.ndim == 1 else w.reshape(K, 4)
+        img, outside, self.readout_ms = abi.spot_image_sweep(self._handle, slot, K, w, nx, nz)
+        return w, img, outside
 
     def optical_power(self, pd, field=None):
         """optical_power(pd) of every configuration, [n]: the trapezoid rule of Photodetector.optical_power on each configuration's field."""

@@ -496,6 +496,56 @@ int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, int32_t n_c
                             const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
                             double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Spot read-out: the spot diagram of a Spotdetector (Spotdetector.jl:21-61 keeps the local x, z of every hit) as a binned image and as
+ * moment statistics, computed on the device from the rows where they lie.  No reference counterpart: the reference's users bin and
+ * average `sd.data` themselves.
+ *
+ * rows : [n_rows][row_cols] doubles, x in column 0 and z in column 1, row_cols in 2..9: the packed columns of bmo_result_copy_hit_columns,
+ *        Spotdetector data, or the 9-column rows of bmo_result_device_hits (rows_on_device != 0: a pointer on `device`).
+ * The _sweep forms read the rows of Spotdetector slot `detector` still resident in `res`, one image / one set of statistics per
+ * configuration; n_configs must be the sweep's, or 1 for an ordinary (non-sweep) result.  They work on record_segments = 0 results (the
+ * hit table is kept).  Configuration c is read exactly as the single call reads its rows: equal images, statistics equal bit for bit.
+ *
+ * Image, window (x0, x1, z0, z1), sx = nx / (x1 - x0) and sz = nz / (z1 - z0) computed once in FP64:
+ *   a row is inside iff x >= x0 && x <= x1 && z >= z0 && z <= z1          (plain compares: a NaN is outside, the upper edge is closed)
+ *   i = min((int64)floor((x - x0) * sx), nx - 1),  j likewise from z,  the row counts in image[i + nx * j]
+ *   outside = rows that are not inside, so sum(image) + outside = n_rows.
+ * image [n_configs][nx * nz], outside [n_configs], windows [n_configs][4].  Counts are integers: the image does not depend on the order
+ * in which the device adds them.
+ *
+ * Statistics, stats [n_configs][BMO_SPOT_STAT_N] at the BMO_SPOT_STAT_* indices: the row count, the centroid, the extrema, the central
+ * moments MXX = sum (x - cx)^2 / n, MZZ, MXZ about the COMPUTED centroid (two passes: sum x^2 - n cx^2 would lose every digit of a small
+ * spot far off centre), RMS_R = sqrt(MXX + MZZ) and GEO_R = sqrt(max (x - cx)^2 + (z - cz)^2).  Count and extrema are exact; the sums run in
+ * a fixed blocked order that depends on the row count only.  No rows: N = 0 and NaN in the other eleven; one row: moments and radii +0.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer, nx or nz <= 0 (or nx * nz >= 2^31), row_cols outside 2..9, a
+ * window that is not finite or has not x1 > x0 and z1 > z0 (or whose extent has no finite bin width), a slot out of range or not a
+ * Spotdetector's, a wrong n_configs.  BMO_ERR_UNSUPPORTED: a GaussianBeamlet result (no Spotdetector method for beamlets,
+ * Spotdetector.jl:50; such slots hold three rows per beamlet).  kernel_ms: optional, HIP-event time of the launches.             */
+enum bmo_spot_stat {
+    BMO_SPOT_STAT_N_ROWS = 0, /* N: the row count                                  */
+    BMO_SPOT_STAT_CX = 1,
+    BMO_SPOT_STAT_CZ = 2,
+    BMO_SPOT_STAT_X_MIN = 3,
+    BMO_SPOT_STAT_X_MAX = 4,
+    BMO_SPOT_STAT_Z_MIN = 5,
+    BMO_SPOT_STAT_Z_MAX = 6,
+    BMO_SPOT_STAT_MXX = 7,
+    BMO_SPOT_STAT_MZZ = 8,
+    BMO_SPOT_STAT_MXZ = 9,
+    BMO_SPOT_STAT_RMS_R = 10,
+    BMO_SPOT_STAT_GEO_R = 11
+};
+#define BMO_SPOT_STAT_N 12
+int bmo_spot_image(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, const double window[4], int32_t nx,
+                   int32_t nz, int32_t device, int64_t* image, int64_t* outside, double* kernel_ms);
+int bmo_spot_image_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* windows, int32_t nx, int32_t nz,
+                         int64_t* image, int64_t* outside, double* kernel_ms);
+int bmo_spot_stats(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, double* stats,
+                   double* kernel_ms);
+int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, double* stats, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
