@@ -20,6 +20,11 @@ PLANES_REC = {0: 11, 1: 17, 2: 33}
 SPOT_STAT_N = 12
 (SPOT_N, SPOT_CX, SPOT_CZ, SPOT_X_MIN, SPOT_X_MAX, SPOT_Z_MIN, SPOT_Z_MAX, SPOT_MXX, SPOT_MZZ, SPOT_MXZ, SPOT_RMS_R, SPOT_GEO_R) = range(SPOT_STAT_N)
 
+# BMO_PSF_STAT_*: columns of the wavefront statistics of PSF rows (bmo_psf_stats)
+PSF_STAT_N = 21
+(PSF_N, PSF_S, PSF_CX, PSF_CZ, PSF_X_MIN, PSF_X_MAX, PSF_Z_MIN, PSF_Z_MAX, PSF_HWX, PSF_HWZ, PSF_X_REF, PSF_Z_REF, PSF_W_MEAN, PSF_W_RMS, PSF_W_LO,
+ PSF_W_HI, PSF_F_RE, PSF_F_IM, PSF_STREHL, PSF_K_MIN, PSF_K_MAX) = range(PSF_STAT_N)
+
 NODE_MISS, NODE_STOPPED, NODE_RMAX, NODE_SPLIT, NODE_DETECTED, NODE_ERR_UNIT, NODE_GAUSS_DIVERGED, NODE_BLOCKED, NODE_ERR_ORTHO = (
     1, 2, 4, 8, 16, 32, 64, 128, 256)
 
@@ -241,6 +246,8 @@ def load_engine():
     lib.bmo_spot_image_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, ip, ip, dp]
     lib.bmo_spot_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     lib.bmo_spot_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
+    lib.bmo_psf_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp]
+    lib.bmo_psf_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -362,4 +369,43 @@ def spot_stats_sweep(res_handle, detector, n_configs):
     st = np.zeros((max(K, 1), SPOT_STAT_N))
     ms = C.c_double()
     check(lib, lib.bmo_spot_stats_sweep(res_handle, int(detector), K, st.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ms)), "bmo_spot_stats_sweep")
+    return st[:K], ms.value
+
+
+def psf_stats(hits, origin, e1, e2, ref=None, device=0, hits_device_ptr=None, n_hits=None):
+    """bmo_psf_stats: the 21 wavefront statistics (PSF_* columns) of PSF rows at the detector pose (origin, e1, e2), three passes on the
+    device.  ref: the reference point (x, z) in detector-local coordinates, None for the centroid.  `hits` is a host [H, 9] array, or pass
+    `hits_device_ptr` + `n_hits` for rows already resident on `device` (bmo_result_device_hits).  Returns (stats [21], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
+    if hits_device_ptr is None:
+        h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
+        hp, nh, on_dev = h.ctypes.data_as(C.c_void_p), len(h), 0
+    else:
+        hp, nh, on_dev = C.c_void_p(int(hits_device_ptr)), int(n_hits), 1
+    st = np.zeros(PSF_STAT_N)
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
+                                 int(device), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats")
+    return st, ms.value
+
+
+def psf_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, ref=None):
+    """bmo_psf_stats_sweep on the result handle `res_handle`: origins / e1s / e2s [K, 3], ref None (every configuration's centroid), one
+    (x, z) for all or [K, 2].  Returns (stats [K, 21], kernel_ms); row c equals psf_stats on the rows of configuration c bit for bit."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
+    r = None
+    if ref is not None:
+        r = np.asarray(ref, dtype=np.float64)
+        r = np.ascontiguousarray(np.tile(r, (K1, 1)) if r.ndim == 1 else r.reshape(K1, 2))
+    st = np.zeros((K1, PSF_STAT_N))
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_stats_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
+                                       None if r is None else r.ctypes.data_as(dp), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats_sweep")
     return st[:K], ms.value

@@ -430,6 +430,45 @@ def psf_sample_axes(rows, position, orientation, n=100, crop_factor=1.0, center=
     return la.linrange(_x_min, _x_max, n) + x0_shift, la.linrange(_z_min, _z_max, n) + z0_shift
 
 
+def psf_axes_from_stats(stats, n=100, crop_factor=1.0, center="centroid", x_min=math.inf, x_max=math.inf, z_min=math.inf, z_max=math.inf,
+                        x0_shift=0.0, z0_shift=0.0):
+    """The rule of psf_sample_axes applied to wavefront statistics (abi.PSF_* columns, bmo_psf_stats) instead of rows: (xs, zs) of [n] for
+    one row of statistics, of [K, n] for [K, 21].  "centroid": CX -+ HWX * crop_factor; otherwise the centre of the bounding box,
+    (X_MIN + X_MAX) / 2, and the half-width about it from the extrema (the largest |x - centre| is attained at X_MIN or X_MAX)."""
+    from . import abi
+
+    st = np.asarray(stats, dtype=np.float64)
+    s2 = st.reshape(-1, abi.PSF_STAT_N)
+    if center == "centroid":
+        x0, z0 = s2[:, abi.PSF_CX], s2[:, abi.PSF_CZ]
+        hx, hz = s2[:, abi.PSF_HWX], s2[:, abi.PSF_HWZ]
+    else:
+        x0, z0 = (s2[:, abi.PSF_X_MIN] + s2[:, abi.PSF_X_MAX]) / 2, (s2[:, abi.PSF_Z_MIN] + s2[:, abi.PSF_Z_MAX]) / 2
+        hx = np.maximum(np.abs(s2[:, abi.PSF_X_MIN] - x0), np.abs(s2[:, abi.PSF_X_MAX] - x0))
+        hz = np.maximum(np.abs(s2[:, abi.PSF_Z_MIN] - z0), np.abs(s2[:, abi.PSF_Z_MAX] - z0))
+    hwx, hwz = hx * crop_factor, hz * crop_factor
+    lims = [x0 - hwx, x0 + hwx, z0 - hwz, z0 + hwz]
+    if x_min != math.inf and x_max != math.inf:
+        lims[0], lims[1] = np.full(len(s2), float(x_min)), np.full(len(s2), float(x_max))
+    if z_min != math.inf and z_max != math.inf:
+        lims[2], lims[3] = np.full(len(s2), float(z_min)), np.full(len(s2), float(z_max))
+    t = np.arange(int(n), dtype=np.float64) / max(int(n) - 1, 1)  # la.linrange, row by row
+    xs = ((1 - t)[None, :] * lims[0][:, None] + t[None, :] * lims[1][:, None]) + x0_shift
+    zs = ((1 - t)[None, :] * lims[2][:, None] + t[None, :] * lims[3][:, None]) + z0_shift
+    return (xs[0], zs[0]) if st.ndim == 1 else (xs, zs)
+
+
+def psf_marechal(stats):
+    """The extended Marechal estimate exp(-(k W_RMS)^2) of the Strehl ratio from wavefront statistics ([21] or [K, 21]); NaN where the rows
+    hold more than one wave number (K_MIN != K_MAX) or no row."""
+    from . import abi
+
+    st = np.asarray(stats, dtype=np.float64)
+    k, rms = st[..., abi.PSF_K_MIN], st[..., abi.PSF_W_RMS]
+    with np.errstate(invalid="ignore"):
+        return np.where(k == st[..., abi.PSF_K_MAX], np.exp(-(k * rms) ** 2), np.nan)
+
+
 class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
     kind = O_PSF
 
@@ -454,6 +493,14 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
         """The (xs, zs) sample coordinates of intensity(psf; ...) PSFDetector.jl:205-217."""
         return psf_sample_axes(self.data, self.position(), self.orientation(), n=n, crop_factor=crop_factor, center=center, x_min=x_min,
                                x_max=x_max, z_min=z_min, z_max=z_max, x0_shift=x0_shift, z0_shift=z0_shift)
+
+    def stats(self, ref=None, device=0):
+        """The 21 wavefront statistics (abi.PSF_* columns: window, RMS wavefront error, peak-to-valley, Strehl ratio) of all rows accumulated so
+        far at the detector's pose, about the reference point ref = (x, z) in local coordinates (None: the centroid)."""
+        from . import abi
+
+        o = self.orientation()
+        return abi.psf_stats(self.data, self.position(), o[:, 0], o[:, 2], ref=ref, device=device)[0]
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

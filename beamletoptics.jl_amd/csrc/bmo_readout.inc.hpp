@@ -23,31 +23,37 @@ namespace {
 
 constexpr int PSF_TILE = 256;
 
-// The point-pt term of the workgroup's grid (origin + x * e1 + z * e2, left to right) summed over hits h0 .. h1 - 1 in hit order.  Every
-// lane of the workgroup calls it (it stages the hits through `tile` and syncs); a lane past the grid (`live` false) only helps to load.
+// origin + x * e1 + z * e2 (left to right): the point (x, z) of the detector plane
+__device__ __forceinline__ d3 psf_point(const d3& origin, const d3& e1, const d3& e2, double x, double z) {
+    return d3{(origin.x + x * e1.x) + z * e2.x, (origin.y + x * e1.y) + z * e2.y, (origin.z + x * e1.z) + z * e2.z};
+}
+// opl + l of row r seen from p, l = dot(p - hit, dir): the path whose k-fold is the phase of the row at p
+__device__ __forceinline__ double psf_path(const d3& p, const double* r) {
+    const double l = ((p.x - r[0]) * r[3] + (p.y - r[1]) * r[4]) + (p.z - r[2]) * r[5];
+    return r[6] + l;
+}
+// rows base .. base + cnt - 1 staged into `tile` with coalesced loads; every lane of the workgroup calls it (it syncs)
+__device__ __forceinline__ void psf_stage_rows(const double* __restrict__ hits, int64_t base, int cnt, double* tile) {
+    __syncthreads();
+    for (int q = threadIdx.x; q < cnt * 9; q += 256) tile[q] = hits[base * 9 + q];
+    __syncthreads();
+}
+
+// The point-pt term of the workgroup's grid (psf_point of its axes) summed over hits h0 .. h1 - 1 in hit order.  Every lane of the
+// workgroup calls it (it stages the hits through `tile` and syncs); a lane past the grid (`live` false) only helps to load.
 __device__ __forceinline__ double2 psf_sum_range(const double* __restrict__ hits, int64_t h0, int64_t h1, const double* __restrict__ xs,
                                                  const double* __restrict__ zs, int32_t n, int64_t pt, bool live, const d3& origin, const d3& e1,
                                                  const d3& e2, double* tile) {
-    double px = 0, py = 0, pz = 0;
-    if (live) {
-        const int i = (int)(pt % n), j = (int)(pt / n);
-        const double x = xs[i], z = zs[j];
-        // origin_pd + x * e1 + z * e2  (left to right)
-        px = (origin.x + x * e1.x) + z * e2.x;
-        py = (origin.y + x * e1.y) + z * e2.y;
-        pz = (origin.z + x * e1.z) + z * e2.z;
-    }
+    d3 p{0, 0, 0};
+    if (live) p = psf_point(origin, e1, e2, xs[(int)(pt % n)], zs[(int)(pt / n)]);
     double re = 0.0, im = 0.0;
     for (int64_t base = h0; base < h1; base += PSF_TILE) {
         const int cnt = (int)(h1 - base < PSF_TILE ? h1 - base : PSF_TILE);
-        __syncthreads();
-        for (int q = threadIdx.x; q < cnt * 9; q += 256) tile[q] = hits[base * 9 + q];
-        __syncthreads();
+        psf_stage_rows(hits, base, cnt, tile);
         if (live) {
             for (int h = 0; h < cnt; ++h) {
                 const double* r = tile + 9 * h;
-                const double l = ((px - r[0]) * r[3] + (py - r[1]) * r[4]) + (pz - r[2]) * r[5];
-                const double phase = r[8] * (r[6] + l);
+                const double phase = r[8] * psf_path(p, r);
                 double s, c;
                 sincos(phase, &s, &c);
                 re += r[7] * c;
@@ -1174,4 +1180,330 @@ extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int
     Ranges R;
     if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_spot_stats_sweep: rows out of configuration order", 0, R)) return rc;
     return spot_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], 9, R, stats, kernel_ms, "bmo_spot_stats_sweep");
+}
+
+// ====================================================================================================================
+// Wavefront read-out: the statistics of a PSFDetector's rows (include/bmo.h "Wavefront read-out"): the proj-weighted centroid, the extrema
+// and half-widths of calc_local_lims (PSFDetector.jl:115-140), and the wavefront error and Strehl ratio at a reference point of the
+// detector plane.  The plumbing of the spot statistics (slot_ranges, spot_plan, work items on the grid's x dimension, lane / shuffle / wave
+// / split order of the sums), three accumulate passes with a per-configuration reduce each, queued behind one synchronisation:
+//   A  N, S, sum proj x, sum proj z, the extrema of x, z and k; its reduce leaves the centroid and the reference point p on the device
+//   B  half-widths about the computed centroid, sum proj W, F = sum proj cis(k W); writes (proj, W) of every row to a scratch column
+//   C  sum proj (W - W_MEAN)^2 and the extrema of W - W_MEAN, from the 16-byte scratch rows instead of the 72-byte rows
+// A reduce is one workgroup per configuration: it stages the configuration's partial sums through LDS and thread 0 folds them in split order
+// (psf_stats_fold).
+// Passes A and B use all nine columns: they stage tiles of 256 rows through LDS with coalesced loads (psf_stage_rows) and lane l then
+// reads row l of the tile (a 72-byte stride: the lanes of a half-wave fall on distinct even banks).
+namespace {
+
+struct PsfStatSumA {
+    double s, sx, sz, x_min, x_max, z_min, z_max, k_min, k_max;
+};
+struct PsfStatSumB {
+    double hwx, hwz, sw, re, im;
+};
+struct PsfStatSumC {
+    double var, lo, hi;
+};
+// what the later passes need of configuration c
+struct PsfStatMid {
+    double cx, cz, w_mean;
+    d3 p;  // the reference point in world coordinates
+};
+
+// local coordinate of row r along axis e (PSFDetector.jl:95-97): dot(hit - origin, e), left to right
+__device__ __forceinline__ double psf_local(const double* r, const d3& o, const d3& e) {
+    return ((r[0] - o.x) * e.x + (r[1] - o.y) * e.y) + (r[2] - o.z) * e.z;
+}
+
+// pass A of work item blockIdx.x
+__global__ __launch_bounds__(256) void psf_stats_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
+                                                             PsfStatSumA* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const PsfPose C = pose[W.cfg];
+    double s = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf(), k_min = kinf(), k_max = -kinf();
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
+            const double w = r[7], k = r[8];
+            s += w;
+            sx += w * x;
+            sz += w * z;
+            x_min = x < x_min ? x : x_min;
+            x_max = x > x_max ? x : x_max;
+            z_min = z < z_min ? z : z_min;
+            z_max = z > z_max ? z : z_max;
+            k_min = k < k_min ? k : k_min;
+            k_max = k > k_max ? k : k_max;
+        }
+    }
+    PsfStatSumA a;
+    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
+    a.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
+    a.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
+    a.x_min = spot_wg_reduce(x_min, SpotMin{}, sh);
+    a.x_max = spot_wg_reduce(x_max, SpotMax{}, sh);
+    a.z_min = spot_wg_reduce(z_min, SpotMin{}, sh);
+    a.z_max = spot_wg_reduce(z_max, SpotMax{}, sh);
+    a.k_min = spot_wg_reduce(k_min, SpotMin{}, sh);
+    a.k_max = spot_wg_reduce(k_max, SpotMax{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+
+// The partial sums of one configuration folded in split order by thread 0 of the workgroup.  A configuration of 2 048 splits would keep one
+// thread waiting on 2 048 dependent trips to memory; instead the workgroup copies them to `lds` with coalesced loads, PSF_FOLD_CHUNK at a
+// time, and thread 0 folds them from there.  Every thread of the workgroup calls it (it syncs); `fold` runs on thread 0 only.
+constexpr int PSF_FOLD_CHUNK = 512;
+template <class P, class Fold>
+__device__ __forceinline__ void psf_stats_fold(const P* __restrict__ partial, const SplitCfg& C, double* lds, Fold&& fold) {
+    constexpr int W = (int)(sizeof(P) / sizeof(double));
+    for (int s0 = 0; s0 < C.n_splits; s0 += PSF_FOLD_CHUNK) {
+        const int cnt = C.n_splits - s0 < PSF_FOLD_CHUNK ? C.n_splits - s0 : PSF_FOLD_CHUNK;
+        const double* src = (const double*)(partial + C.first_work + s0);
+        __syncthreads();
+        for (int q = threadIdx.x; q < cnt * W; q += blockDim.x) lds[q] = src[q];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < cnt; ++i) fold(*(const P*)(lds + i * W));
+    }
+}
+
+// configuration blockIdx.x: the splits of pass A in split order; N, S, the centroid, the extrema and the reference point go to stats[c], what the
+// later passes need to mid[c].  ref_xz: nullptr (the centroid) or [K][2]
+__global__ void psf_stats_sums_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfPose* __restrict__ pose,
+                                             const double* __restrict__ ref_xz, const PsfStatSumA* __restrict__ partial, double* __restrict__ stats,
+                                             PsfStatMid* __restrict__ mid) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumA) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;  // one workgroup per configuration
+    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+    const int64_t n = count[c];
+    if (n == 0) {
+        if (threadIdx.x == 0) {
+            out[BMO_PSF_STAT_N_ROWS] = 0.0;
+            for (int q = 1; q < BMO_PSF_STAT_N; ++q) out[q] = knan();
+            mid[c] = PsfStatMid{0.0, 0.0, 0.0, d3{0.0, 0.0, 0.0}};
+        }
+        return;
+    }
+    double s = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf(), k_min = kinf(), k_max = -kinf();
+    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumA& p) {
+        s += p.s;
+        sx += p.sx;
+        sz += p.sz;
+        x_min = p.x_min < x_min ? p.x_min : x_min;
+        x_max = p.x_max > x_max ? p.x_max : x_max;
+        z_min = p.z_min < z_min ? p.z_min : z_min;
+        z_max = p.z_max > z_max ? p.z_max : z_max;
+        k_min = p.k_min < k_min ? p.k_min : k_min;
+        k_max = p.k_max > k_max ? p.k_max : k_max;
+    });
+    if (threadIdx.x != 0) return;
+    out[BMO_PSF_STAT_N_ROWS] = (double)n;
+    const double cx = sx / s, cz = sz / s;
+    const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+    out[BMO_PSF_STAT_S] = s;
+    out[BMO_PSF_STAT_CX] = cx;
+    out[BMO_PSF_STAT_CZ] = cz;
+    out[BMO_PSF_STAT_X_MIN] = x_min;
+    out[BMO_PSF_STAT_X_MAX] = x_max;
+    out[BMO_PSF_STAT_Z_MIN] = z_min;
+    out[BMO_PSF_STAT_Z_MAX] = z_max;
+    out[BMO_PSF_STAT_X_REF] = x_ref;
+    out[BMO_PSF_STAT_Z_REF] = z_ref;
+    out[BMO_PSF_STAT_K_MIN] = k_min;
+    out[BMO_PSF_STAT_K_MAX] = k_max;
+    const PsfPose P = pose[c];
+    mid[c] = PsfStatMid{cx, cz, 0.0, psf_point(P.origin, P.e1, P.e2, x_ref, z_ref)};
+}
+
+// pass B of work item blockIdx.x; pw[h] = (proj, W) of row h for pass C
+__global__ __launch_bounds__(256) void psf_stats_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
+                                                             const PsfStatMid* __restrict__ mid, double2* __restrict__ pw, PsfStatSumB* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const PsfPose C = pose[W.cfg];
+    const PsfStatMid M = mid[W.cfg];
+    double hwx = 0.0, hwz = 0.0, sw = 0.0, re = 0.0, im = 0.0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double ax = fabs(psf_local(r, C.origin, C.e1) - M.cx), az = fabs(psf_local(r, C.origin, C.e2) - M.cz);
+            hwx = ax > hwx ? ax : hwx;
+            hwz = az > hwz ? az : hwz;
+            const double w = r[7];
+            const double path = psf_path(M.p, r);
+            const double phase = r[8] * path;
+            double sn, cs;
+            sincos(phase, &sn, &cs);
+            sw += w * path;
+            re += w * cs;
+            im += w * sn;
+            pw[base + threadIdx.x] = make_double2(w, path);
+        }
+    }
+    PsfStatSumB b;
+    b.hwx = spot_wg_reduce(hwx, SpotMax{}, sh);
+    b.hwz = spot_wg_reduce(hwz, SpotMax{}, sh);
+    b.sw = spot_wg_reduce(sw, SpotAdd{}, sh);
+    b.re = spot_wg_reduce(re, SpotAdd{}, sh);
+    b.im = spot_wg_reduce(im, SpotAdd{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+}
+
+__global__ void psf_stats_wave_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfStatSumB* __restrict__ partial,
+                                             double* __restrict__ stats, PsfStatMid* __restrict__ mid) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumB) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;
+    if (count[c] == 0) return;  // NaN already
+    double hwx = 0.0, hwz = 0.0, sw = 0.0, re = 0.0, im = 0.0;
+    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumB& p) {
+        hwx = p.hwx > hwx ? p.hwx : hwx;
+        hwz = p.hwz > hwz ? p.hwz : hwz;
+        sw += p.sw;
+        re += p.re;
+        im += p.im;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+    const double s = out[BMO_PSF_STAT_S];
+    const double w_mean = sw / s;
+    out[BMO_PSF_STAT_HWX] = hwx;
+    out[BMO_PSF_STAT_HWZ] = hwz;
+    out[BMO_PSF_STAT_W_MEAN] = w_mean;
+    out[BMO_PSF_STAT_F_RE] = re;
+    out[BMO_PSF_STAT_F_IM] = im;
+    out[BMO_PSF_STAT_STREHL] = (re * re + im * im) / (s * s);
+    mid[c].w_mean = w_mean;
+}
+
+// pass C of work item blockIdx.x, on the scratch column of pass B
+__global__ __launch_bounds__(256) void psf_stats_spread_kernel(const double2* __restrict__ pw, const SplitWork* __restrict__ work, const PsfStatMid* __restrict__ mid,
+                                                               PsfStatSumC* __restrict__ partial) {
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const double w_mean = mid[W.cfg].w_mean;
+    double var = 0.0, lo = kinf(), hi = -kinf();
+    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+        const double2 v = pw[h];
+        const double d = v.y - w_mean;
+        var += v.x * (d * d);
+        lo = d < lo ? d : lo;
+        hi = d > hi ? d : hi;
+    }
+    PsfStatSumC s;
+    s.var = spot_wg_reduce(var, SpotAdd{}, sh);
+    s.lo = spot_wg_reduce(lo, SpotMin{}, sh);
+    s.hi = spot_wg_reduce(hi, SpotMax{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void psf_stats_spread_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfStatSumC* __restrict__ partial,
+                                               double* __restrict__ stats) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumC) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;
+    if (count[c] == 0) return;  // NaN already
+    double var = 0.0, lo = kinf(), hi = -kinf();
+    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumC& p) {
+        var += p.var;
+        lo = p.lo < lo ? p.lo : lo;
+        hi = p.hi > hi ? p.hi : hi;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+    out[BMO_PSF_STAT_W_RMS] = sqrt(var / out[BMO_PSF_STAT_S]);
+    out[BMO_PSF_STAT_W_LO] = lo;
+    out[BMO_PSF_STAT_W_HI] = hi;
+}
+
+}  // namespace
+
+// N = 0 and NaN in the other twenty: what a configuration without rows reads
+static void psf_stats_empty(double* stats, int32_t n_configs) {
+    for (int32_t c = 0; c < n_configs; ++c) {
+        double* out = stats + (size_t)c * BMO_PSF_STAT_N;
+        std::fill(out, out + BMO_PSF_STAT_N, std::nan(""));
+        out[BMO_PSF_STAT_N_ROWS] = 0.0;
+    }
+}
+
+// The statistics [K][BMO_PSF_STAT_N] of the K configurations from the n_rows device rows `hits` [..][9]: poses [K][3], ref_xz nullptr or [K][2].
+static int psf_stats_read(const double* hits, int64_t n_rows, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* ref_xz,
+                          double* stats, double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    hipStream_t st = 0;
+    const SplitPlan plan = spot_plan(R);
+    unsigned n_items = 0;
+    if (int rc = spot_items(plan, who, n_items)) return rc;
+    std::vector<PsfPose> pose(K);
+    for (size_t c = 0; c < K; ++c) {
+        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
+        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
+    }
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(pose);
+    const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0;
+    DevBuf pa, pb, pc, d_stats, d_mid, d_pw;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = pa.alloc((size_t)n_items * sizeof(PsfStatSumA))) || (rc = pb.alloc((size_t)n_items * sizeof(PsfStatSumB))) ||
+        (rc = pc.alloc((size_t)n_items * sizeof(PsfStatSumC))) || (rc = d_stats.alloc(K * BMO_PSF_STAT_N * 8)) || (rc = d_mid.alloc(K * sizeof(PsfStatMid))) ||
+        (rc = d_pw.alloc((size_t)n_rows * sizeof(double2))))
+        return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    const dim3 kb((unsigned)K);  // the reduces: one workgroup per configuration
+    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
+    const SplitWork* d_work = up.at<SplitWork>(o_work);
+    const int64_t* d_count = up.at<int64_t>(o_count);
+    const PsfPose* d_pose = up.at<PsfPose>(o_pose);
+    if (n_items > 0) hipLaunchKernelGGL(psf_stats_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (PsfStatSumA*)pa.p);
+    hipLaunchKernelGGL(psf_stats_sums_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr,
+                       (const PsfStatSumA*)pa.p, (double*)d_stats.p, (PsfStatMid*)d_mid.p);
+    if (n_items > 0)
+        hipLaunchKernelGGL(psf_stats_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const PsfStatMid*)d_mid.p, (double2*)d_pw.p, (PsfStatSumB*)pb.p);
+    hipLaunchKernelGGL(psf_stats_wave_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const PsfStatSumB*)pb.p, (double*)d_stats.p, (PsfStatMid*)d_mid.p);
+    if (n_items > 0)
+        hipLaunchKernelGGL(psf_stats_spread_kernel, dim3(n_items), dim3(256), 0, st, (const double2*)d_pw.p, d_work, (const PsfStatMid*)d_mid.p, (PsfStatSumC*)pc.p);
+    hipLaunchKernelGGL(psf_stats_spread_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const PsfStatSumC*)pc.p, (double*)d_stats.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_PSF_STAT_N * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                             const double* ref_xz, int32_t device, double* stats, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !stats || n_hits < 0 || (n_hits > 0 && !hits)) return fail(BMO_ERR_INVALID, "bmo_psf_stats: bad argument (null pointer, n_hits < 0)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = spot_single_rows("bmo_psf_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    return psf_stats_read(hits, n_hits, Ranges{{0}, {n_hits}}, origin, e1, e2, ref_xz, stats, kernel_ms, "bmo_psf_stats");
+}
+
+extern "C" int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                   const double* ref_xz, double* stats, double* kernel_ms) {
+    if (!res || !origins || !e1s || !e2s || !stats) return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: bad detector slot");
+    if (res->kind == BMO_BEAM_GAUSSIAN)
+        return fail(BMO_ERR_UNSUPPORTED, "bmo_psf_stats_sweep: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
+        return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: the slot is not a PSFDetector's");
+    if (n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        psf_stats_empty(stats, n_configs);
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    Ranges R;
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_stats_sweep: rows out of configuration order", 0, R)) return rc;
+    return psf_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, stats, kernel_ms, "bmo_psf_stats_sweep");
 }

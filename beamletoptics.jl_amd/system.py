@@ -473,6 +473,26 @@ class EngineSolution:
         st, self.readout_ms = abi.spot_stats_sweep(self.handle, slot, 1)
         return st[0]
 
+    def psf_stats(self, slot, position, orientation, ref=None):
+        """bmo_psf_stats_sweep on the resident rows of PSFDetector slot `slot` at the pose (position, orientation): the 21 wavefront statistics
+        (abi.PSF_* columns) about ref = (x, z) in local coordinates (None: the centroid)."""
+        o = np.asarray(orientation, dtype=np.float64)
+        st, self.readout_ms = abi.psf_stats_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], ref=ref)
+        return st[0]
+
+    def psf_intensity(self, slot, position, orientation, n=100, **window_kw):
+        """intensity(psf; ...) of the resident rows of PSFDetector slot `slot`: (xs, zs, I[n, n]).  The window comes from psf_stats
+        (components.psf_axes_from_stats takes window_kw), the image from bmo_psf_intensity_sweep: only the image leaves the device."""
+        st = self.psf_stats(slot, position, orientation)
+        ms = self.readout_ms
+        if st[abi.PSF_N] == 0:
+            raise ValueError("psf_intensity: the PSFDetector recorded no hit")
+        xs, zs = cp.psf_axes_from_stats(st, n=n, **window_kw)
+        o = np.asarray(orientation, dtype=np.float64)
+        I, _, ms2 = abi.psf_intensity_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], xs, zs)
+        self.readout_ms = ms + ms2
+        return xs, zs, I[0]
+
 
 def _engine_solve(scene, bundle, r_max, prev, device=0, max_beams=0):
     """One solve on the HIP engine: bmo_trace, or bmo_retrace when `prev` (an EngineSolution) is given."""
@@ -814,12 +834,16 @@ class SweepSolution:
         return np.ascontiguousarray(f.transpose(0, 2, 1))
 
     def psf_intensity(self, det, n=100, crop_factor=1, center="centroid", x_min=math.inf, x_max=math.inf, z_min=math.inf, z_max=math.inf,
-                      x0_shift=0, z0_shift=0, axes=None, want_field=False):
+                      x0_shift=0, z0_shift=0, axes=None, want_field=False, window="host"):
         """intensity(psf; ...) of PSFDetector `det` in every configuration, in one batched read-out (bmo_psf_intensity_sweep): (xs[n_cfg, n],
         zs[n_cfg, n], I[n_cfg, n, n]), and the complex field [n_cfg, n, n] as well with `want_field`.  Configuration c samples the axes
         PSFDetector.sample_axes gives for its rows at its detector pose, and equals PSFDetector.intensity after a solve of its snapshot bit for
         bit.  axes=(xs, zs) samples every configuration on that one window instead (a through-focus comparison); without it a configuration
-        whose detector recorded no hit has no window, a ValueError."""
+        whose detector recorded no hit has no window, a ValueError.  window="device" takes every configuration's axes from one psf_stats
+        read-out (components.psf_axes_from_stats) instead of the host copy of the rows: the same rule, with the centroid summed in the
+        device's order, so the axes may differ from the "host" ones in their last bits."""
+        if window not in ("host", "device"):
+            raise ValueError('psf_intensity: window must be "host" or "device"')
         slot = self._slot(det)
         K = self.n
         pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
@@ -829,7 +853,16 @@ class SweepSolution:
             if ax.ndim != 1 or ax.shape != az.shape:
                 raise ValueError("psf_intensity: axes must be two 1-D arrays of one length")
             xs, zs = np.tile(ax, (K, 1)), np.tile(az, (K, 1))
+            stats_ms = 0.0
+        elif window == "device":
+            st, stats_ms = abi.psf_stats_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2])
+            empty = np.flatnonzero(st[:, abi.PSF_N] == 0)
+            if len(empty):
+                raise ValueError(f"psf_intensity: the PSFDetector recorded no hit in configuration {empty[0]}; pass axes=(xs, zs) to read it")
+            xs, zs = cp.psf_axes_from_stats(st, n=n, crop_factor=crop_factor, center=center, x_min=x_min, x_max=x_max, z_min=z_min, z_max=z_max,
+                                            x0_shift=x0_shift, z0_shift=z0_shift)
         else:
+            stats_ms = 0.0
             nodes = self.res.detector_nodes(slot)
             cfg = self.res.node_root[nodes] // max(1, self.n_roots)
             start = np.searchsorted(cfg, np.arange(K + 1))  # rows are in configuration order
@@ -841,8 +874,19 @@ class SweepSolution:
                 xs[c], zs[c] = cp.psf_sample_axes(rows[start[c]:start[c + 1]], pos[c], ori[c], n=n, crop_factor=crop_factor, center=center,
                                                   x_min=x_min, x_max=x_max, z_min=z_min, z_max=z_max, x0_shift=x0_shift, z0_shift=z0_shift)
         I, field, ms = abi.psf_intensity_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], xs, zs, want_field=want_field)
-        self.readout_ms = ms
+        self.readout_ms = ms + stats_ms
         return (xs, zs, I, field) if want_field else (xs, zs, I)
+
+    def psf_stats(self, det, ref=None):
+        """The wavefront statistics [n_cfg, 21] (abi.PSF_* columns) of PSFDetector `det` in every configuration, in one batched read-out
+        (bmo_psf_stats_sweep) at each configuration's detector pose; ref: None (each centroid), one (x, z) or [n_cfg, 2].  Row c equals
+        abi.psf_stats on detector_hits(det, c) bit for bit, a configuration without rows reads N = 0 and NaN."""
+        slot = self._slot(det)
+        K = self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
+        st, self.readout_ms = abi.psf_stats_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], ref=ref)
+        return st
 
     def spot_stats(self, det):
         """The spot statistics [n_cfg, 12] (abi.SPOT_* columns) of Spotdetector `det` in every configuration, in one batched read-out

@@ -546,6 +546,64 @@ int bmo_spot_stats(const double* rows, int64_t n_rows, int32_t row_cols, int32_t
                    double* kernel_ms);
 int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, double* stats, double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Wavefront read-out: the scalar statistics of a PSFDetector's rows, computed on the device from the rows where they lie: the sampling
+ * window of calc_local_lims (PSFDetector.jl:115-140), and the wavefront error and Strehl ratio that PSFDetector.jl:185-188 announces
+ * ("a Strehl estimator will be added") but does not have.
+ *
+ * hits : [n_hits][9] doubles as for bmo_psf_intensity (hit xyz, dir xyz, opl, proj, k); origin, e1, e2 the detector pose as there.
+ * ref_xz : the reference point (x, z) in detector-local coordinates, [2] (the _sweep form: [n_configs][2]); NULL: the centroid.
+ * stats : [n_configs][BMO_PSF_STAT_N] at the BMO_PSF_STAT_* indices.  Everything is FP64, each expression evaluated left to right as
+ * written, without contraction, h running over the rows:
+ *   x_h = ((hx - ox) * e1x + (hy - oy) * e1y) + (hz - oz) * e1z,   z_h the same with e2                     (PSFDetector.jl:95-97)
+ *   S = sum proj_h,   CX = (sum proj_h * x_h) / S,   CZ = (sum proj_h * z_h) / S                              (PSFDetector.jl:126-128)
+ *   X_MIN .. Z_MAX, K_MIN, K_MAX: the extrema of x_h, z_h and k_h
+ *   HWX = max |x_h - CX|,   HWZ = max |z_h - CZ|   about the COMPUTED centroid                                (PSFDetector.jl:135-136)
+ *   (X_REF, Z_REF) = ref_xz or (CX, CZ);   p = (origin + X_REF * e1) + Z_REF * e2 per component   (the grid point of bmo_psf_intensity)
+ *   l_h = ((px - hx) * dx + (py - hy) * dy) + (pz - hz) * dz,   W_h = opl_h + l_h,   phase_h = k_h * W_h      (PSFDetector.jl:229-230)
+ *   W_MEAN = (sum proj_h * W_h) / S
+ *   W_RMS = sqrt((sum proj_h * ((W_h - W_MEAN) * (W_h - W_MEAN))) / S)   in metres, about the computed mean in a pass of its own
+ *   W_LO = min (W_h - W_MEAN),   W_HI = max (W_h - W_MEAN)                (peak-to-valley = W_HI - W_LO)
+ *   F = sum proj_h * cis(phase_h)  (F_RE, F_IM: the field of bmo_psf_intensity at p),   STREHL = (F_RE * F_RE + F_IM * F_IM) / (S * S)
+ * STREHL is the intensity at p over its value if every row arrived in phase: <= 1, rows of several wavelengths summed coherently as
+ * intensity(psf) sums them.  No rows: N_ROWS = 0 and NaN in the other twenty.  The sums run in a fixed blocked order that depends on the
+ * row count only (the order of bmo_spot_stats), so configuration c of the _sweep form equals the single call on its rows and resident
+ * rows equal host rows, bit for bit.  The _sweep form reads the rows of PSFDetector slot `detector` still resident in `res` at the poses
+ * origins / e1s / e2s [n_configs][3]; n_configs must be the sweep's, or 1 for an ordinary result; it works on record_segments = 0
+ * results (the hit table is kept).
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer (ref_xz excepted), n_hits < 0, a slot out of range or not a
+ * PSFDetector's, a wrong n_configs.  BMO_ERR_UNSUPPORTED: a GaussianBeamlet result (three rows per beamlet).  BMO_ERR_INTERNAL, never a
+ * wrong answer, if the rows of a configuration are not consecutive.  kernel_ms: optional, HIP-event time of the launches.            */
+enum bmo_psf_stat {
+    BMO_PSF_STAT_N_ROWS = 0, /* N: the row count */
+    BMO_PSF_STAT_S = 1,
+    BMO_PSF_STAT_CX = 2,
+    BMO_PSF_STAT_CZ = 3,
+    BMO_PSF_STAT_X_MIN = 4,
+    BMO_PSF_STAT_X_MAX = 5,
+    BMO_PSF_STAT_Z_MIN = 6,
+    BMO_PSF_STAT_Z_MAX = 7,
+    BMO_PSF_STAT_HWX = 8,
+    BMO_PSF_STAT_HWZ = 9,
+    BMO_PSF_STAT_X_REF = 10,
+    BMO_PSF_STAT_Z_REF = 11,
+    BMO_PSF_STAT_W_MEAN = 12,
+    BMO_PSF_STAT_W_RMS = 13,
+    BMO_PSF_STAT_W_LO = 14,
+    BMO_PSF_STAT_W_HI = 15,
+    BMO_PSF_STAT_F_RE = 16,
+    BMO_PSF_STAT_F_IM = 17,
+    BMO_PSF_STAT_STREHL = 18,
+    BMO_PSF_STAT_K_MIN = 19,
+    BMO_PSF_STAT_K_MAX = 20
+};
+#define BMO_PSF_STAT_N 21
+int bmo_psf_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                  const double e2[3], const double* ref_xz, int32_t device, double* stats, double* kernel_ms);
+int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                        const double* e2s, const double* ref_xz, double* stats, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

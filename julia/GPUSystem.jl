@@ -880,3 +880,41 @@ function gpu_intensity(psf::PSFDetector{T}; n::Int = 100, crop_factor::Real = 1,
         pointer(hits), length(psf.data), 0, origin, e1, e2, xs, zs, n, device, I, C_NULL, C_NULL))
     return xs, zs, I
 end
+
+# BMO_PSF_STAT_*: columns of the wavefront statistics (include/bmo.h "Wavefront read-out"), zero-based as in the header
+const PSF_STAT_N_ROWS, PSF_STAT_S, PSF_STAT_CX, PSF_STAT_CZ, PSF_STAT_X_MIN, PSF_STAT_X_MAX, PSF_STAT_Z_MIN, PSF_STAT_Z_MAX, PSF_STAT_HWX, PSF_STAT_HWZ, PSF_STAT_X_REF, PSF_STAT_Z_REF, PSF_STAT_W_MEAN, PSF_STAT_W_RMS, PSF_STAT_W_LO, PSF_STAT_W_HI, PSF_STAT_F_RE, PSF_STAT_F_IM, PSF_STAT_STREHL, PSF_STAT_K_MIN, PSF_STAT_K_MAX = Int32.(0:20)
+const PSF_STAT_N = Int32(21)
+
+"""
+    psf_stats(sys::GPUSystem, psf::PSFDetector; ref = nothing, device = 0)
+    psf_stats(sys::GPUSystem, key, slot::Integer, psf::PSFDetector; ref = nothing)
+
+The 21 wavefront statistics of a PSFDetector's rows (`bmo_psf_stats`; index `PSF_STAT_* + 1`): the window of `calc_local_lims`, the RMS
+wavefront error, its extrema and the Strehl ratio about `ref = (x, z)` in detector-local coordinates (`nothing`: the centroid).  The first
+form reads the rows accumulated in `psf.data`; the second the rows of detector slot `slot` still resident in the solution of the beams
+`key` (`bmo_psf_stats_sweep` with one configuration), at the pose of `psf`.
+"""
+function psf_stats(sys::GPUSystem, psf::PSFDetector; ref = nothing, device::Integer = 0)
+    hits = reinterpret(Float64, psf.data)
+    R = orientation(psf)
+    origin, e1, e2 = collect(Float64, position(psf)), collect(Float64, R[:, 1]), collect(Float64, R[:, 3])
+    r = ref === nothing ? Float64[] : collect(Float64, ref)
+    stats = Vector{Float64}(undef, PSF_STAT_N)
+    GC.@preserve hits origin e1 e2 r stats check(ccall((:bmo_psf_stats, LIBBMO), Cint,
+        (Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+        pointer(hits), length(psf.data), 0, origin, e1, e2, ref === nothing ? C_NULL : pointer(r), device, stats, C_NULL))
+    return stats
+end
+
+function psf_stats(sys::GPUSystem, key, slot::Integer, psf::PSFDetector; ref = nothing)
+    res = get(sys.solved, key, C_NULL)
+    res == C_NULL && error("psf_stats: these beams have no resident solution")
+    R = orientation(psf)
+    origin, e1, e2 = collect(Float64, position(psf)), collect(Float64, R[:, 1]), collect(Float64, R[:, 3])
+    r = ref === nothing ? Float64[] : collect(Float64, ref)
+    stats = Vector{Float64}(undef, PSF_STAT_N)
+    GC.@preserve origin e1 e2 r stats check(ccall((:bmo_psf_stats_sweep, LIBBMO), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        res, slot, 1, origin, e1, e2, ref === nothing ? C_NULL : pointer(r), stats, C_NULL))
+    return stats
+end
