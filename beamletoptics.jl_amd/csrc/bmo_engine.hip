@@ -229,7 +229,8 @@ struct OldSolution {
 };
 constexpr int OLD_LOC_SHIFT = 40;
 // planes and slot of stored record k of beam `node` of the previous solution
-__device__ __forceinline__ const double* old_record(const OldSolution& O, int32_t node, int32_t k, int64_t& cap, int64_t& slot) {
+template <class Old>  // (OldSolution, in a kernel's arguments or behind step_params_again)
+__device__ __forceinline__ const double* old_record(Old& O, int32_t node, int32_t k, int64_t& cap, int64_t& slot) {
     const int64_t loc = O.rec_loc[(int64_t)O.rec_start[node] + k];
     const OldChunk c = O.chunks[loc >> OLD_LOC_SHIFT];
     cap = c.cap;
@@ -309,18 +310,54 @@ struct StepParams {
 #endif
 };
 
+// The launch parameters where they are used.  A step kernel's only argument is its StepParams, ~2 KB at offset 0 of the kernel-argument
+// segment: constant-address-space memory the wave reads with scalar loads.  Read as `P.field`, every field the code BEHIND the marches
+// wants (chunks, node arrays, counters: some forty pointers and sizes) is loaded once at the kernel's entry, and as the marches leave no
+// scalar register free the values are parked in the lanes of vector registers for the whole kernel — 124 v_writelane in the headline
+// kernel's prologue, several hundred v_readlane at the level boundaries, each a vector instruction of a kernel that is bound by vector
+// issue.  step_params_again() hands out the address of the same arguments through an empty asm the optimiser cannot see through: the
+// fields read through it are loaded where the statement stands, by scalar loads served by the scalar cache, and are dead again before
+// the next march.  Called once per level at the loop head and once behind tracing_step; only what the marches themselves need (the
+// SceneView) is read from `P` directly.  Nothing is copied: the struct is never addressed in scratch.
+// PRECONDITION: the StepParams is the kernel's FIRST explicit argument (offset 0 of the segment) and the caller is inlined into that
+// __global__ function — the address is the running kernel's argument segment, whatever kernel that is.  Both step kernels take the
+// StepParams as their only argument (launch_step is their one launch site) and say so at their signatures.
+// HELD = true gives the plain address of `P` instead, i.e. the form before: the sweep builds keep it (with the lanes-below mask and the
+// thread index as they were, prefix_rank / step_tid below) — read again, seven of them needed 4 - 16 B MORE scratch per lane.
+typedef const BMO_KONST StepParams KStepParams;
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ KStepParams* kernel_args_again() {
+    KStepParams* q = (KStepParams*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(q));
+    return q;
+}
+#else
+__host__ __device__ inline KStepParams* kernel_args_again() { return nullptr; }  // (host pass of the kernels' bodies: never runs)
+#endif
+template <bool HELD>
+__device__ __forceinline__ auto step_params_again(const StepParams& P) {
+    if constexpr (HELD) return &P;
+    else return kernel_args_again();
+}
+// a chunk of the launch as the HELD builds have it, a copy, where the others have its address in the arguments (both: c->cap, c->d, c->i)
+struct HeldChunk {
+    Chunk c;
+    __device__ const Chunk* operator->() const { return &c; }
+};
+
 // Per-lane retrace context (shared by the Beam and the GaussianBeamlet step kernels; tests/emu walks the same rules)
 struct RetraceLane {
     int32_t old = -1, old_n = 0, probe_obj = -1;
     bool probe = false, fresh_allowed = true, missed = false;
 };
-__device__ __forceinline__ RetraceLane retrace_lane(const StepParams& P, int32_t node, int32_t k) {
+template <class Params>  // (const StepParams*, or what step_params_again hands out)
+__device__ __forceinline__ RetraceLane retrace_lane(Params* P, int32_t node, int32_t k) {
     RetraceLane r;
-    r.old = P.nodes.old[node];
+    r.old = P->nodes.old[node];
     if (r.old >= 0) {
-        r.old_n = P.old.nseg[r.old];
-        r.probe_obj = P.old.rec_obj[(int64_t)P.old.rec_start[r.old] + k];
-        r.fresh_allowed = k + 1 < P.r_max;
+        r.old_n = P->old.nseg[r.old];
+        r.probe_obj = P->old.rec_obj[(int64_t)P->old.rec_start[r.old] + k];
+        r.fresh_allowed = k + 1 < P->r_max;
         r.probe = r.probe_obj >= 0;
         r.missed = !r.probe;  // a stored ray without intersection: cleanup, trace_system! goes on without a hint
     }
@@ -328,8 +365,17 @@ __device__ __forceinline__ RetraceLane retrace_lane(const StepParams& P, int32_t
 }
 
 __device__ inline int lane_id() { return (int)(threadIdx.x & 63); }
+// lanes below this one that are set in `mask`
+template <bool MBCNT = true>
 __device__ inline int prefix_rank(unsigned long long mask) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (!MBCNT) return __popcll(mask & ((1ull << lane_id()) - 1ull));
+    // (the count instruction made for it: the mask of the lanes below, a loop invariant, is not built — the step kernels held it in two
+    //  registers, or 8 B of scratch, across their marches)
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+#else
     return __popcll(mask & ((1ull << lane_id()) - 1ull));
+#endif
 }
 
 
@@ -365,20 +411,28 @@ __device__ __forceinline__ int32_t sweep_lane(const StepParams& P, int64_t gwave
 // profiles/r04_ab_scheduling.txt item 9).  The slot allocation below is per workgroup either way; with one wave its barriers compile away.
 #define BMO_BLOCK 64
 #endif
+// Thread of its workgroup, for the step kernels (launched with BMO_BLOCK lanes per workgroup).  With one wave per workgroup the lane number says it
+// all, and said so — the compiler does not take it from the launch bounds — the wave of the workgroup is the constant 0 and the wave of the
+// grid a scalar, where they were per-lane values held (the wide kernels: spilled to scratch) across the marches.
+// (HELD: threadIdx.x and blockDim.x as they come — the sweep builds, see step_params_again)
+template <bool HELD = false>
+__device__ __forceinline__ unsigned step_tid() { return (BMO_BLOCK == 64 && !HELD) ? (threadIdx.x & 63u) : threadIdx.x; }
+template <bool HELD = false>
+__device__ __forceinline__ unsigned step_block() { return HELD ? blockDim.x : (unsigned)BMO_BLOCK; }
 struct SlotAlloc {
     unsigned long long surv_base, child_base, node_base;
     unsigned long long m_surv, m_split;
 };
 // PAIRS = false: the second channel counts single records that need no new nodes (reflected children a lane kept for itself and
 // could not get to before its wave's loop ended, StepParams::pend): block layout [survivors of wave 0..3][kept children of wave 0..3].
-template <bool PAIRS = true>
-__device__ __forceinline__ SlotAlloc block_alloc(bool survive, bool split, uint32_t calls, const StepParams& P, char* scratch, int level = 0) {
+template <bool PAIRS, bool HELD, class Params>
+__device__ __forceinline__ SlotAlloc block_alloc(bool survive, bool split, uint32_t calls, Params* P, char* scratch, int level = 0) {
     uint32_t* w32 = reinterpret_cast<uint32_t*>(scratch);                         // [0..3] surv, [4..7] split, [8..11] calls, [12..15] level
     unsigned long long* w64 = reinterpret_cast<unsigned long long*>(scratch + 32);  // [0] base, [1] nbase
     SlotAlloc a;
     a.m_surv = __ballot(survive);
     a.m_split = __ballot(split);
-    const int wave = (int)(threadIdx.x >> 6);
+    const int wave = (int)(step_tid<HELD>() >> 6);
     unsigned int c = calls;
     for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
     if (lane_id() == 0) {
@@ -388,7 +442,7 @@ __device__ __forceinline__ SlotAlloc block_alloc(bool survive, bool split, uint3
         w32[12 + wave] = (uint32_t)level;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (step_tid<HELD>() == 0) {
         uint32_t ts = 0, tp = 0, tc = 0, ml = 0;
         for (int w = 0; w < BMO_BLOCK / 64; ++w) {
             ts += w32[w];
@@ -396,11 +450,11 @@ __device__ __forceinline__ SlotAlloc block_alloc(bool survive, bool split, uint3
             tc += w32[8 + w];
             ml = w32[12 + w] > ml ? w32[12 + w] : ml;
         }
-        if (ml) atomicMax(&P.ctr->max_level[P.parity], (unsigned long long)ml);
+        if (ml) atomicMax(&P->ctr->max_level[P->parity], (unsigned long long)ml);
         unsigned long long b = 0, nb = 0;
-        if (ts + tp) b = atomicAdd(&P.ctr->next_count[P.parity], (unsigned long long)(ts + (PAIRS ? 2 : 1) * tp));
-        if (PAIRS && tp) nb = atomicAdd(&P.ctr->node_count, (unsigned long long)(2 * tp));
-        if (tc) atomicAdd(&P.call_shards[(blockIdx.x & 63u) * 16u], (unsigned long long)tc);  // sharded, no return value
+        if (ts + tp) b = atomicAdd(&P->ctr->next_count[P->parity], (unsigned long long)(ts + (PAIRS ? 2 : 1) * tp));
+        if (PAIRS && tp) nb = atomicAdd(&P->ctr->node_count, (unsigned long long)(2 * tp));
+        if (tc) atomicAdd(&P->call_shards[(blockIdx.x & 63u) * 16u], (unsigned long long)tc);  // sharded, no return value
         w64[0] = b;
         w64[1] = nb;
     }
@@ -459,11 +513,11 @@ constexpr int step_waves() {
 // less register room — the large launches of the BASELINE configs run 2 - 7 % faster that way (profiles/r03_ab_inwave.txt).
 // SWEEP (bmo_trace_sweep, fresh solves only): lane -> slot through StepParams::sweep, scene tables of the wave's configuration.
 template <int KIND, int EXT, bool RETR, bool INW, int WAVES = step_waves<KIND, EXT, RETR>(), bool SWEEP = false>
-__global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
+__global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {  // (P: the ONLY argument — step_params_again reads the segment from offset 0)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
     char* scratch = lds;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (blockIdx.x == 0 && step_tid<SWEEP>() == 0) {
         P.ctr->next_count[P.parity ^ 1] = 0;
         P.ctr->max_level[P.parity ^ 1] = 0;
         P.ctr->inwave[P.parity ^ 1] = 0;
@@ -471,9 +525,9 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     using L = Layout<KIND>;
     const unsigned tile = P.tile_order ? (unsigned)P.tile_order[blockIdx.x] : tile_of_block(P.reverse, blockIdx.x, gridDim.x);
 #if !defined(BMO_NO_TILE_COST)
-    if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
+    if (P.tile_cost && step_tid<SWEEP>() == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
 #endif
-    const int64_t gwave = ((int64_t)tile * blockDim.x + threadIdx.x) >> 6;  // wave of the grid
+    const int64_t gwave = ((int64_t)tile * step_block<SWEEP>() + step_tid<SWEEP>()) >> 6;  // wave of the grid
     int64_t sweep_j = 0;
     bool sweep_valid = false;
     if constexpr (SWEEP) {
@@ -485,7 +539,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     const int64_t m = P.cur.count;
     const bool valid = SWEEP ? sweep_valid : (j < m && lane_id() < (1 << P.lane_shift));
 #if defined(BMO_DEV_TIMELINE)
-    if (P.tl && (threadIdx.x & 63) == 0 && (gwave << P.lane_shift) < P.cur.count) P.tl[2 * gwave] = wall_clock64();
+    if (P.tl && lane_id() == 0 && (gwave << P.lane_shift) < P.cur.count) P.tl[2 * gwave] = wall_clock64();
 #endif
 
     // A lane carries nothing but `alive` from one fused bounce to the next: it writes its next record and reads it back at the
@@ -494,10 +548,10 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     // to the loop top still costs 64 B of them and 0.8 % (round 2).
     bool alive = valid;
     uint32_t calls = 0;
-    auto write_ray = [&](const Chunk& C, int64_t slot, const RayS& r, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double opl) {
-        const int64_t ncap = C.cap;
-        double* D = C.d;
-        int32_t* I = C.i;
+    auto write_ray = [&](auto C, int64_t slot, const RayS& r, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double opl) {
+        const int64_t ncap = C->cap;
+        double* D = C->d;
+        int32_t* I = C->i;
         D[0 * ncap + slot] = r.pos.x;
         D[1 * ncap + slot] = r.pos.y;
         D[2 * ncap + slot] = r.pos.z;
@@ -528,7 +582,9 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
     unsigned long long tk0 = 0, tk1 = 0, tk2 = 0, tk_last = wall_clock64();  // time before / in / after tracing_step, summed over the levels
 #endif
     for (;;) {
-        const Chunk C = b == 0 ? P.cur : P.inner[b - 1];
+        // (the launch's parameters are read where they are used: step_params_again)
+        const auto Qh = step_params_again<SWEEP>(P);
+        [[maybe_unused]] const HeldChunk held{SWEEP ? (b == 0 ? P.cur : P.inner[b - 1]) : Chunk{}};  // (the sweep builds: the level's chunk, held)
         // ---- the tracing step.  Only what it needs is read before it, and nothing the interaction needs is computed before it: the
         //      record addresses, node id and segment index are derived again behind it from a copy of the slot index the optimiser
         //      cannot see through (`jj`), so no address or header value of this level is held in a register (or spilled) across the
@@ -539,13 +595,13 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         int32_t x_obj = -1, x_shape = -1;
         double x_t = kinf();
         bool traced = false;  // the lane ran a tracing step at this level (its record is not a pushed-but-never-traced one)
-        const LaneMem lm{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + threadIdx.x, BMO_BLOCK};
+        const LaneMem lm{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + step_tid<SWEEP>(), BMO_BLOCK};
         const int32_t t_node = c_node, t_k = c_k, t_ho = c_ho, t_hs = c_hs, t_fl = c_fl;
         c_node = c_k = c_ho = c_hs = c_fl = 0;  // (dead from here to the next in-place write, in every lane: no register across the marches)
         if (alive) {
-            const int64_t cap = C.cap;
-            const double* D = C.d;
-            const int32_t* I = C.i;
+            const int64_t cap = SWEEP ? held->cap : Qh->cur.cap;  // (the input chunk: read at level 0 only)
+            const double* D = SWEEP ? held->d : Qh->cur.d;
+            const int32_t* I = SWEEP ? held->i : Qh->cur.i;
             int32_t flags = t_fl, ho = t_ho, hs = t_hs;
             node = t_node;
             k = t_k;
@@ -557,7 +613,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
                 k = I[I_K * cap + j];
             }
             if (RETR) {
-                rt = retrace_lane(P, node, k);
+                rt = retrace_lane(Qh, node, k);
                 if (rt.old >= 0 && !rt.probe) ho = hs = -1;
             }
             traced = !((flags & F_DEAD) || (RETR && rt.old >= 0 && !rt.probe && !rt.fresh_allowed));  // else: pushed but never traced (System.jl:133)
@@ -570,14 +626,14 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
                     // from level 1 on they are there already: the beam's constants do not change along a lane, children included)
                     lm.m[7 * lm.stride] = D[6 * cap + j];
                     lm.m[8 * lm.stride] = D[L::OPL * cap + j];
-                    lm.m[9 * lm.stride] = (double)P.nodes.li[node];
-                    lm.m[10 * lm.stride] = P.nodes.lambda[node];
+                    lm.m[9 * lm.stride] = (double)Qh->nodes.li[node];
+                    lm.m[10 * lm.stride] = Qh->nodes.lambda[node];
                 } else {
                     pos = lm.get3(0);
                     dir = lm.get3(3);
                 }
                 // per-lane column of LDS behind the block_alloc scratch: Lipschitz memory of the union children (bmo_lane.hpp sdf_any)
-                ChildCache cc{reinterpret_cast<double*>(scratch + 64) + threadIdx.x, BMO_BLOCK, 0};
+                ChildCache cc{reinterpret_cast<double*>(scratch + 64) + step_tid<SWEEP>(), BMO_BLOCK, 0};
 #if defined(BMO_DEV_TIMELINE)
                 {
                     const unsigned long long t = wall_clock64();
@@ -601,6 +657,11 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         // ---- the interaction and the record of this level
         int64_t jj = j;
         asm volatile("" : "+v"(jj));
+        const auto Q = step_params_again<SWEEP>(P);
+        const auto C = [&] {  // the chunk of this level
+            if constexpr (SWEEP) return held;
+            else return b == 0 ? &Q->cur : &Q->inner[b - 1];
+        }();
         bool survive = false, split = false, still = false, old_kids = false, stale_kids = false;
         double opl_next = 0.0, lambda = 0.0;
         int32_t li = 0;
@@ -612,7 +673,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         o.det = nullptr;
         // header of the record that follows a surviving bounce: r_max flag and hint, with the retrace overrides
         auto next_header = [&](int32_t& fl, int32_t& ho, int32_t& hs) {
-            fl = (k + 2 < P.r_max) ? 0 : F_DEAD;
+            fl = (k + 2 < Q->r_max) ? 0 : F_DEAD;
             ho = o.hint_obj;
             hs = o.hint_shape;
             if (RETR && still) {
@@ -621,9 +682,9 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
             }
         };
         if (alive) {
-            const int64_t cap = C.cap;
-            double* D = C.d;
-            int32_t* I = C.i;
+            const int64_t cap = C->cap;
+            double* D = C->d;
+            int32_t* I = C->i;
             Hit X;
             X.t = x_t;
             X.obj = x_obj;
@@ -645,7 +706,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
                 const double opl_acc = lm.m[8 * lm.stride];
                 li = (int32_t)lm.m[9 * lm.stride];
                 lambda = lm.m[10 * lm.stride];
-                o.det = P.nodes.hit + (int64_t)node * 9;  // a detector hit ends the beam: its record goes straight to the node's slot
+                o.det = Q->nodes.hit + (int64_t)node * 9;  // a detector hit ends the beam: its record goes straight to the node's slot
                 // (the ray that goes on is put into the lane memory — hit normal, origin and plate mark there are spent — as soon as a
                 //  branch of the interaction has it, and comes back from there when its record is written: bmo_lane.hpp NextInOut)
                 interact<KIND>(S, ray, X, li, lambda, opl_acc, o, NextInLaneMem{lm});
@@ -659,22 +720,22 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
                     opl_next = opl_acc + X.t * ray.n;
                 } else {
                     status |= BMO_NODE_STOPPED;
-                    if (RETR && rt.old >= 0 && rt.probe && !rt.missed && P.old.first_child[rt.old] >= 0) {
+                    if (RETR && rt.old >= 0 && rt.probe && !rt.missed && Q->old.first_child[rt.old] >= 0) {
                         // The re-walk ends here in a `nothing` interaction, before the splitter the stored beam ended on: the reference cuts the
                         // tail but KEEPS the children (cleanup_children stays false, System.jl:232-240); solve_system! then retraces each of them
                         // from its stored first ray (System.jl:446-458).  The two stored heads take the places a splitter's children have: the
                         // transmitted one in the lane memory (o.next for the field vector), the reflected one in o.refl.
                         stale_kids = true;
                         opl_next = opl_acc + X.t * ray.n;  // optical_path_length(parent): every ray of the cut beam up to this hit (Beam.jl:137-149)
-                        const int32_t oc = P.old.first_child[rt.old];
+                        const int32_t oc = Q->old.first_child[rt.old];
                         int64_t hc, hs;
-                        const double* H = old_record(P.old, oc, 0, hc, hs);
+                        const double* H = old_record(Q->old, oc, 0, hc, hs);
                         lm.put3(0, d3{H[0 * hc + hs], H[1 * hc + hs], H[2 * hc + hs]});
                         lm.put3(3, d3{H[3 * hc + hs], H[4 * hc + hs], H[5 * hc + hs]});
                         lm.m[7 * lm.stride] = H[6 * hc + hs];
                         if (KIND == BMO_BEAM_POLARIZED)
                             for (int c = 0; c < 3; ++c) o.next.E0[c] = {H[(11 + 2 * c) * hc + hs], H[(12 + 2 * c) * hc + hs]};
-                        H = old_record(P.old, oc + 1, 0, hc, hs);
+                        H = old_record(Q->old, oc + 1, 0, hc, hs);
                         o.refl.pos = d3{H[0 * hc + hs], H[1 * hc + hs], H[2 * hc + hs]};
                         o.refl.dir = d3{H[3 * hc + hs], H[4 * hc + hs], H[5 * hc + hs]};
                         o.refl.n = H[6 * hc + hs];
@@ -692,17 +753,17 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
             I[I_SHAPE * cap + jj] = X.shape;
             if (RETR) {
                 still = rt.old >= 0 && rt.probe && !rt.missed;  // the stored path held at this ray
-                old_kids = still && P.old.first_child[rt.old] >= 0;  // (not the SPLIT status: kept stale children hang on a beam that did not split)
+                old_kids = still && Q->old.first_child[rt.old] >= 0;  // (not the SPLIT status: kept stale children hang on a beam that did not split)
                 if (stale_kids) {  // from here on like a splitter's children, but the beam did not split: no BMO_NODE_SPLIT
                     status |= BMO_NODE_RETRACE_STALE;
                     split = true;
                 }
-                if (rt.old >= 0 && !(survive && still && k + 1 < rt.old_n)) P.nodes.old[node] = -1;
+                if (rt.old >= 0 && !(survive && still && k + 1 < rt.old_n)) Q->nodes.old[node] = -1;
             }
             if (!survive) {  // node ends here
-                P.nodes.nseg[node] = k + 1;
-                P.nodes.status[node] = status;
-                if (o.det_slot >= 0) P.nodes.hit_det[node] = o.det_slot;
+                Q->nodes.nseg[node] = k + 1;
+                Q->nodes.status[node] = status;
+                if (o.det_slot >= 0) Q->nodes.hit_det[node] = o.det_slot;
             }
         }
 #if defined(BMO_DEV_TIMELINE)
@@ -712,35 +773,35 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
             tk_last = t;
         }
 #endif
-        const int64_t ncap = P.nxt.cap;
+        const int64_t ncap = Q->nxt.cap;
         auto write_next = [&](int64_t slot, const RayS& r, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double opl) {
             if (slot >= ncap) {
-                atomicAdd(&P.ctr->overflow, 1ull);
+                atomicAdd(&Q->ctr->overflow, 1ull);
                 return;
             }
-            write_ray(P.nxt, slot, r, nd, kk, ho, hs, fl, opl);
+            write_ray(&Q->nxt, slot, r, nd, kk, ho, hs, fl, opl);
         };
         // the two children of a splitting lane: nodes cn (transmitted) and cn + 1 (reflected)
         auto make_children = [&](int64_t cn) {
-            const unsigned long long pkey = P.nodes.key[node];
+            const unsigned long long pkey = Q->nodes.key[node];
             const unsigned long long depth = pkey >> 32, path = pkey & 0xFFFFFFFFull;
-            const int32_t root = P.nodes.root[node];
-            atomicMax(&P.ctr->max_depth, depth + 1ull);
-            if (P.nodes.tbits && depth < 5) atomicOr(&P.nodes.tbits[root], 3ull << ((2ull << depth) - 1ull + (path << 1)));  // both children's heap indices
+            const int32_t root = Q->nodes.root[node];
+            atomicMax(&Q->ctr->max_depth, depth + 1ull);
+            if (Q->nodes.tbits && depth < 5) atomicOr(&Q->nodes.tbits[root], 3ull << ((2ull << depth) - 1ull + (path << 1)));  // both children's heap indices
             for (int w = 0; w < 2; ++w) {
                 const int64_t c = cn + w;
-                P.nodes.root[c] = root;
-                P.nodes.parent[c] = node;
-                P.nodes.nseg[c] = 1;
-                P.nodes.status[c] = 0;
-                P.nodes.li[c] = li;
-                P.nodes.lambda[c] = lambda;
-                P.nodes.hit_det[c] = -1;
-                P.nodes.key[c] = ((depth + 1) << 32) | (((path << 1) | (unsigned long long)w) & 0xFFFFFFFFull);
-                if (RETR) P.nodes.old[c] = old_kids ? P.old.first_child[rt.old] + w : -1;  // children!: the stored child is re-walked
+                Q->nodes.root[c] = root;
+                Q->nodes.parent[c] = node;
+                Q->nodes.nseg[c] = 1;
+                Q->nodes.status[c] = 0;
+                Q->nodes.li[c] = li;
+                Q->nodes.lambda[c] = lambda;
+                Q->nodes.hit_det[c] = -1;
+                Q->nodes.key[c] = ((depth + 1) << 32) | (((path << 1) | (unsigned long long)w) & 0xFFFFFFFFull);
+                if (RETR) Q->nodes.old[c] = old_kids ? Q->old.first_child[rt.old] + w : -1;  // children!: the stored child is re-walked
             }
         };
-        const int32_t child_flags = ((RETR && old_kids) || 1 < P.r_max) ? 0 : F_DEAD;
+        const int32_t child_flags = ((RETR && old_kids) || 1 < Q->r_max) ? 0 : F_DEAD;
         auto next_ray = [&]() {
             RayS r = o.next;  // (E0 of a PolarizedRay stays where it is)
             r.pos = lm.get3(0);
@@ -748,7 +809,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
             r.n = lm.m[7 * lm.stride];
             return r;
         };
-        bool go_on = b + 1 < P.n_fuse;
+        bool go_on = b + 1 < Q->n_fuse;
         // wave-uniform decisions: every wave runs its own fused loop (no workgroup barrier per level: the four waves of a workgroup used to
         // wait for the slowest of them at every bounce); the workgroup meets again at block_alloc below.
         // Beam splitters first, wherever in the loop they are met: one reservation per wave — a run of node pairs and a run of slots in
@@ -759,7 +820,7 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
 #if defined(BMO_NO_KEEP)
         const bool keep = false;
 #else
-        const bool keep = INW && P.pend.d != nullptr;  // reflected children stay with their lane (StepParams::pend)
+        const bool keep = INW && Q->pend.d != nullptr;  // reflected children stay with their lane (StepParams::pend)
 #endif
         if (!INW) {
             if (go_on) go_on = !__any(split ? 1 : 0);
@@ -771,36 +832,39 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
             unsigned long long r1 = 0, r2 = 0;
             // the node pairs first: their running count is also the number of in-loop splits of this launch so far (every node a launch of
             // this kernel makes is made here), which the launch's room bounds — one returning atomic instead of two in a row
-            if (lane_id() == 0) r2 = atomicAdd(&P.ctr->node_count, 2ull * ns);
+            if (lane_id() == 0) r2 = atomicAdd(&Q->ctr->node_count, 2ull * ns);
             r2 = __shfl(r2, 0);
-            if (go_on && (int64_t)((r2 - (unsigned long long)P.nodes0) / 2ull + ns) > P.inwave_cap) go_on = false;  // (kept child or not: the bound also sizes the node table)
+            if (go_on && (int64_t)((r2 - (unsigned long long)Q->nodes0) / 2ull + ns) > Q->inwave_cap) go_on = false;  // (kept child or not: the bound also sizes the node table)
             if (!go_on || np) {
-                if (lane_id() == 0) r1 = atomicAdd(&P.ctr->next_count[P.parity], (unsigned long long)(go_on ? np : 2 * ns));
+                if (lane_id() == 0) r1 = atomicAdd(&Q->ctr->next_count[Q->parity], (unsigned long long)(go_on ? np : 2 * ns));
                 r1 = __shfl(r1, 0);
             }
             if (split) {
-                const int r = prefix_rank(m_split);
+                const int r = prefix_rank<!SWEEP>(m_split);
                 const int64_t cn = (int64_t)r2 + 2 * r;
-                if (cn + 1 < P.nodes.cap) {
+                if (cn + 1 < Q->nodes.cap) {
                     make_children(cn);
-                    const Chunk T = go_on ? P.inner[b] : P.nxt;  // (wave-uniform)
+                    const auto T = [&] {  // (wave-uniform)
+                        if constexpr (SWEEP) return HeldChunk{go_on ? P.inner[b] : P.nxt};
+                        else return go_on ? &Q->inner[b] : &Q->nxt;
+                    }();
                     const int64_t ts = go_on ? jj : (int64_t)r1 + 2 * r;
-                    if (ts < T.cap) write_ray(T, ts, next_ray(), (int32_t)cn, 0, -1, -1, child_flags, opl_next);
-                    else atomicAdd(&P.ctr->overflow, 1ull);
+                    if (ts < T->cap) write_ray(T, ts, next_ray(), (int32_t)cn, 0, -1, -1, child_flags, opl_next);
+                    else atomicAdd(&Q->ctr->overflow, 1ull);
                     c_node = (int32_t)cn;
                     c_k = 0;
                     c_ho = c_hs = -1;
                     c_fl = child_flags;
                     lm.m[8 * lm.stride] = opl_next;
                     if (go_on && keep && pend_node < 0) {  // the reflected child waits for this lane
-                        write_ray(P.pend, jj, o.refl, (int32_t)(cn + 1), 0, -1, -1, child_flags, opl_next);
+                        write_ray(&Q->pend, jj, o.refl, (int32_t)(cn + 1), 0, -1, -1, child_flags, opl_next);
                         pend_node = (int32_t)(cn + 1);
                     } else {
-                        write_next(go_on ? (int64_t)r1 + prefix_rank(m_push) : (int64_t)r1 + 2 * r + 1, o.refl, (int32_t)(cn + 1), 0, -1, -1, child_flags, opl_next);
+                        write_next(go_on ? (int64_t)r1 + prefix_rank<!SWEEP>(m_push) : (int64_t)r1 + 2 * r + 1, o.refl, (int32_t)(cn + 1), 0, -1, -1, child_flags, opl_next);
                     }
                     kid_here = go_on;
                 } else {
-                    atomicAdd(&P.ctr->overflow, 1ull);
+                    atomicAdd(&Q->ctr->overflow, 1ull);
                 }
             }
         }
@@ -809,7 +873,10 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         if (go_on) go_on = __any((survive || kid_here || take_kept) ? 1 : 0) != 0;
         if (go_on) {
             // go on in place: the next record of a surviving lane is written to the same slot of the next inner chunk
-            const Chunk N = P.inner[b];
+            const auto N = [&] {
+                if constexpr (SWEEP) return HeldChunk{P.inner[b]};
+                else return &Q->inner[b];
+            }();
             if (valid) {
                 if (alive && survive) {
                     int32_t fl, ho, hs;
@@ -824,25 +891,25 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
                 } else if (take_kept) {
                     // the kept child's first record moves into the log (this level, this slot); its ray goes where a lane that goes on in
                     // place expects it: position, direction, index and optical path in the lane memory, the header in registers
-                    const int64_t pc = P.pend.cap, nc = N.cap;
+                    const int64_t pc = Q->pend.cap, nc = N->cap;
                     BMO_NOUNROLL
-                    for (int q = 0; q < L::ND; ++q) N.d[q * nc + jj] = P.pend.d[q * pc + jj];
-                    c_fl = P.pend.i[I_FLAGS * pc + jj];
-                    N.i[I_NODE * nc + jj] = pend_node;
-                    N.i[I_K * nc + jj] = 0;
-                    N.i[I_HOBJ * nc + jj] = -1;
-                    N.i[I_HSHAPE * nc + jj] = -1;
-                    N.i[I_FLAGS * nc + jj] = c_fl;
-                    lm.put3(0, d3{P.pend.d[0 * pc + jj], P.pend.d[1 * pc + jj], P.pend.d[2 * pc + jj]});
-                    lm.put3(3, d3{P.pend.d[3 * pc + jj], P.pend.d[4 * pc + jj], P.pend.d[5 * pc + jj]});
-                    lm.m[7 * lm.stride] = P.pend.d[6 * pc + jj];
-                    lm.m[8 * lm.stride] = P.pend.d[L::OPL * pc + jj];
+                    for (int q = 0; q < L::ND; ++q) N->d[q * nc + jj] = Q->pend.d[q * pc + jj];
+                    c_fl = Q->pend.i[I_FLAGS * pc + jj];
+                    N->i[I_NODE * nc + jj] = pend_node;
+                    N->i[I_K * nc + jj] = 0;
+                    N->i[I_HOBJ * nc + jj] = -1;
+                    N->i[I_HSHAPE * nc + jj] = -1;
+                    N->i[I_FLAGS * nc + jj] = c_fl;
+                    lm.put3(0, d3{Q->pend.d[0 * pc + jj], Q->pend.d[1 * pc + jj], Q->pend.d[2 * pc + jj]});
+                    lm.put3(3, d3{Q->pend.d[3 * pc + jj], Q->pend.d[4 * pc + jj], Q->pend.d[5 * pc + jj]});
+                    lm.m[7 * lm.stride] = Q->pend.d[6 * pc + jj];
+                    lm.m[8 * lm.stride] = Q->pend.d[L::OPL * pc + jj];
                     c_node = pend_node;
                     c_k = 0;
                     c_ho = c_hs = -1;
                     pend_node = -1;
                 } else if (!kid_here) {
-                    N.i[I_NODE * N.cap + jj] = -1;  // no record of this beam at this level
+                    N->i[I_NODE * N->cap + jj] = -1;  // no record of this beam at this level
                     alive = false;
                 }
             }
@@ -853,51 +920,51 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) {
         //      across the march of the next iteration): note how far the wave got — the in-place levels beyond are never written and
         //      never read (Chunk::wl) —, then compact into the next launch's chunk
         if constexpr (SWEEP) {  // (a wave's slots are not consecutive: the level is noted per slot, Chunk::wl_shift = 0)
-            if (P.wave_last && valid) P.wave_last[j] = (uint8_t)b;
-        } else if (P.wave_last && lane_id() == 0) {
-            P.wave_last[gwave] = (uint8_t)b;
+            if (Q->wave_last && valid) Q->wave_last[j] = (uint8_t)b;
+        } else if (Q->wave_last && lane_id() == 0) {
+            Q->wave_last[gwave] = (uint8_t)b;
         }
 #if defined(BMO_DEV_TIMELINE)
-        if (P.tl && (threadIdx.x & 63) == 0 && (gwave << P.lane_shift) < P.cur.count) {  // (tail waves of the grid have no slot in the timeline)
-            P.tl[2 * gwave + 1] = wall_clock64();  // before the workgroup barrier of block_alloc
-            const int64_t nw = (P.cur.count + (1 << P.lane_shift) - 1) >> P.lane_shift;
-            atomicAdd(&P.tl[2 * nw + 0], tk0);
-            atomicAdd(&P.tl[2 * nw + 1], tk1);
-            atomicAdd(&P.tl[2 * nw + 2], tk2);
+        if (Q->tl && lane_id() == 0 && (gwave << Q->lane_shift) < Q->cur.count) {  // (tail waves of the grid have no slot in the timeline)
+            Q->tl[2 * gwave + 1] = wall_clock64();  // before the workgroup barrier of block_alloc
+            const int64_t nw = (Q->cur.count + (1 << Q->lane_shift) - 1) >> Q->lane_shift;
+            atomicAdd(&Q->tl[2 * nw + 0], tk0);
+            atomicAdd(&Q->tl[2 * nw + 1], tk1);
+            atomicAdd(&Q->tl[2 * nw + 2], tk2);
         }
 #endif
-        const SlotAlloc al = INW ? block_alloc<false>(survive, pend_node >= 0, calls, P, scratch, b) : block_alloc<true>(survive, split, calls, P, scratch, b);
+        const SlotAlloc al = INW ? block_alloc<false, SWEEP>(survive, pend_node >= 0, calls, Q, scratch, b) : block_alloc<true, SWEEP>(survive, split, calls, Q, scratch, b);
         if (survive) {  // survivors first
-            const int64_t slot = (int64_t)al.surv_base + prefix_rank(al.m_surv);
+            const int64_t slot = (int64_t)al.surv_base + prefix_rank<!SWEEP>(al.m_surv);
             int32_t fl, ho, hs;
             next_header(fl, ho, hs);
             write_next(slot, next_ray(), node, k + 1, ho, hs, fl, opl_next);
         }
         if (INW && pend_node >= 0) {  // then the reflected children their lanes did not get to: whole records, P.pend -> P.nxt
-            const int64_t slot = (int64_t)al.child_base + prefix_rank(al.m_split);
+            const int64_t slot = (int64_t)al.child_base + prefix_rank<!SWEEP>(al.m_split);
             if (slot < ncap) {
-                const int64_t pc = P.pend.cap;
+                const int64_t pc = Q->pend.cap;
                 BMO_NOUNROLL
-                for (int q = 0; q < L::ND; ++q) P.nxt.d[q * ncap + slot] = P.pend.d[q * pc + jj];
+                for (int q = 0; q < L::ND; ++q) Q->nxt.d[q * ncap + slot] = Q->pend.d[q * pc + jj];
                 BMO_NOUNROLL
-                for (int q = 0; q < NI; ++q) P.nxt.i[q * ncap + slot] = P.pend.i[q * pc + jj];
+                for (int q = 0; q < NI; ++q) Q->nxt.i[q * ncap + slot] = Q->pend.i[q * pc + jj];
             } else {
-                atomicAdd(&P.ctr->overflow, 1ull);
+                atomicAdd(&Q->ctr->overflow, 1ull);
             }
         }
 #if !defined(BMO_NO_TILE_COST)
-        if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64() - P.tile_cost[tile];  // (behind block_alloc's barrier: all four waves are done)
+        if (Q->tile_cost && step_tid<SWEEP>() == 0) Q->tile_cost[tile] = (uint32_t)wall_clock64() - Q->tile_cost[tile];  // (behind block_alloc's barrier: all four waves are done)
 #endif
         if (!INW && split) {  // then 2 children per splitting lane
-            const int r = prefix_rank(al.m_split);
+            const int r = prefix_rank<!SWEEP>(al.m_split);
             const int64_t slot = (int64_t)al.child_base + 2 * r;
             const int64_t cn = (int64_t)al.node_base + 2 * r;
-            if (cn + 1 < P.nodes.cap) {
+            if (cn + 1 < Q->nodes.cap) {
                 make_children(cn);
                 write_next(slot, next_ray(), (int32_t)cn, 0, -1, -1, child_flags, opl_next);
                 write_next(slot + 1, o.refl, (int32_t)(cn + 1), 0, -1, -1, child_flags, opl_next);
             } else {
-                atomicAdd(&P.ctr->overflow, 1ull);
+                atomicAdd(&Q->ctr->overflow, 1ull);
             }
         }
         return;
@@ -1040,20 +1107,20 @@ struct GaussRecDevNoHint : GaussRecDev {
 // the last fused level until they are compacted into P.nxt).  Beam splitters are handled in the loop: the transmitted child goes on in
 // place, the reflected child's rays wait in the staging planes and are pushed to P.nxt (StepParams::inwave_cap).
 template <int EXT, bool RETR, bool SWEEP = false>
-__global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_gauss(StepParams P) {
+__global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_gauss(StepParams P) {  // (P: the ONLY argument — step_params_again reads the segment from offset 0)
     extern __shared__ __attribute__((aligned(16))) char lds[];
     SceneView S = view_of((const char*)P.blob, &P.hdr);  // scene tables: global memory, scalar loads (bmo_lane.hpp)
     char* scratch = lds;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (blockIdx.x == 0 && step_tid<SWEEP>() == 0) {
         P.ctr->next_count[P.parity ^ 1] = 0;
         P.ctr->max_level[P.parity ^ 1] = 0;
         P.ctr->inwave[P.parity ^ 1] = 0;
     }
     const unsigned tile = P.tile_order ? (unsigned)P.tile_order[blockIdx.x] : tile_of_block(P.reverse, blockIdx.x, gridDim.x);
 #if !defined(BMO_NO_TILE_COST)
-    if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
+    if (P.tile_cost && step_tid<SWEEP>() == 0) P.tile_cost[tile] = (uint32_t)wall_clock64();  // start stamp; turned into the tile's time at the end
 #endif
-    const int64_t gwave = ((int64_t)tile * blockDim.x + threadIdx.x) >> 6;  // wave of the grid
+    const int64_t gwave = ((int64_t)tile * step_block<SWEEP>() + step_tid<SWEEP>()) >> 6;  // wave of the grid
     int64_t sweep_j = 0;
     bool sweep_valid = false;
     if constexpr (SWEEP) {
@@ -1066,48 +1133,12 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
     const bool valid = SWEEP ? sweep_valid : (j < m && lane_id() < (1 << P.lane_shift));
     bool alive = valid;
     uint32_t calls = 0;
-    const int64_t ncap = P.nxt.cap;
     int32_t pend_node = -1;  // node of the reflected child this lane keeps for itself in P.gkeep (StepParams::pend), -1: none
-    // (measured twice, profiles/r04_ab_scheduling.txt items 5 and 11: while the leaves' dispatch still cost this kernel 196 B of scratch the kept
-    //  child made it 228 B and config 3 2 % slower, 10.56 against 10.34 ms; with the pinned dispatch — 140 B, 164 with the kept child — it is
-    //  2 % FASTER, 9.41 against 9.62 ms, and one launch per solve.  -DBMO_NO_GAUSS_KEEP compiles it out.)
-#if defined(BMO_NO_GAUSS_KEEP)
-    const bool keep = false;
-#else
-    const bool keep = P.gkeep != nullptr;
-#endif
-    // accumulators and header of a record whose rays are in place already
-    auto write_tail = [&](const Chunk& T, int64_t slot, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double lenA, double lenB, double oplC,
-                          double oplW, double oplD) {
-        const int64_t tcap = T.cap;
-        double* D = T.d;
-        int32_t* I = T.i;
-        D[33 * tcap + slot] = lenA;
-        D[34 * tcap + slot] = lenB;
-        D[35 * tcap + slot] = oplC;
-        D[36 * tcap + slot] = oplW;
-        D[37 * tcap + slot] = oplD;
-        I[I_NODE * tcap + slot] = nd;
-        I[I_K * tcap + slot] = kk;
-        I[I_HOBJ * tcap + slot] = ho;
-        I[I_HSHAPE * tcap + slot] = hs;
-        I[I_FLAGS * tcap + slot] = fl;
-    };
-    // a whole record in P.nxt: rays from `src` (plane r * rstride + c of capacity scap, at slot j), then accumulators and header
-    auto write_next = [&](int64_t slot, const double* src, int64_t scap, int rstride, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double lenA,
-                          double lenB, double oplC, double oplW, double oplD) {
-        if (slot >= ncap) {
-            atomicAdd(&P.ctr->overflow, 1ull);
-            return;
-        }
-        double* D = P.nxt.d;
-        BMO_NOUNROLL
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 7; ++c) D[(11 * r + c) * ncap + slot] = src[(int64_t)(rstride * r + c) * scap + j];
-        write_tail(P.nxt, slot, nd, kk, ho, hs, fl, lenA, lenB, oplC, oplW, oplD);
-    };
     int b = 0;
     for (;;) {
+        // (this level's chunk and the next one's come from `P` itself and are held: gauss_step_rec reads and writes the record through `rec`
+        //  before, between and after its three marches, so their addresses are wanted all through the step; only what the code BEHIND the
+        //  step wants — node arrays, counters, `nxt`, the kept children, the next chunk once more as Nq — is read again there)
         const Chunk C = b == 0 ? P.cur : P.inner[b - 1];
         const Chunk N = P.inner[b];
         const int64_t cap = C.cap;
@@ -1129,11 +1160,11 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             o.det = P.nodes.hit + (int64_t)node * 27;  // a detector hit ends the beamlet: its records go straight to the node's slot
             bool no_hint = false;
             if (RETR) {
-                rt = retrace_lane(P, node, k);
+                rt = retrace_lane(&P, node, k);
                 no_hint = rt.old >= 0 && !rt.probe;
             }
             // (lane memory slots 9, 10: wavelength index and wavelength; loaded where the lane's first record of this launch is read)
-            const LaneMem lmw{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + threadIdx.x, BMO_BLOCK};
+            const LaneMem lmw{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + step_tid<SWEEP>(), BMO_BLOCK};
             if (b == 0) {
                 lmw.m[9 * lmw.stride] = (double)P.nodes.li[node];
                 lmw.m[10 * lmw.stride] = P.nodes.lambda[node];
@@ -1143,8 +1174,8 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                 status = BMO_NODE_RMAX;
                 rec.clear_hits();
             } else {
-                ChildCache cc{reinterpret_cast<double*>(scratch + 64) + threadIdx.x, BMO_BLOCK, 0};
-                const LaneMem lm{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + threadIdx.x, BMO_BLOCK};
+                ChildCache cc{reinterpret_cast<double*>(scratch + 64) + step_tid<SWEEP>(), BMO_BLOCK, 0};
+                const LaneMem lm{reinterpret_cast<double*>(scratch + 64) + BMO_CC_MAX * BMO_BLOCK + step_tid<SWEEP>(), BMO_BLOCK};
                 if (RETR && no_hint) {
                     GaussRecDevNoHint rn{{D, I, P.nodes, cap, j, node, N.d, N.cap, P.gstage, P.gstage_cap, rec.li, rec.lambda}};
                     gauss_step_rec<EXT, RETR>(S, rn, o, calls, cc, lm, rt.probe, rt.probe_obj, rt.fresh_allowed, &rt.missed);
@@ -1161,21 +1192,23 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                     status |= BMO_NODE_SPLIT | BMO_NODE_STOPPED;
                 } else if (o.outcome == OUT_STOP) status |= BMO_NODE_STOPPED;
             }
+            // (behind the marches the launch's parameters are read again where they are used: step_params_again)
+            const auto Qa = step_params_again<SWEEP>(P);
             I[I_OBJ * cap + j] = o.hit_obj;
             I[I_SHAPE * cap + j] = o.hit_shape;
             if (RETR) {
                 still = rt.old >= 0 && rt.probe && !rt.missed;
-                old_kids = still && P.old.first_child[rt.old] >= 0;  // (not the SPLIT status: kept stale children hang on a beamlet that did not split)
+                old_kids = still && Qa->old.first_child[rt.old] >= 0;  // (not the SPLIT status: kept stale children hang on a beamlet that did not split)
                 if (!survive && old_kids && !split && !(flags & F_DEAD)) {
                     // The re-walk ends in a `nothing` interaction before the splitter the stored beamlet ended on: the reference keeps the children
                     // (System.jl:393-400) and retraces each from its stored first rays.  They take a splitter's children's places: the transmitted
                     // one's rays in the next level's record, the reflected one's in the staging planes; w0 and E0 stay the stored ones.
                     status |= BMO_NODE_RETRACE_STALE;
-                    const int32_t oc = P.old.first_child[rt.old];
+                    const int32_t oc = Qa->old.first_child[rt.old];
                     BMO_NOUNROLL
                     for (int w = 0; w < 2; ++w) {
                         int64_t hc, hs;
-                        const double* H = old_record(P.old, oc + w, 0, hc, hs);
+                        const double* H = old_record(Qa->old, oc + w, 0, hc, hs);
                         BMO_NOUNROLL
                         for (int r = 0; r < 3; ++r) {
                             const int64_t b11 = 11 * (int64_t)r;
@@ -1187,26 +1220,67 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                             else rec.put_refl(r, x);
                         }
                     }
-                    o.child_l0 = o.lenA + P.nodes.aux[(int64_t)node * 4 + 0];  // length(parent chief): its rays up to this hit + its own parents (Beam.jl:125-130)
-                    o.child_w0 = P.old.aux[(int64_t)oc * 4 + 1];
-                    o.Et = {P.old.aux[(int64_t)oc * 4 + 2], P.old.aux[(int64_t)oc * 4 + 3]};
-                    o.Er = {P.old.aux[(int64_t)(oc + 1) * 4 + 2], P.old.aux[(int64_t)(oc + 1) * 4 + 3]};
+                    o.child_l0 = o.lenA + Qa->nodes.aux[(int64_t)node * 4 + 0];  // length(parent chief): its rays up to this hit + its own parents (Beam.jl:125-130)
+                    o.child_w0 = Qa->old.aux[(int64_t)oc * 4 + 1];
+                    o.Et = {Qa->old.aux[(int64_t)oc * 4 + 2], Qa->old.aux[(int64_t)oc * 4 + 3]};
+                    o.Er = {Qa->old.aux[(int64_t)(oc + 1) * 4 + 2], Qa->old.aux[(int64_t)(oc + 1) * 4 + 3]};
                     split = true;  // from here on like a splitter's children, but the beamlet did not split: no BMO_NODE_SPLIT
                 }
                 // a split before the end of the stored path: the reference sizes the children (w0, E0) with the stale tail still attached
                 // to the beamlet (gauss_parameters(gauss, length(gauss)), ThinBeamsplitter.jl:125) — gauss_step_rec's `tail`; the flag stays as a note
                 if ((status & BMO_NODE_SPLIT) && still && k + 1 < rt.old_n) status |= BMO_NODE_RETRACE_STALE;
-                if (rt.old >= 0 && !(survive && still && k + 1 < rt.old_n)) P.nodes.old[node] = -1;
+                if (rt.old >= 0 && !(survive && still && k + 1 < rt.old_n)) Qa->nodes.old[node] = -1;
             }
             if (!survive) {
-                P.nodes.nseg[node] = k + 1;
-                P.nodes.status[node] = status;
-                if (o.det_slot >= 0 && !(flags & F_DEAD)) P.nodes.hit_det[node] = o.det_slot;
+                Qa->nodes.nseg[node] = k + 1;
+                Qa->nodes.status[node] = status;
+                if (o.det_slot >= 0 && !(flags & F_DEAD)) Qa->nodes.hit_det[node] = o.det_slot;
             }
         }
+        const auto Q = step_params_again<SWEEP>(P);
+        const auto Nq = &Q->inner[b];  // the next level's record, same slot
+        const int64_t ncap = Q->nxt.cap;
+        // (measured twice, profiles/r04_ab_scheduling.txt items 5 and 11: while the leaves' dispatch still cost this kernel 196 B of scratch the kept
+        //  child made it 228 B and config 3 2 % slower, 10.56 against 10.34 ms; with the pinned dispatch — 140 B, 164 with the kept child — it is
+        //  2 % FASTER, 9.41 against 9.62 ms, and one launch per solve.  -DBMO_NO_GAUSS_KEEP compiles it out.)
+#if defined(BMO_NO_GAUSS_KEEP)
+        const bool keep = false;
+#else
+        const bool keep = Q->gkeep != nullptr;
+#endif
+        // accumulators and header of a record whose rays are in place already
+        auto write_tail = [&](auto T, int64_t slot, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double lenA, double lenB, double oplC,
+                              double oplW, double oplD) {
+            const int64_t tcap = T->cap;
+            double* D = T->d;
+            int32_t* I = T->i;
+            D[33 * tcap + slot] = lenA;
+            D[34 * tcap + slot] = lenB;
+            D[35 * tcap + slot] = oplC;
+            D[36 * tcap + slot] = oplW;
+            D[37 * tcap + slot] = oplD;
+            I[I_NODE * tcap + slot] = nd;
+            I[I_K * tcap + slot] = kk;
+            I[I_HOBJ * tcap + slot] = ho;
+            I[I_HSHAPE * tcap + slot] = hs;
+            I[I_FLAGS * tcap + slot] = fl;
+        };
+        // a whole record in P.nxt: rays from `src` (plane r * rstride + c of capacity scap, at slot j), then accumulators and header
+        auto write_next = [&](int64_t slot, const double* src, int64_t scap, int rstride, int32_t nd, int32_t kk, int32_t ho, int32_t hs, int32_t fl, double lenA,
+                              double lenB, double oplC, double oplW, double oplD) {
+            if (slot >= ncap) {
+                atomicAdd(&Q->ctr->overflow, 1ull);
+                return;
+            }
+            double* D = Q->nxt.d;
+            BMO_NOUNROLL
+            for (int r = 0; r < 3; ++r)
+                for (int c = 0; c < 7; ++c) D[(11 * r + c) * ncap + slot] = src[(int64_t)(rstride * r + c) * scap + j];
+            write_tail(&Q->nxt, slot, nd, kk, ho, hs, fl, lenA, lenB, oplC, oplW, oplD);
+        };
         // header of the record that follows a surviving bounce
         auto next_header = [&](int32_t& fl, int32_t& ho, int32_t& hs) {
-            fl = (k + 2 < P.r_max) ? 0 : F_DEAD;
+            fl = (k + 2 < Q->r_max) ? 0 : F_DEAD;
             ho = o.hint_obj;
             hs = o.hint_shape;
             if (RETR && still) {
@@ -1214,7 +1288,7 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                 else ho = hs = -1;
             }
         };
-        bool go_on = b + 1 < P.n_fuse;
+        bool go_on = b + 1 < Q->n_fuse;
         // beam splitters, wherever in the loop they are met (see step_kernel): one reservation per wave
         const unsigned long long m_split = __ballot(split);
         bool kid_here = false;
@@ -1223,61 +1297,61 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             const unsigned long long m_push = keep ? (m_split & __ballot(pend_node >= 0)) : m_split;  // reflected children that go to P.nxt at once
             const int np = __popcll(m_push);
             unsigned long long r1 = 0, r2 = 0;
-            if (lane_id() == 0) r2 = atomicAdd(&P.ctr->node_count, 2ull * ns);  // (also counts the launch's in-loop splits: see step_kernel)
+            if (lane_id() == 0) r2 = atomicAdd(&Q->ctr->node_count, 2ull * ns);  // (also counts the launch's in-loop splits: see step_kernel)
             r2 = __shfl(r2, 0);
-            if (go_on && (int64_t)((r2 - (unsigned long long)P.nodes0) / 2ull + ns) > P.inwave_cap) go_on = false;
+            if (go_on && (int64_t)((r2 - (unsigned long long)Q->nodes0) / 2ull + ns) > Q->inwave_cap) go_on = false;
             if (!go_on || np) {
-                if (lane_id() == 0) r1 = atomicAdd(&P.ctr->next_count[P.parity], (unsigned long long)(go_on ? np : 2 * ns));
+                if (lane_id() == 0) r1 = atomicAdd(&Q->ctr->next_count[Q->parity], (unsigned long long)(go_on ? np : 2 * ns));
                 r1 = __shfl(r1, 0);
             }
             if (split) {
-                const int r = prefix_rank(m_split);
+                const int r = prefix_rank<!SWEEP>(m_split);
                 const int64_t cn = (int64_t)r2 + 2 * r;
-                if (cn + 1 < P.nodes.cap) {
-                    const unsigned long long pkey = P.nodes.key[node];
+                if (cn + 1 < Q->nodes.cap) {
+                    const unsigned long long pkey = Q->nodes.key[node];
                     const unsigned long long depth = pkey >> 32, path = pkey & 0xFFFFFFFFull;
-                    const int32_t root = P.nodes.root[node];
-                    atomicMax(&P.ctr->max_depth, depth + 1ull);
-                    if (P.nodes.tbits && depth < 5) atomicOr(&P.nodes.tbits[root], 3ull << ((2ull << depth) - 1ull + (path << 1)));
+                    const int32_t root = Q->nodes.root[node];
+                    atomicMax(&Q->ctr->max_depth, depth + 1ull);
+                    if (Q->nodes.tbits && depth < 5) atomicOr(&Q->nodes.tbits[root], 3ull << ((2ull << depth) - 1ull + (path << 1)));
                     for (int w = 0; w < 2; ++w) {
                         const int64_t c = cn + w;
-                        P.nodes.root[c] = root;
-                        P.nodes.parent[c] = node;
-                        P.nodes.nseg[c] = 1;
-                        P.nodes.status[c] = 0;
-                        P.nodes.li[c] = P.nodes.li[node];
-                        P.nodes.lambda[c] = P.nodes.lambda[node];
-                        P.nodes.hit_det[c] = -1;
-                        P.nodes.key[c] = ((depth + 1) << 32) | (((path << 1) | (unsigned long long)w) & 0xFFFFFFFFull);
-                        P.nodes.aux[c * 4 + 0] = o.child_l0;
-                        P.nodes.aux[c * 4 + 1] = o.child_w0;
-                        P.nodes.aux[c * 4 + 2] = w == 0 ? o.Et.re : o.Er.re;
-                        P.nodes.aux[c * 4 + 3] = w == 0 ? o.Et.im : o.Er.im;
+                        Q->nodes.root[c] = root;
+                        Q->nodes.parent[c] = node;
+                        Q->nodes.nseg[c] = 1;
+                        Q->nodes.status[c] = 0;
+                        Q->nodes.li[c] = Q->nodes.li[node];
+                        Q->nodes.lambda[c] = Q->nodes.lambda[node];
+                        Q->nodes.hit_det[c] = -1;
+                        Q->nodes.key[c] = ((depth + 1) << 32) | (((path << 1) | (unsigned long long)w) & 0xFFFFFFFFull);
+                        Q->nodes.aux[c * 4 + 0] = o.child_l0;
+                        Q->nodes.aux[c * 4 + 1] = o.child_w0;
+                        Q->nodes.aux[c * 4 + 2] = w == 0 ? o.Et.re : o.Er.re;
+                        Q->nodes.aux[c * 4 + 3] = w == 0 ? o.Et.im : o.Er.im;
                         if (RETR) {
-                            const int32_t oc = old_kids ? P.old.first_child[rt.old] + w : -1;
-                            P.nodes.old[c] = oc;
-                            if (oc >= 0) P.nodes.aux[c * 4 + 1] = P.old.aux[(int64_t)oc * 4 + 1];  // _modify_beam_head! keeps the stored w0 (Gaussian.jl:154-161)
+                            const int32_t oc = old_kids ? Q->old.first_child[rt.old] + w : -1;
+                            Q->nodes.old[c] = oc;
+                            if (oc >= 0) Q->nodes.aux[c * 4 + 1] = Q->old.aux[(int64_t)oc * 4 + 1];  // _modify_beam_head! keeps the stored w0 (Gaussian.jl:154-161)
                         }
                     }
-                    const int32_t fl = ((RETR && old_kids) || 1 < P.r_max) ? 0 : F_DEAD;
+                    const int32_t fl = ((RETR && old_kids) || 1 < Q->r_max) ? 0 : F_DEAD;
                     // children: chief inherits the parent chain (parent! Gaussian.jl:113-117); waist/div beams have no parent
-                    if (go_on) write_tail(N, j, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);  // (its rays are in place)
-                    else write_next((int64_t)r1 + 2 * r, N.d, N.cap, 11, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);
+                    if (go_on) write_tail(Nq, j, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);  // (its rays are in place)
+                    else write_next((int64_t)r1 + 2 * r, Nq->d, Nq->cap, 11, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);
                     if (go_on && keep && pend_node < 0) {  // the reflected child waits for this lane (the staging planes serve the next split)
-                        const int64_t gc = P.gstage_cap;
+                        const int64_t gc = Q->gstage_cap;
                         BMO_NOUNROLL
-                        for (int q = 0; q < 21; ++q) P.gkeep[q * gc + j] = P.gstage[q * gc + j];
-                        P.gkeep[21 * gc + j] = o.child_l0;
-                        P.gkeep[22 * gc + j] = o.oplC;
-                        P.gkeep[23 * gc + j] = (double)fl;
+                        for (int q = 0; q < 21; ++q) Q->gkeep[q * gc + j] = Q->gstage[q * gc + j];
+                        Q->gkeep[21 * gc + j] = o.child_l0;
+                        Q->gkeep[22 * gc + j] = o.oplC;
+                        Q->gkeep[23 * gc + j] = (double)fl;
                         pend_node = (int32_t)(cn + 1);
                     } else {
-                        write_next(go_on ? (int64_t)r1 + prefix_rank(m_push) : (int64_t)r1 + 2 * r + 1, P.gstage, P.gstage_cap, 7, (int32_t)(cn + 1), 0, -1, -1, fl, 0.0,
+                        write_next(go_on ? (int64_t)r1 + prefix_rank<!SWEEP>(m_push) : (int64_t)r1 + 2 * r + 1, Q->gstage, Q->gstage_cap, 7, (int32_t)(cn + 1), 0, -1, -1, fl, 0.0,
                                    o.child_l0, o.oplC, 0.0, 0.0);
                     }
                     kid_here = go_on;
                 } else {
-                    atomicAdd(&P.ctr->overflow, 1ull);
+                    atomicAdd(&Q->ctr->overflow, 1ull);
                 }
             }
         }
@@ -1288,16 +1362,16 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                 if (alive && survive) {
                     int32_t fl, ho, hs;
                     next_header(fl, ho, hs);
-                    write_tail(N, j, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
+                    write_tail(Nq, j, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
                 } else if (take_kept) {
-                    const int64_t gc = P.gstage_cap, nc = N.cap;
+                    const int64_t gc = Q->gstage_cap, nc = Nq->cap;
                     BMO_NOUNROLL
                     for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 7; ++c) N.d[(11 * r + c) * nc + j] = P.gkeep[(int64_t)(7 * r + c) * gc + j];
-                    write_tail(N, j, pend_node, 0, -1, -1, (int32_t)P.gkeep[23 * gc + j], 0.0, P.gkeep[21 * gc + j], P.gkeep[22 * gc + j], 0.0, 0.0);
+                        for (int c = 0; c < 7; ++c) Nq->d[(11 * r + c) * nc + j] = Q->gkeep[(int64_t)(7 * r + c) * gc + j];
+                    write_tail(Nq, j, pend_node, 0, -1, -1, (int32_t)Q->gkeep[23 * gc + j], 0.0, Q->gkeep[21 * gc + j], Q->gkeep[22 * gc + j], 0.0, 0.0);
                     pend_node = -1;
                 } else if (!kid_here) {
-                    N.i[I_NODE * N.cap + j] = -1;  // no record of this beamlet at this level
+                    Nq->i[I_NODE * Nq->cap + j] = -1;  // no record of this beamlet at this level
                     alive = false;
                 }
             }
@@ -1306,23 +1380,23 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
         }
         // ---- last fused bounce of this wave
         if constexpr (SWEEP) {  // (a wave's slots are not consecutive: the level is noted per slot, Chunk::wl_shift = 0)
-            if (P.wave_last && valid) P.wave_last[j] = (uint8_t)b;
-        } else if (P.wave_last && lane_id() == 0) {
-            P.wave_last[gwave] = (uint8_t)b;
+            if (Q->wave_last && valid) Q->wave_last[j] = (uint8_t)b;
+        } else if (Q->wave_last && lane_id() == 0) {
+            Q->wave_last[gwave] = (uint8_t)b;
         }
-        const SlotAlloc al = block_alloc<false>(survive, pend_node >= 0, calls, P, scratch, b);
+        const SlotAlloc al = block_alloc<false, SWEEP>(survive, pend_node >= 0, calls, Q, scratch, b);
         if (survive) {
-            const int64_t slot = (int64_t)al.surv_base + prefix_rank(al.m_surv);
+            const int64_t slot = (int64_t)al.surv_base + prefix_rank<!SWEEP>(al.m_surv);
             int32_t fl, ho, hs;
             next_header(fl, ho, hs);
-            write_next(slot, N.d, N.cap, 11, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
+            write_next(slot, Nq->d, Nq->cap, 11, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
         }
         if (pend_node >= 0) {  // the reflected children their lanes did not get to
-            const int64_t gc = P.gstage_cap;
-            write_next((int64_t)al.child_base + prefix_rank(al.m_split), P.gkeep, gc, 7, pend_node, 0, -1, -1, (int32_t)P.gkeep[23 * gc + j], 0.0, P.gkeep[21 * gc + j],
-                       P.gkeep[22 * gc + j], 0.0, 0.0);
+            const int64_t gc = Q->gstage_cap;
+            write_next((int64_t)al.child_base + prefix_rank<!SWEEP>(al.m_split), Q->gkeep, gc, 7, pend_node, 0, -1, -1, (int32_t)Q->gkeep[23 * gc + j], 0.0, Q->gkeep[21 * gc + j],
+                       Q->gkeep[22 * gc + j], 0.0, 0.0);
         }
-        if (P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)wall_clock64() - P.tile_cost[tile];
+        if (Q->tile_cost && step_tid<SWEEP>() == 0) Q->tile_cost[tile] = (uint32_t)wall_clock64() - Q->tile_cost[tile];
         return;
     }
 }

@@ -466,6 +466,7 @@ int launch_step(DevCtx& ctx, const StepKernels& kern, const LaunchPlan& plan, co
     const bool wide = kern.plain_wide && plan.n_waves >= wide_min_waves;
     const StepKernel k = (plan.inwave_cap > 0 && kern.inw) ? (wide ? kern.inw_wide : kern.inw) : (wide ? kern.plain_wide : kern.plain);
     if (!k) return fail(BMO_ERR_INTERNAL, "no step kernel selected for this beam kind / scene level");
+    DBG("step %d kernel build: %s, %s", step, wide ? "4 waves per SIMD" : "default waves per SIMD", (plan.inwave_cap > 0 && kern.inw) ? "in-loop splitters" : "splits end the loop");
     hipLaunchKernelGGL(k, dim3(plan.n_blocks), dim3(BMO_BLOCK), STEP_LDS_BYTES, stream, P);
     HIP_TRY(hipEventRecord(ctx.step_ev[2 * step + 1], stream));
     HIP_TRY(hipMemcpyAsync(ctx.pinned, d_ctr, sizeof(Counters), hipMemcpyDeviceToHost, stream));
