@@ -25,6 +25,12 @@ PSF_STAT_N = 21
 (PSF_N, PSF_S, PSF_CX, PSF_CZ, PSF_X_MIN, PSF_X_MAX, PSF_Z_MIN, PSF_Z_MAX, PSF_HWX, PSF_HWZ, PSF_X_REF, PSF_Z_REF, PSF_W_MEAN, PSF_W_RMS, PSF_W_LO,
  PSF_W_HI, PSF_F_RE, PSF_F_IM, PSF_STREHL, PSF_K_MIN, PSF_K_MAX) = range(PSF_STAT_N)
 
+# BMO_ZERNIKE_*: columns of the info row of the Zernike read-out (bmo_psf_zernike)
+ZERN_INFO_N = 13
+ZERN_MAX_ORDER = 6
+(ZERN_N, ZERN_STATUS, ZERN_S, ZERN_X_REF, ZERN_Z_REF, ZERN_U0, ZERN_V0, ZERN_RHO, ZERN_W_MEAN, ZERN_FIT_RMS, ZERN_E_LO, ZERN_E_HI,
+ ZERN_N_OUT) = range(ZERN_INFO_N)
+
 NODE_MISS, NODE_STOPPED, NODE_RMAX, NODE_SPLIT, NODE_DETECTED, NODE_ERR_UNIT, NODE_GAUSS_DIVERGED, NODE_BLOCKED, NODE_ERR_ORTHO = (
     1, 2, 4, 8, 16, 32, 64, 128, 256)
 
@@ -248,6 +254,8 @@ def load_engine():
     lib.bmo_spot_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
     lib.bmo_psf_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp]
     lib.bmo_psf_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
+    lib.bmo_psf_zernike.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_zernike_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -409,3 +417,62 @@ def psf_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, ref=None
     check(lib, lib.bmo_psf_stats_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                        None if r is None else r.ctypes.data_as(dp), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats_sweep")
     return st[:K], ms.value
+
+
+def zernike_sizes(order):
+    """(J, E): the terms up to radial order `order`, and the entries of the packed augmented Gram matrix."""
+    J = (int(order) + 1) * (int(order) + 2) // 2
+    return J, (J + 1) * (J + 2) // 2
+
+
+def psf_zernike(hits, origin, e1, e2, order=4, ref=None, pupil=None, device=0, hits_device_ptr=None, n_hits=None, want_gram=False):
+    """bmo_psf_zernike: the least-squares Zernike coefficients (OSA/ANSI order, metres) of the wavefront of PSF rows at the detector pose
+    (origin, e1, e2), four passes on the device.  ref: the reference point (x, z), None for the centroid; pupil: (U0, V0, RHO) in direction
+    cosines, None for the proj-weighted centre and the largest radius of the rows.  `hits` is a host [H, 9] array, or pass
+    `hits_device_ptr` + `n_hits` for resident rows.  Returns (coef [J], info [13] at the ZERN_* columns, gram or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
+    q = None if pupil is None else np.ascontiguousarray(pupil, dtype=np.float64).reshape(3)
+    if hits_device_ptr is None:
+        h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
+        hp, nh, on_dev = h.ctypes.data_as(C.c_void_p), len(h), 0
+    else:
+        hp, nh, on_dev = C.c_void_p(int(hits_device_ptr)), int(n_hits), 1
+    J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
+    coef, info = np.zeros(J), np.zeros(ZERN_INFO_N)
+    gram = np.zeros(E) if want_gram else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_zernike(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
+                                   None if q is None else q.ctypes.data_as(dp), int(order), int(device), coef.ctypes.data_as(dp), info.ctypes.data_as(dp),
+                                   gram.ctypes.data_as(dp) if want_gram else None, C.byref(ms)), "bmo_psf_zernike")
+    return coef, info, gram, ms.value
+
+
+def psf_zernike_sweep(res_handle, detector, n_configs, origins, e1s, e2s, order=4, ref=None, pupil=None, want_gram=False):
+    """bmo_psf_zernike_sweep on the result handle `res_handle`: origins / e1s / e2s [K, 3]; ref None, one (x, z) for all or [K, 2]; pupil
+    None, one (U0, V0, RHO) for all or [K, 3].  Returns (coef [K, J], info [K, 13], gram [K, E] or None, kernel_ms); row c equals
+    psf_zernike on the rows of configuration c bit for bit."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
+
+    def per_config(v, cols):
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=np.float64)
+        return np.ascontiguousarray(np.tile(v, (K1, 1)) if v.ndim == 1 else v.reshape(K1, cols))
+
+    r, q = per_config(ref, 2), per_config(pupil, 3)
+    J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
+    coef, info = np.zeros((K1, J)), np.zeros((K1, ZERN_INFO_N))
+    gram = np.zeros((K1, E)) if want_gram else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_zernike_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
+                                         None if r is None else r.ctypes.data_as(dp), None if q is None else q.ctypes.data_as(dp), int(order),
+                                         coef.ctypes.data_as(dp), info.ctypes.data_as(dp), gram.ctypes.data_as(dp) if want_gram else None, C.byref(ms)),
+          "bmo_psf_zernike_sweep")
+    return coef[:K], info[:K], None if gram is None else gram[:K], ms.value

@@ -469,6 +469,46 @@ def psf_marechal(stats):
         return np.where(k == st[..., abi.PSF_K_MAX], np.exp(-(k * rms) ** 2), np.nan)
 
 
+def zernike_terms(order):
+    """The (n, m) of the Zernike terms up to radial order `order` in OSA/ANSI order: j = (n (n + 2) + m) / 2."""
+    return [(n, m) for n in range(int(order) + 1) for m in range(-n, n + 1, 2)]
+
+
+def zernike_radial(n, am):
+    """[q_0 .. q_K], K = (n - am) / 2: the integer coefficients of R_n^am(rho) / rho^am as a polynomial in t = rho^2."""
+    K, f = (n - am) // 2, math.factorial
+    return [(-1) ** (K - s) * (f(n - K + s) // (f(K - s) * f((n + am) // 2 - K + s) * f(s))) for s in range(K + 1)]
+
+
+def zernike_basis(x, y, order):
+    """Z [J, ...] of the terms at the points (x, y) of the unit disc, by the expressions of include/bmo.h "Zernike read-out" in elementwise
+    numpy (+, -, * only, one rounding each, left to right): what the engine evaluates, bit for bit.  Orthonormal over the uniform disc."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    t = x * x + y * y
+    Cc, Sc = [np.ones_like(x)], [np.zeros_like(x)]
+    for k in range(int(order)):
+        Cc.append(Cc[k] * x - Sc[k] * y)
+        Sc.append(Sc[k] * x + Cc[k] * y)
+    out = []
+    for n, m in zernike_terms(order):
+        q = zernike_radial(n, abs(m))
+        r = np.full_like(t, float(q[-1]))
+        for s in range(len(q) - 2, -1, -1):
+            r = r * t + float(q[s])
+        nrm = math.sqrt(float(n + 1)) if m == 0 else math.sqrt(float(2 * (n + 1)))
+        out.append(nrm * (r * (Cc[m] if m >= 0 else Sc[-m])))
+    return np.array(out)
+
+
+def zernike_surface(coef, n, order):
+    """The fitted surface sum_j coef_j Z_j on an n x n grid of the unit square [-1, 1]^2, indexed [i, j] = (x_i, y_j); NaN outside the disc."""
+    t = np.linspace(-1.0, 1.0, int(n))
+    x, y = np.meshgrid(t, t, indexing="ij")
+    Z = zernike_basis(x, y, order)
+    c = np.asarray(coef, dtype=np.float64).reshape(len(Z))
+    return np.where(x * x + y * y <= 1.0, np.tensordot(c, Z, axes=1), np.nan)
+
+
 class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
     kind = O_PSF
 
@@ -501,6 +541,16 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
 
         o = self.orientation()
         return abi.psf_stats(self.data, self.position(), o[:, 0], o[:, 2], ref=ref, device=device)[0]
+
+    def zernike(self, order=4, ref=None, pupil=None, device=0):
+        """The Zernike fit of the wavefront of all rows accumulated so far (bmo_psf_zernike): (coef [J] in metres, OSA/ANSI order as
+        zernike_terms(order); info [13] at the abi.ZERN_* columns).  ref = (x, z): the reference point in local coordinates (None: the
+        centroid); pupil = (U0, V0, RHO) in direction cosines (None: the rows' own centre and largest radius)."""
+        from . import abi
+
+        o = self.orientation()
+        coef, info, _, _ = abi.psf_zernike(self.data, self.position(), o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil, device=device)
+        return coef, info
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

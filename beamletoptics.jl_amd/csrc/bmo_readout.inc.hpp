@@ -1507,3 +1507,578 @@ extern "C" int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int3
     if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_stats_sweep: rows out of configuration order", 0, R)) return rc;
     return psf_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, stats, kernel_ms, "bmo_psf_stats_sweep");
 }
+
+// ====================================================================================================================
+// Zernike read-out: the least-squares Zernike coefficients of a PSFDetector's wavefront (include/bmo.h "Zernike read-out").  The plumbing
+// and the first two passes are those of the wavefront statistics (same expressions, same lane / wave / split order: S, X_REF, Z_REF and
+// W_MEAN are that call's bit for bit); four accumulate passes with a per-configuration reduce each, queued behind one synchronisation:
+//   A  S, sum proj x, sum proj z, sum proj u, sum proj v over the 9-column rows; its reduce leaves p, U0, V0
+//   B  sum proj W and the largest squared pupil radius; writes (proj, W, u, v) of every row to a 32-byte scratch column; its reduce
+//      leaves W_MEAN and RHO
+//   C  the Gram matrix of the augmented columns (Z_0 .. Z_{J-1}, D): per tile of 256 rows every lane evaluates the columns of its own row
+//      into LDS, then every thread owns a 2 x 2 block of the (J + 1)(J + 2) / 2 entries and walks the tile's rows in row order, its accumulators
+//      carried across the tiles of the work item: an entry of a work item is the left fold over its rows.  Its reduce folds the work items
+//      in split order, one thread per entry, and thread 0 runs the Cholesky solve from LDS.  No float atomics.
+//   D  the residual sums and extrema and N_OUT from the scratch column and the coefficients
+// The order is a template parameter of the kernels that evaluate terms: every loop over terms unrolls, the terms live in registers.
+namespace {
+
+constexpr int ZERN_MAX_J = (BMO_ZERNIKE_MAX_ORDER + 1) * (BMO_ZERNIKE_MAX_ORDER + 2) / 2;  // 28
+constexpr int ZERN_MAX_E = (ZERN_MAX_J + 1) * (ZERN_MAX_J + 2) / 2;                        // 435
+constexpr int ZERN_ROW_BATCH = 8;    // tile rows whose LDS reads are in flight together in pass C
+constexpr int ZERN_FOLD_BATCH = 16;  // partial sums of one entry in flight in pass C's reduce
+constexpr int zern_terms_of(int order) { return (order + 1) * (order + 2) / 2; }
+// doubles per row of pass C's tile: the J + 1 augmented columns and proj, padded to an odd count (the lanes' writes of one column then
+// spread over the banks; the reads of a wave go to one row, whose columns are distinct banks as it is shorter than the 64 banks)
+constexpr int zern_row_stride(int order) { return (zern_terms_of(order) + 2) | 1; }
+
+constexpr double zern_fact(int k) {
+    double f = 1.0;
+    for (int q = 2; q <= k; ++q) f *= q;
+    return f;
+}
+// q_s of R_n^am(rho) / rho^am as a polynomial in t = rho^2 (integers, exact in FP64)
+constexpr double zern_q(int n, int am, int s) {
+    const int K = (n - am) / 2;
+    return (((K - s) & 1) ? -1.0 : 1.0) * (zern_fact(n - K + s) / (zern_fact(K - s) * zern_fact((n + am) / 2 - K + s) * zern_fact(s)));
+}
+// sqrt((double)k), correctly rounded, k = 0 .. 14
+constexpr double ZERN_SQRT[15] = {0.0,
+                                  1.0,
+                                  1.4142135623730951,
+                                  1.7320508075688772,
+                                  2.0,
+                                  2.23606797749979,
+                                  2.449489742783178,
+                                  2.6457513110645907,
+                                  2.8284271247461903,
+                                  3.0,
+                                  3.1622776601683795,
+                                  3.3166247903554,
+                                  3.4641016151377544,
+                                  3.605551275463989,
+                                  3.7416573867739413};
+constexpr double zern_norm(int n, int m) { return ZERN_SQRT[m == 0 ? n + 1 : 2 * (n + 1)]; }
+
+// Horner steps s = S .. 0 of the radial polynomial: r = r * t + q_s.  q_s is a constant expression, so it is a literal in the code.
+template <int N, int AM, int S>
+__device__ __forceinline__ double zern_horner(double r, double t) {
+    if constexpr (S < 0) {
+        return r;
+    } else {
+        constexpr double q = zern_q(N, AM, S);
+        return zern_horner<N, AM, S - 1>(r * t + q, t);
+    }
+}
+// One term: Z = N * (r * A) with Horner in t from the top.
+template <int N, int M>
+__device__ __forceinline__ double zern_term(double t, const double* Cc, const double* Sc) {
+    constexpr int AM = M < 0 ? -M : M, K = (N - AM) / 2;
+    constexpr double q_top = zern_q(N, AM, K), nrm = zern_norm(N, M);
+    const double r = zern_horner<N, AM, K - 1>(q_top, t);
+    return nrm * (r * (M >= 0 ? Cc[AM] : Sc[AM]));
+}
+template <int N, int M, int ORDER, class F>
+__device__ __forceinline__ void zern_walk(double t, const double* Cc, const double* Sc, F&& f) {
+    if constexpr (N <= ORDER) {
+        f((N * (N + 2) + M) / 2, zern_term<N, M>(t, Cc, Sc));
+        if constexpr (M + 2 <= N) zern_walk<N, M + 2, ORDER>(t, Cc, Sc, f);
+        else zern_walk<N + 1, -(N + 1), ORDER>(t, Cc, Sc, f);
+    }
+}
+// f(j, Z_j(x, y)) for j = 0 .. J - 1 in ascending j; j is a constant in every call
+template <int ORDER, class F>
+__device__ __forceinline__ void zern_terms(double x, double y, F&& f) {
+    const double t = x * x + y * y;
+    double Cc[ORDER + 1], Sc[ORDER + 1];
+    Cc[0] = 1.0;
+    Sc[0] = 0.0;
+#pragma unroll
+    for (int k = 0; k < ORDER; ++k) {
+        Cc[k + 1] = Cc[k] * x - Sc[k] * y;
+        Sc[k + 1] = Sc[k] * x + Cc[k] * y;
+    }
+    zern_walk<0, 0, ORDER>(t, Cc, Sc, f);
+}
+
+struct ZernSumA {
+    double s, sx, sz, su, sv;
+};
+struct ZernSumB {
+    double sw, r2;
+};
+struct ZernSumD {
+    double var, lo, hi, n_out;
+};
+// what the later passes need of configuration c
+struct ZernMid {
+    d3 p;  // the reference point in world coordinates
+    double u0, v0, rho, w_mean;
+};
+
+// direction cosine of row r along axis e
+__device__ __forceinline__ double zern_cosine(const double* r, const d3& e) { return (r[3] * e.x + r[4] * e.y) + r[5] * e.z; }
+
+// pass A of work item blockIdx.x
+__global__ __launch_bounds__(256) void psf_zernike_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
+                                                               ZernSumA* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const PsfPose C = pose[W.cfg];
+    double s = 0.0, sx = 0.0, sz = 0.0, su = 0.0, sv = 0.0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
+            const double w = r[7];
+            s += w;
+            sx += w * x;
+            sz += w * z;
+            su += w * zern_cosine(r, C.e1);
+            sv += w * zern_cosine(r, C.e2);
+        }
+    }
+    ZernSumA a;
+    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
+    a.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
+    a.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
+    a.su = spot_wg_reduce(su, SpotAdd{}, sh);
+    a.sv = spot_wg_reduce(sv, SpotAdd{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+
+// configuration blockIdx.x: the splits of pass A in split order.  ref_xz: nullptr (the centroid) or [K][2]; pupil: nullptr or [K][3].
+// A configuration without rows gets its whole answer here: N = 0, STATUS = 1, NaN elsewhere.
+__global__ void psf_zernike_sums_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfPose* __restrict__ pose,
+                                               const double* __restrict__ ref_xz, const double* __restrict__ pupil, const ZernSumA* __restrict__ partial,
+                                               double* __restrict__ info, ZernMid* __restrict__ mid) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumA) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;
+    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+    const int64_t n = count[c];
+    if (n == 0) {
+        if (threadIdx.x == 0) {
+            for (int q = 0; q < BMO_ZERNIKE_INFO_N; ++q) out[q] = knan();
+            out[BMO_ZERNIKE_N_ROWS] = 0.0;
+            out[BMO_ZERNIKE_STATUS] = 1.0;
+            mid[c] = ZernMid{d3{0.0, 0.0, 0.0}, 0.0, 0.0, 0.0, 0.0};
+        }
+        return;
+    }
+    double s = 0.0, sx = 0.0, sz = 0.0, su = 0.0, sv = 0.0;
+    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumA& p) {
+        s += p.s;
+        sx += p.sx;
+        sz += p.sz;
+        su += p.su;
+        sv += p.sv;
+    });
+    if (threadIdx.x != 0) return;
+    const double cx = sx / s, cz = sz / s;
+    const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+    const double u0 = pupil ? pupil[3 * c] : su / s, v0 = pupil ? pupil[3 * c + 1] : sv / s;
+    out[BMO_ZERNIKE_N_ROWS] = (double)n;
+    out[BMO_ZERNIKE_STATUS] = 0.0;
+    out[BMO_ZERNIKE_S] = s;
+    out[BMO_ZERNIKE_X_REF] = x_ref;
+    out[BMO_ZERNIKE_Z_REF] = z_ref;
+    out[BMO_ZERNIKE_U0] = u0;
+    out[BMO_ZERNIKE_V0] = v0;
+    const PsfPose P = pose[c];
+    mid[c] = ZernMid{psf_point(P.origin, P.e1, P.e2, x_ref, z_ref), u0, v0, 0.0, 0.0};
+}
+
+// pass B of work item blockIdx.x; col[h] = (proj, W, u, v) of row h for passes C and D
+__global__ __launch_bounds__(256) void psf_zernike_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
+                                                               const ZernMid* __restrict__ mid, double4* __restrict__ col, ZernSumB* __restrict__ partial) {
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const PsfPose C = pose[W.cfg];
+    const ZernMid M = mid[W.cfg];
+    double sw = 0.0, r2 = 0.0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double w = r[7];
+            const double path = psf_path(M.p, r);
+            const double u = zern_cosine(r, C.e1), v = zern_cosine(r, C.e2);
+            sw += w * path;
+            const double q = (u - M.u0) * (u - M.u0) + (v - M.v0) * (v - M.v0);
+            r2 = q > r2 ? q : r2;
+            col[base + threadIdx.x] = make_double4(w, path, u, v);
+        }
+    }
+    ZernSumB b;
+    b.sw = spot_wg_reduce(sw, SpotAdd{}, sh);
+    b.r2 = spot_wg_reduce(r2, SpotMax{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+}
+
+__global__ void psf_zernike_wave_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const double* __restrict__ pupil,
+                                               const ZernSumB* __restrict__ partial, double* __restrict__ info, ZernMid* __restrict__ mid) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumB) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;
+    if (count[c] == 0) return;  // answered already
+    double sw = 0.0, r2 = 0.0;
+    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumB& p) {
+        sw += p.sw;
+        r2 = p.r2 > r2 ? p.r2 : r2;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+    const double w_mean = sw / out[BMO_ZERNIKE_S];
+    const double rho = pupil ? pupil[3 * c + 2] : sqrt(r2);
+    out[BMO_ZERNIKE_W_MEAN] = w_mean;
+    out[BMO_ZERNIKE_RHO] = rho;
+    mid[c].w_mean = w_mean;
+    mid[c].rho = rho;
+}
+
+// entry e of the packed lower triangle: (i, k), i >= k
+__device__ __forceinline__ void zern_entry(int e, int& i, int& k) {
+    i = 0;
+    while ((i + 1) * (i + 2) / 2 <= e) ++i;
+    k = e - i * (i + 1) / 2;
+}
+
+// pass C of work item blockIdx.x: partial[blockIdx.x][e] = the left fold of (proj * B_i) * B_k over its rows.  A thread owns a 2 x 2 block of
+// entries, columns (2 bi, 2 bi + 1) x (2 bk, 2 bk + 1) with bi >= bk: five LDS reads per row (proj and four columns) feed its four products,
+// and every entry is still the sum over the rows in row order.  The reads are volatile so that each stays a single-address 8-byte read
+// (64 banks; the columns of one tile row are distinct banks): left to itself the compiler pairs the reads of unrolled rows into
+// two-address reads, which see 32 banks and conflict.
+template <int ORDER>
+__global__ __launch_bounds__(256) void psf_zernike_gram_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
+                                                               double* __restrict__ partial) {
+    constexpr int J = zern_terms_of(ORDER), NC = J + 1, E = (J + 1) * (J + 2) / 2, STRIDE = zern_row_stride(ORDER);
+    constexpr int NB = (NC + 1) / 2, NBLK = NB * (NB + 1) / 2;  // at most 15 block rows, 120 blocks
+    __shared__ double tile[PSF_TILE * STRIDE];
+    const SplitWork W = work[blockIdx.x];
+    const ZernMid M = mid[W.cfg];
+    const bool owner = (int)threadIdx.x < NBLK;
+    int bi, bk;
+    zern_entry(owner ? (int)threadIdx.x : 0, bi, bk);
+    const int i0 = 2 * bi, k0 = 2 * bk;
+    const bool has_i1 = i0 + 1 < NC, has_k1 = k0 + 1 < NC;
+    const int i1 = has_i1 ? i0 + 1 : i0, k1 = has_k1 ? k0 + 1 : k0;  // a column past the last one reads its neighbour and is not written
+    double a00 = 0.0, a01 = 0.0, a10 = 0.0, a11 = 0.0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            const double4 q = col[base + threadIdx.x];
+            double* row = tile + STRIDE * threadIdx.x;
+            const double x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
+            zern_terms<ORDER>(x, y, [&](int j, double Z) { row[j] = Z; });
+            row[J] = q.y - M.w_mean;
+            row[J + 1] = q.x;
+        }
+        __syncthreads();
+        if (owner) {
+            auto add_row = [&](double p, double bi0, double bi1, double bk0, double bk1) {
+                const double pi0 = p * bi0, pi1 = p * bi1;
+                a00 += pi0 * bk0;
+                a01 += pi0 * bk1;
+                a10 += pi1 * bk0;
+                a11 += pi1 * bk1;
+            };
+            // the reads of ZERN_ROW_BATCH rows are issued together, then the rows are added in row order: one LDS latency per batch
+            int h = 0;
+            for (; h + ZERN_ROW_BATCH <= cnt; h += ZERN_ROW_BATCH) {
+                double p[ZERN_ROW_BATCH], bi0[ZERN_ROW_BATCH], bi1[ZERN_ROW_BATCH], bk0[ZERN_ROW_BATCH], bk1[ZERN_ROW_BATCH];
+#pragma unroll
+                for (int q = 0; q < ZERN_ROW_BATCH; ++q) {
+                    const volatile double* row = tile + STRIDE * (h + q);
+                    p[q] = row[J + 1], bi0[q] = row[i0], bi1[q] = row[i1], bk0[q] = row[k0], bk1[q] = row[k1];
+                }
+#pragma unroll
+                for (int q = 0; q < ZERN_ROW_BATCH; ++q) add_row(p[q], bi0[q], bi1[q], bk0[q], bk1[q]);
+            }
+            for (; h < cnt; ++h) {
+                const volatile double* row = tile + STRIDE * h;
+                const double p = row[J + 1], bi0 = row[i0], bi1 = row[i1], bk0 = row[k0], bk1 = row[k1];
+                add_row(p, bi0, bi1, bk0, bk1);
+            }
+        }
+    }
+    if (!owner) return;
+    double* out = partial + (int64_t)blockIdx.x * E;
+    out[i0 * (i0 + 1) / 2 + k0] = a00;
+    if (has_k1 && k0 + 1 <= i0) out[i0 * (i0 + 1) / 2 + k0 + 1] = a01;  // above the diagonal in a diagonal block
+    if (has_i1) {
+        out[(i0 + 1) * (i0 + 2) / 2 + k0] = a10;
+        if (has_k1) out[(i0 + 1) * (i0 + 2) / 2 + k0 + 1] = a11;
+    }
+}
+
+// configuration blockIdx.x: the work items' Gram entries folded in split order, one thread per entry; thread 0 then solves (the loops of
+// include/bmo.h) from LDS and writes coef, STATUS and gram.  J terms; gram: nullptr or [K][E].
+__global__ __launch_bounds__(256) void psf_zernike_gram_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, int32_t J,
+                                                                      const double* __restrict__ partial, double* __restrict__ info, double* __restrict__ coef,
+                                                                      double* __restrict__ gram) {
+    __shared__ double G[ZERN_MAX_E];
+    __shared__ double L[ZERN_MAX_J * (ZERN_MAX_J + 1) / 2];
+    __shared__ double yv[ZERN_MAX_J];
+    const int32_t c = (int32_t)blockIdx.x;
+    const int E = (J + 1) * (J + 2) / 2;
+    const int64_t n = count[c];
+    double* cf = coef + (int64_t)c * J;
+    if (n == 0) {
+        for (int q = threadIdx.x; q < J; q += 256) cf[q] = knan();
+        if (gram)
+            for (int q = threadIdx.x; q < E; q += 256) gram[(int64_t)c * E + q] = knan();
+        return;
+    }
+    const SplitCfg C = cfg[c];
+    // an entry's partial sums lie E doubles apart; ZERN_FOLD_BATCH loads are issued together and then added in split order, so the thread
+    // waits for memory once per batch and not once per work item
+    for (int e = threadIdx.x; e < E; e += 256) {
+        const double* src = partial + C.first_work * E + e;
+        double g = 0.0;
+        int s = 0;
+        for (; s + ZERN_FOLD_BATCH <= C.n_splits; s += ZERN_FOLD_BATCH) {
+            double v[ZERN_FOLD_BATCH];
+#pragma unroll
+            for (int q = 0; q < ZERN_FOLD_BATCH; ++q) v[q] = src[(int64_t)(s + q) * E];
+#pragma unroll
+            for (int q = 0; q < ZERN_FOLD_BATCH; ++q) g += v[q];
+        }
+        for (; s < C.n_splits; ++s) g += src[(int64_t)s * E];
+        G[e] = g;
+        if (gram) gram[(int64_t)c * E + e] = g;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+    const double rho = out[BMO_ZERNIKE_RHO];
+    int status = 0;
+    if (n < J || rho == 0.0 || !isfinite(rho)) status = 1;
+    for (int j = 0; j < J && status == 0; ++j) {
+        const double* Lj = L + j * (j + 1) / 2;
+        double d = G[j * (j + 1) / 2 + j];
+        for (int k = 0; k < j; ++k) d = d - Lj[k] * Lj[k];
+        if (!(d > 0.0)) {
+            status = 2;
+            break;
+        }
+        const double ljj = sqrt(d);
+        L[j * (j + 1) / 2 + j] = ljj;
+        for (int i = j + 1; i < J; ++i) {
+            double* Li = L + i * (i + 1) / 2;
+            double s = G[i * (i + 1) / 2 + j];
+            for (int k = 0; k < j; ++k) s = s - Li[k] * Lj[k];
+            Li[j] = s / ljj;
+        }
+    }
+    out[BMO_ZERNIKE_STATUS] = (double)status;
+    if (status != 0) {
+        for (int q = 0; q < J; ++q) cf[q] = knan();
+        return;
+    }
+    const double* b = G + J * (J + 1) / 2;
+    for (int i = 0; i < J; ++i) {
+        const double* Li = L + i * (i + 1) / 2;
+        double s = b[i];
+        for (int k = 0; k < i; ++k) s = s - Li[k] * yv[k];
+        yv[i] = s / Li[i];
+    }
+    for (int i = J - 1; i >= 0; --i) {  // c overwrites y from the top
+        double s = yv[i];
+        for (int k = i + 1; k < J; ++k) s = s - L[k * (k + 1) / 2 + i] * yv[k];
+        yv[i] = s / L[i * (i + 1) / 2 + i];
+    }
+    for (int q = 0; q < J; ++q) cf[q] = yv[q];
+}
+
+// pass D of work item blockIdx.x, on the scratch column: the residual of the fit
+template <int ORDER>
+__global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
+                                                                   const double* __restrict__ coef, ZernSumD* __restrict__ partial) {
+    constexpr int J = zern_terms_of(ORDER);
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const ZernMid M = mid[W.cfg];
+    double cf[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
+    double var = 0.0, lo = kinf(), hi = -kinf(), n_out = 0.0;
+    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+        const double4 q = col[h];
+        const double x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
+        const double t = x * x + y * y;
+        double f = 0.0;
+        zern_terms<ORDER>(x, y, [&](int j, double Z) { f = j == 0 ? cf[0] * Z : f + cf[j] * Z; });
+        const double e = (q.y - M.w_mean) - f;
+        var += q.x * (e * e);
+        lo = e < lo ? e : lo;
+        hi = e > hi ? e : hi;
+        n_out += t > 1.0 ? 1.0 : 0.0;
+    }
+    ZernSumD s;
+    s.var = spot_wg_reduce(var, SpotAdd{}, sh);
+    s.lo = spot_wg_reduce(lo, SpotMin{}, sh);
+    s.hi = spot_wg_reduce(hi, SpotMax{}, sh);
+    s.n_out = spot_wg_reduce(n_out, SpotAdd{}, sh);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+__global__ void psf_zernike_residual_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const ZernSumD* __restrict__ partial,
+                                                   double* __restrict__ info) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumD) / sizeof(double))];
+    const int32_t c = (int32_t)blockIdx.x;
+    if (count[c] == 0) return;  // answered already
+    double var = 0.0, lo = kinf(), hi = -kinf(), n_out = 0.0;
+    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumD& p) {
+        var += p.var;
+        lo = p.lo < lo ? p.lo : lo;
+        hi = p.hi > hi ? p.hi : hi;
+        n_out += p.n_out;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+    const bool solved = out[BMO_ZERNIKE_STATUS] == 0.0;
+    out[BMO_ZERNIKE_FIT_RMS] = solved ? sqrt(var / out[BMO_ZERNIKE_S]) : knan();
+    out[BMO_ZERNIKE_E_LO] = solved ? lo : knan();
+    out[BMO_ZERNIKE_E_HI] = solved ? hi : knan();
+    out[BMO_ZERNIKE_N_OUT] = n_out;
+}
+
+template <int ORDER>
+static void zern_launch_gram(unsigned n_items, hipStream_t st, const double4* col, const SplitWork* work, const ZernMid* mid, double* partial) {
+    hipLaunchKernelGGL(psf_zernike_gram_kernel<ORDER>, dim3(n_items), dim3(256), 0, st, col, work, mid, partial);
+}
+template <int ORDER>
+static void zern_launch_residual(unsigned n_items, hipStream_t st, const double4* col, const SplitWork* work, const ZernMid* mid, const double* coef, ZernSumD* partial) {
+    hipLaunchKernelGGL(psf_zernike_residual_kernel<ORDER>, dim3(n_items), dim3(256), 0, st, col, work, mid, coef, partial);
+}
+
+}  // namespace
+
+// what a configuration without rows reads: N = 0, STATUS = 1, NaN elsewhere
+static void psf_zernike_empty(int32_t n_configs, int32_t J, double* coef, double* info, double* gram) {
+    const size_t E = (size_t)(J + 1) * (J + 2) / 2;
+    std::fill(coef, coef + (size_t)n_configs * J, std::nan(""));
+    if (gram) std::fill(gram, gram + (size_t)n_configs * E, std::nan(""));
+    for (int32_t c = 0; c < n_configs; ++c) {
+        double* out = info + (size_t)c * BMO_ZERNIKE_INFO_N;
+        std::fill(out, out + BMO_ZERNIKE_INFO_N, std::nan(""));
+        out[BMO_ZERNIKE_N_ROWS] = 0.0;
+        out[BMO_ZERNIKE_STATUS] = 1.0;
+    }
+}
+
+// order in range and every given pupil (U0, V0, RHO) usable
+static bool psf_zernike_args_ok(const double* pupil, int32_t n_configs, int32_t order) {
+    if (order < 0 || order > BMO_ZERNIKE_MAX_ORDER) return false;
+    for (int32_t c = 0; pupil && c < n_configs; ++c) {
+        const double* q = pupil + 3 * c;
+        if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || !(q[2] > 0)) return false;
+    }
+    return true;
+}
+
+// The fits of the K configurations from the n_rows device rows `hits` [..][9]: poses [K][3], ref_xz nullptr or [K][2], pupil nullptr or [K][3];
+// coef [K][J], info [K][BMO_ZERNIKE_INFO_N], gram nullptr or [K][(J + 1)(J + 2) / 2].
+static int psf_zernike_read(const double* hits, int64_t n_rows, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* ref_xz,
+                            const double* pupil, int32_t order, double* coef, double* info, double* gram, double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    const int32_t J = zern_terms_of(order);
+    const size_t E = (size_t)(J + 1) * (J + 2) / 2;
+    hipStream_t st = 0;
+    const SplitPlan plan = spot_plan(R);
+    unsigned n_items = 0;
+    if (int rc = spot_items(plan, who, n_items)) return rc;
+    std::vector<PsfPose> pose(K);
+    for (size_t c = 0; c < K; ++c) {
+        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
+        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
+    }
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(pose);
+    const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0, o_pupil = pupil ? up.add(pupil, 3 * K) : 0;
+    DevBuf pa, pb, pc, pd, d_info, d_coef, d_gram, d_mid, d_col;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = pa.alloc((size_t)n_items * sizeof(ZernSumA))) || (rc = pb.alloc((size_t)n_items * sizeof(ZernSumB))) ||
+        (rc = pc.alloc((size_t)n_items * E * 8)) || (rc = pd.alloc((size_t)n_items * sizeof(ZernSumD))) || (rc = d_info.alloc(K * BMO_ZERNIKE_INFO_N * 8)) ||
+        (rc = d_coef.alloc(K * (size_t)J * 8)) || (gram && (rc = d_gram.alloc(K * E * 8))) || (rc = d_mid.alloc(K * sizeof(ZernMid))) ||
+        (rc = d_col.alloc((size_t)n_rows * sizeof(double4))))
+        return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    const dim3 kb((unsigned)K);  // the reduces: one workgroup per configuration
+    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
+    const SplitWork* d_work = up.at<SplitWork>(o_work);
+    const int64_t* d_count = up.at<int64_t>(o_count);
+    const PsfPose* d_pose = up.at<PsfPose>(o_pose);
+    const double* d_pupil = pupil ? up.at<double>(o_pupil) : (const double*)nullptr;
+    double* const g_info = (double*)d_info.p;
+    ZernMid* const g_mid = (ZernMid*)d_mid.p;
+    double4* const g_col = (double4*)d_col.p;
+    if (n_items > 0) hipLaunchKernelGGL(psf_zernike_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (ZernSumA*)pa.p);
+    hipLaunchKernelGGL(psf_zernike_sums_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, d_pupil,
+                       (const ZernSumA*)pa.p, g_info, g_mid);
+    if (n_items > 0) hipLaunchKernelGGL(psf_zernike_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const ZernMid*)g_mid, g_col, (ZernSumB*)pb.p);
+    hipLaunchKernelGGL(psf_zernike_wave_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pupil, (const ZernSumB*)pb.p, g_info, g_mid);
+    if (n_items > 0) {
+        void (*const launch[])(unsigned, hipStream_t, const double4*, const SplitWork*, const ZernMid*, double*) = {
+            zern_launch_gram<0>, zern_launch_gram<1>, zern_launch_gram<2>, zern_launch_gram<3>, zern_launch_gram<4>, zern_launch_gram<5>, zern_launch_gram<6>};
+        launch[order](n_items, st, g_col, d_work, g_mid, (double*)pc.p);
+    }
+    hipLaunchKernelGGL(psf_zernike_gram_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, J, (const double*)pc.p, g_info, (double*)d_coef.p,
+                       gram ? (double*)d_gram.p : (double*)nullptr);
+    if (n_items > 0) {
+        void (*const launch[])(unsigned, hipStream_t, const double4*, const SplitWork*, const ZernMid*, const double*, ZernSumD*) = {
+            zern_launch_residual<0>, zern_launch_residual<1>, zern_launch_residual<2>, zern_launch_residual<3>,
+            zern_launch_residual<4>, zern_launch_residual<5>, zern_launch_residual<6>};
+        launch[order](n_items, st, g_col, d_work, g_mid, (const double*)d_coef.p, (ZernSumD*)pd.p);
+    }
+    hipLaunchKernelGGL(psf_zernike_residual_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const ZernSumD*)pd.p, g_info);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(info, d_info.p, K * BMO_ZERNIKE_INFO_N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(coef, d_coef.p, K * (size_t)J * 8, hipMemcpyDeviceToHost));
+    if (gram) HIP_TRY(hipMemcpy(gram, d_gram.p, K * E * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_zernike(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                               const double* ref_xz, const double* pupil, int32_t order, int32_t device, double* coef, double* info, double* gram,
+                               double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !coef || !info || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_zernike: bad argument (null pointer, n_hits < 0)");
+    if (!psf_zernike_args_ok(pupil, 1, order))
+        return fail(BMO_ERR_INVALID, "bmo_psf_zernike: order must be 0 .. 6, a given pupil (U0, V0, RHO) finite with RHO > 0");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = spot_single_rows("bmo_psf_zernike", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    return psf_zernike_read(hits, n_hits, Ranges{{0}, {n_hits}}, origin, e1, e2, ref_xz, pupil, order, coef, info, gram, kernel_ms, "bmo_psf_zernike");
+}
+
+extern "C" int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                     const double* ref_xz, const double* pupil, int32_t order, double* coef, double* info, double* gram, double* kernel_ms) {
+    if (!res || !origins || !e1s || !e2s || !coef || !info) return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: bad detector slot");
+    if (res->kind == BMO_BEAM_GAUSSIAN)
+        return fail(BMO_ERR_UNSUPPORTED, "bmo_psf_zernike_sweep: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
+        return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: the slot is not a PSFDetector's");
+    if (n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (!psf_zernike_args_ok(pupil, n_configs, order))
+        return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: order must be 0 .. 6, every given pupil (U0, V0, RHO) finite with RHO > 0");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        psf_zernike_empty(n_configs, zern_terms_of(order), coef, info, gram);
+        return BMO_OK;
+    }
+    HIP_TRY(hipSetDevice(res->device));
+    Ranges R;
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_zernike_sweep: rows out of configuration order", 0, R)) return rc;
+    return psf_zernike_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, info, gram, kernel_ms,
+                            "bmo_psf_zernike_sweep");
+}

@@ -480,6 +480,13 @@ class EngineSolution:
         st, self.readout_ms = abi.psf_stats_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], ref=ref)
         return st[0]
 
+    def psf_zernike(self, slot, position, orientation, order=4, ref=None, pupil=None):
+        """bmo_psf_zernike_sweep on the resident rows of PSFDetector slot `slot` at the pose (position, orientation): (coef [J], info [13] at
+        the abi.ZERN_* columns) of the Zernike fit of the wavefront, as PSFDetector.zernike gives them from host rows."""
+        o = np.asarray(orientation, dtype=np.float64)
+        coef, info, _, self.readout_ms = abi.psf_zernike_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil)
+        return coef[0], info[0]
+
     def psf_intensity(self, slot, position, orientation, n=100, **window_kw):
         """intensity(psf; ...) of the resident rows of PSFDetector slot `slot`: (xs, zs, I[n, n]).  The window comes from psf_stats
         (components.psf_axes_from_stats takes window_kw), the image from bmo_psf_intensity_sweep: only the image leaves the device."""
@@ -887,6 +894,19 @@ class SweepSolution:
         ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
         st, self.readout_ms = abi.psf_stats_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], ref=ref)
         return st
+
+    def psf_zernike(self, det, order=4, ref=None, pupil=None, want_gram=False):
+        """The Zernike fit of the wavefront of PSFDetector `det` in every configuration, in one batched read-out (bmo_psf_zernike_sweep) at
+        each configuration's detector pose: (coef [n_cfg, J], info [n_cfg, 13] at the abi.ZERN_* columns), with want_gram also the packed
+        normal equations [n_cfg, E].  ref: None, one (x, z) or [n_cfg, 2]; pupil: None, one (U0, V0, RHO) or [n_cfg, 3].  Row c equals
+        abi.psf_zernike on detector_hits(det, c) bit for bit; a configuration without rows reads N = 0, STATUS = 1 and NaN."""
+        slot = self._slot(det)
+        K = self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
+        coef, info, gram, self.readout_ms = abi.psf_zernike_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], order=order, ref=ref, pupil=pupil,
+                                                                  want_gram=want_gram)
+        return (coef, info, gram) if want_gram else (coef, info)
 
     def spot_stats(self, det):
         """The spot statistics [n_cfg, 12] (abi.SPOT_* columns) of Spotdetector `det` in every configuration, in one batched read-out

@@ -604,6 +604,72 @@ int bmo_psf_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, co
 int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
                         const double* e2s, const double* ref_xz, double* stats, double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Zernike read-out: the least-squares Zernike coefficients of a PSFDetector's wavefront, computed on the device from the rows where they
+ * lie: how much of the wavefront error of bmo_psf_stats is tilt, defocus, astigmatism, coma or spherical aberration.
+ *
+ * hits, origin, e1, e2, ref_xz, the _sweep form and its conventions: exactly those of bmo_psf_stats.
+ * order : the highest radial order, 0 .. BMO_ZERNIKE_MAX_ORDER; J = (order + 1)(order + 2) / 2 terms (28 at most).
+ * pupil : NULL or (U0, V0, RHO), [3] (the _sweep form: [n_configs][3]): centre and radius of the pupil in direction cosines.
+ * coef  : [n_configs][J], metres.   info : [n_configs][BMO_ZERNIKE_INFO_N] at the BMO_ZERNIKE_* indices.
+ * gram  : NULL or [n_configs][(J + 1)(J + 2) / 2], the packed lower triangle (row-major: entry (i, k), i >= k, at i (i + 1) / 2 + k) of the
+ *         augmented normal equations below.
+ * Everything is FP64, each expression evaluated left to right as written, without contraction, h running over the rows:
+ *   X_REF, Z_REF, p, W_h, S, W_MEAN: as bmo_psf_stats defines them, the same expressions in the same blocked order: equal bit for bit.
+ *   u_h = (dx * e1x + dy * e1y) + dz * e1z,   v_h the same with e2                  (the row's direction cosines in the detector frame)
+ *   (U0, V0, RHO) = pupil, or U0 = (sum proj_h * u_h) / S,  V0 = (sum proj_h * v_h) / S,
+ *                             RHO = sqrt(max_h ((u_h - U0) * (u_h - U0) + (v_h - V0) * (v_h - V0)))        about the computed centre
+ *   x_h = (u_h - U0) / RHO,   y_h = (v_h - V0) / RHO,   t_h = x_h * x_h + y_h * y_h;   N_OUT = the rows with t_h > 1 (they are still fitted)
+ *   Terms in OSA/ANSI order, j = (n (n + 2) + m) / 2 for n = 0 .. order, m = -n, -n + 2, .., n, in Cartesian form with +, -, * only:
+ *     C_0 = 1, S_0 = 0, C_{k+1} = C_k * x - S_k * y, S_{k+1} = S_k * x + C_k * y                          (rho^k cos k theta, rho^k sin k theta)
+ *     q_s, s = 0 .. K = (n - |m|) / 2: the integer coefficients of R_n^|m|(rho) / rho^|m| as a polynomial in t,
+ *       q_s = (-1)^(K - s) (n - K + s)! / ((K - s)! ((n + |m|) / 2 - K + s)! s!);   Horner from the top: r = q_K; r = r * t + q_s, s = K - 1 .. 0
+ *     Z_j = N * (r * A),  A = C_|m| for m >= 0 and S_|m| for m < 0,  N = sqrt((double)(n + 1)) for m = 0 and sqrt((double)(2 (n + 1)))
+ *     otherwise (the correctly rounded root).  Z_0 evaluates to 1; the terms are orthonormal over the uniform unit disc.
+ *   D_h = W_h - W_MEAN.  The fit minimises sum proj_h (D_h - sum_j c_j Z_j(x_h, y_h))^2.
+ *   Augmented columns B_0 .. B_{J-1} = Z_j, B_J = D;  G_ik = sum_h (proj_h * B_i) * B_k for i >= k: the last row of `gram` holds the right
+ *   hand side b_j = G_Jj and sum proj D^2.  Each entry's sum runs over the rows of a split in row order, the splits are folded in split
+ *   order (the splits of bmo_spot_stats): a fixed order that depends on the row count only.
+ *   Solve, a plain Cholesky factorisation G = L L^T of the J x J block, then two substitutions (sqrt and / IEEE):
+ *     for j = 0 .. J-1:  d = G_jj;  for k = 0 .. j-1: d = d - L_jk * L_jk;   STATUS = 2 unless d > 0;   L_jj = sqrt(d);
+ *                        for i = j+1 .. J-1:  s = G_ij;  for k = 0 .. j-1: s = s - L_ik * L_jk;   L_ij = s / L_jj
+ *     for i = 0 .. J-1:  s = b_i;  for k = 0 .. i-1: s = s - L_ik * y_k;   y_i = s / L_ii
+ *     for i = J-1 .. 0:  s = y_i;  for k = i+1 .. J-1: s = s - L_ki * c_k;   c_i = s / L_ii
+ *   STATUS = 1, without solving, if N < J or RHO is zero or not finite; STATUS = 2 if a pivot is not > 0; for either, coef, FIT_RMS, E_LO
+ *   and E_HI are NaN and the rest of info is still filled.
+ *   F_h = ((c_0 * Z_0 + c_1 * Z_1) + ...) in ascending j,   E_h = D_h - F_h,   FIT_RMS = sqrt((sum proj_h * (E_h * E_h)) / S),
+ *   E_LO = min E_h,  E_HI = max E_h.
+ * No rows: N_ROWS = 0, STATUS = 1, NaN elsewhere (coef and gram too).  Configuration c of the _sweep form equals the single call on its
+ * rows and resident rows equal host rows, bit for bit.  W_RMS is not repeated here: bmo_psf_stats has it.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than ref_xz, pupil, gram, kernel_ms; n_hits < 0; order
+ * outside 0 .. BMO_ZERNIKE_MAX_ORDER; a given RHO that is not finite and > 0; a given U0 or V0 that is not finite; a slot out of range or
+ * not a PSFDetector's; a wrong n_configs.  BMO_ERR_UNSUPPORTED: a GaussianBeamlet result.  BMO_ERR_INTERNAL, never a wrong answer, if the
+ * rows of a configuration are not consecutive.  kernel_ms: optional, HIP-event time of the launches.                                 */
+enum bmo_zernike_info {
+    BMO_ZERNIKE_N_ROWS = 0, /* N: the row count */
+    BMO_ZERNIKE_STATUS = 1, /* 0: solved, 1: not attempted, 2: a pivot was not > 0 */
+    BMO_ZERNIKE_S = 2,
+    BMO_ZERNIKE_X_REF = 3,
+    BMO_ZERNIKE_Z_REF = 4,
+    BMO_ZERNIKE_U0 = 5,
+    BMO_ZERNIKE_V0 = 6,
+    BMO_ZERNIKE_RHO = 7,
+    BMO_ZERNIKE_W_MEAN = 8,
+    BMO_ZERNIKE_FIT_RMS = 9,
+    BMO_ZERNIKE_E_LO = 10,
+    BMO_ZERNIKE_E_HI = 11,
+    BMO_ZERNIKE_N_OUT = 12
+};
+#define BMO_ZERNIKE_INFO_N 13
+#define BMO_ZERNIKE_MAX_ORDER 6
+int bmo_psf_zernike(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                    const double e2[3], const double* ref_xz, const double* pupil, int32_t order, int32_t device, double* coef,
+                    double* info, double* gram, double* kernel_ms);
+int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                          const double* e2s, const double* ref_xz, const double* pupil, int32_t order, double* coef, double* info,
+                          double* gram, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -918,3 +918,48 @@ function psf_stats(sys::GPUSystem, key, slot::Integer, psf::PSFDetector; ref = n
         res, slot, 1, origin, e1, e2, ref === nothing ? C_NULL : pointer(r), stats, C_NULL))
     return stats
 end
+
+# BMO_ZERNIKE_*: columns of the info row of the Zernike read-out (include/bmo.h "Zernike read-out"), zero-based as in the header
+const ZERNIKE_N_ROWS, ZERNIKE_STATUS, ZERNIKE_S, ZERNIKE_X_REF, ZERNIKE_Z_REF, ZERNIKE_U0, ZERNIKE_V0, ZERNIKE_RHO, ZERNIKE_W_MEAN, ZERNIKE_FIT_RMS, ZERNIKE_E_LO, ZERNIKE_E_HI, ZERNIKE_N_OUT = Int32.(0:12)
+const ZERNIKE_INFO_N = Int32(13)
+const ZERNIKE_MAX_ORDER = Int32(6)
+
+"""
+    psf_zernike(sys::GPUSystem, psf::PSFDetector; order = 4, ref = nothing, pupil = nothing, device = 0)
+    psf_zernike(sys::GPUSystem, key, slot::Integer, psf::PSFDetector; order = 4, ref = nothing, pupil = nothing)
+
+The least-squares Zernike coefficients (OSA/ANSI order, metres) of the wavefront of a PSFDetector's rows (`bmo_psf_zernike`) and the info
+row (index `ZERNIKE_* + 1`), about `ref = (x, z)` in detector-local coordinates (`nothing`: the centroid) over the pupil
+`pupil = (U0, V0, RHO)` in direction cosines (`nothing`: the rows' own centre and largest radius).  The first form reads the rows
+accumulated in `psf.data`; the second the rows of detector slot `slot` still resident in the solution of the beams `key`
+(`bmo_psf_zernike_sweep` with one configuration), at the pose of `psf`.
+"""
+function psf_zernike(sys::GPUSystem, psf::PSFDetector; order::Integer = 4, ref = nothing, pupil = nothing, device::Integer = 0)
+    hits = reinterpret(Float64, psf.data)
+    R = orientation(psf)
+    origin, e1, e2 = collect(Float64, position(psf)), collect(Float64, R[:, 1]), collect(Float64, R[:, 3])
+    r = ref === nothing ? Float64[] : collect(Float64, ref)
+    q = pupil === nothing ? Float64[] : collect(Float64, pupil)
+    coef = Vector{Float64}(undef, div((order + 1) * (order + 2), 2))
+    info = Vector{Float64}(undef, ZERNIKE_INFO_N)
+    GC.@preserve hits origin e1 e2 r q coef info check(ccall((:bmo_psf_zernike, LIBBMO), Cint,
+        (Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        pointer(hits), length(psf.data), 0, origin, e1, e2, ref === nothing ? C_NULL : pointer(r), pupil === nothing ? C_NULL : pointer(q), order, device, coef, info,
+        C_NULL, C_NULL))
+    return coef, info
+end
+
+function psf_zernike(sys::GPUSystem, key, slot::Integer, psf::PSFDetector; order::Integer = 4, ref = nothing, pupil = nothing)
+    res = get(sys.solved, key, C_NULL)
+    res == C_NULL && error("psf_zernike: these beams have no resident solution")
+    R = orientation(psf)
+    origin, e1, e2 = collect(Float64, position(psf)), collect(Float64, R[:, 1]), collect(Float64, R[:, 3])
+    r = ref === nothing ? Float64[] : collect(Float64, ref)
+    q = pupil === nothing ? Float64[] : collect(Float64, pupil)
+    coef = Vector{Float64}(undef, div((order + 1) * (order + 2), 2))
+    info = Vector{Float64}(undef, ZERNIKE_INFO_N)
+    GC.@preserve origin e1 e2 r q coef info check(ccall((:bmo_psf_zernike_sweep, LIBBMO), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        res, slot, 1, origin, e1, e2, ref === nothing ? C_NULL : pointer(r), pupil === nothing ? C_NULL : pointer(q), order, coef, info, C_NULL, C_NULL))
+    return coef, info
+end
