@@ -86,8 +86,10 @@ def test_empty_batch(engine_ok, oracle):
 
 # Rounds 1 - 3 compared polarized / Gaussian traces at north_star's 1e-10: acos / sin / cos (Fresnel, P-matrix) and tan / acos / atan
 # (gauss_parameters) came from ocml on the device and glibc in the oracle.  Round 4: both sides evaluate Julia Base's own algorithms
-# (csrc/bmo_jlmath.hpp, oracle/jl_trig.hpp), so the tolerance of a trace is zero for every beam kind.  (The read-outs — PSF, Photodetector
-# field — still call sincos / exp of the platform's library on phases of 10^5 rad and keep 1e-10.)
+# (csrc/bmo_jlmath.hpp, oracle/jl_trig.hpp), so the tolerance of a trace is zero for every beam kind, gauss_parameters included.  (The read-outs
+# — PSF, Photodetector field — still call sincos / exp of the platform's library on phases of 10^5 rad; they are held to the oracle by derived
+# bounds in ulp of the sum of the terms' moduli, beside older checks at 1e-9 of the peak: psf_engine_bound in tests/readout_ref.py, TAIL_ULPS in
+# tests/test_photodetector.py, and to 40- / 50-digit evaluations by tests/test_readout_reference.py and tests/test_pd_field_reference.py.)
 LIBM_RTOL = 0.0
 
 
@@ -342,10 +344,7 @@ def test_full_size_properties(engine_ok, oracle, kind):
             lo, cnt = int(full.det_offset[slot]), int(full.det_count[slot])
             roots_of_hits = full.node_root[full.det_node[lo:lo + cnt]]
             mine, theirs = full.detector_hits(slot)[np.isin(roots_of_hits, idx)], ref.detector_hits(slot)
-            if kind == "ray":
-                assert np.array_equal(mine, theirs), slot
-            else:
-                assert mine.shape == theirs.shape and np.allclose(mine, theirs, rtol=1e-10, atol=0), slot
+            assert mine.shape == theirs.shape and np.array_equal(mine, theirs), (kind, slot)  # the same doubles for either kind
     finally:
         eng.close()
 
