@@ -1,0 +1,825 @@
+"""The scenes of tests/test_trace_reference.py and tests/test_trace_reference_gpu.py, and the comparison both make (not a test file).
+
+A scene is written twice from the same prescription: once for the host mirror (bmo objects, what oracle, emulator and engine trace) and once
+for the exact evaluator of tests/trace_ref.py, which gets the prescription's numbers and the pose doubles position() / orientation() of each
+object and nothing else of the host's scene."""
+import dataclasses
+import math
+
+import numpy as np
+
+import bmo_amd as bmo
+import trace_ref as tr
+
+mm = 1e-3
+R_MAX = 30
+
+
+@dataclasses.dataclass
+class Case:
+    """What a scene carries.  The builders fill the first block, compile_case the second, the tests the third."""
+
+    name: str = ""
+    system: object = None      # bmo.System: what oracle, emulator and engine trace
+    exact: list = None         # the same objects for tests/trace_ref.py, in the order of the system's leaves
+    bundle: object = None      # bmo.RayBundle
+    lens: object = None        # the singlet / asphere scenes' lens (the retrace test moves it)
+    det: object = None
+
+    scene: object = None       # bmo.CompiledScene
+    consts: dict = None        # the march constants of the compiled scene
+    shape_part: dict = None    # shape id of the record -> part of its doublet
+
+    res: object = None         # the oracle's TraceResult
+    cache: dict = None         # exact evaluation and bound per bounce of res
+    held: object = None        # Held of res
+    small: object = None       # the bundle before widen()
+
+    __hash__ = object.__hash__
+
+
+# ------------------------------------------------------------------------------------------------ ray fans
+def _frame(axis):
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    e1 = np.cross(a, [0.0, 0.0, 1.0] if abs(a[2]) < 0.9 else [1.0, 0.0, 0.0])
+    e1 /= np.linalg.norm(e1)
+    return a, e1, np.cross(a, e1)
+
+
+def ring(center, axis, radius, n, back=30 * mm, phase=0.1, slope=0.0):
+    """n rays through a ring of `radius` about `center`, starting `back` before it along their own direction; slope tilts each ray outwards
+    (the tangent of its angle to the axis)."""
+    a, e1, e2 = _frame(axis)
+    phi = phase + 2 * math.pi * np.arange(n) / n
+    rad = np.cos(phi)[:, None] * e1 + np.sin(phi)[:, None] * e2
+    d = a[None, :] + slope * rad
+    d = d / np.linalg.norm(d, axis=1)[:, None]
+    return np.asarray(center) + radius * rad - back * d, d
+
+
+def disc(center, direction, diameter, n, back=30 * mm):
+    """A Fibonacci disc of n parallel rays (BeamGroups.jl:232-243) through `center`."""
+    a, e1, e2 = _frame(direction)
+    k = np.arange(n)
+    r = diameter / 2 * np.sqrt((k + 0.5) / n)
+    phi = k * (2 * math.pi / (1 + math.sqrt(5)))
+    pos = np.asarray(center) + (r * np.cos(phi))[:, None] * e1 + (r * np.sin(phi))[:, None] * e2 - back * a
+    return pos, np.tile(a, (n, 1))
+
+
+def bundle(kind, pos, dirs, lam=1.064e-6):
+    pos, dirs = np.vstack(pos), np.vstack(dirs)
+    b = bmo.RayBundle.rays(pos, dirs, lam)
+    if kind == "ray":
+        return b
+    d = b.planes[3:6].T
+    E = np.tile(np.array([1.0, 0.2, 0.5]), (b.n, 1))
+    for _ in range(3):  # Gram-Schmidt against the direction, to 1e-16 (PolarizedRays.jl:54: orthogonal to 1e-14)
+        E = E - (E * d).sum(axis=1)[:, None] * d
+    E = E / np.linalg.norm(E, axis=1)[:, None]
+    P = np.zeros((14, b.n))
+    P[:8] = b.planes
+    P[8:14:2] = E.T
+    P[9:14:2] = 0.3 * np.cross(d, E).T  # an elliptical state: Im(E0) = 0.3 dir x Re(E0), orthogonal to dir as well
+    return bmo.RayBundle(bmo.BEAM_POLARIZED, P)
+
+
+def gauss_bundle(pos, dirs, lam=1.064e-6, w0=50e-6, support=(1.0, 0.0, 0.0)):
+    """GaussianBeamlet(pos, dir, lam, w0; support) per ray, as the reference's constructor builds chief, waist and divergence ray
+    (Gaussian.jl:215-256; the layout of tests/scenes.py gaussian_bundle)."""
+    b = bmo.RayBundle.rays(np.vstack(pos), np.vstack(dirs), lam)
+    p, d = b.planes[0:3].T, b.planes[3:6].T
+    s1 = np.asarray(support, dtype=np.float64)
+    tan_t = np.tan(np.asarray(lam, dtype=np.float64) / (math.pi * w0)) * np.ones(b.n)
+    dd = d + s1[None, :] * tan_t[:, None]
+    dd = dd / np.sqrt((dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]) + dd[:, 2] * dd[:, 2])[:, None]
+    P = np.zeros((25, b.n))
+    P[0:3], P[3:6] = p.T, d.T
+    P[6:9], P[9:12] = (p + s1[None, :] * w0).T, d.T
+    P[12:15], P[15:18] = p.T, dd.T
+    P[18], P[19], P[20] = lam, 1.0, w0
+    P[21] = math.sqrt(2 * (2 * 1e-3 / (math.pi * w0 ** 2)) * bmo.linalg.Z_vacuum)
+    return bmo.RayBundle(bmo.BEAM_GAUSSIAN, P)
+
+
+def widen(b, n):
+    """The case's bundle repeated with small deterministic offsets up to n rays (the GPU tests' 1 024)."""
+    reps = -(-n // b.n)
+    P = np.tile(b.planes, (1, reps))[:, :n].copy()
+    k = np.arange(n) // b.n
+    for x in ((0, 6, 12) if b.kind == bmo.BEAM_GAUSSIAN else (0,)):
+        P[x] += 1.7e-6 * k
+        P[x + 2] -= 2.3e-6 * k
+    return bmo.RayBundle(b.kind, P)
+
+
+# ------------------------------------------------------------------------------------------------ scene 1: biconvex singlet
+S1 = dict(r1=40 * mm, r2=-60 * mm, l=4 * mm, d=25.4 * mm, n=1.6)
+
+
+def singlet(kind="ray", planted=None, move=None):
+    """SphericalLens(40 mm, -60 mm, 4 mm, 25.4 mm, 1.6) tilted 7 degrees about x and decentred 1.5 mm, a PSFDetector 60 mm behind it.  Rays: a
+    12 degree oblique disc over 0.9 of the aperture, two rays on the lens's own axis (the apex tie), rings at 0.5 and 0.99 of the clear aperture
+    along the axis, and a steep outward ring that enters through the face and meets the barrel from inside."""
+    c = Case()
+    lens = bmo.SphericalLens(S1["r1"], S1["r2"], S1["l"], S1["d"], S1["n"])
+    bmo.xrotate3d(lens, math.radians(7))
+    bmo.translate3d(lens, [1.5 * mm, 20 * mm, 0])
+    # a PSFDetector takes Rays only (PSFDetector.jl:77), a Spotdetector Beams only (Spotdetector.jl:50): beamlets end on a plain stop
+    det = {"ray": lambda: bmo.PSFDetector(90 * mm), "pol": lambda: bmo.Spotdetector(90 * mm),
+           "gauss": lambda: bmo.IntersectableObject(bmo.QuadraticFlatMesh(90 * mm))}[kind]()
+    dk = {"ray": "psf", "pol": "spot", "gauss": "stop"}[kind]
+    bmo.translate3d(det, [0, 80 * mm, 0])
+    if move is not None:  # the kinematic move of the retrace test
+        bmo.translate3d(lens, move[0])
+        bmo.zrotate3d(lens, move[1])
+    c.system, c.lens, c.det = bmo.System([lens, det]), lens, det
+    c.exact = [tr.ExactLens(tr.Surface(S1["r1"]), tr.Surface(S1["r2"]), S1["l"], S1["d"], lambda lam: S1["n"], lens.position(), lens.orientation(), planted),
+               tr.ExactFlat(90 * mm, det.position(), det.orientation(), dk)]
+    p0 = np.array([1.5 * mm, 20 * mm, 0.0])                 # where the un-moved lens's front vertex is: the fans do not follow a move
+    t7 = math.radians(7)
+    axis = np.array([0.0, math.cos(t7), math.sin(t7)])      # its axis: +y turned by 7 degrees about x
+    mid = p0 + 2 * mm * axis
+    ob = math.radians(12)
+    P, D = zip(disc(mid, [math.sin(ob), math.cos(ob), 0.0], 0.9 * S1["d"], 36),
+               ring(p0, axis, 0.0, 2),
+               ring(p0, axis, 0.5 * S1["d"] / 2, 8),
+               ring(p0, axis, 0.99 * S1["d"] / 2, 8, phase=0.37),
+               ring(p0 + 1.9 * mm * axis, axis, 0.985 * S1["d"] / 2, 10, back=6 * mm, phase=0.2, slope=0.8))
+    c.bundle = gauss_bundle(P[:3] + (ring(p0, axis, 0.25 * S1["d"] / 2, 2, phase=1.3)[0],), D[:3] + (ring(p0, axis, 0.25 * S1["d"] / 2, 2, phase=1.3)[1],)) if kind == "gauss" else bundle(kind, P, D)  # beamlets: without the edge rings (their three rays part there)
+    c.name = "singlet-" + kind
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 4: AL50100J asphere
+AL = dict(R=50.3583 * mm, D=50 * mm, CT=10.2 * mm, K=-0.789119, N=1.5036, A=[0, 2.10405e-7 * (1e3) ** 3, 1.76468e-11 * (1e3) ** 5, 1.02641e-15 * (1e3) ** 7])
+
+
+def asphere(flip=False, planted=None):
+    """Thorlabs AL50100J (the prescription of the reference's test, runtests.jl: radius, conic constant, A4 - A8, 50 mm, 10.2 mm), curved side
+    (flip: plane side) towards a bundle that fills 0.98 of the aperture, 3 degrees oblique."""
+    c = Case()
+    lens = bmo.Lens(bmo.EvenAsphericalSurface(AL["R"], AL["D"], AL["K"], AL["A"]), AL["CT"], lambda lam: AL["N"])
+    if flip:
+        bmo.xrotate3d(lens, math.radians(180))
+        bmo.translate3d(lens, [0, AL["CT"], 0])
+    bmo.zrotate3d(lens, math.radians(2))
+    bmo.translate3d(lens, [0.4 * mm, 30 * mm, -0.3 * mm])
+    det = bmo.PSFDetector(120 * mm)
+    bmo.translate3d(det, [0, 90 * mm, 0])
+    c.system, c.lens, c.det = bmo.System([lens, det]), lens, det
+    c.exact = [tr.ExactLens(tr.Surface(AL["R"], AL["K"], AL["A"]), tr.Surface(math.inf), AL["CT"], AL["D"], lambda lam: AL["N"], lens.position(),
+                            lens.orientation(), planted),
+               tr.ExactFlat(120 * mm, det.position(), det.orientation(), "psf")]
+    mid = np.array([0.4 * mm, 30 * mm + AL["CT"] / 2, -0.3 * mm])
+    ob = math.radians(3)
+    P, D = zip(disc(mid, [0.0, math.cos(ob), math.sin(ob)], 0.9 * AL["D"], 40, back=40 * mm),
+               ring(mid, [0, 1, 0], 0.98 * AL["D"] / 2, 8, back=40 * mm, phase=0.3),
+               ring(mid, [0, 1, 0], 0.0, 1, back=40 * mm))
+    c.bundle = bundle("ray", P, D)
+    c.name = "asphere-" + ("plane-first" if flip else "curved-first")
+    return c
+
+
+_K = 1e3
+L3 = dict(front=(3.618e-3, 3.04e-3, -44.874, [0, -0.14756 * _K ** 3, 0.035194 * _K ** 5, -0.0032262 * _K ** 7, 0.0018592 * _K ** 9, 0.00036658 * _K ** 11,
+                                              -0.00016039 * _K ** 13, -3.1846e-5 * _K ** 15]),
+          back=(2.161e-3, 3.7e-3, -10.719, [0, -0.096568 * _K ** 3, 0.026771 * _K ** 5, -0.011261 * _K ** 7, 0.0019879 * _K ** 9, 0.00015579 * _K ** 11,
+                                            -0.00012433 * _K ** 13, 1.5264e-5 * _K ** 15]),
+          ct=0.7e-3, n=1.580200)  # (radius, clear aperture, conic constant, A2 .. A16) of element L3 (runtests.jl:1581-1696; tests/test_asphere_system.py)
+
+
+L3_CREST = 0.600108e-3  # where the front profile's sag is largest (22.51 um): sag' = 0, found in the test in 50 digits
+
+
+def phone_l3(planted=None, crest=False):
+    """Element L3 of the phone objective: two even aspheres of order 16 whose profiles are INFLECTED (the sag rises to 22 um / 90 um and falls to
+    -188 um / -404 um at the edge), clear apertures 3.04 mm and 3.7 mm.  The reference closes the front leaf at its largest sag and the back
+    leaf at its edge height, and levels the step with a ring that reaches down to the front edge (Lenses.jl:234-246): the centre thickness,
+    both largest sags and both edge sags decide where every face lies.  A line can cross such a profile more than once.  Rays: a 3 degree oblique
+    disc over 0.98 of the front aperture (38 rays: none within 15 um of the crest of the front profile, which is a seam - crest=True aims there),
+    axis-parallel rays onto the ring's plane face, one on the axis."""
+    c = Case()
+    E = bmo.EvenAsphericalSurface
+    (r1, d1, k1, a1), (r2, d2, k2, a2) = L3["front"], L3["back"]
+    lens = bmo.Lens(E(r1, d1, k1, a1), E(r2, d2, k2, a2), L3["ct"], lambda lam: L3["n"])
+    bmo.xrotate3d(lens, math.radians(2))
+    bmo.translate3d(lens, [0.05 * mm, 5 * mm, -0.03 * mm])
+    det = bmo.PSFDetector(12 * mm)
+    bmo.translate3d(det, [0, 9 * mm, 0])
+    c.system, c.lens, c.det = bmo.System([lens, det]), lens, det
+    c.exact = [tr.ExactRingLens(tr.Surface(r1, k1, a1), tr.Surface(r2, k2, a2), L3["ct"], lambda lam: L3["n"], d1, d2, d1, d2, lens.position(),
+                                lens.orientation(), planted),
+               tr.ExactFlat(12 * mm, det.position(), det.orientation(), "psf")]
+    at = np.array([0.05 * mm, 5 * mm, -0.03 * mm])
+    ob = math.radians(2.5)
+    P, D = zip(disc(at, [0.0, math.cos(ob), math.sin(ob)], 0.98 * d1, 38, back=3 * mm), ring(at, [0, 1, 0], 1.7 * mm, 9, back=3 * mm, phase=0.2),
+               ring(at, [0, 1, 0], 0.0, 1, back=3 * mm))
+    # two rays across the face, 50 um and 90 um in front of the vertex plane: in through the ring's barrel, out through the falling profile, over
+    # the air in front of the central rise, in through the profile again and out of the far barrel - the line crosses the ASPHERE twice, and the
+    # inside march records one segment from barrel to barrel (AbstractSDF.jl:132-159)
+    o, p0 = np.asarray(lens.orientation()), np.asarray(lens.position())
+    P += (np.array([p0 + o @ np.array([-3 * mm, y, 0.2 * mm]) for y in (-0.05 * mm, -0.09 * mm)]),)
+    D += (np.array([o @ np.array([1.0, 0.004, 0.02]), o @ np.array([1.0, -0.003, -0.05])]),)
+    if crest:  # eight rays along the lens's own axis onto the crest of the front profile, where the leaf under the surface thins to nothing
+        o = np.asarray(lens.orientation())
+        P, D = ring(np.asarray(lens.position()), o[:, 1], L3_CREST + 0.5e-6, 8, back=3 * mm, phase=0.4)
+        P, D = [P], [D]
+    c.bundle = bundle("ray", P, D)
+    c.name = "phone-l3"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 5: cylinder and acylinder lenses
+AYL = dict(R=15.538 * mm, D=25 * mm, H=50 * mm, K=-1.0, CT=7.5 * mm, N=1.777,
+           A=[0, 1.1926075e-5 * (1e3) ** 3, -2.9323497e-9 * (1e3) ** 5, -1.8718889e-11 * (1e3) ** 7, -1.7009961e-14 * (1e3) ** 9,
+              3.5481542e-17 * (1e3) ** 11, 6.5241296e-20 * (1e3) ** 13])  # Thorlabs AYL2520 (runtests.jl:1744-1785)
+
+
+def cylinders(acyl=False, planted=None):
+    """A convex cylinder lens (R = 30 mm) and a concave one (R = -40 mm) rolled 20 degrees about the beam, 40 mm x 40 mm; or the AYL2520
+    acylinder, convex, and concave rolled 35 degrees.  The bundle fills the long (uncurved) axis of the first lens to 0.98; the second lens is
+    rolled under it, so part of the bundle meets its plane side faces, from outside and from inside (some in total internal reflection)."""
+    c = Case()
+    if acyl:
+        q = AYL
+        mk = lambda sgn, n: bmo.Lens(bmo.AcylindricalSurface(sgn * q["R"], q["D"], q["H"], q["K"], q["A"]), q["CT"], lambda lam: n)
+        ex = lambda o, sgn, n: tr.ExactCylLens(tr.Surface(sgn * q["R"], q["K"], q["A"]), tr.Surface(math.inf), q["CT"], q["D"], q["H"], lambda lam: n,
+                                               o.position(), o.orientation(), planted)
+        l1, l2, n1, n2, roll, gap, d, hgt = mk(1, 1.777), mk(-1, 1.6), 1.777, 1.6, 35, 20 * mm, q["D"], q["H"]
+    else:
+        mk = lambda r, ct, n: bmo.Lens(bmo.CylindricalSurface(r, 40 * mm, 40 * mm), ct, lambda lam: n)
+        l1, l2, n1, n2, roll, gap, d, hgt = mk(30 * mm, 8 * mm, 1.517), mk(-40 * mm, 4 * mm, 1.6), 1.517, 1.6, 20, 25 * mm, 40 * mm, 40 * mm
+    bmo.xrotate3d(l1, math.radians(2))
+    bmo.translate3d(l1, [0, 30 * mm, 0])
+    bmo.translate3d(l2, [0, 30 * mm + gap, 0])
+    bmo.yrotate3d(l2, math.radians(roll))
+    det = bmo.PSFDetector(150 * mm)
+    bmo.translate3d(det, [0, 120 * mm, 0])
+    c.system = bmo.System([l1, l2, det])
+    if acyl:
+        c.exact = [ex(l1, 1, n1), ex(l2, -1, n2)]
+    else:
+        cyl = lambda o, r, ct, n: tr.ExactCylLens(tr.Surface(r), tr.Surface(math.inf), ct, 40 * mm, 40 * mm, lambda lam: n, o.position(), o.orientation(), planted)
+        c.exact = [cyl(l1, 30 * mm, 8 * mm, n1), cyl(l2, -40 * mm, 4 * mm, n2)]
+    c.exact.append(tr.ExactFlat(150 * mm, det.position(), det.orientation(), "psf"))
+    at = np.array([0.0, 30 * mm, 0.0])
+    k = np.arange(48)
+    x = 0.98 * hgt / 2 * np.cos(k * 2.399963)  # the long axis is x: filled to 0.98
+    z = 0.9 * d / 2 * np.sqrt((k + 0.5) / 48) * np.sin(k * 2.399963) * (0.5 if acyl else 0.6)  # the concave second lens is rolled: stay inside it
+    P = at + np.stack([x, np.full(48, -30 * mm), z], axis=1)
+    D = np.tile(np.array([0.004, 1.0, -0.006]), (48, 1))
+    c.bundle = bundle("ray", [P], [D])
+    c.name = "acylinders" if acyl else "cylinders"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 6: a block of glass
+def block(kind="ray", planted=None):
+    """Lens(BoxSDF(12 mm, 6 mm, 10 mm), 1.52) tilted 17 / -8 degrees: flat faces only, where the march may end on or inside the surface and the
+    normal fall back to central differences; a steep ring meets the side faces from inside beyond the critical angle."""
+    c = Case()
+    box = bmo.Lens(bmo.BoxSDF(12 * mm, 6 * mm, 10 * mm), lambda lam: 1.52)
+    bmo.xrotate3d(box, math.radians(17))
+    bmo.zrotate3d(box, math.radians(-8))
+    bmo.translate3d(box, [0.2 * mm, 30 * mm, -0.1 * mm])
+    det = bmo.PSFDetector(150 * mm) if kind == "ray" else bmo.Spotdetector(150 * mm)
+    bmo.translate3d(det, [0, 70 * mm, 0])
+    c.system = bmo.System([box, det])
+    c.exact = [tr.ExactBox(12 * mm, 6 * mm, 10 * mm, lambda lam: 1.52, box.position(), box.orientation()),
+               tr.ExactFlat(150 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    at = np.array([0.2 * mm, 30 * mm, -0.1 * mm])
+    P, D = zip(disc(at, [0.03, 1.0, -0.02], 7 * mm, 40), ring(at - [0, 3 * mm, 0], [0, 1, 0], 3.4 * mm, 12, back=10 * mm, phase=0.3, slope=0.9))
+    c.bundle = bundle(kind, P, D)
+    c.name = "block-" + kind
+    return c
+
+
+def prism(kind="ray", planted=None):
+    """RightAnglePrism(20 mm, 15 mm, 1.5) used in total internal reflection: the bundle enters through the leg x = -10 mm, meets the hypotenuse
+    at about 45 degrees (beyond the critical angle of 41.8), and leaves through the other leg; the prism is tilted 3 / -2 degrees."""
+    c = Case()
+    pr = bmo.RightAnglePrism(20 * mm, 15 * mm, lambda lam: 1.5)
+    bmo.zrotate3d(pr, math.radians(3))
+    bmo.xrotate3d(pr, math.radians(-2))
+    bmo.translate3d(pr, [40 * mm, 1 * mm, -0.5 * mm])
+    det = bmo.PSFDetector(80 * mm) if kind == "ray" else bmo.Spotdetector(80 * mm)
+    bmo.translate3d(det, [37 * mm, -40 * mm, 0])
+    c.system = bmo.System([pr, det])
+    c.exact = [tr.ExactPrism(20 * mm, 15 * mm, lambda lam: 1.5, pr.position(), pr.orientation()),
+               tr.ExactFlat(80 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    at = np.array([30 * mm, -2.5 * mm, -0.5 * mm])
+    P, D = zip(disc(at, [1.0, 0.02, -0.01], 5 * mm, 40), ring(at, [1, 0, 0], 1.5 * mm, 8, slope=0.06))
+    c.bundle = bundle(kind, P, D)
+    c.name = "prism-" + kind
+    return c
+
+
+RHOMB = dict(x=0.5, y=1.25, z=0.5, theta=math.radians(53.3), n=1.5, shift=[-0.25, 0, -0.25], roll=math.radians(135))
+
+
+def rhomb(planted=None):
+    """The Fresnel rhomb of the reference's test (runtests.jl:2339-2362): Lens(CuboidMesh(0.5, 1.25, 0.5, 53.3 degrees), 1.5), a mesh of glass,
+    rolled 135 degrees so that a field along z enters at 45 degrees to the plane of the two total internal reflections: complex rs / rp on flat
+    mesh faces, and a known answer - the field that leaves is circular, arg(Ez) - arg(Ex) = pi / 2."""
+    c = Case()
+    q = RHOMB
+    s1 = bmo.CuboidMesh(q["x"], q["y"], q["z"], q["theta"])
+    l1 = bmo.Lens(s1, lambda lam: q["n"])
+    bmo.translate3d(l1, q["shift"])
+    bmo.set_new_origin3d(s1)
+    bmo.yrotate3d(l1, q["roll"])
+    c.system = bmo.System([l1])
+    c.exact = [tr.ExactMesh.cuboid(q["x"], q["y"], q["z"], q["theta"], q["shift"], l1.position(), l1.orientation(), lambda lam: q["n"])]
+    at = np.array([0.0, 0.0, 0.0])
+    P, D = zip(ring(at, [0, 1, 0], 0.0, 1, back=1.0), disc(at, [0.0, 1.0, 0.0], 0.2, 39, back=1.0), ring(at, [0, 1, 0], 0.05, 8, back=1.0, slope=0.01))
+    pos, dirs = np.vstack(P), np.vstack(D)
+    b = bmo.RayBundle.rays(pos, dirs, 1000e-9)
+    Pl = np.zeros((14, b.n))
+    Pl[:8] = b.planes
+    E = np.tile(np.array([0.0, 0.0, 1.0]), (b.n, 1))  # [0, 0, electric_field(1)] up to its modulus; made orthogonal to the oblique rays
+    d = b.planes[3:6].T
+    for _ in range(3):
+        E = E - (E * d).sum(axis=1)[:, None] * d
+    Pl[8:14:2] = E.T
+    c.bundle = bmo.RayBundle(bmo.BEAM_POLARIZED, Pl)
+    c.name = "rhomb"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 9: the miniscope's first three elements
+MS = dict(n={532e-9: 1.5195, 1064e-9: 1.5066},  # N-BK7 at the two wavelengths of the train's table
+          l1=(math.inf, -1.448 * mm, 1.3 * mm, 2.288 * mm),
+          # (r_front, d_front, md_front, r_back, d_back, md_back, centre thickness) of the four lenses of the two cemented doublets
+          dl11=(38.184 * mm, 3.68 * mm, 4.76 * mm, 3.467 * mm, 4.12 * mm, 4.76 * mm, 0.5 * mm),
+          dl12=(3.467 * mm, 4.12 * mm, 4.76 * mm, -5.020 * mm, 4.76 * mm, 4.76 * mm, 2.5 * mm),
+          dl21=(7.744 * mm, 5.624 * mm, 6 * mm, -3.642 * mm, 6 * mm, 6 * mm, 3.4 * mm),
+          dl22=(-3.642 * mm, 6 * mm, 6 * mm, -14.413 * mm, 5.624 * mm, 6 * mm, 1.0 * mm))
+
+
+def miniscope(planted=None):
+    """The first three elements of the miniscope train of tests/scenes.py (objective lens, two cemented doublets whose four lenses have unequal
+    clear apertures and mechanical rings: five lenses, ten surface crossings), turned onto the z axis as there, and a PSFDetector behind them.
+    Rays leave an object point field 0.77 mm in front of the first face in cones of up to 0.14 rad.  Rays only: the reference's DoubletLens has an
+    interact3d method for Beam{T, Ray} alone (DoubletLenses.jl:66), so a PolarizedRay cannot pass the two doublets of this train."""
+    from scenes import miniscope_objects
+
+    c = Case()
+    group = miniscope_objects()[0]
+    o1, d1, d2 = group.objects
+    det = bmo.PSFDetector(8 * mm)
+    bmo.xrotate3d(det, math.radians(90))
+    bmo.translate3d(det, [0, 0, 17 * mm])
+    c.system = bmo.System([o1, d1, d2, det])
+    n = lambda lam: MS["n"][lam]
+    rl = lambda o, q: tr.ExactRingLens(tr.Surface(q[0]), tr.Surface(q[3]), q[6], n, q[1], q[4], q[2], q[5], o.position(), o.orientation())
+    q = MS["l1"]
+    c.exact = [tr.ExactLens(tr.Surface(q[0]), tr.Surface(q[1]), q[2], q[3], n, o1.position(), o1.orientation()),
+               tr.ExactParts([rl(d1.front, MS["dl11"]), rl(d1.back, MS["dl12"])]),
+               tr.ExactParts([rl(d2.front, MS["dl21"]), rl(d2.back, MS["dl22"])]),
+               tr.ExactFlat(8 * mm, det.position(), det.orientation(), "psf")]
+    P, D = [], []
+    for k, (x, z) in enumerate(((0.0, 0.0), (0.1 * mm, 0.0), (-0.07 * mm, 0.08 * mm), (0.03 * mm, -0.12 * mm))):
+        for slope, cnt in ((0.0, 1), (0.07, 5), (0.14, 6)) if k else ((0.0, 1), (0.05, 5), (0.12, 6)):
+            p, d = ring([x, z, -0.77 * mm], [0, 0, 1], 0.0, cnt, back=0.0, phase=0.3 + k, slope=slope)
+            P.append(p)
+            D.append(d)
+    c.bundle = bundle("ray", P, D)
+    c.name = "miniscope"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 7: plane mirror, retroreflector
+def mirror(kind="ray", angle=45.0, planted=None):
+    """SquarePlanoMirror2D(120 mm) turned about x until the bundle along +y meets it at `angle` degrees from its normal (45: a fold, 85: near
+    grazing), a detector 50 mm down the reflected beam."""
+    c = Case()
+    m = bmo.SquarePlanoMirror2D(120 * mm)
+    th = math.radians(angle)
+    bmo.xrotate3d(m, th)
+    bmo.zrotate3d(m, math.radians(3))
+    bmo.translate3d(m, [0.5 * mm, 40 * mm, -0.2 * mm])
+    out = np.array([0.0, -math.cos(2 * th), -math.sin(2 * th)])  # the reflected direction before the 3 degree roll
+    det = bmo.PSFDetector(60 * mm) if kind == "ray" else bmo.Spotdetector(60 * mm)
+    bmo.xrotate3d(det, math.atan2(out[2], out[1]))
+    bmo.translate3d(det, np.array([0.5 * mm, 40 * mm, -0.2 * mm]) + 50 * mm * out)
+    c.system = bmo.System([m, det])
+    c.exact = [tr.ExactFlat(120 * mm, m.position(), m.orientation(), "mirror"),
+               tr.ExactFlat(60 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    at = np.array([0.5 * mm, 40 * mm, -0.2 * mm])
+    P, D = zip(disc(at, [0.01, 1.0, 0.005], (6 if angle < 80 else 4) * mm, 40), ring(at, [0, 1, 0], 1 * mm, 8, slope=0.02), ring(at, [0, 1, 0], 0.0, 1))
+    c.bundle = bundle(kind, P, D)
+    c.name = "mirror%g-%s" % (angle, kind)
+    return c
+
+
+def retro(kind="ray", planted=None):
+    """Retroreflector(30 mm) (the three faces of a cube corner, mesh triangles), rolled and decentred; the bundle comes down the cube diagonal,
+    1.5 mm beside the corner, bounces three times and lands on a detector behind its source."""
+    c = Case()
+    rr = bmo.Retroreflector(30 * mm)
+    bmo.zrotate3d(rr, math.radians(4))
+    bmo.xrotate3d(rr, math.radians(-3))
+    bmo.translate3d(rr, [1 * mm, 2 * mm, 0])
+    det = bmo.PSFDetector(80 * mm) if kind == "ray" else bmo.Spotdetector(80 * mm)
+    bmo.translate3d(det, [80 * mm, 80 * mm, 80 * mm])
+    c.system = bmo.System([rr, det])
+    c.exact = [tr.ExactMesh.retro(30 * mm, rr.position(), rr.orientation()),
+               tr.ExactFlat(80 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    diag = np.array([1.0, 1.0, 1.0]) / math.sqrt(3)
+    at = np.array([6 * mm, 7.5 * mm, 5 * mm])
+    P, D = zip(disc(at, -diag, 5 * mm, 40, back=40 * mm), ring(at, -diag, 1 * mm, 8, back=40 * mm, slope=0.03))
+    c.bundle = bundle(kind, P, D)
+    c.name = "retro-" + kind
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 8: thin splitter, a singlet per arm
+def splitter(kind="ray", planted=None):
+    """ThinBeamsplitter(20 mm) at 45 degrees; the transmitted arm goes on along +y through the singlet of scene 1 to a detector, the reflected
+    arm along -z through a second one.  Held: the children's first rays and fields, and every bounce of both arms."""
+    c = Case()
+    bs = bmo.ThinBeamsplitter(20 * mm)
+    bmo.xrotate3d(bs, math.radians(45))
+    bmo.translate3d(bs, [0, 30 * mm, 0])
+    lt = bmo.SphericalLens(S1["r1"], S1["r2"], S1["l"], S1["d"], S1["n"])
+    bmo.xrotate3d(lt, math.radians(2))
+    bmo.translate3d(lt, [0.3 * mm, 50 * mm, 0])
+    lr = bmo.SphericalLens(S1["r1"], S1["r2"], S1["l"], S1["d"], S1["n"])
+    bmo.xrotate3d(lr, math.radians(-88))
+    bmo.translate3d(lr, [0, 30 * mm, -20 * mm])
+    D = bmo.PSFDetector if kind == "ray" else bmo.Spotdetector
+    dt, dr = D(60 * mm), D(60 * mm)
+    bmo.translate3d(dt, [0, 110 * mm, 0])
+    bmo.xrotate3d(dr, math.radians(90))
+    bmo.translate3d(dr, [0, 30 * mm, -80 * mm])
+    c.system = bmo.System([bs, lt, dt, lr, dr])
+    dk = "psf" if kind == "ray" else "spot"
+    lens = lambda o: tr.ExactLens(tr.Surface(S1["r1"]), tr.Surface(S1["r2"]), S1["l"], S1["d"], lambda lam: S1["n"], o.position(), o.orientation(), planted)
+    c.exact = [tr.ExactFlat(20 * mm, bs.position(), bs.orientation(), "thin_bs", reflectance=0.5), lens(lt), tr.ExactFlat(60 * mm, dt.position(), dt.orientation(), dk),
+               lens(lr), tr.ExactFlat(60 * mm, dr.position(), dr.orientation(), dk)]
+    at = np.array([0.0, 30 * mm, 0.0])
+    P, Dn = zip(disc(at, [0.02, 1.0, -0.01], 9 * mm, 40), ring(at, [0, 1, 0], 2 * mm, 8, slope=0.05))
+    c.bundle = bundle(kind, P, Dn)
+    c.name = "splitter-" + kind
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 2: biconcave lens and meniscus
+S2A = dict(r1=-30 * mm, r2=40 * mm, l=3 * mm, d=25.4 * mm, n=1.5)
+S2B = dict(r1=30 * mm, r2=60 * mm, l=2.5 * mm, d=25.4 * mm, n=1.6)
+
+
+def concave(kind="ray", planted=None, pairs=False):
+    """A biconcave SphericalLens(-30 mm, 40 mm, 3 mm) tilted 3 degrees and a positive meniscus SphericalLens(30 mm, 60 mm, 2.5 mm) behind it.  Rays
+    parallel to the biconcave lens's own axis 5 um, 24 um and 1 mm beside the concave apex (where the cap's wedge of glass is thinner than the
+    central-difference stencil: the normals there must be the dual-number ones), a 2 degree oblique disc, and two skew rays that enter through
+    the barrel inside the rim, cross the air pocket of the concave face and re-enter the rim on the far side: the inside march returns the LAST
+    crossing before its first 1 m step outside, so the record holds one segment from barrel to barrel."""
+    c = Case()
+    a, b = S2A, S2B
+    md = 30 * mm  # pairs: the same lens from two SphericalSurface records with a mechanical ring out to 30 mm (another path of the host builder)
+    if pairs:
+        la_ = bmo.Lens(bmo.SphericalSurface(a["r1"], a["d"], md), bmo.SphericalSurface(a["r2"], a["d"], md), a["l"], lambda lam: a["n"])
+    else:
+        la_ = bmo.SphericalLens(a["r1"], a["r2"], a["l"], a["d"], a["n"])
+    bmo.xrotate3d(la_, math.radians(3))
+    bmo.translate3d(la_, [0.4 * mm, 20 * mm, 0])
+    lb_ = bmo.SphericalLens(b["r1"], b["r2"], b["l"], b["d"], b["n"])
+    assert isinstance(lb_.shape, bmo.MeniscusLensSDF)
+    bmo.zrotate3d(lb_, math.radians(-2))
+    bmo.translate3d(lb_, [0.5 * mm, 35 * mm, -0.3 * mm])
+    det = bmo.PSFDetector(90 * mm) if kind == "ray" else bmo.Spotdetector(90 * mm)
+    bmo.translate3d(det, [0, 80 * mm, 0])
+    c.system = bmo.System([la_, lb_, det])
+    lens = lambda o, q: tr.ExactLens(tr.Surface(q["r1"]), tr.Surface(q["r2"]), q["l"], q["d"], lambda lam: q["n"], o.position(), o.orientation(), planted)
+    c.exact = [lens(la_, a), lens(lb_, b), tr.ExactFlat(90 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    if pairs:
+        c.exact[0] = tr.ExactRingLens(tr.Surface(a["r1"]), tr.Surface(a["r2"]), a["l"], lambda lam: a["n"], a["d"], a["d"], md, md, la_.position(),
+                                      la_.orientation())
+    p0, o = np.asarray(la_.position()), np.asarray(la_.orientation())
+    axis = o[:, 1]
+    rim_p = [p0 + o @ np.array([-20 * mm, y, 1 * mm]) for y in (-0.5 * mm, -0.9 * mm)]
+    rim_d = [o @ np.array([1.0, 0.01, 0.03]), o @ np.array([1.0, -0.005, -0.02])]
+    P, D = zip(disc(p0 + 1.5 * mm * axis, [math.sin(math.radians(2)), math.cos(math.radians(2)), 0.0], 0.85 * a["d"], 34),
+               ring(p0, axis, 5e-6, 4), ring(p0, axis, 24e-6, 4, phase=0.5), ring(p0, axis, 1 * mm, 4, phase=0.9),
+               (np.array(rim_p), np.array(rim_d)))
+    c.bundle = bundle(kind, P, D)
+    c.name = "concave-" + ("pairs-" if pairs else "") + kind
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 3: cemented doublet
+AC254 = dict(r1=87.9 * mm, r2=-105.6 * mm, r3=math.inf, l1=6 * mm, l2=3 * mm, d=25.4 * mm, lams=[488e-9, 707e-9, 1064e-9],
+             n1=[1.6591, 1.6456, 1.6374], n2=[1.7460, 1.7168, 1.7021])  # AC254-150-AB, N-LAK22 / N-SF10 (runtests.jl:1273-1321)
+
+
+def doublet(kind="ray", planted=None):
+    """SphericalDoubletLens AC254-150-AB at 488 / 707 / 1064 nm (a three-wavelength index table per glass), tilted 4 degrees, rolled 30 degrees
+    about its axis and decentred; 16 rays per wavelength over 0.9 of the aperture, 2 degrees oblique."""
+    c = Case()
+    a = AC254
+    dl = bmo.SphericalDoubletLens(a["r1"], a["r2"], a["r3"], a["l1"], a["l2"], a["d"], bmo.DiscreteRefractiveIndex(a["lams"], a["n1"]),
+                                  bmo.DiscreteRefractiveIndex(a["lams"], a["n2"]))
+    bmo.xrotate3d(dl, math.radians(4))
+    bmo.rotate3d(dl, dl.orientation()[:, 1], math.radians(30))
+    bmo.translate3d(dl, [-0.6 * mm, 25 * mm, 0.8 * mm])
+    det = bmo.PSFDetector(60 * mm) if kind == "ray" else bmo.IntersectableObject(bmo.QuadraticFlatMesh(60 * mm))  # beamlets end on a plain stop
+    bmo.translate3d(det, [0, 100 * mm, 0])
+    c.system = bmo.System([dl, det])
+    table = lambda ns: (lambda lam: dict(zip(a["lams"], ns))[lam])
+    c.exact = [tr.ExactDoublet(a["r1"], a["r2"], a["r3"], a["l1"], a["l2"], a["d"], table(a["n1"]), table(a["n2"]), dl.position(), dl.orientation(), planted),
+               tr.ExactFlat(60 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "stop")]
+    at = np.array([-0.6 * mm, 25 * mm + 4 * mm, 0.8 * mm])
+    ob = math.radians(2)
+    P, D = disc(at, [math.sin(ob), math.cos(ob), 0.0], 0.9 * a["d"], 48)
+    lam = np.tile(a["lams"], 16)
+    c.bundle = bundle("ray", [P], [D], lam=lam) if kind == "ray" else gauss_bundle([P], [D], lam=lam)
+    c.name = "doublet" if kind == "ray" else "doublet-gauss"
+    return c
+
+
+SCENES = {
+    "phone-l3": phone_l3,
+    "prism-ray": lambda **kw: prism("ray", **kw),
+    "prism-pol": lambda **kw: prism("pol", **kw),
+    "rhomb": rhomb,
+    "miniscope": miniscope,
+    "concave-pairs-ray": lambda **kw: concave("ray", pairs=True, **kw),
+    "concave-pairs-pol": lambda **kw: concave("pol", pairs=True, **kw),
+    "doublet-gauss": lambda **kw: doublet("gauss", **kw),
+    "cylinders": lambda **kw: cylinders(False, **kw),
+    "acylinders": lambda **kw: cylinders(True, **kw),
+    "block-ray": lambda **kw: block("ray", **kw),
+    "block-pol": lambda **kw: block("pol", **kw),
+    "concave-ray": lambda **kw: concave("ray", **kw),
+    "concave-pol": lambda **kw: concave("pol", **kw),
+    "doublet": doublet,
+    "mirror45-ray": lambda **kw: mirror("ray", 45.0, **kw),
+    "mirror45-pol": lambda **kw: mirror("pol", 45.0, **kw),
+    "mirror85-ray": lambda **kw: mirror("ray", 85.0, **kw),
+    "mirror85-pol": lambda **kw: mirror("pol", 85.0, **kw),
+    "retro-ray": lambda **kw: retro("ray", **kw),
+    "retro-pol": lambda **kw: retro("pol", **kw),
+    "splitter-ray": lambda **kw: splitter("ray", **kw),
+    "splitter-pol": lambda **kw: splitter("pol", **kw),
+    "singlet-gauss": lambda **kw: singlet("gauss", **kw),
+    "singlet-ray": lambda **kw: singlet("ray", **kw),
+    "singlet-pol": lambda **kw: singlet("pol", **kw),
+    "asphere-curved-first": lambda **kw: asphere(False, **kw),
+    "asphere-plane-first": lambda **kw: asphere(True, **kw),
+}
+NO_EXCLUSIONS = ("phone-l3", "cylinders", "acylinders", "doublet", "doublet-gauss", "asphere-curved-first", "asphere-plane-first")  # the issue's scenes 3 - 5 allow none
+# Each planted mistake, and the scenes that exercise it.
+PLANTED_ON = [
+    ("conic_sign", "phone-l3"),
+    ("coef_shift", "phone-l3"),
+    ("conic_sign", "asphere-curved-first"),
+    ("coef_shift", "asphere-curved-first"),
+    ("coef_shift", "asphere-plane-first"),
+    ("back_vertex_edge_sag", "singlet-ray"),
+    ("cylinder_extruded_along_z", "cylinders"),
+    ("cylinder_extruded_along_z", "acylinders"),
+    ("exit_normal_not_flipped", "singlet-ray"),
+    ("exit_normal_not_flipped", "asphere-curved-first"),
+    ("n2_glass_on_exit", "singlet-ray"),
+    ("ts_tp_swapped", "singlet-pol"),
+    ("tir_phase_conjugated", "singlet-pol"),
+    ("tir_phase_conjugated", "block-pol"),
+    ("tir_phase_conjugated", "rhomb"),
+    ("tir_phase_conjugated", "prism-pol"),
+    ("opl_next_medium", "singlet-ray"),
+]
+
+
+# ------------------------------------------------------------------------------------------------ the comparison
+QUANT = ("t", "n", "pos", "dir", "index", "E0", "opl", "row_pos", "row_dir", "proj", "k")
+
+
+class Held:
+    """What hold() found: worst absolute differences and worst difference / bound per quantity, the counts, and the bounces over their bound."""
+
+    def __init__(self):
+        self.abs = {q: 0.0 for q in QUANT}
+        self.ratio = {q: 0.0 for q in QUANT}
+        self.bounces = self.excluded = self.tir = self.barrel = self.leaving = self.children = 0
+        self.over = []
+
+    def note(self, q, diff, bound, where):
+        diff, bound = float(diff), float(bound)
+        self.abs[q] = max(self.abs[q], diff)
+        r = diff / bound if bound > 0 else (0.0 if diff == 0 else math.inf)
+        self.ratio[q] = max(self.ratio[q], r)
+        if r > 1.0:
+            self.over.append((q, where, diff, bound))
+
+    def worst(self):
+        return max(self.ratio.values())
+
+    def worst_finite(self):
+        """The largest ratio among the quantities whose bound is not zero."""
+        return max([r for r in self.ratio.values() if math.isfinite(r)], default=0.0)
+
+    def line(self, name):
+        return ("%s: %d bounces (%d leaving, %d on the barrel, %d TIR, %d splits), %d excluded; worst |dt| %.3g m, |dn| %.3g, |ddir| %.3g, |dE0| %.3g, |dopl| %.3g m; "
+                "worst recorded / bound %.3g (%s)" % (name, self.bounces, self.leaving, self.barrel, self.tir, self.children, self.excluded, self.abs["t"], self.abs["n"],
+                                                    self.abs["dir"], self.abs["E0"], self.abs["opl"], self.worst(), max(self.ratio, key=self.ratio.get)))
+
+
+def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
+    """Every recorded bounce of beams `nodes` of the TraceResult against exact_step within step_bound -> Held.  wrong / planted: the exact
+    objects built with a planted mistake, and the switch: then the differences are taken to THAT evaluation (the bound stays the right one's).
+    cache: a dict that keeps the right evaluation and the bound of every bounce of THIS result between calls."""
+    mp = tr._mp()
+    h = Held()
+    with mp.workdps(50):
+        det_row = {}
+        for slot in range(res.n_detectors):
+            for row, nd in zip(res.detector_hits(slot), res.detector_nodes(slot)):
+                det_row[int(nd)] = row
+        for node, sub in [(n, j) for n in (range(res.n_nodes) if nodes is None else nodes) for j in range(3 if res.rec_planes == 33 else 1)]:
+            segs = tr.segments_of(res, node, sub)
+            anc = tr.ancestors(res, node)
+            base = tr.exact_opl(anc, len(anc))
+            for k, seg in enumerate(segs):
+                if seg["obj"] < 0:
+                    continue
+                where = (int(node), k, sub)
+                seg = dict(seg, opl=base + tr.exact_opl(segs, k))
+                obj = solid_of(case, case.exact, seg)
+                if cache is not None and where in cache:
+                    ex, b = cache[where]
+                else:
+                    ex = tr.exact_step(seg, obj, consts)
+                    assert ex is not None, ("the record has a hit where the exact evaluator has none", where)
+                    b = None if tr.excluded(ex) else tr.step_bound(seg, ex, obj, consts, n_seg=len(anc) + k + 1)
+                    if cache is not None:
+                        cache[where] = (ex, b)
+                h.bounces += 1
+                if b is None:
+                    h.excluded += 1
+                    continue
+                h.leaving += bool(ex["hit"]["leaving"])
+                h.barrel += ex["hit"]["piece"] == "barrel"
+                cmp_ = ex
+                if planted is not None:
+                    cmp_ = tr.exact_step(dict(seg, opl=base + tr.exact_opl(segs, k, planted)), solid_of(case, wrong, seg), consts, planted)
+                    if cmp_ is None or (cmp_["next"] is None) != (ex["next"] is None):
+                        h.note("t", math.inf, 1.0, where)
+                        continue
+                dt = tr._f(seg["t"]) - cmp_["t"]
+                h.note("t", abs(dt), b["t_lo"] if dt < 0 else b["t_hi"], where)
+                h.note("n", tr.fdiff(seg["normal"], cmp_["normal"]), b["n"], where)
+                nx = cmp_["next"]
+                if nx is not None and k + 1 < len(segs):
+                    h.tir += bool(cmp_["interaction"]["tir"]) and obj.kind == "lens"
+                    s2 = segs[k + 1]
+                    h.note("pos", tr.fdiff(s2["pos"], nx["pos"]), b["pos"], where)
+                    h.note("dir", tr.fdiff(s2["dir"], nx["dir"]), b["dir"], where)
+                    h.note("index", tr.fdiff(s2["n"], nx["n"]), 0.0, where)
+                    if nx["E0"] is not None:
+                        h.note("E0", tr.fdiff(s2["E0"], nx["E0"]), b["E0"], where)
+                if cmp_["children"] is not None:  # the first rays of the two beams a splitter spawns, transmitted first (Beamsplitters.jl:16-19)
+                    first = int(res.node_first_child[node])
+                    assert first >= 0, where
+                    h.children += 1
+                    for i, o in enumerate(cmp_["children"]):
+                        s2 = tr.segments_of(res, first + i)[0]
+                        assert int(res.node_parent[first + i]) == node
+                        h.note("pos", tr.fdiff(s2["pos"], o["pos"]), b["pos"], where)
+                        h.note("dir", tr.fdiff(s2["dir"], o["dir"]), b["outs"][i]["dir"], where)
+                        h.note("index", tr.fdiff(s2["n"], o["n"]), 0.0, where)
+                        if o["E0"] is not None:
+                            h.note("E0", tr.fdiff(s2["E0"], o["E0"]), b["outs"][i]["E0"], where)
+                if cmp_["row"] is not None:
+                    row = det_row[int(node)]
+                    x = cmp_["row"]
+                    u = tr.U
+                    if len(x) == 2:  # a Spotdetector's (x, z): two dot products of hit - position with the axes (Spotdetector.jl:50-61)
+                        mag = float(tr._norm(cmp_["point"])) + obj.pos_mag
+                        h.note("row_pos", tr.fdiff(row[0:2], x), 1.5 * b["pos"] + 8 * u * mag, where)
+                        continue
+                    h.note("row_pos", tr.fdiff(row[0:3], x[0:3]), b["pos"], where)
+                    h.note("row_dir", tr.fdiff(row[3:6], x[3:6]), 0.0, where)
+                    h.note("opl", tr.fdiff(row[6], x[6]), b["opl"] + u * float(x[6]), where)
+                    h.note("proj", tr.fdiff(row[7], x[7]), b["proj"], where)
+                    h.note("k", tr.fdiff(row[8], x[8]), 3 * u * float(x[8]), where)
+    return h
+
+
+def solid_of(case, exact, seg):
+    """The solid of the exact scene that the record says was hit: the object, and for a doublet the part whose shape the record names."""
+    obj = exact[seg["obj"]]
+    return obj.parts[case.shape_part[seg["shape"]]] if hasattr(obj, "parts") else obj
+
+
+def compile_case(c):
+    """The compiled scene of a case, the march constants, and which part of a doublet every shape id of the record means."""
+    c.scene = bmo.CompiledScene(c.system, c.bundle.lambdas)
+    c.consts = tr.consts_of(c.scene)
+    c.shape_part = {c.scene.shape_id(s): i for o in c.system.objects() if isinstance(o, bmo.DoubletLens) for i, s in enumerate(o.parts())}
+    return c
+
+
+def tree_nodes(res, roots):
+    """The beams of the trees of the given root rays (indices into the bundle): the root's node and everything below it."""
+    top = np.flatnonzero(res.node_parent < 0)
+    out, todo = [], [int(top[i]) for i in roots]
+    while todo:
+        n = todo.pop()
+        out.append(n)
+        first = int(res.node_first_child[n])
+        if first >= 0:
+            todo += [first, first + 1]
+    return sorted(out)
+
+
+def root_of(bundle, i):
+    P = bundle.planes
+    if bundle.kind == bmo.BEAM_GAUSSIAN:  # the chief ray
+        return dict(pos=P[0:3, i].copy(), dir=P[3:6, i].copy(), lam=float(P[18, i]), n=float(P[19, i]), E0=None)
+    r = dict(pos=P[0:3, i].copy(), dir=P[3:6, i].copy(), lam=float(P[6, i]), n=float(P[7, i]), E0=None)
+    if bundle.kind == bmo.BEAM_POLARIZED:
+        r["E0"] = [complex(P[8, i], P[9, i]), complex(P[10, i], P[11, i]), complex(P[12, i], P[13, i])]
+    return r
+
+
+def sequence(res, node, case):
+    """((object, part of a doublet) per segment, detected) of a recorded beam."""
+    first, nseg = int(res.node_first_rec[node]), int(res.node_nseg[node])
+    return [(int(o), case.shape_part.get(int(sh), 0)) for o, sh in zip(res.rec_obj[first:first + nseg], res.rec_shape[first:first + nseg])], bool(
+        res.node_status[node] & 16)
+
+
+def exact_sequence(trace, case):
+    objs = [(s["obj"], s["part"]) for s in trace]
+    detected = trace[-1]["ex"] is not None and getattr(case.exact[trace[-1]["obj"]], "kind", None) in ("psf", "spot")
+    return objs, detected
+
+
+def left_out(trace):
+    """True where some bounce of the exact trace (its children's included) meets the exclusion criterion."""
+    return any((s["ex"] is not None and tr.excluded(s["ex"], s["tie"])) or any(left_out(c) for c in s.get("children", ())) for s in trace)
+
+
+def same_tree(trace, res, node, case):
+    """The exact trace and the recorded beam tree below `node`: the same objects in the same order, the same end, the same children."""
+    assert exact_sequence(trace, case) == sequence(res, node, case), node
+    kids = trace[-1].get("children")
+    first = int(res.node_first_child[node])
+    assert (kids is None) == (first < 0), node
+    for i, sub in enumerate(kids or ()):
+        same_tree(sub, res, first + i, case)
+
+
+def _part(case, s):
+    obj = case.exact[s["obj"]]
+    return obj.parts[s["part"]] if hasattr(obj, "parts") else obj
+
+
+def end_to_end(res, case, consts, roots):
+    """exact_trace from the root doubles to the detector against the recorded detector row, inside
+    sum_bounces |d(final) / d(bounce output)| step_bound, each sensitivity a difference of the exact trace in 50 digits -> Held (row_pos, row_dir, opl)."""
+    mp = tr._mp()
+    h = Held()
+    with mp.workdps(50):
+        det_row = {int(nd): row for slot in range(res.n_detectors) for row, nd in zip(res.detector_hits(slot), res.detector_nodes(slot))}
+        step = mp.mpf(10) ** -13
+        for i in roots:
+            if i not in det_row:
+                continue
+            root = root_of(case.bundle, i)
+            base = tr.exact_trace(root, case.exact, consts, R_MAX)
+            if base[-1]["ex"] is None or base[-1]["ex"]["row"] is None or any(tr.excluded(s["ex"], s["tie"]) for s in base):
+                continue
+            final = base[-1]["ex"]["row"]
+            last = base[-1]
+            bl = tr.step_bound(last["seg"], last["ex"], _part(case, last), consts, n_seg=len(base))
+            bound = dict(pos=bl["pos"], dir=mp.mpf(0), opl=bl["opl"] + tr.U * final[6])
+            for j, s in enumerate(base[:-1]):
+                b = tr.step_bound(s["seg"], s["ex"], _part(case, s), consts, n_seg=j + 1)
+                bound["opl"] += b["opl_inc"]
+                d_in = s["seg"]["dir"]
+                dt = max(b["t_lo"], b["t_hi"])
+                kicks = [((tr._scale(step, d_in), [0, 0, 0]), dt)]
+                for e in ([1, 0, 0], [0, 1, 0], [0, 0, 1]):
+                    kicks.append(((tr._scale(step, e), [0, 0, 0]), b["pos"] - dt))
+                for e in tr._tangents(s["ex"]["next"]["dir"]):
+                    kicks.append((([0, 0, 0], tr._scale(step, e)), b["dir"]))
+                for (dp, dd), size in kicks:
+                    # the ray that leaves bounce j, moved; it is followed through the solids the un-moved trace met (a kick of 1e-13 changes none)
+                    nx = s["ex"]["next"]
+                    moved = tr.exact_trace(dict(pos=tr._add(nx["pos"], dp), dir=tr._unit(tr._add(nx["dir"], dd)), n=nx["n"], lam=root["lam"], opl=s["ex"]["opl"]),
+                                           case.exact, consts, R_MAX, follow=[(m["obj"], m["part"]) for m in base[j + 1:]])
+                    assert len(moved) == len(base) - j - 1 and moved[-1]["ex"] is not None
+                    f2 = moved[-1]["ex"]["row"]
+                    bound["pos"] += tr._norm(tr._sub(f2[0:3], final[0:3])) / step * size
+                    bound["dir"] += tr._norm(tr._sub(f2[3:6], final[3:6])) / step * size
+                    bound["opl"] += abs(f2[6] - final[6]) / step * size
+            row = det_row[i]
+            h.bounces += 1
+            h.note("row_pos", tr.fdiff(row[0:3], final[0:3]), bound["pos"], (i, "end"))
+            h.note("row_dir", tr.fdiff(row[3:6], final[3:6]), bound["dir"], (i, "end"))
+            h.note("opl", tr.fdiff(row[6], final[6]), bound["opl"], (i, "end"))
+    return h
