@@ -31,6 +31,10 @@ ZERN_MAX_ORDER = 6
 (ZERN_N, ZERN_STATUS, ZERN_S, ZERN_X_REF, ZERN_Z_REF, ZERN_U0, ZERN_V0, ZERN_RHO, ZERN_W_MEAN, ZERN_FIT_RMS, ZERN_E_LO, ZERN_E_HI,
  ZERN_N_OUT) = range(ZERN_INFO_N)
 
+# BMO_FOCUS_STAT_*: columns of the focus statistics (bmo_psf_focus_stats)
+FOCUS_STAT_N = 12
+(FOCUS_N, FOCUS_S, FOCUS_CX, FOCUS_CZ, FOCUS_X_MIN, FOCUS_X_MAX, FOCUS_Z_MIN, FOCUS_Z_MAX, FOCUS_HWX, FOCUS_HWZ, FOCUS_RMS_R, FOCUS_MAX_R) = range(FOCUS_STAT_N)
+
 NODE_MISS, NODE_STOPPED, NODE_RMAX, NODE_SPLIT, NODE_DETECTED, NODE_ERR_UNIT, NODE_GAUSS_DIVERGED, NODE_BLOCKED, NODE_ERR_ORTHO = (
     1, 2, 4, 8, 16, 32, 64, 128, 256)
 
@@ -256,6 +260,9 @@ def load_engine():
     lib.bmo_psf_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
     lib.bmo_psf_zernike.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
     lib.bmo_psf_zernike_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_through_focus.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, dp, dp]
+    lib.bmo_psf_focus_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
+    lib.bmo_result_psf_rows.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     _engine = lib
     return lib
 
@@ -417,6 +424,52 @@ def psf_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, ref=None
     check(lib, lib.bmo_psf_stats_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                        None if r is None else r.ctypes.data_as(dp), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats_sweep")
     return st[:K], ms.value
+
+
+def _psf_rows(hits, hits_device_ptr, n_hits):
+    """(pointer, row count, on_device, keep-alive) of the PSF rows of a single read-out."""
+    if hits_device_ptr is not None:
+        return C.c_void_p(int(hits_device_ptr)), int(n_hits), 1, None
+    h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
+    return h.ctypes.data_as(C.c_void_p), len(h), 0, h
+
+
+def psf_through_focus(hits, origin, e1, e2, displacements, xs, zs, device=0, hits_device_ptr=None, n_hits=None, want_field=False):
+    """bmo_psf_through_focus: the PSF of the rows on the grid (xs, zs) displaced by each of `displacements` [M, 3] (world vectors), in one
+    pass over the rows.  Returns (I[M, n, n] indexed [m, i, j], field [M, n, n] or None, kernel_ms); the plane with a zero displacement
+    equals psf_intensity bit for bit.  `hits` is a host [H, 9] array, or pass `hits_device_ptr` + `n_hits` for resident rows."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    d = np.ascontiguousarray(np.asarray(displacements, dtype=np.float64).reshape(-1, 3))
+    x, z = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(zs, dtype=np.float64)
+    n, M = len(x), len(d)
+    if len(z) != n:
+        raise ValueError("xs and zs must have the same length")
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    out = np.zeros(M * n * n)
+    fld = np.zeros(2 * M * n * n) if want_field else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_through_focus(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M,
+                                         x.ctypes.data_as(dp), z.ctypes.data_as(dp), n, int(device), out.ctypes.data_as(dp),
+                                         fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_through_focus")
+    field = np.ascontiguousarray((fld[0::2] + 1j * fld[1::2]).reshape(M, n, n).transpose(0, 2, 1)) if want_field else None
+    return np.ascontiguousarray(out.reshape(M, n, n).transpose(0, 2, 1)), field, ms.value
+
+
+def psf_focus_stats(hits, origin, e1, e2, axis, offsets, device=0, hits_device_ptr=None, n_hits=None):
+    """bmo_psf_focus_stats: the twelve spot statistics (FOCUS_* columns) of the rows propagated along their directions to the detector
+    plane moved by offsets[m] * axis, two passes on the device.  Returns (stats [M, 12], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2, ax = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2, axis))
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64).reshape(-1))
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    st = np.zeros((len(off), FOCUS_STAT_N))
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_focus_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp),
+                                       off.ctypes.data_as(dp), len(off), int(device), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_focus_stats")
+    return st, ms.value
 
 
 def zernike_sizes(order):

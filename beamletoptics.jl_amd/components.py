@@ -469,6 +469,55 @@ def psf_marechal(stats):
         return np.where(k == st[..., abi.PSF_K_MAX], np.exp(-(k * rms) ** 2), np.nan)
 
 
+def best_focus(offsets, values, kind="min"):
+    """(offset, value) of the extremum of a focus curve sampled at `offsets`: the vertex of the parabola through the extremal sample
+    (kind "min" or "max"; NaN samples are passed over) and its two neighbours; at an end of the range, the end sample itself."""
+    if kind not in ("min", "max"):
+        raise ValueError('best_focus: kind must be "min" or "max"')
+    x, y = np.asarray(offsets, dtype=np.float64).reshape(-1), np.asarray(values, dtype=np.float64).reshape(-1)
+    if len(x) != len(y) or len(x) == 0 or np.isnan(y).all():
+        raise ValueError("best_focus: offsets and values must be two arrays of one length with a sample that is not NaN")
+    i = int(np.nanargmin(y) if kind == "min" else np.nanargmax(y))
+    if i == 0 or i == len(x) - 1 or math.isnan(y[i - 1]) or math.isnan(y[i + 1]):
+        return float(x[i]), float(y[i])
+    d1, d2 = (y[i] - y[i - 1]) / (x[i] - x[i - 1]), (y[i + 1] - y[i]) / (x[i + 1] - x[i])
+    a = (d2 - d1) / (x[i + 1] - x[i - 1])  # Newton's form: y = y0 + d1 (x - x0) + a (x - x0)(x - x1)
+    if a == 0:
+        return float(x[i]), float(y[i])
+    xv = (x[i - 1] + x[i]) / 2 - d1 / (2 * a)
+    return float(xv), float(y[i - 1] + d1 * (xv - x[i - 1]) + a * (xv - x[i - 1]) * (xv - x[i]))
+
+
+def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0):
+    """The through-focus stack of PSF rows read through stats_fn(axis, offsets) -> focus statistics [M, 12] and stack_fn(displacements, xs, zs)
+    -> I[M, n, n]: what PSFDetector.through_focus and EngineSolution.psf_through_focus share.  Plane m is the detector plane moved by
+    offsets[m] along `axis` (None: the detector's local y).  The window is common to the stack: the half-widths of plane `window_plane`
+    (None: the plane of least RMS radius) times crop_factor, xs and zs running over -hw .. +hw about each plane's centre.  The centre of
+    plane m is its own centroid (follow="centroid": the grid follows the chief ray) or the centroid of the window plane (follow=None).
+    Returns (xs, zs, displacements [M, 3], I[M, n, n], stats): the point (i, j) of plane m lies at origin + xs[i] e1 + zs[j] e2 + d_m."""
+    from . import abi
+
+    if follow not in ("centroid", None):
+        raise ValueError('through_focus: follow must be "centroid" or None')
+    o = np.asarray(orientation, dtype=np.float64)
+    e1, e2 = o[:, 0], o[:, 2]
+    ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
+    off = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    if len(off) == 0:
+        raise ValueError("through_focus: no offsets")
+    st = stats_fn(ax, off)
+    if st[0, abi.FOCUS_N] == 0:
+        raise ValueError("through_focus: the PSFDetector recorded no hit")
+    if np.isnan(st[:, abi.FOCUS_RMS_R]).all():
+        raise ValueError("through_focus: no plane has statistics (a row runs parallel to the detector plane)")
+    w = int(np.nanargmin(st[:, abi.FOCUS_RMS_R])) if window_plane is None else int(window_plane)
+    hwx, hwz = st[w, abi.FOCUS_HWX] * crop_factor, st[w, abi.FOCUS_HWZ] * crop_factor
+    xs, zs = la.linrange(-hwx, hwx, n), la.linrange(-hwz, hwz, n)
+    centre = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]] if follow == "centroid" else np.tile(st[w, [abi.FOCUS_CX, abi.FOCUS_CZ]], (len(off), 1))
+    d = off[:, None] * ax[None, :] + centre[:, 0:1] * e1[None, :] + centre[:, 1:2] * e2[None, :]
+    return xs, zs, d, stack_fn(d, xs, zs), st
+
+
 def zernike_terms(order):
     """The (n, m) of the Zernike terms up to radial order `order` in OSA/ANSI order: j = (n (n + 2) + m) / 2."""
     return [(n, m) for n in range(int(order) + 1) for m in range(-n, n + 1, 2)]
@@ -551,6 +600,24 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
         o = self.orientation()
         coef, info, _, _ = abi.psf_zernike(self.data, self.position(), o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil, device=device)
         return coef, info
+
+    def focus_stats(self, offsets, axis=None, device=0):
+        """The twelve spot statistics (abi.FOCUS_* columns) of all rows accumulated so far, propagated along their directions to the detector
+        plane moved by each of `offsets` along `axis` (None: the detector's local y): [M, 12] (bmo_psf_focus_stats)."""
+        from . import abi
+
+        o = self.orientation()
+        return abi.psf_focus_stats(self.data, self.position(), o[:, 0], o[:, 2], o[:, 1] if axis is None else axis, offsets, device=device)[0]
+
+    def through_focus(self, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0, device=0):
+        """The PSF of all rows accumulated so far on the detector plane moved by each of `offsets` along `axis`, in one pass over the rows
+        (bmo_psf_through_focus; no re-trace): (xs, zs, displacements, I[M, n, n], stats) as psf_through_focus describes them."""
+        from . import abi
+
+        o, pos = self.orientation(), self.position()
+        return psf_through_focus(lambda ax, off: abi.psf_focus_stats(self.data, pos, o[:, 0], o[:, 2], ax, off, device=device)[0],
+                                 lambda d, xs, zs: abi.psf_through_focus(self.data, pos, o[:, 0], o[:, 2], d, xs, zs, device=device)[0],
+                                 o, offsets, n=n, axis=axis, follow=follow, window_plane=window_plane, crop_factor=crop_factor)
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

@@ -2082,3 +2082,405 @@ extern "C" int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, in
     return psf_zernike_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, info, gram, kernel_ms,
                             "bmo_psf_zernike_sweep");
 }
+
+// ====================================================================================================================
+// Through-focus read-out (include/bmo.h "Through-focus read-out"): the PSF of one set of rows on a stack of displaced grids, and the spot
+// statistics of the rows propagated to a stack of planes.
+//
+// The stack.  The split plan, the point blocks and the order of the sum over rows are bmo_psf_intensity's for the same (n_hits, n); a
+// workgroup owns 256 grid points, one split and one chunk of MP planes, whose 2 * MP accumulators every lane keeps in registers.  Per row
+// and point the lane evaluates the sincos of psf_sum_range once and multiplies it by the row's MP plane factors u = cis(k dot(d_m, dir)).
+// The factors do not depend on the point: for every psf_focus_rows(MP) rows of the staged tile the workgroup computes them cooperatively
+// (at most 1 024 factors, four per lane) into at most 16 KB of LDS laid out [plane][row] (the lanes that write are consecutive in `row`:
+// no bank conflict), and every lane then reads the factor of (plane, row) at the same address (a broadcast read).  18 KB of row tile +
+// 16 KB of factors: four workgroups, 16 waves, per CU.  A stack runs as chunks of PSF_FOCUS_MP planes on the grid's z dimension, each of
+// which repeats the per-point sincos, and one launch of the next power of two for the planes that are left (MP = 1, 2, 4, 8 ...), so a
+// single plane pays for one factor per row and point and not for sixteen.  The partial sums are [item][plane][point], which
+// reduce_splits_kernel reads as one configuration of n_planes * n_pts points; a stack whose partial sums would pass 1 GiB runs in several
+// passes of whole chunks.
+#ifndef BMO_PSF_FOCUS_MP
+#define BMO_PSF_FOCUS_MP 16  // planes per full chunk: 8 or 16 (the A/B that chose it: profiles/psf_through_focus_bench.txt)
+#endif
+namespace {
+
+constexpr int PSF_FOCUS_MP = BMO_PSF_FOCUS_MP;
+static_assert(PSF_FOCUS_MP == 8 || PSF_FOCUS_MP == 16, "PSF_FOCUS_MP: 8 or 16");
+// rows whose factors are in LDS together for chunks of mp planes: 1 024 factors, at most the tile
+constexpr int psf_focus_rows(int mp) { return 1024 / mp < PSF_TILE ? 1024 / mp : PSF_TILE; }
+
+// split blockIdx.y of the rows, planes m_first + blockIdx.z * MP .. of the n_planes displacements `disp` [n_planes][3]; the partial
+// plane of a pass that starts at plane m_pass and holds pass_planes planes: [split][m - m_pass][pt]
+template <int MP>
+__global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split,
+                                                                   const double* __restrict__ xs, const double* __restrict__ zs, int32_t n, d3 origin, d3 e1,
+                                                                   d3 e2, const double* __restrict__ disp, int32_t n_planes, int32_t m_first,
+                                                                   int32_t m_pass, int32_t pass_planes, double2* __restrict__ partial) {
+    constexpr int FR = psf_focus_rows(MP);
+    static_assert(PSF_TILE % FR == 0 && (MP * FR) % 256 == 0, "whole factor sub-tiles, every lane computes as many factors");
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double2 fac[MP * FR];
+    __shared__ double dsp[MP * 3];
+    const int64_t n_pts = (int64_t)n * n;
+    const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = pt < n_pts;
+    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
+    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
+    const int32_t m0 = m_first + (int32_t)blockIdx.z * MP;
+    const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;  // planes of this chunk; the slots past them run on d = 0 and are not stored
+    if ((int)threadIdx.x < MP * 3) dsp[threadIdx.x] = (int)threadIdx.x < mcnt * 3 ? disp[(int64_t)m0 * 3 + threadIdx.x] : 0.0;
+    d3 p{0, 0, 0};
+    if (live) p = psf_point(origin, e1, e2, xs[(int)(pt % n)], zs[(int)(pt / n)]);
+    double re[MP], im[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) re[m] = 0.0, im[m] = 0.0;
+    for (int64_t base = h0; base < h1; base += PSF_TILE) {
+        const int cnt = (int)(h1 - base < PSF_TILE ? h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);  // its syncs also publish dsp
+        for (int sub = 0; sub < cnt; sub += FR) {
+            const int scnt = cnt - sub < FR ? cnt - sub : FR;
+            if (sub > 0) __syncthreads();  // the factors of the rows before are read
+            for (int q = threadIdx.x; q < MP * FR; q += 256) {
+                const int row = q % FR, m = q / FR;
+                if (row < scnt) {
+                    const double* r = tile + 9 * (sub + row);
+                    const double g = (dsp[3 * m] * r[3] + dsp[3 * m + 1] * r[4]) + dsp[3 * m + 2] * r[5];
+                    double s, c;
+                    sincos(r[8] * g, &s, &c);
+                    fac[q] = make_double2(c, s);
+                }
+            }
+            __syncthreads();
+            if (live) {
+                for (int h = 0; h < scnt; ++h) {
+                    const double* r = tile + 9 * (sub + h);
+                    const double phase = r[8] * psf_path(p, r);
+                    double s, c;
+                    sincos(phase, &s, &c);
+                    const double t_re = r[7] * c, t_im = r[7] * s;
+#pragma unroll
+                    for (int m = 0; m < MP; ++m) {
+                        const double2 u = fac[m * FR + h];
+                        re[m] += t_re * u.x - t_im * u.y;
+                        im[m] += t_re * u.y + t_im * u.x;
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+    double2* out = partial + ((int64_t)blockIdx.y * pass_planes + (m0 - m_pass)) * n_pts + pt;
+#pragma unroll
+    for (int m = 0; m < MP; ++m)
+        if (m < mcnt) out[(int64_t)m * n_pts] = make_double2(re[m], im[m]);
+}
+
+}  // namespace
+
+// The stack of n_planes planes from the n_hits > 0 device rows `hits`.
+static int psf_focus_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* disp, int32_t n_planes,
+                          const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field, double* kernel_ms) {
+    const int64_t n_pts = (int64_t)n * n;
+    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
+    const size_t n_out = (size_t)n_planes * (size_t)n_pts;
+    hipStream_t st = 0;
+    const Ranges R{{0}, {n_hits}};
+    const SplitPlan plan(R, pt_blocks, n_pts, psf_splits);  // bmo_psf_intensity's splits of these rows on this grid
+    const PsfPose pose{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}};
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_xs = up.add(xs, (size_t)n), o_zs = up.add(zs, (size_t)n), o_d = up.add(disp, (size_t)n_planes * 3);
+    DevBuf d_int, d_field;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_int.alloc(n_out * sizeof(double))) || (out_field && (rc = d_field.alloc(n_out * sizeof(double2))))) return rc;
+    // planes per pass: whole chunks, partial sums of at most 1 GiB (one chunk if a single one needs more)
+    const int64_t fit = ((int64_t)1 << 30) / (plan.max_nw * n_pts * (int64_t)sizeof(double2)) / PSF_FOCUS_MP * PSF_FOCUS_MP;
+    const int32_t per_pass = (int32_t)std::min<int64_t>(std::max<int64_t>(fit, PSF_FOCUS_MP), (int64_t)65535 * PSF_FOCUS_MP);
+    EventTimer timer;
+    for (int32_t m_pass = 0; m_pass < n_planes; m_pass += per_pass) {
+        const int32_t pass_planes = std::min(per_pass, n_planes - m_pass);
+        auto accumulate = [&](dim3, const SplitPlan::Launch& L, double2* partial) {
+            auto launch = [&](auto mp, int32_t m_first, int32_t chunks) {
+                hipLaunchKernelGGL(psf_focus_accumulate_kernel<decltype(mp)::value>, dim3(pt_blocks, (unsigned)L.nw, (unsigned)chunks), dim3(256), 0, st, hits, n_hits,
+                                   plan.per_split[0], up.at<double>(o_xs), up.at<double>(o_zs), n, pose.origin, pose.e1, pose.e2, up.at<double>(o_d), n_planes, m_first,
+                                   m_pass, pass_planes, partial);
+            };
+            const int32_t full = pass_planes / PSF_FOCUS_MP, rest = pass_planes % PSF_FOCUS_MP, m_rest = m_pass + full * PSF_FOCUS_MP;
+            if (full > 0) launch(std::integral_constant<int, PSF_FOCUS_MP>{}, m_pass, full);
+            if (rest > 8) launch(std::integral_constant<int, 16>{}, m_rest, 1);  // the slots past the last plane run idle
+            else if (rest > 4) launch(std::integral_constant<int, 8>{}, m_rest, 1);
+            else if (rest > 2) launch(std::integral_constant<int, 4>{}, m_rest, 1);
+            else if (rest > 1) launch(std::integral_constant<int, 2>{}, m_rest, 1);
+            else if (rest > 0) launch(std::integral_constant<int, 1>{}, m_rest, 1);
+        };
+        const PsfFinish finish{(double*)d_int.p + (int64_t)m_pass * n_pts, out_field ? (double2*)d_field.p + (int64_t)m_pass * n_pts : nullptr};
+        if ((rc = split_reduce(plan, up.at<SplitCfg>(o_cfg), (int64_t)pass_planes * n_pts, st, timer, kernel_ms, accumulate, finish))) return rc;
+    }
+    HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, n_out * sizeof(double2), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_through_focus(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                                     const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, int32_t device,
+                                     double* out_intensity, double* out_field, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !displacements || !xs || !zs || !out_intensity || n <= 0 || n_planes <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_through_focus: bad argument (null pointer, n <= 0, n_planes <= 0, n_hits < 0)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = spot_single_rows("bmo_psf_through_focus", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (n_hits == 0) {
+        const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+        std::fill(out_intensity, out_intensity + n_out, 0.0);
+        if (out_field) std::fill(out_field, out_field + 2 * n_out, 0.0);
+        return BMO_OK;
+    }
+    return psf_focus_read(hits, n_hits, origin, e1, e2, displacements, n_planes, xs, zs, n, out_intensity, out_field, kernel_ms);
+}
+
+// The focus statistics.  The plumbing of the wavefront statistics (spot_plan, work items on the grid's x dimension, tiles of 256 rows staged
+// through LDS, lane l reads row l, the lane / shuffle / wave / split order of the sums, psf_stats_fold), two accumulate passes with a reduce
+// each: A the sums and extrema, its reduce leaves the centroids on the device; C the spreads about them.  A workgroup owns one work item and
+// one chunk of FOCUS_STAT_MP planes (the grid's y dimension), whose accumulators every lane keeps in registers: the rows are read once per
+// pass and chunk.  The partial sums are [plane][item], one workgroup per plane folds them in split order.
+namespace {
+
+constexpr int FOCUS_STAT_MP = 8;
+
+struct FocusSumA {
+    double s, bad, sx, sz, x_min, x_max, z_min, z_max;
+};
+struct FocusSumC {
+    double hwx, hwz, sr2, r2_max;
+};
+struct FocusFrame {
+    d3 origin, e1, e2, axis, nrm;
+};
+
+// (x, z) of row r propagated to the plane through o; den = dot(dir, nrm)
+__device__ __forceinline__ void focus_local(const double* r, const FocusFrame& F, const d3& o, double den, double& x, double& z) {
+    const double s = (((o.x - r[0]) * F.nrm.x + (o.y - r[1]) * F.nrm.y) + (o.z - r[2]) * F.nrm.z) / den;
+    const d3 q{r[0] + s * r[3], r[1] + s * r[4], r[2] + s * r[5]};
+    x = ((q.x - o.x) * F.e1.x + (q.y - o.y) * F.e1.y) + (q.z - o.z) * F.e1.z;
+    z = ((q.x - o.x) * F.e2.x + (q.y - o.y) * F.e2.y) + (q.z - o.z) * F.e2.z;
+}
+__device__ __forceinline__ d3 focus_origin(const FocusFrame& F, double off) { return d3{F.origin.x + off * F.axis.x, F.origin.y + off * F.axis.y, F.origin.z + off * F.axis.z}; }
+__device__ __forceinline__ double focus_den(const double* r, const FocusFrame& F) { return (r[3] * F.nrm.x + r[4] * F.nrm.y) + r[5] * F.nrm.z; }
+
+// pass A of work item blockIdx.x on planes blockIdx.y * FOCUS_STAT_MP ..
+__global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                             const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
+    constexpr int MP = FOCUS_STAT_MP;
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const int32_t m0 = (int32_t)blockIdx.y * MP;
+    const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
+    d3 o[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) o[m] = focus_origin(F, offsets[m0 + (m < mcnt ? m : 0)]);
+    double s = 0.0, bad = 0.0, sx[MP], sz[MP], x_min[MP], x_max[MP], z_min[MP], z_max[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) sx[m] = 0.0, sz[m] = 0.0, x_min[m] = kinf(), x_max[m] = -kinf(), z_min[m] = kinf(), z_max[m] = -kinf();
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double w = r[7], den = focus_den(r, F);
+            s += w;
+            bad += den == 0.0 ? 1.0 : 0.0;
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                double x, z;
+                focus_local(r, F, o[m], den, x, z);
+                sx[m] += w * x;
+                sz[m] += w * z;
+                x_min[m] = x < x_min[m] ? x : x_min[m];
+                x_max[m] = x > x_max[m] ? x : x_max[m];
+                z_min[m] = z < z_min[m] ? z : z_min[m];
+                z_max[m] = z > z_max[m] ? z : z_max[m];
+            }
+        }
+    }
+    FocusSumA a;
+    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
+    a.bad = spot_wg_reduce(bad, SpotAdd{}, sh);
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        a.sx = spot_wg_reduce(sx[m], SpotAdd{}, sh);
+        a.sz = spot_wg_reduce(sz[m], SpotAdd{}, sh);
+        a.x_min = spot_wg_reduce(x_min[m], SpotMin{}, sh);
+        a.x_max = spot_wg_reduce(x_max[m], SpotMax{}, sh);
+        a.z_min = spot_wg_reduce(z_min[m], SpotMin{}, sh);
+        a.z_max = spot_wg_reduce(z_max[m], SpotMax{}, sh);
+        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = a;
+    }
+}
+
+// plane blockIdx.x: the work items of pass A in split order; the sums, the centroid and the extrema go to stats[m], the centroid to mid[m]
+__global__ void psf_focus_sums_reduce_kernel(int32_t n_items, int64_t n_rows, const FocusSumA* __restrict__ partial, double* __restrict__ stats,
+                                             double2* __restrict__ mid) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(FocusSumA) / sizeof(double))];
+    const int32_t m = (int32_t)blockIdx.x;
+    double s = 0.0, bad = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
+    psf_stats_fold(partial, SplitCfg{(int64_t)m * n_items, n_items, 0}, lds, [&](const FocusSumA& p) {
+        s += p.s;
+        bad += p.bad;
+        sx += p.sx;
+        sz += p.sz;
+        x_min = p.x_min < x_min ? p.x_min : x_min;
+        x_max = p.x_max > x_max ? p.x_max : x_max;
+        z_min = p.z_min < z_min ? p.z_min : z_min;
+        z_max = p.z_max > z_max ? p.z_max : z_max;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
+    out[BMO_FOCUS_STAT_N_ROWS] = (double)n_rows;
+    if (bad != 0.0) {  // a row parallel to the planes: no statistics
+        for (int q = 1; q < BMO_FOCUS_STAT_N; ++q) out[q] = knan();
+        mid[m] = make_double2(knan(), knan());
+        return;
+    }
+    const double cx = sx / s, cz = sz / s;
+    out[BMO_FOCUS_STAT_S] = s;
+    out[BMO_FOCUS_STAT_CX] = cx;
+    out[BMO_FOCUS_STAT_CZ] = cz;
+    out[BMO_FOCUS_STAT_X_MIN] = x_min;
+    out[BMO_FOCUS_STAT_X_MAX] = x_max;
+    out[BMO_FOCUS_STAT_Z_MIN] = z_min;
+    out[BMO_FOCUS_STAT_Z_MAX] = z_max;
+    mid[m] = make_double2(cx, cz);
+}
+
+// pass C of work item blockIdx.x on planes blockIdx.y * FOCUS_STAT_MP ..
+__global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                               const double* __restrict__ offsets, int32_t n_planes, const double2* __restrict__ mid,
+                                                               FocusSumC* __restrict__ partial) {
+    constexpr int MP = FOCUS_STAT_MP;
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double sh[4];
+    const SplitWork W = work[blockIdx.x];
+    const int32_t m0 = (int32_t)blockIdx.y * MP;
+    const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
+    d3 o[MP];
+    double2 c[MP];
+    double hwx[MP], hwz[MP], sr2[MP], r2_max[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        const int32_t mm = m0 + (m < mcnt ? m : 0);
+        o[m] = focus_origin(F, offsets[mm]);
+        c[m] = mid[mm];
+        hwx[m] = 0.0, hwz[m] = 0.0, sr2[m] = 0.0, r2_max[m] = 0.0;
+    }
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double w = r[7], den = focus_den(r, F);
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                double x, z;
+                focus_local(r, F, o[m], den, x, z);
+                const double ax = x - c[m].x, az = z - c[m].y;
+                const double fx = fabs(ax), fz = fabs(az);
+                const double r2 = ax * ax + az * az;
+                hwx[m] = fx > hwx[m] ? fx : hwx[m];
+                hwz[m] = fz > hwz[m] ? fz : hwz[m];
+                sr2[m] += w * r2;
+                r2_max[m] = r2 > r2_max[m] ? r2 : r2_max[m];
+            }
+        }
+    }
+    FocusSumC v;
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        v.hwx = spot_wg_reduce(hwx[m], SpotMax{}, sh);
+        v.hwz = spot_wg_reduce(hwz[m], SpotMax{}, sh);
+        v.sr2 = spot_wg_reduce(sr2[m], SpotAdd{}, sh);
+        v.r2_max = spot_wg_reduce(r2_max[m], SpotMax{}, sh);
+        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = v;
+    }
+}
+
+__global__ void psf_focus_spread_reduce_kernel(int32_t n_items, const FocusSumC* __restrict__ partial, double* __restrict__ stats) {
+    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(FocusSumC) / sizeof(double))];
+    const int32_t m = (int32_t)blockIdx.x;
+    double hwx = 0.0, hwz = 0.0, sr2 = 0.0, r2_max = 0.0;
+    psf_stats_fold(partial, SplitCfg{(int64_t)m * n_items, n_items, 0}, lds, [&](const FocusSumC& p) {
+        hwx = p.hwx > hwx ? p.hwx : hwx;
+        hwz = p.hwz > hwz ? p.hwz : hwz;
+        sr2 += p.sr2;
+        r2_max = p.r2_max > r2_max ? p.r2_max : r2_max;
+    });
+    if (threadIdx.x != 0) return;
+    double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
+    const double s = out[BMO_FOCUS_STAT_S];
+    if (s != s) return;  // NaN already
+    out[BMO_FOCUS_STAT_HWX] = hwx;
+    out[BMO_FOCUS_STAT_HWZ] = hwz;
+    out[BMO_FOCUS_STAT_RMS_R] = sqrt(sr2 / s);
+    out[BMO_FOCUS_STAT_MAX_R] = sqrt(r2_max);
+}
+
+}  // namespace
+
+extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                                   const double axis[3], const double* offsets, int32_t n_planes, int32_t device, double* stats, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !axis || !offsets || !stats || n_planes <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_focus_stats: bad argument (null pointer, n_planes <= 0, n_hits < 0)");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = spot_single_rows("bmo_psf_focus_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (n_hits == 0) {
+        for (int32_t m = 0; m < n_planes; ++m) {
+            double* out = stats + (size_t)m * BMO_FOCUS_STAT_N;
+            std::fill(out, out + BMO_FOCUS_STAT_N, std::nan(""));
+            out[BMO_FOCUS_STAT_N_ROWS] = 0.0;
+        }
+        return BMO_OK;
+    }
+    hipStream_t st = 0;
+    const SplitPlan plan = spot_plan(Ranges{{0}, {n_hits}});
+    unsigned n_items = 0;
+    if (int rc = spot_items(plan, "bmo_psf_focus_stats", n_items)) return rc;
+    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
+    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
+    if (chunks > 65535) return fail(BMO_ERR_LIMIT, "bmo_psf_focus_stats: more planes than one launch holds");
+    Packed up;
+    const size_t o_work = up.add(plan.work), o_off = up.add(offsets, (size_t)n_planes);
+    DevBuf pa, pc, d_stats, d_mid;
+    int rc;
+    const size_t cells = (size_t)n_planes * n_items;
+    if ((rc = up.upload(st)) || (rc = pa.alloc(cells * sizeof(FocusSumA))) || (rc = pc.alloc(cells * sizeof(FocusSumC))) ||
+        (rc = d_stats.alloc((size_t)n_planes * BMO_FOCUS_STAT_N * 8)) || (rc = d_mid.alloc((size_t)n_planes * sizeof(double2))))
+        return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    const SplitWork* d_work = up.at<SplitWork>(o_work);
+    const double* d_off = up.at<double>(o_off);
+    hipLaunchKernelGGL(psf_focus_sums_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (FocusSumA*)pa.p);
+    hipLaunchKernelGGL(psf_focus_sums_reduce_kernel, dim3((unsigned)n_planes), dim3(256), 0, st, (int32_t)n_items, n_hits, (const FocusSumA*)pa.p, (double*)d_stats.p,
+                       (double2*)d_mid.p);
+    hipLaunchKernelGGL(psf_focus_spread_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (const double2*)d_mid.p, (FocusSumC*)pc.p);
+    hipLaunchKernelGGL(psf_focus_spread_reduce_kernel, dim3((unsigned)n_planes), dim3(256), 0, st, (int32_t)n_items, (const FocusSumC*)pc.p, (double*)d_stats.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, d_stats.p, (size_t)n_planes * BMO_FOCUS_STAT_N * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// the resident PSF rows of slot `detector`, for the single-call read-outs that take a device pointer: bmo_result_device_hits with the checks
+// of the _sweep forms
+extern "C" int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, const double** data, int64_t* count, int32_t* device) {
+    if (!res || !data || !count) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: bad argument");
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: bad detector slot");
+    if (res->kind == BMO_BEAM_GAUSSIAN)
+        return fail(BMO_ERR_UNSUPPORTED, "bmo_result_psf_rows: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
+        return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: the slot is not a PSFDetector's");
+    if (res->n_configs > 0) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: a sweep result holds the rows of several configurations");
+    *count = res->det_count[detector];
+    *data = res->det_data.p ? (const double*)res->det_data.p + 9 * res->det_offset[detector] : nullptr;
+    if (device) *device = res->device;
+    return BMO_OK;
+}

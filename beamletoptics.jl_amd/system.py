@@ -487,6 +487,41 @@ class EngineSolution:
         coef, info, _, self.readout_ms = abi.psf_zernike_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil)
         return coef[0], info[0]
 
+    def _psf_resident_rows(self, slot):
+        """(device pointer, count, device) of the resident rows of PSFDetector slot `slot` (bmo_result_psf_rows: the library refuses a slot that
+        is not a PSFDetector's and a GaussianBeamlet solution), for the single-call read-outs."""
+        p, cnt, dev = C.POINTER(C.c_double)(), C.c_int64(), C.c_int32()
+        abi.check(self.lib, self.lib.bmo_result_psf_rows(self.handle, int(slot), C.byref(p), C.byref(cnt), C.byref(dev)), "bmo_result_psf_rows")
+        return C.cast(p, C.c_void_p).value or 0, cnt.value, dev.value
+
+    def psf_focus_stats(self, slot, position, orientation, offsets, axis=None):
+        """bmo_psf_focus_stats on the resident rows of PSFDetector slot `slot` at the pose (position, orientation): the twelve spot statistics
+        (abi.FOCUS_* columns) of the rows propagated to the detector plane moved by each of `offsets` along `axis` (None: local y): [M, 12]."""
+        o = np.asarray(orientation, dtype=np.float64)
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        st, self.readout_ms = abi.psf_focus_stats(None, position, o[:, 0], o[:, 2], o[:, 1] if axis is None else axis, offsets, device=dev,
+                                                  hits_device_ptr=ptr, n_hits=cnt)
+        return st
+
+    def psf_through_focus(self, slot, position, orientation, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0):
+        """The through-focus PSF stack of the resident rows of PSFDetector slot `slot` (bmo_psf_focus_stats, then bmo_psf_through_focus on the
+        device pointer: no row leaves the device): (xs, zs, displacements, I[M, n, n], stats) as PSFDetector.through_focus gives them."""
+        o = np.asarray(orientation, dtype=np.float64)
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        ms = [0.0, 0.0]
+
+        def stats_fn(ax, off):
+            st, ms[0] = abi.psf_focus_stats(None, position, o[:, 0], o[:, 2], ax, off, device=dev, hits_device_ptr=ptr, n_hits=cnt)
+            return st
+
+        def stack_fn(d, xs, zs):
+            I, _, ms[1] = abi.psf_through_focus(None, position, o[:, 0], o[:, 2], d, xs, zs, device=dev, hits_device_ptr=ptr, n_hits=cnt)
+            return I
+
+        out = cp.psf_through_focus(stats_fn, stack_fn, o, offsets, n=n, axis=axis, follow=follow, window_plane=window_plane, crop_factor=crop_factor)
+        self.readout_ms = ms[0] + ms[1]
+        return out
+
     def psf_intensity(self, slot, position, orientation, n=100, **window_kw):
         """intensity(psf; ...) of the resident rows of PSFDetector slot `slot`: (xs, zs, I[n, n]).  The window comes from psf_stats
         (components.psf_axes_from_stats takes window_kw), the image from bmo_psf_intensity_sweep: only the image leaves the device."""

@@ -670,6 +670,69 @@ int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, int32_t n_con
                           const double* e2s, const double* ref_xz, const double* pupil, int32_t order, double* coef, double* info,
                           double* gram, double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Through-focus read-out: the PSF of the same rows on a stack of displaced sample grids, and the spot statistics of the rows propagated to
+ * a stack of planes, in one pass each over the rows where they lie.
+ *
+ * A PSF row carries its direction, so the field of bmo_psf_intensity at p + d depends on d through one factor per row:
+ *   F_m(i,j) = sum_h proj_h * cis(k_h * (opl_h + dot(p_ij - hit_h, dir_h))) * cis(k_h * dot(d_m, dir_h))
+ * which is what a PSFDetector translated by d_m and solved again reads (in a medium of index 1 the ray travels s further: hit' = hit + s dir,
+ * opl' = opl + s, and k (opl' + dot(p + d - hit', dir)) is unchanged).  The first factor is the sincos per (row, point) of one plane; the
+ * second is one sincos per (row, plane); a plane more costs one complex multiply-add per (row, point).
+ *
+ * bmo_psf_through_focus: hits, origin, e1, e2, xs, zs, n, device, kernel_ms as for bmo_psf_intensity.  displacements: [n_planes][3] world
+ * vectors d_m (host).  out_intensity: host, [n_planes][n*n], plane m element (i,j) at [m*n*n + i + n*j]; out_field: optional, the same
+ * order as (re, im) pairs.  FP64, no contraction, each expression left to right as written; per row r and point p = psf_point(xs[i], zs[j]):
+ *   l = ((px - hx) * dx + (py - hy) * dy) + (pz - hz) * dz,   phase = k * (opl + l),   (s, c) = sincos(phase)     (bmo_psf_intensity's)
+ *   t_re = proj * c,   t_im = proj * s
+ *   g_m = (d_mx * dx + d_my * dy) + d_mz * dz,   (u_im, u_re) = sincos(k * g_m)
+ *   re_m += t_re * u_re - t_im * u_im,   im_m += t_re * u_im + t_im * u_re
+ * over the rows in the blocked order of bmo_psf_intensity for the same (n_hits, n): the plane with d_m = 0 has the factor (1, 0) and
+ * equals bmo_psf_intensity's intensity bit for bit (its field as numbers: a zero may differ in sign).  n_hits = 0: zeros.
+ *
+ * bmo_psf_focus_stats: plane m is the detector plane moved to o_m = origin + offsets[m] * axis (per component), same e1, e2.  stats:
+ * [n_planes][BMO_FOCUS_STAT_N] at the BMO_FOCUS_STAT_* indices.  Per row and plane, each expression left to right as written:
+ *   nrm = e1 x e2   (nrm_x = e1y * e2z - e1z * e2y, nrm_y = e1z * e2x - e1x * e2z, nrm_z = e1x * e2y - e1y * e2x)
+ *   den = (dx * nrm_x + dy * nrm_y) + dz * nrm_z
+ *   s = (((omx - hx) * nrm_x + (omy - hy) * nrm_y) + (omz - hz) * nrm_z) / den
+ *   q = hit + s * dir (per component)
+ *   x = ((qx - omx) * e1x + (qy - omy) * e1y) + (qz - omz) * e1z,   z the same with e2
+ *   S = sum proj,   CX = (sum proj * x) / S,   CZ = (sum proj * z) / S,   X_MIN .. Z_MAX the extrema of x and z           (first pass)
+ *   ax = x - CX,  az = z - CZ about the COMPUTED centroid;   HWX = max |ax|,  HWZ = max |az|            (calc_local_lims at that plane)
+ *   r2 = ax * ax + az * az,   RMS_R = sqrt((sum proj * r2) / S),   MAX_R = sqrt(max r2)                                 (second pass)
+ * The sums run in the blocked order of bmo_psf_stats (it depends on n_hits only).  No rows, or a row with den = 0: N_ROWS = n_hits and NaN
+ * in the other columns of every plane.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than out_field / kernel_ms, n <= 0, n_planes <= 0,
+ * n_hits < 0.  There is no _sweep form and no GaussianBeamlet form.
+ *
+ * bmo_result_psf_rows: the device pointer, the row count and (optional) the device ordinal of the rows of PSFDetector slot `detector` still
+ * resident in `res`, to hand to the two calls above (hits_on_device != 0).  It is bmo_result_device_hits with the refusals of the _sweep
+ * read-outs: BMO_ERR_INVALID for a null pointer, a slot out of range or not a PSFDetector's, or a sweep result; BMO_ERR_UNSUPPORTED for a
+ * GaussianBeamlet result (three rows per beamlet).                                                                                      */
+enum bmo_focus_stat {
+    BMO_FOCUS_STAT_N_ROWS = 0,
+    BMO_FOCUS_STAT_S = 1,
+    BMO_FOCUS_STAT_CX = 2,
+    BMO_FOCUS_STAT_CZ = 3,
+    BMO_FOCUS_STAT_X_MIN = 4,
+    BMO_FOCUS_STAT_X_MAX = 5,
+    BMO_FOCUS_STAT_Z_MIN = 6,
+    BMO_FOCUS_STAT_Z_MAX = 7,
+    BMO_FOCUS_STAT_HWX = 8,
+    BMO_FOCUS_STAT_HWZ = 9,
+    BMO_FOCUS_STAT_RMS_R = 10,
+    BMO_FOCUS_STAT_MAX_R = 11
+};
+#define BMO_FOCUS_STAT_N 12
+int bmo_psf_through_focus(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                          const double e2[3], const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n,
+                          int32_t device, double* out_intensity, double* out_field, double* kernel_ms);
+int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                        const double e2[3], const double axis[3], const double* offsets, int32_t n_planes, int32_t device, double* stats,
+                        double* kernel_ms);
+int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, const double** data, int64_t* count, int32_t* device);
+
 #ifdef __cplusplus
 }
 #endif
