@@ -318,6 +318,52 @@ static int split_reduce(const SplitPlan& plan, const SplitCfg* d_cfg, int64_t n_
     return timer.stop(kernel_ms);
 }
 
+// the device and the device copy of the rows of a single call (d_rows holds an upload of host rows)
+static int single_rows(const char* who, const double*& rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, DevBuf& d_rows) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BMO_ERR_NO_DEVICE, std::string(who) + ": no HIP device (there is no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(BMO_ERR_INVALID, std::string(who) + ": bad device ordinal");
+    HIP_TRY(hipSetDevice(device));
+    if (!rows_on_device && n_rows > 0) {
+        const size_t bytes = (size_t)n_rows * (size_t)row_cols * sizeof(double);
+        if (int rc = d_rows.alloc(bytes)) return rc;
+        HIP_TRY(hipMemcpy(d_rows.p, rows, bytes, hipMemcpyHostToDevice));
+        rows = (const double*)d_rows.p;
+    }
+    return BMO_OK;
+}
+
+// What a read-out of resident rows checks of its result and slot before a device is touched: the slot exists and is a detector of `kind`
+// (BMO_OBJ_SPOTDETECTOR or BMO_OBJ_PSFDETECTOR); with refuse_gaussian, the result is no GaussianBeamlet solution.  n_configs < 0: not checked.
+static int slot_check(const char* who, const bmo_trace_result* res, int32_t detector, int32_t kind, bool refuse_gaussian, int32_t n_configs) {
+    const bool spot = kind == BMO_OBJ_SPOTDETECTOR;
+    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, std::string(who) + ": bad detector slot");
+    if (refuse_gaussian && res->kind == BMO_BEAM_GAUSSIAN)
+        return fail(BMO_ERR_UNSUPPORTED, std::string(who) + (spot ? ": a GaussianBeamlet solution has no Spotdetector rows (Spotdetector.jl:50 has no method for beamlets)"
+                                                                  : ": a GaussianBeamlet solution has three rows per beamlet, not PSF rows"));
+    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != kind)
+        return fail(BMO_ERR_INVALID, std::string(who) + (spot ? ": the slot is not a Spotdetector's" : ": the slot is not a PSFDetector's"));
+    if (n_configs >= 0 && n_configs != std::max<int32_t>(res->n_configs, 1))
+        return fail(BMO_ERR_INVALID, std::string(who) + ": n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    return BMO_OK;
+}
+
+// K rows of N columns as a configuration without rows reads: 0 in column 0 (the row count), NaN elsewhere
+static void fill_empty_stats(double* out, size_t K, size_t N) {
+    std::fill(out, out + K * N, std::nan(""));
+    for (size_t c = 0; c < K; ++c) out[c * N] = 0.0;
+}
+
+// poses [K][3] as the kernels read them
+static std::vector<PsfPose> psf_poses(size_t K, const double* origins, const double* e1s, const double* e2s) {
+    std::vector<PsfPose> pose(K);
+    for (size_t c = 0; c < K; ++c) {
+        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
+        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
+    }
+    return pose;
+}
+
 // The PSF of the K = R.count.size() configurations from the device rows `hits`: poses [K][3], axes [K][n], outputs [K][n * n].
 static int psf_read(const double* hits, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* xs, const double* zs, int32_t n,
                     double* out_intensity, double* out_field, double* kernel_ms) {
@@ -325,11 +371,7 @@ static int psf_read(const double* hits, const Ranges& R, const double* origins, 
     const int64_t n_pts = (int64_t)n * n;
     hipStream_t st = 0;
     const SplitPlan plan(R, (unsigned)((n_pts + 255) / 256), n_pts, psf_splits);
-    std::vector<PsfPose> pose(K);
-    for (size_t c = 0; c < K; ++c) {
-        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
-        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
-    }
+    const std::vector<PsfPose> pose = psf_poses(K, origins, e1s, e2s);
     Packed up;
     const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_pose = up.add(pose), o_xs = up.add(xs, K * n), o_zs = up.add(zs, K * n);
     DevBuf d_int, d_field;
@@ -355,16 +397,8 @@ extern "C" int bmo_psf_intensity(const double* hits, int64_t n_hits, int32_t hit
                                  const double* xs, const double* zs, int32_t n, int32_t device, double* out_intensity, double* out_field, double* kernel_ms) {
     if (!origin || !e1 || !e2 || !xs || !zs || !out_intensity || n <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
         return fail(BMO_ERR_INVALID, "bmo_psf_intensity: bad argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BMO_ERR_NO_DEVICE, "bmo_psf_intensity: no HIP device (there is no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(BMO_ERR_INVALID, "bmo_psf_intensity: bad device ordinal");
-    HIP_TRY(hipSetDevice(device));
     DevBuf d_hits;
-    if (!hits_on_device && n_hits > 0) {
-        if (int rc = d_hits.alloc((size_t)n_hits * 9 * sizeof(double))) return rc;
-        HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t)n_hits * 9 * sizeof(double), hipMemcpyHostToDevice));
-        hits = (const double*)d_hits.p;
-    }
+    if (int rc = single_rows("bmo_psf_intensity", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
     return psf_read(hits, Ranges{{0}, {n_hits}}, origin, e1, e2, xs, zs, n, out_intensity, out_field, kernel_ms);
 }
 
@@ -373,11 +407,7 @@ extern "C" int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, 
                                        const double* e2s, const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field,
                                        double* kernel_ms) {
     if (!res || !origins || !e1s || !e2s || !xs || !zs || !out_intensity || n <= 0) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad argument");
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: bad detector slot");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
-        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: the slot is not a PSFDetector's");
-    if (n_configs != std::max<int32_t>(res->n_configs, 1))
-        return fail(BMO_ERR_INVALID, "bmo_psf_intensity_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (int rc = slot_check("bmo_psf_intensity_sweep", res, detector, BMO_OBJ_PSFDETECTOR, false, n_configs)) return rc;  // Gaussian results are not refused here
     if (kernel_ms) *kernel_ms = 0.0;
     const int64_t n_pts = (int64_t)n * n;
     const int64_t H = res->det_count[detector];
@@ -781,7 +811,9 @@ extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t dete
 //     the result does not depend on the order of the adds.  Lanes of a wave that hit the same bin are counted by one of them (spot_add).
 //   * statistics: two accumulate kernels with a per-configuration reduce each, queued behind one synchronisation; the centroid stays on
 //     the device for the second pass.  Lane l of a workgroup sums rows h0 + l, h0 + l + 256, ... sequentially, a fixed tree runs over the
-//     lanes of a wave and the four waves, the splits are summed in split order: deterministic for a given row count.
+//     lanes of a wave and the four waves, the splits are summed in split order: deterministic for a given row count.  The sums of a pass
+//     are a sum record (below), which the wavefront, Zernike and focus statistics share with this read-out, as they do rows_plan,
+//     rows_items and single_rows.
 namespace {
 
 constexpr int SPOT_MIN_SPLIT = 2048;   // rows: shorter splits would spend their time on the histogram, not on rows
@@ -856,140 +888,205 @@ __global__ __launch_bounds__(256) void spot_image_kernel(const double* __restric
     }
 }
 
-// The sums of the workgroup's lanes by a fixed tree: over the lanes of a wave, then (w0 + w1) + (w2 + w3).  Thread 0 returns the result.
-struct SpotAdd {
+// --------------------------------------------------------------------------------------------------------------------
+// Sum records: what the statistics passes of the spot, wavefront, Zernike and focus read-outs share.  A pass keeps a few running sums,
+// minima and maxima.  SUM_RECORD declares them once, as a list F(name, operation); the record has one double per field, and the identity,
+// the merge of two partial results, the reduction over the workgroup and the fold of a configuration's work items all come from that list.
+// An accumulate kernel starts every lane from sum_identity, updates the named fields with its own arithmetic and writes sum_wg_reduce of
+// the record, one per work item; sum_reduce_kernel folds the work items of a configuration in split order and hands the result to a Finish.
+struct SumAdd {
+    static __device__ double identity() { return 0.0; }
     __device__ double operator()(double a, double b) const { return a + b; }
 };
-struct SpotMin {
+struct SumMin {
+    static __device__ double identity() { return kinf(); }
     __device__ double operator()(double a, double b) const { return b < a ? b : a; }
 };
-struct SpotMax {
+struct SumMax {
+    static __device__ double identity() { return -kinf(); }
     __device__ double operator()(double a, double b) const { return b > a ? b : a; }
 };
-template <class Op>
-__device__ __forceinline__ double spot_wg_reduce(double v, Op op, double* sh) {
-    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_down(v, off));
+// the maximum of a quantity that is never negative (a half-width, a squared radius): it starts at 0, so rows that compare false (NaN)
+// leave 0 and not -inf
+struct SumMax0 : SumMax {
+    static __device__ double identity() { return 0.0; }
+};
+
+#define SUM_FIELD_DECL(name, Op) double name;
+#define SUM_FIELD_COUNT(name, Op) +1
+#define SUM_FIELD_VISIT(name, Op) f(a.name, b.name, Op{});
+#define SUM_RECORD(Name, FIELDS)                                                                         \
+    struct Name {                                                                                        \
+        FIELDS(SUM_FIELD_DECL)                                                                           \
+        static constexpr int N = 0 FIELDS(SUM_FIELD_COUNT);                                              \
+        /* f(field of a, field of b, the field's operation) for every field in the order of the list */  \
+        template <class A, class B, class F>                                                             \
+        static __device__ __forceinline__ void visit(A& a, B& b, F&& f) {                                \
+            FIELDS(SUM_FIELD_VISIT)                                                                      \
+        }                                                                                                \
+    };                                                                                                   \
+    static_assert(sizeof(Name) == Name::N * sizeof(double), "a sum record is its fields")
+
+template <class R>
+__device__ __forceinline__ R sum_identity() {
+    R r;
+    R::visit(r, r, [](double& v, const double&, auto op) { v = op.identity(); });
+    return r;
+}
+// acc and other merged field by field, the accumulator on the left
+template <class R>
+__device__ __forceinline__ void sum_merge(R& acc, const R& other) {
+    R::visit(acc, other, [](double& a, const double& b, auto op) { a = op(a, b); });
+}
+// The records of the workgroup's 256 lanes merged by a fixed tree per field: over the lanes of a wave, then (w0 + w1) + (w2 + w3).  Thread 0
+// returns the result.  Every lane calls it (it syncs); all fields cross LDS between one pair of barriers.
+template <class R>
+__device__ __forceinline__ R sum_wg_reduce(R r) {
+    __shared__ double sh[R::N][4];
+    R::visit(r, r, [](double& v, const double&, auto op) {
+        for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_down(v, off));
+    });
     __syncthreads();  // sh is free again
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    if ((threadIdx.x & 63) == 0) {
+        int q = 0;
+        R::visit(r, r, [&](double& v, const double&, auto) { sh[q++][threadIdx.x >> 6] = v; });
+    }
     __syncthreads();
-    return op(op(sh[0], sh[1]), op(sh[2], sh[3]));
+    int q = 0;
+    R::visit(r, r, [&](double& v, const double&, auto op) {
+        v = op(op(sh[q][0], sh[q][1]), op(sh[q][2], sh[q][3]));
+        ++q;
+    });
+    return r;
 }
 
-struct SpotSum1 {
-    double sx, sz, x_min, x_max, z_min, z_max;
-};
-struct SpotSum2 {
-    double xx, zz, xz, r2;
-};
+// The records first .. first + n - 1 folded in that order by thread 0 of the workgroup, which returns the result.  A configuration of 2 048
+// splits would keep one thread waiting on 2 048 dependent trips to memory; instead the workgroup copies them to `lds` with coalesced loads,
+// SUM_FOLD_CHUNK at a time, and thread 0 folds them from there.  Every thread of the workgroup calls it (it syncs).
+constexpr int SUM_FOLD_CHUNK = 512;
+template <class R>
+__device__ __forceinline__ R sum_fold(const R* __restrict__ partial, int64_t first, int n, double* lds) {
+    R acc = sum_identity<R>();
+    for (int s0 = 0; s0 < n; s0 += SUM_FOLD_CHUNK) {
+        const int cnt = n - s0 < SUM_FOLD_CHUNK ? n - s0 : SUM_FOLD_CHUNK;
+        const double* src = (const double*)(partial + first + s0);
+        __syncthreads();
+        for (int q = threadIdx.x; q < cnt * R::N; q += blockDim.x) lds[q] = src[q];
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int i = 0; i < cnt; ++i) sum_merge(acc, *(const R*)(lds + i * R::N));
+    }
+    return acc;
+}
+
+// Range blockIdx.x of `cfg` (a configuration, or a plane of the focus statistics): its records folded in split order, then thread 0 calls
+// finish(blockIdx.x, record), or finish.empty(blockIdx.x) for a range without records.  The functor owns what the passes differ in: what
+// goes to the caller's statistics and what stays on the device for the next pass.
+template <class R, class Finish>
+__global__ void sum_reduce_kernel(const SplitCfg* __restrict__ cfg, const R* __restrict__ partial, Finish finish) {
+    __shared__ double lds[SUM_FOLD_CHUNK * R::N];
+    const int32_t c = (int32_t)blockIdx.x;
+    const SplitCfg C = cfg[c];
+    if (C.n_splits == 0) {
+        if (threadIdx.x == 0) finish.empty(c);
+        return;
+    }
+    const R r = sum_fold(partial, C.first_work, C.n_splits, lds);
+    if (threadIdx.x == 0) finish(c, r);
+}
+// the reduce of the n ranges of `cfg` over the records R of `partial`: one workgroup per range
+template <class R, class Finish>
+static void sum_reduce(unsigned n, hipStream_t st, const SplitCfg* cfg, const DevBuf& partial, Finish finish) {
+    hipLaunchKernelGGL((sum_reduce_kernel<R, Finish>), dim3(n), dim3(256), 0, st, cfg, (const R*)partial.p, finish);
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// Spot statistics
+#define SPOT_SUM1(F) F(sx, SumAdd) F(sz, SumAdd) F(x_min, SumMin) F(x_max, SumMax) F(z_min, SumMin) F(z_max, SumMax)
+#define SPOT_SUM2(F) F(xx, SumAdd) F(zz, SumAdd) F(xz, SumAdd) F(r2, SumMax0)
+SUM_RECORD(SpotSum1, SPOT_SUM1);
+SUM_RECORD(SpotSum2, SPOT_SUM2);
 
 // first pass of work item blockIdx.x: sums and extrema of its rows
 __global__ __launch_bounds__(256) void spot_centroid_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
                                                             SpotSum1* __restrict__ partial) {
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
-    double sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
+    SpotSum1 a = sum_identity<SpotSum1>();
     for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
         const double* r = rows + h * cols;
         const double x = r[0], z = r[1];
-        sx += x;
-        sz += z;
-        x_min = x < x_min ? x : x_min;
-        x_max = x > x_max ? x : x_max;
-        z_min = z < z_min ? z : z_min;
-        z_max = z > z_max ? z : z_max;
+        a.sx += x;
+        a.sz += z;
+        a.x_min = x < a.x_min ? x : a.x_min;
+        a.x_max = x > a.x_max ? x : a.x_max;
+        a.z_min = z < a.z_min ? z : a.z_min;
+        a.z_max = z > a.z_max ? z : a.z_max;
     }
-    SpotSum1 s;
-    s.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
-    s.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
-    s.x_min = spot_wg_reduce(x_min, SpotMin{}, sh);
-    s.x_max = spot_wg_reduce(x_max, SpotMax{}, sh);
-    s.z_min = spot_wg_reduce(z_min, SpotMin{}, sh);
-    s.z_max = spot_wg_reduce(z_max, SpotMax{}, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    a = sum_wg_reduce(a);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
-// configuration c: its splits summed in split order; N, the centroid and the extrema go to stats[c], the centroid to cent[c] for the second pass
-__global__ void spot_centroid_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, int32_t K, const SpotSum1* __restrict__ partial,
-                                            double* __restrict__ stats, double2* __restrict__ cent) {
-    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (c >= K) return;
-    double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
-    const int64_t n = count[c];
-    out[BMO_SPOT_STAT_N_ROWS] = (double)n;
-    if (n == 0) {
+// N, the centroid and the extrema go to stats[c], the centroid to cent[c] for the second pass
+struct SpotCentroidFinish {
+    const int64_t* count;
+    double* stats;
+    double2* cent;
+    __device__ void empty(int32_t c) const {
+        double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
+        out[BMO_SPOT_STAT_N_ROWS] = 0.0;
         for (int q = 1; q < BMO_SPOT_STAT_N; ++q) out[q] = knan();
         cent[c] = make_double2(0.0, 0.0);
-        return;
     }
-    const SplitCfg C = cfg[c];
-    double sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
-    for (int s = 0; s < C.n_splits; ++s) {
-        const SpotSum1 p = partial[C.first_work + s];
-        sx += p.sx;
-        sz += p.sz;
-        x_min = p.x_min < x_min ? p.x_min : x_min;
-        x_max = p.x_max > x_max ? p.x_max : x_max;
-        z_min = p.z_min < z_min ? p.z_min : z_min;
-        z_max = p.z_max > z_max ? p.z_max : z_max;
+    __device__ void operator()(int32_t c, const SpotSum1& s) const {
+        double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
+        const int64_t n = count[c];
+        const double cx = s.sx / (double)n, cz = s.sz / (double)n;
+        out[BMO_SPOT_STAT_N_ROWS] = (double)n;
+        out[BMO_SPOT_STAT_CX] = cx;
+        out[BMO_SPOT_STAT_CZ] = cz;
+        out[BMO_SPOT_STAT_X_MIN] = s.x_min;
+        out[BMO_SPOT_STAT_X_MAX] = s.x_max;
+        out[BMO_SPOT_STAT_Z_MIN] = s.z_min;
+        out[BMO_SPOT_STAT_Z_MAX] = s.z_max;
+        cent[c] = make_double2(cx, cz);
     }
-    const double cx = sx / (double)n, cz = sz / (double)n;
-    out[BMO_SPOT_STAT_CX] = cx;
-    out[BMO_SPOT_STAT_CZ] = cz;
-    out[BMO_SPOT_STAT_X_MIN] = x_min;
-    out[BMO_SPOT_STAT_X_MAX] = x_max;
-    out[BMO_SPOT_STAT_Z_MIN] = z_min;
-    out[BMO_SPOT_STAT_Z_MAX] = z_max;
-    cent[c] = make_double2(cx, cz);
-}
+};
 
 // second pass of work item blockIdx.x: central moments of its rows about the computed centroid of its configuration
 __global__ __launch_bounds__(256) void spot_moments_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
                                                            const double2* __restrict__ cent, SpotSum2* __restrict__ partial) {
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const double2 c = cent[W.cfg];
-    double xx = 0.0, zz = 0.0, xz = 0.0, r2 = 0.0;
+    SpotSum2 a = sum_identity<SpotSum2>();
     for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
         const double* r = rows + h * cols;
         const double dx = r[0] - c.x, dz = r[1] - c.y;
-        const double a = dx * dx, b = dz * dz;
-        xx += a;
-        zz += b;
-        xz += dx * dz;
-        const double q = a + b;
-        r2 = q > r2 ? q : r2;
+        const double xx = dx * dx, zz = dz * dz;
+        a.xx += xx;
+        a.zz += zz;
+        a.xz += dx * dz;
+        const double q = xx + zz;
+        a.r2 = q > a.r2 ? q : a.r2;
     }
-    SpotSum2 s;
-    s.xx = spot_wg_reduce(xx, SpotAdd{}, sh);
-    s.zz = spot_wg_reduce(zz, SpotAdd{}, sh);
-    s.xz = spot_wg_reduce(xz, SpotAdd{}, sh);
-    s.r2 = spot_wg_reduce(r2, SpotMax{}, sh);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    a = sum_wg_reduce(a);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
-__global__ void spot_moments_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, int32_t K, const SpotSum2* __restrict__ partial,
-                                           double* __restrict__ stats) {
-    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (c >= K) return;
-    const int64_t n = count[c];
-    if (n == 0) return;  // NaN already
-    const SplitCfg C = cfg[c];
-    double xx = 0.0, zz = 0.0, xz = 0.0, r2 = 0.0;
-    for (int s = 0; s < C.n_splits; ++s) {
-        const SpotSum2 p = partial[C.first_work + s];
-        xx += p.xx;
-        zz += p.zz;
-        xz += p.xz;
-        r2 = p.r2 > r2 ? p.r2 : r2;
+struct SpotMomentsFinish {
+    const int64_t* count;
+    double* stats;
+    __device__ void empty(int32_t) const {}  // NaN already
+    __device__ void operator()(int32_t c, const SpotSum2& s) const {
+        double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
+        const int64_t n = count[c];
+        const double mxx = s.xx / (double)n, mzz = s.zz / (double)n;
+        out[BMO_SPOT_STAT_MXX] = mxx;
+        out[BMO_SPOT_STAT_MZZ] = mzz;
+        out[BMO_SPOT_STAT_MXZ] = s.xz / (double)n;
+        out[BMO_SPOT_STAT_RMS_R] = sqrt(mxx + mzz);
+        out[BMO_SPOT_STAT_GEO_R] = sqrt(s.r2);
     }
-    double* out = stats + (int64_t)c * BMO_SPOT_STAT_N;
-    const double mxx = xx / (double)n, mzz = zz / (double)n;
-    out[BMO_SPOT_STAT_MXX] = mxx;
-    out[BMO_SPOT_STAT_MZZ] = mzz;
-    out[BMO_SPOT_STAT_MXZ] = xz / (double)n;
-    out[BMO_SPOT_STAT_RMS_R] = sqrt(mxx + mzz);
-    out[BMO_SPOT_STAT_GEO_R] = sqrt(r2);
-}
+};
 
 }  // namespace
 
@@ -1006,13 +1103,14 @@ static void spot_splits(int64_t n_rows, int64_t& n_splits, int64_t& rows_per_spl
     n_splits = n_rows > 0 ? (n_rows + rows_per_split - 1) / rows_per_split : 1;
 }
 
-// the plan of a spot read-out: splits by spot_splits (which knows no point blocks), no launch batching
-static SplitPlan spot_plan(const Ranges& R) {
+// the plan of a read-out that walks rows without a grid of points (the spot image and every statistics pass): splits by spot_splits
+// (which knows no point blocks), no launch batching
+static SplitPlan rows_plan(const Ranges& R) {
     return SplitPlan(R, 1, [](int64_t n_rows, unsigned, int64_t& n_splits, int64_t& rows_per_split) { spot_splits(n_rows, n_splits, rows_per_split); });
 }
 
-// the work items of a spot read-out on the grid's x dimension
-static int spot_items(const SplitPlan& plan, const char* who, unsigned& n_items) {
+// the work items of such a read-out on the grid's x dimension
+static int rows_items(const SplitPlan& plan, const char* who, unsigned& n_items) {
     if (plan.work.size() > (size_t)0x7fffffff) return fail(BMO_ERR_LIMIT, std::string(who) + ": more work items than one launch holds");
     for (int64_t per : plan.per_split)
         if (per > (int64_t)0xffffffff) return fail(BMO_ERR_LIMIT, std::string(who) + ": more rows per split than a 32-bit counter holds");
@@ -1035,9 +1133,9 @@ static int spot_image_read(const double* rows, int32_t cols, const Ranges& R, co
     const size_t K = R.count.size();
     const int64_t n_bins = (int64_t)nx * nz;
     hipStream_t st = 0;
-    const SplitPlan plan = spot_plan(R);
+    const SplitPlan plan = rows_plan(R);
     unsigned n_items = 0;
-    if (int rc = spot_items(plan, who, n_items)) return rc;
+    if (int rc = rows_items(plan, who, n_items)) return rc;
     Packed up;
     const size_t o_work = up.add(plan.work), o_win = up.add(win);
     DevBuf d_img, d_out;
@@ -1065,9 +1163,9 @@ static int spot_image_read(const double* rows, int32_t cols, const Ranges& R, co
 static int spot_stats_read(const double* rows, int32_t cols, const Ranges& R, double* stats, double* kernel_ms, const char* who) {
     const size_t K = R.count.size();
     hipStream_t st = 0;
-    const SplitPlan plan = spot_plan(R);
+    const SplitPlan plan = rows_plan(R);
     unsigned n_items = 0;
-    if (int rc = spot_items(plan, who, n_items)) return rc;
+    if (int rc = rows_items(plan, who, n_items)) return rc;
     Packed up;
     const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count);
     DevBuf p1, p2, d_stats, d_cent;
@@ -1077,44 +1175,16 @@ static int spot_stats_read(const double* rows, int32_t cols, const Ranges& R, do
         return rc;
     EventTimer timer;
     if ((rc = timer.start(st))) return rc;
-    const dim3 kb((unsigned)((K + 255) / 256));
+    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
+    const int64_t* d_count = up.at<int64_t>(o_count);
     if (n_items > 0)
         hipLaunchKernelGGL(spot_centroid_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (SpotSum1*)p1.p);
-    hipLaunchKernelGGL(spot_centroid_reduce_kernel, kb, dim3(256), 0, st, up.at<SplitCfg>(o_cfg), up.at<int64_t>(o_count), (int32_t)K, (const SpotSum1*)p1.p,
-                       (double*)d_stats.p, (double2*)d_cent.p);
+    sum_reduce<SpotSum1>((unsigned)K, st, d_cfg, p1, SpotCentroidFinish{d_count, (double*)d_stats.p, (double2*)d_cent.p});
     if (n_items > 0)
         hipLaunchKernelGGL(spot_moments_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (const double2*)d_cent.p, (SpotSum2*)p2.p);
-    hipLaunchKernelGGL(spot_moments_reduce_kernel, kb, dim3(256), 0, st, up.at<SplitCfg>(o_cfg), up.at<int64_t>(o_count), (int32_t)K, (const SpotSum2*)p2.p,
-                       (double*)d_stats.p);
+    sum_reduce<SpotSum2>((unsigned)K, st, d_cfg, p2, SpotMomentsFinish{d_count, (double*)d_stats.p});
     if ((rc = timer.stop(kernel_ms))) return rc;
     HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_SPOT_STAT_N * 8, hipMemcpyDeviceToHost));
-    return BMO_OK;
-}
-
-// the device and the device copy of the rows of a single call (d_rows holds an upload of host rows)
-static int spot_single_rows(const char* who, const double*& rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, DevBuf& d_rows) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(BMO_ERR_NO_DEVICE, std::string(who) + ": no HIP device (there is no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(BMO_ERR_INVALID, std::string(who) + ": bad device ordinal");
-    HIP_TRY(hipSetDevice(device));
-    if (!rows_on_device && n_rows > 0) {
-        const size_t bytes = (size_t)n_rows * (size_t)row_cols * sizeof(double);
-        if (int rc = d_rows.alloc(bytes)) return rc;
-        HIP_TRY(hipMemcpy(d_rows.p, rows, bytes, hipMemcpyHostToDevice));
-        rows = (const double*)d_rows.p;
-    }
-    return BMO_OK;
-}
-
-// what the _sweep forms check of their result and slot before a device is touched
-static int spot_slot_check(const char* who, const bmo_trace_result* res, int32_t detector, int32_t n_configs) {
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, std::string(who) + ": bad detector slot");
-    if (res->kind == BMO_BEAM_GAUSSIAN)
-        return fail(BMO_ERR_UNSUPPORTED, std::string(who) + ": a GaussianBeamlet solution has no Spotdetector rows (Spotdetector.jl:50 has no method for beamlets)");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_SPOTDETECTOR)
-        return fail(BMO_ERR_INVALID, std::string(who) + ": the slot is not a Spotdetector's");
-    if (n_configs != std::max<int32_t>(res->n_configs, 1))
-        return fail(BMO_ERR_INVALID, std::string(who) + ": n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
     return BMO_OK;
 }
 
@@ -1128,7 +1198,7 @@ extern "C" int bmo_spot_image(const double* rows, int64_t n_rows, int32_t row_co
     if (!spot_window(window, nx, nz, win[0])) return fail(BMO_ERR_INVALID, "bmo_spot_image: the window must be finite with x1 > x0 and z1 > z0");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_rows;
-    if (int rc = spot_single_rows("bmo_spot_image", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
+    if (int rc = single_rows("bmo_spot_image", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
     return spot_image_read(rows, row_cols, Ranges{{0}, {n_rows}}, win, nx, nz, image, outside, kernel_ms, "bmo_spot_image");
 }
 
@@ -1136,7 +1206,7 @@ extern "C" int bmo_spot_image_sweep(bmo_trace_result* res, int32_t detector, int
                                     int64_t* outside, double* kernel_ms) {
     if (!res || !windows || !image || !outside || !spot_image_shape_ok(nx, nz))
         return fail(BMO_ERR_INVALID, "bmo_spot_image_sweep: bad argument (null pointer, nx or nz <= 0 or nx * nz >= 2^31)");
-    if (int rc = spot_slot_check("bmo_spot_image_sweep", res, detector, n_configs)) return rc;
+    if (int rc = slot_check("bmo_spot_image_sweep", res, detector, BMO_OBJ_SPOTDETECTOR, true, n_configs)) return rc;
     std::vector<SpotWindow> win((size_t)n_configs);
     for (int32_t c = 0; c < n_configs; ++c)
         if (!spot_window(windows + 4 * c, nx, nz, win[(size_t)c]))
@@ -1159,21 +1229,17 @@ extern "C" int bmo_spot_stats(const double* rows, int64_t n_rows, int32_t row_co
         return fail(BMO_ERR_INVALID, "bmo_spot_stats: bad argument (null pointer, row_cols outside 2..9)");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_rows;
-    if (int rc = spot_single_rows("bmo_spot_stats", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
+    if (int rc = single_rows("bmo_spot_stats", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
     return spot_stats_read(rows, row_cols, Ranges{{0}, {n_rows}}, stats, kernel_ms, "bmo_spot_stats");
 }
 
 extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, double* stats, double* kernel_ms) {
     if (!res || !stats) return fail(BMO_ERR_INVALID, "bmo_spot_stats_sweep: bad argument");
-    if (int rc = spot_slot_check("bmo_spot_stats_sweep", res, detector, n_configs)) return rc;
+    if (int rc = slot_check("bmo_spot_stats_sweep", res, detector, BMO_OBJ_SPOTDETECTOR, true, n_configs)) return rc;
     if (kernel_ms) *kernel_ms = 0.0;
     const int64_t H = res->det_count[detector];
     if (H == 0) {  // every configuration reads like a call with n_rows = 0
-        for (int32_t c = 0; c < n_configs; ++c) {
-            double* out = stats + (size_t)c * BMO_SPOT_STAT_N;
-            std::fill(out, out + BMO_SPOT_STAT_N, std::nan(""));
-            out[BMO_SPOT_STAT_N_ROWS] = 0.0;
-        }
+        fill_empty_stats(stats, (size_t)n_configs, BMO_SPOT_STAT_N);
         return BMO_OK;
     }
     HIP_TRY(hipSetDevice(res->device));
@@ -1185,26 +1251,24 @@ extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int
 // ====================================================================================================================
 // Wavefront read-out: the statistics of a PSFDetector's rows (include/bmo.h "Wavefront read-out"): the proj-weighted centroid, the extrema
 // and half-widths of calc_local_lims (PSFDetector.jl:115-140), and the wavefront error and Strehl ratio at a reference point of the
-// detector plane.  The plumbing of the spot statistics (slot_ranges, spot_plan, work items on the grid's x dimension, lane / shuffle / wave
-// / split order of the sums), three accumulate passes with a per-configuration reduce each, queued behind one synchronisation:
+// detector plane.  The plumbing of the spot statistics (slot_ranges, rows_plan, work items on the grid's x dimension, sum records: lane /
+// shuffle / wave / split order of the sums), three accumulate passes with a per-configuration reduce each, queued behind one synchronisation:
 //   A  N, S, sum proj x, sum proj z, the extrema of x, z and k; its reduce leaves the centroid and the reference point p on the device
 //   B  half-widths about the computed centroid, sum proj W, F = sum proj cis(k W); writes (proj, W) of every row to a scratch column
 //   C  sum proj (W - W_MEAN)^2 and the extrema of W - W_MEAN, from the 16-byte scratch rows instead of the 72-byte rows
-// A reduce is one workgroup per configuration: it stages the configuration's partial sums through LDS and thread 0 folds them in split order
-// (psf_stats_fold).
+// A reduce is sum_reduce_kernel with the pass's Finish: one workgroup per configuration stages the configuration's partial sums through LDS
+// and thread 0 folds them in split order (sum_fold).
 // Passes A and B use all nine columns: they stage tiles of 256 rows through LDS with coalesced loads (psf_stage_rows) and lane l then
 // reads row l of the tile (a 72-byte stride: the lanes of a half-wave fall on distinct even banks).
 namespace {
 
-struct PsfStatSumA {
-    double s, sx, sz, x_min, x_max, z_min, z_max, k_min, k_max;
-};
-struct PsfStatSumB {
-    double hwx, hwz, sw, re, im;
-};
-struct PsfStatSumC {
-    double var, lo, hi;
-};
+#define PSF_STAT_SUM_A(F) \
+    F(s, SumAdd) F(sx, SumAdd) F(sz, SumAdd) F(x_min, SumMin) F(x_max, SumMax) F(z_min, SumMin) F(z_max, SumMax) F(k_min, SumMin) F(k_max, SumMax)
+#define PSF_STAT_SUM_B(F) F(hwx, SumMax0) F(hwz, SumMax0) F(sw, SumAdd) F(re, SumAdd) F(im, SumAdd)
+#define PSF_STAT_SUM_C(F) F(var, SumAdd) F(lo, SumMin) F(hi, SumMax)
+SUM_RECORD(PsfStatSumA, PSF_STAT_SUM_A);
+SUM_RECORD(PsfStatSumB, PSF_STAT_SUM_B);
+SUM_RECORD(PsfStatSumC, PSF_STAT_SUM_C);
 // what the later passes need of configuration c
 struct PsfStatMid {
     double cx, cz, w_mean;
@@ -1220,10 +1284,9 @@ __device__ __forceinline__ double psf_local(const double* r, const d3& o, const 
 __global__ __launch_bounds__(256) void psf_stats_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                              PsfStatSumA* __restrict__ partial) {
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
-    double s = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf(), k_min = kinf(), k_max = -kinf();
+    PsfStatSumA a = sum_identity<PsfStatSumA>();
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
         psf_stage_rows(hits, base, cnt, tile);
@@ -1231,224 +1294,145 @@ __global__ __launch_bounds__(256) void psf_stats_sums_kernel(const double* __res
             const double* r = tile + 9 * threadIdx.x;
             const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
             const double w = r[7], k = r[8];
-            s += w;
-            sx += w * x;
-            sz += w * z;
-            x_min = x < x_min ? x : x_min;
-            x_max = x > x_max ? x : x_max;
-            z_min = z < z_min ? z : z_min;
-            z_max = z > z_max ? z : z_max;
-            k_min = k < k_min ? k : k_min;
-            k_max = k > k_max ? k : k_max;
+            a.s += w;
+            a.sx += w * x;
+            a.sz += w * z;
+            a.x_min = x < a.x_min ? x : a.x_min;
+            a.x_max = x > a.x_max ? x : a.x_max;
+            a.z_min = z < a.z_min ? z : a.z_min;
+            a.z_max = z > a.z_max ? z : a.z_max;
+            a.k_min = k < a.k_min ? k : a.k_min;
+            a.k_max = k > a.k_max ? k : a.k_max;
         }
     }
-    PsfStatSumA a;
-    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
-    a.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
-    a.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
-    a.x_min = spot_wg_reduce(x_min, SpotMin{}, sh);
-    a.x_max = spot_wg_reduce(x_max, SpotMax{}, sh);
-    a.z_min = spot_wg_reduce(z_min, SpotMin{}, sh);
-    a.z_max = spot_wg_reduce(z_max, SpotMax{}, sh);
-    a.k_min = spot_wg_reduce(k_min, SpotMin{}, sh);
-    a.k_max = spot_wg_reduce(k_max, SpotMax{}, sh);
+    a = sum_wg_reduce(a);
     if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
-// The partial sums of one configuration folded in split order by thread 0 of the workgroup.  A configuration of 2 048 splits would keep one
-// thread waiting on 2 048 dependent trips to memory; instead the workgroup copies them to `lds` with coalesced loads, PSF_FOLD_CHUNK at a
-// time, and thread 0 folds them from there.  Every thread of the workgroup calls it (it syncs); `fold` runs on thread 0 only.
-constexpr int PSF_FOLD_CHUNK = 512;
-template <class P, class Fold>
-__device__ __forceinline__ void psf_stats_fold(const P* __restrict__ partial, const SplitCfg& C, double* lds, Fold&& fold) {
-    constexpr int W = (int)(sizeof(P) / sizeof(double));
-    for (int s0 = 0; s0 < C.n_splits; s0 += PSF_FOLD_CHUNK) {
-        const int cnt = C.n_splits - s0 < PSF_FOLD_CHUNK ? C.n_splits - s0 : PSF_FOLD_CHUNK;
-        const double* src = (const double*)(partial + C.first_work + s0);
-        __syncthreads();
-        for (int q = threadIdx.x; q < cnt * W; q += blockDim.x) lds[q] = src[q];
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 0; i < cnt; ++i) fold(*(const P*)(lds + i * W));
+// N, S, the centroid, the extrema and the reference point go to stats[c], what the later passes need to mid[c].  ref_xz: nullptr (the
+// centroid) or [K][2]
+struct PsfStatSumsFinish {
+    const int64_t* count;
+    const PsfPose* pose;
+    const double* ref_xz;
+    double* stats;
+    PsfStatMid* mid;
+    __device__ void empty(int32_t c) const {
+        double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+        out[BMO_PSF_STAT_N_ROWS] = 0.0;
+        for (int q = 1; q < BMO_PSF_STAT_N; ++q) out[q] = knan();
+        mid[c] = PsfStatMid{0.0, 0.0, 0.0, d3{0.0, 0.0, 0.0}};
     }
-}
-
-// configuration blockIdx.x: the splits of pass A in split order; N, S, the centroid, the extrema and the reference point go to stats[c], what the
-// later passes need to mid[c].  ref_xz: nullptr (the centroid) or [K][2]
-__global__ void psf_stats_sums_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfPose* __restrict__ pose,
-                                             const double* __restrict__ ref_xz, const PsfStatSumA* __restrict__ partial, double* __restrict__ stats,
-                                             PsfStatMid* __restrict__ mid) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumA) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;  // one workgroup per configuration
-    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
-    const int64_t n = count[c];
-    if (n == 0) {
-        if (threadIdx.x == 0) {
-            out[BMO_PSF_STAT_N_ROWS] = 0.0;
-            for (int q = 1; q < BMO_PSF_STAT_N; ++q) out[q] = knan();
-            mid[c] = PsfStatMid{0.0, 0.0, 0.0, d3{0.0, 0.0, 0.0}};
-        }
-        return;
+    __device__ void operator()(int32_t c, const PsfStatSumA& a) const {
+        double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+        out[BMO_PSF_STAT_N_ROWS] = (double)count[c];
+        const double cx = a.sx / a.s, cz = a.sz / a.s;
+        const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+        out[BMO_PSF_STAT_S] = a.s;
+        out[BMO_PSF_STAT_CX] = cx;
+        out[BMO_PSF_STAT_CZ] = cz;
+        out[BMO_PSF_STAT_X_MIN] = a.x_min;
+        out[BMO_PSF_STAT_X_MAX] = a.x_max;
+        out[BMO_PSF_STAT_Z_MIN] = a.z_min;
+        out[BMO_PSF_STAT_Z_MAX] = a.z_max;
+        out[BMO_PSF_STAT_X_REF] = x_ref;
+        out[BMO_PSF_STAT_Z_REF] = z_ref;
+        out[BMO_PSF_STAT_K_MIN] = a.k_min;
+        out[BMO_PSF_STAT_K_MAX] = a.k_max;
+        const PsfPose P = pose[c];
+        mid[c] = PsfStatMid{cx, cz, 0.0, psf_point(P.origin, P.e1, P.e2, x_ref, z_ref)};
     }
-    double s = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf(), k_min = kinf(), k_max = -kinf();
-    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumA& p) {
-        s += p.s;
-        sx += p.sx;
-        sz += p.sz;
-        x_min = p.x_min < x_min ? p.x_min : x_min;
-        x_max = p.x_max > x_max ? p.x_max : x_max;
-        z_min = p.z_min < z_min ? p.z_min : z_min;
-        z_max = p.z_max > z_max ? p.z_max : z_max;
-        k_min = p.k_min < k_min ? p.k_min : k_min;
-        k_max = p.k_max > k_max ? p.k_max : k_max;
-    });
-    if (threadIdx.x != 0) return;
-    out[BMO_PSF_STAT_N_ROWS] = (double)n;
-    const double cx = sx / s, cz = sz / s;
-    const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
-    out[BMO_PSF_STAT_S] = s;
-    out[BMO_PSF_STAT_CX] = cx;
-    out[BMO_PSF_STAT_CZ] = cz;
-    out[BMO_PSF_STAT_X_MIN] = x_min;
-    out[BMO_PSF_STAT_X_MAX] = x_max;
-    out[BMO_PSF_STAT_Z_MIN] = z_min;
-    out[BMO_PSF_STAT_Z_MAX] = z_max;
-    out[BMO_PSF_STAT_X_REF] = x_ref;
-    out[BMO_PSF_STAT_Z_REF] = z_ref;
-    out[BMO_PSF_STAT_K_MIN] = k_min;
-    out[BMO_PSF_STAT_K_MAX] = k_max;
-    const PsfPose P = pose[c];
-    mid[c] = PsfStatMid{cx, cz, 0.0, psf_point(P.origin, P.e1, P.e2, x_ref, z_ref)};
-}
+};
 
 // pass B of work item blockIdx.x; pw[h] = (proj, W) of row h for pass C
 __global__ __launch_bounds__(256) void psf_stats_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                              const PsfStatMid* __restrict__ mid, double2* __restrict__ pw, PsfStatSumB* __restrict__ partial) {
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
     const PsfStatMid M = mid[W.cfg];
-    double hwx = 0.0, hwz = 0.0, sw = 0.0, re = 0.0, im = 0.0;
+    PsfStatSumB b = sum_identity<PsfStatSumB>();
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
         psf_stage_rows(hits, base, cnt, tile);
         if ((int)threadIdx.x < cnt) {
             const double* r = tile + 9 * threadIdx.x;
             const double ax = fabs(psf_local(r, C.origin, C.e1) - M.cx), az = fabs(psf_local(r, C.origin, C.e2) - M.cz);
-            hwx = ax > hwx ? ax : hwx;
-            hwz = az > hwz ? az : hwz;
+            b.hwx = ax > b.hwx ? ax : b.hwx;
+            b.hwz = az > b.hwz ? az : b.hwz;
             const double w = r[7];
             const double path = psf_path(M.p, r);
             const double phase = r[8] * path;
             double sn, cs;
             sincos(phase, &sn, &cs);
-            sw += w * path;
-            re += w * cs;
-            im += w * sn;
+            b.sw += w * path;
+            b.re += w * cs;
+            b.im += w * sn;
             pw[base + threadIdx.x] = make_double2(w, path);
         }
     }
-    PsfStatSumB b;
-    b.hwx = spot_wg_reduce(hwx, SpotMax{}, sh);
-    b.hwz = spot_wg_reduce(hwz, SpotMax{}, sh);
-    b.sw = spot_wg_reduce(sw, SpotAdd{}, sh);
-    b.re = spot_wg_reduce(re, SpotAdd{}, sh);
-    b.im = spot_wg_reduce(im, SpotAdd{}, sh);
+    b = sum_wg_reduce(b);
     if (threadIdx.x == 0) partial[blockIdx.x] = b;
 }
 
-__global__ void psf_stats_wave_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfStatSumB* __restrict__ partial,
-                                             double* __restrict__ stats, PsfStatMid* __restrict__ mid) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumB) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;
-    if (count[c] == 0) return;  // NaN already
-    double hwx = 0.0, hwz = 0.0, sw = 0.0, re = 0.0, im = 0.0;
-    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumB& p) {
-        hwx = p.hwx > hwx ? p.hwx : hwx;
-        hwz = p.hwz > hwz ? p.hwz : hwz;
-        sw += p.sw;
-        re += p.re;
-        im += p.im;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
-    const double s = out[BMO_PSF_STAT_S];
-    const double w_mean = sw / s;
-    out[BMO_PSF_STAT_HWX] = hwx;
-    out[BMO_PSF_STAT_HWZ] = hwz;
-    out[BMO_PSF_STAT_W_MEAN] = w_mean;
-    out[BMO_PSF_STAT_F_RE] = re;
-    out[BMO_PSF_STAT_F_IM] = im;
-    out[BMO_PSF_STAT_STREHL] = (re * re + im * im) / (s * s);
-    mid[c].w_mean = w_mean;
-}
+struct PsfStatWaveFinish {
+    double* stats;
+    PsfStatMid* mid;
+    __device__ void empty(int32_t) const {}  // NaN already
+    __device__ void operator()(int32_t c, const PsfStatSumB& b) const {
+        double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+        const double s = out[BMO_PSF_STAT_S];
+        const double w_mean = b.sw / s;
+        out[BMO_PSF_STAT_HWX] = b.hwx;
+        out[BMO_PSF_STAT_HWZ] = b.hwz;
+        out[BMO_PSF_STAT_W_MEAN] = w_mean;
+        out[BMO_PSF_STAT_F_RE] = b.re;
+        out[BMO_PSF_STAT_F_IM] = b.im;
+        out[BMO_PSF_STAT_STREHL] = (b.re * b.re + b.im * b.im) / (s * s);
+        mid[c].w_mean = w_mean;
+    }
+};
 
 // pass C of work item blockIdx.x, on the scratch column of pass B
 __global__ __launch_bounds__(256) void psf_stats_spread_kernel(const double2* __restrict__ pw, const SplitWork* __restrict__ work, const PsfStatMid* __restrict__ mid,
                                                                PsfStatSumC* __restrict__ partial) {
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const double w_mean = mid[W.cfg].w_mean;
-    double var = 0.0, lo = kinf(), hi = -kinf();
+    PsfStatSumC s = sum_identity<PsfStatSumC>();
     for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
         const double2 v = pw[h];
         const double d = v.y - w_mean;
-        var += v.x * (d * d);
-        lo = d < lo ? d : lo;
-        hi = d > hi ? d : hi;
+        s.var += v.x * (d * d);
+        s.lo = d < s.lo ? d : s.lo;
+        s.hi = d > s.hi ? d : s.hi;
     }
-    PsfStatSumC s;
-    s.var = spot_wg_reduce(var, SpotAdd{}, sh);
-    s.lo = spot_wg_reduce(lo, SpotMin{}, sh);
-    s.hi = spot_wg_reduce(hi, SpotMax{}, sh);
+    s = sum_wg_reduce(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-__global__ void psf_stats_spread_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfStatSumC* __restrict__ partial,
-                                               double* __restrict__ stats) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(PsfStatSumC) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;
-    if (count[c] == 0) return;  // NaN already
-    double var = 0.0, lo = kinf(), hi = -kinf();
-    psf_stats_fold(partial, cfg[c], lds, [&](const PsfStatSumC& p) {
-        var += p.var;
-        lo = p.lo < lo ? p.lo : lo;
-        hi = p.hi > hi ? p.hi : hi;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
-    out[BMO_PSF_STAT_W_RMS] = sqrt(var / out[BMO_PSF_STAT_S]);
-    out[BMO_PSF_STAT_W_LO] = lo;
-    out[BMO_PSF_STAT_W_HI] = hi;
-}
+struct PsfStatSpreadFinish {
+    double* stats;
+    __device__ void empty(int32_t) const {}  // NaN already
+    __device__ void operator()(int32_t c, const PsfStatSumC& s) const {
+        double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
+        out[BMO_PSF_STAT_W_RMS] = sqrt(s.var / out[BMO_PSF_STAT_S]);
+        out[BMO_PSF_STAT_W_LO] = s.lo;
+        out[BMO_PSF_STAT_W_HI] = s.hi;
+    }
+};
 
 }  // namespace
-
-// N = 0 and NaN in the other twenty: what a configuration without rows reads
-static void psf_stats_empty(double* stats, int32_t n_configs) {
-    for (int32_t c = 0; c < n_configs; ++c) {
-        double* out = stats + (size_t)c * BMO_PSF_STAT_N;
-        std::fill(out, out + BMO_PSF_STAT_N, std::nan(""));
-        out[BMO_PSF_STAT_N_ROWS] = 0.0;
-    }
-}
 
 // The statistics [K][BMO_PSF_STAT_N] of the K configurations from the n_rows device rows `hits` [..][9]: poses [K][3], ref_xz nullptr or [K][2].
 static int psf_stats_read(const double* hits, int64_t n_rows, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* ref_xz,
                           double* stats, double* kernel_ms, const char* who) {
     const size_t K = R.count.size();
     hipStream_t st = 0;
-    const SplitPlan plan = spot_plan(R);
+    const SplitPlan plan = rows_plan(R);
     unsigned n_items = 0;
-    if (int rc = spot_items(plan, who, n_items)) return rc;
-    std::vector<PsfPose> pose(K);
-    for (size_t c = 0; c < K; ++c) {
-        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
-        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
-    }
+    if (int rc = rows_items(plan, who, n_items)) return rc;
     Packed up;
-    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(pose);
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(psf_poses(K, origins, e1s, e2s));
     const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0;
     DevBuf pa, pb, pc, d_stats, d_mid, d_pw;
     int rc;
@@ -1458,20 +1442,20 @@ static int psf_stats_read(const double* hits, int64_t n_rows, const Ranges& R, c
         return rc;
     EventTimer timer;
     if ((rc = timer.start(st))) return rc;
-    const dim3 kb((unsigned)K);  // the reduces: one workgroup per configuration
     const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
     const SplitWork* d_work = up.at<SplitWork>(o_work);
-    const int64_t* d_count = up.at<int64_t>(o_count);
     const PsfPose* d_pose = up.at<PsfPose>(o_pose);
+    double* const g_stats = (double*)d_stats.p;
+    PsfStatMid* const g_mid = (PsfStatMid*)d_mid.p;
     if (n_items > 0) hipLaunchKernelGGL(psf_stats_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (PsfStatSumA*)pa.p);
-    hipLaunchKernelGGL(psf_stats_sums_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr,
-                       (const PsfStatSumA*)pa.p, (double*)d_stats.p, (PsfStatMid*)d_mid.p);
+    sum_reduce<PsfStatSumA>((unsigned)K, st, d_cfg, pa,
+                            PsfStatSumsFinish{up.at<int64_t>(o_count), d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, g_stats, g_mid});
     if (n_items > 0)
-        hipLaunchKernelGGL(psf_stats_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const PsfStatMid*)d_mid.p, (double2*)d_pw.p, (PsfStatSumB*)pb.p);
-    hipLaunchKernelGGL(psf_stats_wave_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const PsfStatSumB*)pb.p, (double*)d_stats.p, (PsfStatMid*)d_mid.p);
+        hipLaunchKernelGGL(psf_stats_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const PsfStatMid*)g_mid, (double2*)d_pw.p, (PsfStatSumB*)pb.p);
+    sum_reduce<PsfStatSumB>((unsigned)K, st, d_cfg, pb, PsfStatWaveFinish{g_stats, g_mid});
     if (n_items > 0)
-        hipLaunchKernelGGL(psf_stats_spread_kernel, dim3(n_items), dim3(256), 0, st, (const double2*)d_pw.p, d_work, (const PsfStatMid*)d_mid.p, (PsfStatSumC*)pc.p);
-    hipLaunchKernelGGL(psf_stats_spread_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const PsfStatSumC*)pc.p, (double*)d_stats.p);
+        hipLaunchKernelGGL(psf_stats_spread_kernel, dim3(n_items), dim3(256), 0, st, (const double2*)d_pw.p, d_work, (const PsfStatMid*)g_mid, (PsfStatSumC*)pc.p);
+    sum_reduce<PsfStatSumC>((unsigned)K, st, d_cfg, pc, PsfStatSpreadFinish{g_stats});
     if ((rc = timer.stop(kernel_ms))) return rc;
     HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_PSF_STAT_N * 8, hipMemcpyDeviceToHost));
     return BMO_OK;
@@ -1482,24 +1466,18 @@ extern "C" int bmo_psf_stats(const double* hits, int64_t n_hits, int32_t hits_on
     if (!origin || !e1 || !e2 || !stats || n_hits < 0 || (n_hits > 0 && !hits)) return fail(BMO_ERR_INVALID, "bmo_psf_stats: bad argument (null pointer, n_hits < 0)");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_hits;
-    if (int rc = spot_single_rows("bmo_psf_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (int rc = single_rows("bmo_psf_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
     return psf_stats_read(hits, n_hits, Ranges{{0}, {n_hits}}, origin, e1, e2, ref_xz, stats, kernel_ms, "bmo_psf_stats");
 }
 
 extern "C" int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
                                    const double* ref_xz, double* stats, double* kernel_ms) {
     if (!res || !origins || !e1s || !e2s || !stats) return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: bad argument");
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: bad detector slot");
-    if (res->kind == BMO_BEAM_GAUSSIAN)
-        return fail(BMO_ERR_UNSUPPORTED, "bmo_psf_stats_sweep: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
-        return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: the slot is not a PSFDetector's");
-    if (n_configs != std::max<int32_t>(res->n_configs, 1))
-        return fail(BMO_ERR_INVALID, "bmo_psf_stats_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (int rc = slot_check("bmo_psf_stats_sweep", res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
     if (kernel_ms) *kernel_ms = 0.0;
     const int64_t H = res->det_count[detector];
     if (H == 0) {  // every configuration reads like a call with n_hits = 0
-        psf_stats_empty(stats, n_configs);
+        fill_empty_stats(stats, (size_t)n_configs, BMO_PSF_STAT_N);
         return BMO_OK;
     }
     HIP_TRY(hipSetDevice(res->device));
@@ -1601,15 +1579,12 @@ __device__ __forceinline__ void zern_terms(double x, double y, F&& f) {
     zern_walk<0, 0, ORDER>(t, Cc, Sc, f);
 }
 
-struct ZernSumA {
-    double s, sx, sz, su, sv;
-};
-struct ZernSumB {
-    double sw, r2;
-};
-struct ZernSumD {
-    double var, lo, hi, n_out;
-};
+#define ZERN_SUM_A(F) F(s, SumAdd) F(sx, SumAdd) F(sz, SumAdd) F(su, SumAdd) F(sv, SumAdd)
+#define ZERN_SUM_B(F) F(sw, SumAdd) F(r2, SumMax0)
+#define ZERN_SUM_D(F) F(var, SumAdd) F(lo, SumMin) F(hi, SumMax) F(n_out, SumAdd)
+SUM_RECORD(ZernSumA, ZERN_SUM_A);
+SUM_RECORD(ZernSumB, ZERN_SUM_B);
+SUM_RECORD(ZernSumD, ZERN_SUM_D);
 // what the later passes need of configuration c
 struct ZernMid {
     d3 p;  // the reference point in world coordinates
@@ -1623,10 +1598,9 @@ __device__ __forceinline__ double zern_cosine(const double* r, const d3& e) { re
 __global__ __launch_bounds__(256) void psf_zernike_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                                ZernSumA* __restrict__ partial) {
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
-    double s = 0.0, sx = 0.0, sz = 0.0, su = 0.0, sv = 0.0;
+    ZernSumA a = sum_identity<ZernSumA>();
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
         psf_stage_rows(hits, base, cnt, tile);
@@ -1634,72 +1608,57 @@ __global__ __launch_bounds__(256) void psf_zernike_sums_kernel(const double* __r
             const double* r = tile + 9 * threadIdx.x;
             const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
             const double w = r[7];
-            s += w;
-            sx += w * x;
-            sz += w * z;
-            su += w * zern_cosine(r, C.e1);
-            sv += w * zern_cosine(r, C.e2);
+            a.s += w;
+            a.sx += w * x;
+            a.sz += w * z;
+            a.su += w * zern_cosine(r, C.e1);
+            a.sv += w * zern_cosine(r, C.e2);
         }
     }
-    ZernSumA a;
-    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
-    a.sx = spot_wg_reduce(sx, SpotAdd{}, sh);
-    a.sz = spot_wg_reduce(sz, SpotAdd{}, sh);
-    a.su = spot_wg_reduce(su, SpotAdd{}, sh);
-    a.sv = spot_wg_reduce(sv, SpotAdd{}, sh);
+    a = sum_wg_reduce(a);
     if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
 
-// configuration blockIdx.x: the splits of pass A in split order.  ref_xz: nullptr (the centroid) or [K][2]; pupil: nullptr or [K][3].
-// A configuration without rows gets its whole answer here: N = 0, STATUS = 1, NaN elsewhere.
-__global__ void psf_zernike_sums_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const PsfPose* __restrict__ pose,
-                                               const double* __restrict__ ref_xz, const double* __restrict__ pupil, const ZernSumA* __restrict__ partial,
-                                               double* __restrict__ info, ZernMid* __restrict__ mid) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumA) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;
-    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
-    const int64_t n = count[c];
-    if (n == 0) {
-        if (threadIdx.x == 0) {
-            for (int q = 0; q < BMO_ZERNIKE_INFO_N; ++q) out[q] = knan();
-            out[BMO_ZERNIKE_N_ROWS] = 0.0;
-            out[BMO_ZERNIKE_STATUS] = 1.0;
-            mid[c] = ZernMid{d3{0.0, 0.0, 0.0}, 0.0, 0.0, 0.0, 0.0};
-        }
-        return;
+// ref_xz: nullptr (the centroid) or [K][2]; pupil: nullptr or [K][3].  A configuration without rows gets its whole answer here: N = 0,
+// STATUS = 1, NaN elsewhere.
+struct ZernSumsFinish {
+    const int64_t* count;
+    const PsfPose* pose;
+    const double *ref_xz, *pupil;
+    double* info;
+    ZernMid* mid;
+    __device__ void empty(int32_t c) const {
+        double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+        for (int q = 0; q < BMO_ZERNIKE_INFO_N; ++q) out[q] = knan();
+        out[BMO_ZERNIKE_N_ROWS] = 0.0;
+        out[BMO_ZERNIKE_STATUS] = 1.0;
+        mid[c] = ZernMid{d3{0.0, 0.0, 0.0}, 0.0, 0.0, 0.0, 0.0};
     }
-    double s = 0.0, sx = 0.0, sz = 0.0, su = 0.0, sv = 0.0;
-    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumA& p) {
-        s += p.s;
-        sx += p.sx;
-        sz += p.sz;
-        su += p.su;
-        sv += p.sv;
-    });
-    if (threadIdx.x != 0) return;
-    const double cx = sx / s, cz = sz / s;
-    const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
-    const double u0 = pupil ? pupil[3 * c] : su / s, v0 = pupil ? pupil[3 * c + 1] : sv / s;
-    out[BMO_ZERNIKE_N_ROWS] = (double)n;
-    out[BMO_ZERNIKE_STATUS] = 0.0;
-    out[BMO_ZERNIKE_S] = s;
-    out[BMO_ZERNIKE_X_REF] = x_ref;
-    out[BMO_ZERNIKE_Z_REF] = z_ref;
-    out[BMO_ZERNIKE_U0] = u0;
-    out[BMO_ZERNIKE_V0] = v0;
-    const PsfPose P = pose[c];
-    mid[c] = ZernMid{psf_point(P.origin, P.e1, P.e2, x_ref, z_ref), u0, v0, 0.0, 0.0};
-}
+    __device__ void operator()(int32_t c, const ZernSumA& a) const {
+        double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+        const double cx = a.sx / a.s, cz = a.sz / a.s;
+        const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+        const double u0 = pupil ? pupil[3 * c] : a.su / a.s, v0 = pupil ? pupil[3 * c + 1] : a.sv / a.s;
+        out[BMO_ZERNIKE_N_ROWS] = (double)count[c];
+        out[BMO_ZERNIKE_STATUS] = 0.0;
+        out[BMO_ZERNIKE_S] = a.s;
+        out[BMO_ZERNIKE_X_REF] = x_ref;
+        out[BMO_ZERNIKE_Z_REF] = z_ref;
+        out[BMO_ZERNIKE_U0] = u0;
+        out[BMO_ZERNIKE_V0] = v0;
+        const PsfPose P = pose[c];
+        mid[c] = ZernMid{psf_point(P.origin, P.e1, P.e2, x_ref, z_ref), u0, v0, 0.0, 0.0};
+    }
+};
 
 // pass B of work item blockIdx.x; col[h] = (proj, W, u, v) of row h for passes C and D
 __global__ __launch_bounds__(256) void psf_zernike_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                                const ZernMid* __restrict__ mid, double4* __restrict__ col, ZernSumB* __restrict__ partial) {
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
     const ZernMid M = mid[W.cfg];
-    double sw = 0.0, r2 = 0.0;
+    ZernSumB b = sum_identity<ZernSumB>();
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
         psf_stage_rows(hits, base, cnt, tile);
@@ -1708,37 +1667,31 @@ __global__ __launch_bounds__(256) void psf_zernike_wave_kernel(const double* __r
             const double w = r[7];
             const double path = psf_path(M.p, r);
             const double u = zern_cosine(r, C.e1), v = zern_cosine(r, C.e2);
-            sw += w * path;
+            b.sw += w * path;
             const double q = (u - M.u0) * (u - M.u0) + (v - M.v0) * (v - M.v0);
-            r2 = q > r2 ? q : r2;
+            b.r2 = q > b.r2 ? q : b.r2;
             col[base + threadIdx.x] = make_double4(w, path, u, v);
         }
     }
-    ZernSumB b;
-    b.sw = spot_wg_reduce(sw, SpotAdd{}, sh);
-    b.r2 = spot_wg_reduce(r2, SpotMax{}, sh);
+    b = sum_wg_reduce(b);
     if (threadIdx.x == 0) partial[blockIdx.x] = b;
 }
 
-__global__ void psf_zernike_wave_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const double* __restrict__ pupil,
-                                               const ZernSumB* __restrict__ partial, double* __restrict__ info, ZernMid* __restrict__ mid) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumB) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;
-    if (count[c] == 0) return;  // answered already
-    double sw = 0.0, r2 = 0.0;
-    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumB& p) {
-        sw += p.sw;
-        r2 = p.r2 > r2 ? p.r2 : r2;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
-    const double w_mean = sw / out[BMO_ZERNIKE_S];
-    const double rho = pupil ? pupil[3 * c + 2] : sqrt(r2);
-    out[BMO_ZERNIKE_W_MEAN] = w_mean;
-    out[BMO_ZERNIKE_RHO] = rho;
-    mid[c].w_mean = w_mean;
-    mid[c].rho = rho;
-}
+struct ZernWaveFinish {
+    const double* pupil;
+    double* info;
+    ZernMid* mid;
+    __device__ void empty(int32_t) const {}  // answered already
+    __device__ void operator()(int32_t c, const ZernSumB& b) const {
+        double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+        const double w_mean = b.sw / out[BMO_ZERNIKE_S];
+        const double rho = pupil ? pupil[3 * c + 2] : sqrt(b.r2);
+        out[BMO_ZERNIKE_W_MEAN] = w_mean;
+        out[BMO_ZERNIKE_RHO] = rho;
+        mid[c].w_mean = w_mean;
+        mid[c].rho = rho;
+    }
+};
 
 // entry e of the packed lower triangle: (i, k), i >= k
 __device__ __forceinline__ void zern_entry(int e, int& i, int& k) {
@@ -1900,13 +1853,12 @@ template <int ORDER>
 __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
                                                                    const double* __restrict__ coef, ZernSumD* __restrict__ partial) {
     constexpr int J = zern_terms_of(ORDER);
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const ZernMid M = mid[W.cfg];
     double cf[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
-    double var = 0.0, lo = kinf(), hi = -kinf(), n_out = 0.0;
+    ZernSumD s = sum_identity<ZernSumD>();
     for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
         const double4 q = col[h];
         const double x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
@@ -1914,39 +1866,27 @@ __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4
         double f = 0.0;
         zern_terms<ORDER>(x, y, [&](int j, double Z) { f = j == 0 ? cf[0] * Z : f + cf[j] * Z; });
         const double e = (q.y - M.w_mean) - f;
-        var += q.x * (e * e);
-        lo = e < lo ? e : lo;
-        hi = e > hi ? e : hi;
-        n_out += t > 1.0 ? 1.0 : 0.0;
+        s.var += q.x * (e * e);
+        s.lo = e < s.lo ? e : s.lo;
+        s.hi = e > s.hi ? e : s.hi;
+        s.n_out += t > 1.0 ? 1.0 : 0.0;
     }
-    ZernSumD s;
-    s.var = spot_wg_reduce(var, SpotAdd{}, sh);
-    s.lo = spot_wg_reduce(lo, SpotMin{}, sh);
-    s.hi = spot_wg_reduce(hi, SpotMax{}, sh);
-    s.n_out = spot_wg_reduce(n_out, SpotAdd{}, sh);
+    s = sum_wg_reduce(s);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-__global__ void psf_zernike_residual_reduce_kernel(const SplitCfg* __restrict__ cfg, const int64_t* __restrict__ count, const ZernSumD* __restrict__ partial,
-                                                   double* __restrict__ info) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(ZernSumD) / sizeof(double))];
-    const int32_t c = (int32_t)blockIdx.x;
-    if (count[c] == 0) return;  // answered already
-    double var = 0.0, lo = kinf(), hi = -kinf(), n_out = 0.0;
-    psf_stats_fold(partial, cfg[c], lds, [&](const ZernSumD& p) {
-        var += p.var;
-        lo = p.lo < lo ? p.lo : lo;
-        hi = p.hi > hi ? p.hi : hi;
-        n_out += p.n_out;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
-    const bool solved = out[BMO_ZERNIKE_STATUS] == 0.0;
-    out[BMO_ZERNIKE_FIT_RMS] = solved ? sqrt(var / out[BMO_ZERNIKE_S]) : knan();
-    out[BMO_ZERNIKE_E_LO] = solved ? lo : knan();
-    out[BMO_ZERNIKE_E_HI] = solved ? hi : knan();
-    out[BMO_ZERNIKE_N_OUT] = n_out;
-}
+struct ZernResidualFinish {
+    double* info;
+    __device__ void empty(int32_t) const {}  // answered already
+    __device__ void operator()(int32_t c, const ZernSumD& s) const {
+        double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
+        const bool solved = out[BMO_ZERNIKE_STATUS] == 0.0;
+        out[BMO_ZERNIKE_FIT_RMS] = solved ? sqrt(s.var / out[BMO_ZERNIKE_S]) : knan();
+        out[BMO_ZERNIKE_E_LO] = solved ? s.lo : knan();
+        out[BMO_ZERNIKE_E_HI] = solved ? s.hi : knan();
+        out[BMO_ZERNIKE_N_OUT] = s.n_out;
+    }
+};
 
 template <int ORDER>
 static void zern_launch_gram(unsigned n_items, hipStream_t st, const double4* col, const SplitWork* work, const ZernMid* mid, double* partial) {
@@ -1964,12 +1904,8 @@ static void psf_zernike_empty(int32_t n_configs, int32_t J, double* coef, double
     const size_t E = (size_t)(J + 1) * (J + 2) / 2;
     std::fill(coef, coef + (size_t)n_configs * J, std::nan(""));
     if (gram) std::fill(gram, gram + (size_t)n_configs * E, std::nan(""));
-    for (int32_t c = 0; c < n_configs; ++c) {
-        double* out = info + (size_t)c * BMO_ZERNIKE_INFO_N;
-        std::fill(out, out + BMO_ZERNIKE_INFO_N, std::nan(""));
-        out[BMO_ZERNIKE_N_ROWS] = 0.0;
-        out[BMO_ZERNIKE_STATUS] = 1.0;
-    }
+    fill_empty_stats(info, (size_t)n_configs, BMO_ZERNIKE_INFO_N);
+    for (int32_t c = 0; c < n_configs; ++c) info[(size_t)c * BMO_ZERNIKE_INFO_N + BMO_ZERNIKE_STATUS] = 1.0;
 }
 
 // order in range and every given pupil (U0, V0, RHO) usable
@@ -1990,16 +1926,11 @@ static int psf_zernike_read(const double* hits, int64_t n_rows, const Ranges& R,
     const int32_t J = zern_terms_of(order);
     const size_t E = (size_t)(J + 1) * (J + 2) / 2;
     hipStream_t st = 0;
-    const SplitPlan plan = spot_plan(R);
+    const SplitPlan plan = rows_plan(R);
     unsigned n_items = 0;
-    if (int rc = spot_items(plan, who, n_items)) return rc;
-    std::vector<PsfPose> pose(K);
-    for (size_t c = 0; c < K; ++c) {
-        const double *o = origins + 3 * c, *a = e1s + 3 * c, *b = e2s + 3 * c;
-        pose[c] = PsfPose{d3{o[0], o[1], o[2]}, d3{a[0], a[1], a[2]}, d3{b[0], b[1], b[2]}};
-    }
+    if (int rc = rows_items(plan, who, n_items)) return rc;
     Packed up;
-    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(pose);
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(psf_poses(K, origins, e1s, e2s));
     const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0, o_pupil = pupil ? up.add(pupil, 3 * K) : 0;
     DevBuf pa, pb, pc, pd, d_info, d_coef, d_gram, d_mid, d_col;
     int rc;
@@ -2020,10 +1951,9 @@ static int psf_zernike_read(const double* hits, int64_t n_rows, const Ranges& R,
     ZernMid* const g_mid = (ZernMid*)d_mid.p;
     double4* const g_col = (double4*)d_col.p;
     if (n_items > 0) hipLaunchKernelGGL(psf_zernike_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (ZernSumA*)pa.p);
-    hipLaunchKernelGGL(psf_zernike_sums_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, d_pupil,
-                       (const ZernSumA*)pa.p, g_info, g_mid);
+    sum_reduce<ZernSumA>((unsigned)K, st, d_cfg, pa, ZernSumsFinish{d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, d_pupil, g_info, g_mid});
     if (n_items > 0) hipLaunchKernelGGL(psf_zernike_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const ZernMid*)g_mid, g_col, (ZernSumB*)pb.p);
-    hipLaunchKernelGGL(psf_zernike_wave_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, d_pupil, (const ZernSumB*)pb.p, g_info, g_mid);
+    sum_reduce<ZernSumB>((unsigned)K, st, d_cfg, pb, ZernWaveFinish{d_pupil, g_info, g_mid});
     if (n_items > 0) {
         void (*const launch[])(unsigned, hipStream_t, const double4*, const SplitWork*, const ZernMid*, double*) = {
             zern_launch_gram<0>, zern_launch_gram<1>, zern_launch_gram<2>, zern_launch_gram<3>, zern_launch_gram<4>, zern_launch_gram<5>, zern_launch_gram<6>};
@@ -2037,7 +1967,7 @@ static int psf_zernike_read(const double* hits, int64_t n_rows, const Ranges& R,
             zern_launch_residual<4>, zern_launch_residual<5>, zern_launch_residual<6>};
         launch[order](n_items, st, g_col, d_work, g_mid, (const double*)d_coef.p, (ZernSumD*)pd.p);
     }
-    hipLaunchKernelGGL(psf_zernike_residual_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, (const ZernSumD*)pd.p, g_info);
+    sum_reduce<ZernSumD>((unsigned)K, st, d_cfg, pd, ZernResidualFinish{g_info});
     if ((rc = timer.stop(kernel_ms))) return rc;
     HIP_TRY(hipMemcpy(info, d_info.p, K * BMO_ZERNIKE_INFO_N * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(coef, d_coef.p, K * (size_t)J * 8, hipMemcpyDeviceToHost));
@@ -2054,20 +1984,14 @@ extern "C" int bmo_psf_zernike(const double* hits, int64_t n_hits, int32_t hits_
         return fail(BMO_ERR_INVALID, "bmo_psf_zernike: order must be 0 .. 6, a given pupil (U0, V0, RHO) finite with RHO > 0");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_hits;
-    if (int rc = spot_single_rows("bmo_psf_zernike", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (int rc = single_rows("bmo_psf_zernike", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
     return psf_zernike_read(hits, n_hits, Ranges{{0}, {n_hits}}, origin, e1, e2, ref_xz, pupil, order, coef, info, gram, kernel_ms, "bmo_psf_zernike");
 }
 
 extern "C" int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
                                      const double* ref_xz, const double* pupil, int32_t order, double* coef, double* info, double* gram, double* kernel_ms) {
     if (!res || !origins || !e1s || !e2s || !coef || !info) return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: bad argument");
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: bad detector slot");
-    if (res->kind == BMO_BEAM_GAUSSIAN)
-        return fail(BMO_ERR_UNSUPPORTED, "bmo_psf_zernike_sweep: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
-        return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: the slot is not a PSFDetector's");
-    if (n_configs != std::max<int32_t>(res->n_configs, 1))
-        return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: n_configs must be the configuration count of the sweep result (1 for an ordinary result)");
+    if (int rc = slot_check("bmo_psf_zernike_sweep", res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
     if (!psf_zernike_args_ok(pupil, n_configs, order))
         return fail(BMO_ERR_INVALID, "bmo_psf_zernike_sweep: order must be 0 .. 6, every given pupil (U0, V0, RHO) finite with RHO > 0");
     if (kernel_ms) *kernel_ms = 0.0;
@@ -2226,7 +2150,7 @@ extern "C" int bmo_psf_through_focus(const double* hits, int64_t n_hits, int32_t
         return fail(BMO_ERR_INVALID, "bmo_psf_through_focus: bad argument (null pointer, n <= 0, n_planes <= 0, n_hits < 0)");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_hits;
-    if (int rc = spot_single_rows("bmo_psf_through_focus", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (int rc = single_rows("bmo_psf_through_focus", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
     if (n_hits == 0) {
         const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
         std::fill(out_intensity, out_intensity + n_out, 0.0);
@@ -2236,21 +2160,19 @@ extern "C" int bmo_psf_through_focus(const double* hits, int64_t n_hits, int32_t
     return psf_focus_read(hits, n_hits, origin, e1, e2, displacements, n_planes, xs, zs, n, out_intensity, out_field, kernel_ms);
 }
 
-// The focus statistics.  The plumbing of the wavefront statistics (spot_plan, work items on the grid's x dimension, tiles of 256 rows staged
-// through LDS, lane l reads row l, the lane / shuffle / wave / split order of the sums, psf_stats_fold), two accumulate passes with a reduce
+// The focus statistics.  The plumbing of the wavefront statistics (rows_plan, work items on the grid's x dimension, tiles of 256 rows staged
+// through LDS, lane l reads row l, sum records: the lane / shuffle / wave / split order of the sums), two accumulate passes with a reduce
 // each: A the sums and extrema, its reduce leaves the centroids on the device; C the spreads about them.  A workgroup owns one work item and
-// one chunk of FOCUS_STAT_MP planes (the grid's y dimension), whose accumulators every lane keeps in registers: the rows are read once per
-// pass and chunk.  The partial sums are [plane][item], one workgroup per plane folds them in split order.
+// one chunk of FOCUS_STAT_MP planes (the grid's y dimension), whose FOCUS_STAT_MP records every lane keeps in registers: the rows are read
+// once per pass and chunk.  The partial sums are [plane][item]; sum_reduce_kernel, one workgroup per plane, folds them in split order.
 namespace {
 
 constexpr int FOCUS_STAT_MP = 8;
 
-struct FocusSumA {
-    double s, bad, sx, sz, x_min, x_max, z_min, z_max;
-};
-struct FocusSumC {
-    double hwx, hwz, sr2, r2_max;
-};
+#define FOCUS_SUM_A(F) F(s, SumAdd) F(bad, SumAdd) F(sx, SumAdd) F(sz, SumAdd) F(x_min, SumMin) F(x_max, SumMax) F(z_min, SumMin) F(z_max, SumMax)
+#define FOCUS_SUM_C(F) F(hwx, SumMax0) F(hwz, SumMax0) F(sr2, SumAdd) F(r2_max, SumMax0)
+SUM_RECORD(FocusSumA, FOCUS_SUM_A);
+SUM_RECORD(FocusSumC, FOCUS_SUM_C);
 struct FocusFrame {
     d3 origin, e1, e2, axis, nrm;
 };
@@ -2270,86 +2192,70 @@ __global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __res
                                                              const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
     constexpr int MP = FOCUS_STAT_MP;
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
     d3 o[MP];
+    FocusSumA a[MP];
 #pragma unroll
-    for (int m = 0; m < MP; ++m) o[m] = focus_origin(F, offsets[m0 + (m < mcnt ? m : 0)]);
-    double s = 0.0, bad = 0.0, sx[MP], sz[MP], x_min[MP], x_max[MP], z_min[MP], z_max[MP];
-#pragma unroll
-    for (int m = 0; m < MP; ++m) sx[m] = 0.0, sz[m] = 0.0, x_min[m] = kinf(), x_max[m] = -kinf(), z_min[m] = kinf(), z_max[m] = -kinf();
+    for (int m = 0; m < MP; ++m) {
+        o[m] = focus_origin(F, offsets[m0 + (m < mcnt ? m : 0)]);
+        a[m] = sum_identity<FocusSumA>();
+    }
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
         psf_stage_rows(hits, base, cnt, tile);
         if ((int)threadIdx.x < cnt) {
             const double* r = tile + 9 * threadIdx.x;
             const double w = r[7], den = focus_den(r, F);
-            s += w;
-            bad += den == 0.0 ? 1.0 : 0.0;
+            a[0].s += w;  // the two sums that every plane shares are kept once
+            a[0].bad += den == 0.0 ? 1.0 : 0.0;
 #pragma unroll
             for (int m = 0; m < MP; ++m) {
                 double x, z;
                 focus_local(r, F, o[m], den, x, z);
-                sx[m] += w * x;
-                sz[m] += w * z;
-                x_min[m] = x < x_min[m] ? x : x_min[m];
-                x_max[m] = x > x_max[m] ? x : x_max[m];
-                z_min[m] = z < z_min[m] ? z : z_min[m];
-                z_max[m] = z > z_max[m] ? z : z_max[m];
+                a[m].sx += w * x;
+                a[m].sz += w * z;
+                a[m].x_min = x < a[m].x_min ? x : a[m].x_min;
+                a[m].x_max = x > a[m].x_max ? x : a[m].x_max;
+                a[m].z_min = z < a[m].z_min ? z : a[m].z_min;
+                a[m].z_max = z > a[m].z_max ? z : a[m].z_max;
             }
         }
     }
-    FocusSumA a;
-    a.s = spot_wg_reduce(s, SpotAdd{}, sh);
-    a.bad = spot_wg_reduce(bad, SpotAdd{}, sh);
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
-        a.sx = spot_wg_reduce(sx[m], SpotAdd{}, sh);
-        a.sz = spot_wg_reduce(sz[m], SpotAdd{}, sh);
-        a.x_min = spot_wg_reduce(x_min[m], SpotMin{}, sh);
-        a.x_max = spot_wg_reduce(x_max[m], SpotMax{}, sh);
-        a.z_min = spot_wg_reduce(z_min[m], SpotMin{}, sh);
-        a.z_max = spot_wg_reduce(z_max[m], SpotMax{}, sh);
-        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = a;
+        a[m].s = a[0].s, a[m].bad = a[0].bad;
+        const FocusSumA v = sum_wg_reduce(a[m]);
+        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = v;
     }
 }
 
-// plane blockIdx.x: the work items of pass A in split order; the sums, the centroid and the extrema go to stats[m], the centroid to mid[m]
-__global__ void psf_focus_sums_reduce_kernel(int32_t n_items, int64_t n_rows, const FocusSumA* __restrict__ partial, double* __restrict__ stats,
-                                             double2* __restrict__ mid) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(FocusSumA) / sizeof(double))];
-    const int32_t m = (int32_t)blockIdx.x;
-    double s = 0.0, bad = 0.0, sx = 0.0, sz = 0.0, x_min = kinf(), x_max = -kinf(), z_min = kinf(), z_max = -kinf();
-    psf_stats_fold(partial, SplitCfg{(int64_t)m * n_items, n_items, 0}, lds, [&](const FocusSumA& p) {
-        s += p.s;
-        bad += p.bad;
-        sx += p.sx;
-        sz += p.sz;
-        x_min = p.x_min < x_min ? p.x_min : x_min;
-        x_max = p.x_max > x_max ? p.x_max : x_max;
-        z_min = p.z_min < z_min ? p.z_min : z_min;
-        z_max = p.z_max > z_max ? p.z_max : z_max;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
-    out[BMO_FOCUS_STAT_N_ROWS] = (double)n_rows;
-    if (bad != 0.0) {  // a row parallel to the planes: no statistics
-        for (int q = 1; q < BMO_FOCUS_STAT_N; ++q) out[q] = knan();
-        mid[m] = make_double2(knan(), knan());
-        return;
+// the sums, the centroid and the extrema go to stats[m], the centroid to mid[m]
+struct FocusSumsFinish {
+    int64_t n_rows;
+    double* stats;
+    double2* mid;
+    __device__ void empty(int32_t) const {}  // a plane has every work item of the call
+    __device__ void operator()(int32_t m, const FocusSumA& a) const {
+        double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
+        out[BMO_FOCUS_STAT_N_ROWS] = (double)n_rows;
+        if (a.bad != 0.0) {  // a row parallel to the planes: no statistics
+            for (int q = 1; q < BMO_FOCUS_STAT_N; ++q) out[q] = knan();
+            mid[m] = make_double2(knan(), knan());
+            return;
+        }
+        const double cx = a.sx / a.s, cz = a.sz / a.s;
+        out[BMO_FOCUS_STAT_S] = a.s;
+        out[BMO_FOCUS_STAT_CX] = cx;
+        out[BMO_FOCUS_STAT_CZ] = cz;
+        out[BMO_FOCUS_STAT_X_MIN] = a.x_min;
+        out[BMO_FOCUS_STAT_X_MAX] = a.x_max;
+        out[BMO_FOCUS_STAT_Z_MIN] = a.z_min;
+        out[BMO_FOCUS_STAT_Z_MAX] = a.z_max;
+        mid[m] = make_double2(cx, cz);
     }
-    const double cx = sx / s, cz = sz / s;
-    out[BMO_FOCUS_STAT_S] = s;
-    out[BMO_FOCUS_STAT_CX] = cx;
-    out[BMO_FOCUS_STAT_CZ] = cz;
-    out[BMO_FOCUS_STAT_X_MIN] = x_min;
-    out[BMO_FOCUS_STAT_X_MAX] = x_max;
-    out[BMO_FOCUS_STAT_Z_MIN] = z_min;
-    out[BMO_FOCUS_STAT_Z_MAX] = z_max;
-    mid[m] = make_double2(cx, cz);
-}
+};
 
 // pass C of work item blockIdx.x on planes blockIdx.y * FOCUS_STAT_MP ..
 __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
@@ -2357,19 +2263,18 @@ __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __r
                                                                FocusSumC* __restrict__ partial) {
     constexpr int MP = FOCUS_STAT_MP;
     __shared__ double tile[PSF_TILE * 9];
-    __shared__ double sh[4];
     const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
     d3 o[MP];
     double2 c[MP];
-    double hwx[MP], hwz[MP], sr2[MP], r2_max[MP];
+    FocusSumC v[MP];
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
         const int32_t mm = m0 + (m < mcnt ? m : 0);
         o[m] = focus_origin(F, offsets[mm]);
         c[m] = mid[mm];
-        hwx[m] = 0.0, hwz[m] = 0.0, sr2[m] = 0.0, r2_max[m] = 0.0;
+        v[m] = sum_identity<FocusSumC>();
     }
     for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
         const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
@@ -2384,43 +2289,36 @@ __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __r
                 const double ax = x - c[m].x, az = z - c[m].y;
                 const double fx = fabs(ax), fz = fabs(az);
                 const double r2 = ax * ax + az * az;
-                hwx[m] = fx > hwx[m] ? fx : hwx[m];
-                hwz[m] = fz > hwz[m] ? fz : hwz[m];
-                sr2[m] += w * r2;
-                r2_max[m] = r2 > r2_max[m] ? r2 : r2_max[m];
+                v[m].hwx = fx > v[m].hwx ? fx : v[m].hwx;
+                v[m].hwz = fz > v[m].hwz ? fz : v[m].hwz;
+                v[m].sr2 += w * r2;
+                v[m].r2_max = r2 > v[m].r2_max ? r2 : v[m].r2_max;
             }
         }
     }
-    FocusSumC v;
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
-        v.hwx = spot_wg_reduce(hwx[m], SpotMax{}, sh);
-        v.hwz = spot_wg_reduce(hwz[m], SpotMax{}, sh);
-        v.sr2 = spot_wg_reduce(sr2[m], SpotAdd{}, sh);
-        v.r2_max = spot_wg_reduce(r2_max[m], SpotMax{}, sh);
-        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = v;
+        const FocusSumC s = sum_wg_reduce(v[m]);
+        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = s;
     }
 }
 
-__global__ void psf_focus_spread_reduce_kernel(int32_t n_items, const FocusSumC* __restrict__ partial, double* __restrict__ stats) {
-    __shared__ double lds[PSF_FOLD_CHUNK * (sizeof(FocusSumC) / sizeof(double))];
-    const int32_t m = (int32_t)blockIdx.x;
-    double hwx = 0.0, hwz = 0.0, sr2 = 0.0, r2_max = 0.0;
-    psf_stats_fold(partial, SplitCfg{(int64_t)m * n_items, n_items, 0}, lds, [&](const FocusSumC& p) {
-        hwx = p.hwx > hwx ? p.hwx : hwx;
-        hwz = p.hwz > hwz ? p.hwz : hwz;
-        sr2 += p.sr2;
-        r2_max = p.r2_max > r2_max ? p.r2_max : r2_max;
-    });
-    if (threadIdx.x != 0) return;
-    double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
-    const double s = out[BMO_FOCUS_STAT_S];
-    if (s != s) return;  // NaN already
-    out[BMO_FOCUS_STAT_HWX] = hwx;
-    out[BMO_FOCUS_STAT_HWZ] = hwz;
-    out[BMO_FOCUS_STAT_RMS_R] = sqrt(sr2 / s);
-    out[BMO_FOCUS_STAT_MAX_R] = sqrt(r2_max);
-}
+struct FocusSpreadFinish {
+    double* stats;
+    __device__ void empty(int32_t) const {}  // a plane has every work item of the call
+    __device__ void operator()(int32_t m, const FocusSumC& v) const {
+        double* out = stats + (int64_t)m * BMO_FOCUS_STAT_N;
+        const double s = out[BMO_FOCUS_STAT_S];
+        if (s != s) {  // no statistics: a row parallel to the planes, or a NaN proj (then pass A left these four unwritten)
+            out[BMO_FOCUS_STAT_HWX] = out[BMO_FOCUS_STAT_HWZ] = out[BMO_FOCUS_STAT_RMS_R] = out[BMO_FOCUS_STAT_MAX_R] = knan();
+            return;
+        }
+        out[BMO_FOCUS_STAT_HWX] = v.hwx;
+        out[BMO_FOCUS_STAT_HWZ] = v.hwz;
+        out[BMO_FOCUS_STAT_RMS_R] = sqrt(v.sr2 / s);
+        out[BMO_FOCUS_STAT_MAX_R] = sqrt(v.r2_max);
+    }
+};
 
 }  // namespace
 
@@ -2430,25 +2328,24 @@ extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t h
         return fail(BMO_ERR_INVALID, "bmo_psf_focus_stats: bad argument (null pointer, n_planes <= 0, n_hits < 0)");
     if (kernel_ms) *kernel_ms = 0.0;
     DevBuf d_hits;
-    if (int rc = spot_single_rows("bmo_psf_focus_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (int rc = single_rows("bmo_psf_focus_stats", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
     if (n_hits == 0) {
-        for (int32_t m = 0; m < n_planes; ++m) {
-            double* out = stats + (size_t)m * BMO_FOCUS_STAT_N;
-            std::fill(out, out + BMO_FOCUS_STAT_N, std::nan(""));
-            out[BMO_FOCUS_STAT_N_ROWS] = 0.0;
-        }
+        fill_empty_stats(stats, (size_t)n_planes, BMO_FOCUS_STAT_N);
         return BMO_OK;
     }
     hipStream_t st = 0;
-    const SplitPlan plan = spot_plan(Ranges{{0}, {n_hits}});
+    const SplitPlan plan = rows_plan(Ranges{{0}, {n_hits}});
     unsigned n_items = 0;
-    if (int rc = spot_items(plan, "bmo_psf_focus_stats", n_items)) return rc;
+    if (int rc = rows_items(plan, "bmo_psf_focus_stats", n_items)) return rc;
     FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
     F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
     const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
     if (chunks > 65535) return fail(BMO_ERR_LIMIT, "bmo_psf_focus_stats: more planes than one launch holds");
+    // the partial sums are [plane][item]: to the reduces a plane is a range of n_items records like a configuration's
+    std::vector<SplitCfg> planes((size_t)n_planes);
+    for (int32_t m = 0; m < n_planes; ++m) planes[(size_t)m] = SplitCfg{(int64_t)m * n_items, (int32_t)n_items, 0};
     Packed up;
-    const size_t o_work = up.add(plan.work), o_off = up.add(offsets, (size_t)n_planes);
+    const size_t o_work = up.add(plan.work), o_off = up.add(offsets, (size_t)n_planes), o_planes = up.add(planes);
     DevBuf pa, pc, d_stats, d_mid;
     int rc;
     const size_t cells = (size_t)n_planes * n_items;
@@ -2459,11 +2356,11 @@ extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t h
     if ((rc = timer.start(st))) return rc;
     const SplitWork* d_work = up.at<SplitWork>(o_work);
     const double* d_off = up.at<double>(o_off);
+    const SplitCfg* d_planes = up.at<SplitCfg>(o_planes);
     hipLaunchKernelGGL(psf_focus_sums_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (FocusSumA*)pa.p);
-    hipLaunchKernelGGL(psf_focus_sums_reduce_kernel, dim3((unsigned)n_planes), dim3(256), 0, st, (int32_t)n_items, n_hits, (const FocusSumA*)pa.p, (double*)d_stats.p,
-                       (double2*)d_mid.p);
+    sum_reduce<FocusSumA>((unsigned)n_planes, st, d_planes, pa, FocusSumsFinish{n_hits, (double*)d_stats.p, (double2*)d_mid.p});
     hipLaunchKernelGGL(psf_focus_spread_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (const double2*)d_mid.p, (FocusSumC*)pc.p);
-    hipLaunchKernelGGL(psf_focus_spread_reduce_kernel, dim3((unsigned)n_planes), dim3(256), 0, st, (int32_t)n_items, (const FocusSumC*)pc.p, (double*)d_stats.p);
+    sum_reduce<FocusSumC>((unsigned)n_planes, st, d_planes, pc, FocusSpreadFinish{(double*)d_stats.p});
     if ((rc = timer.stop(kernel_ms))) return rc;
     HIP_TRY(hipMemcpy(stats, d_stats.p, (size_t)n_planes * BMO_FOCUS_STAT_N * 8, hipMemcpyDeviceToHost));
     return BMO_OK;
@@ -2473,11 +2370,7 @@ extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t h
 // of the _sweep forms
 extern "C" int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, const double** data, int64_t* count, int32_t* device) {
     if (!res || !data || !count) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: bad argument");
-    if (detector < 0 || detector >= res->n_detectors) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: bad detector slot");
-    if (res->kind == BMO_BEAM_GAUSSIAN)
-        return fail(BMO_ERR_UNSUPPORTED, "bmo_result_psf_rows: a GaussianBeamlet solution has three rows per beamlet, not PSF rows");
-    if ((size_t)detector >= res->det_kind.size() || res->det_kind[(size_t)detector] != BMO_OBJ_PSFDETECTOR)
-        return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: the slot is not a PSFDetector's");
+    if (int rc = slot_check("bmo_result_psf_rows", res, detector, BMO_OBJ_PSFDETECTOR, true, -1)) return rc;
     if (res->n_configs > 0) return fail(BMO_ERR_INVALID, "bmo_result_psf_rows: a sweep result holds the rows of several configurations");
     *count = res->det_count[detector];
     *data = res->det_data.p ? (const double*)res->det_data.p + 9 * res->det_offset[detector] : nullptr;

@@ -359,3 +359,18 @@ def test_rows_without_statistics_do_not_fault(case600):
     flat[7] = rows[7]
     st, _ = abi.psf_focus_stats(flat, *frame, [0.0, 1.0, 0.0], [0.0, 1e-4, -1e-4])
     assert np.isfinite(st).all()
+
+
+def test_a_nan_proj_reads_nan_not_what_the_buffer_held(case600):
+    """A NaN proj makes S NaN without a row parallel to the planes: S, the centroid and the four spreads about it read NaN, N and the extrema
+    are those of the rows.  The call before leaves finite statistics of the same shape behind, which the spread columns must not repeat."""
+    rows, pose, o = case600
+    offs = [0.0, 1e-4, -1e-4]
+    good, _ = abi.psf_focus_stats(rows[:300], *pose, o[:, 1], offs)
+    assert np.isfinite(good).all()
+    bad = rows[:300].copy()
+    bad[7, 7] = np.nan
+    st, _ = abi.psf_focus_stats(bad, *pose, o[:, 1], offs)
+    nan_cols = [fr.S, fr.CX, fr.CZ, fr.HWX, fr.HWZ, fr.RMS_R, fr.MAX_R]
+    kept = [fr.N, fr.X_MIN, fr.X_MAX, fr.Z_MIN, fr.Z_MAX]
+    assert np.isnan(st[:, nan_cols]).all() and np.array_equal(st[:, kept], good[:, kept])
