@@ -2,7 +2,6 @@
 library's host entries on the scene blob the GPU reads (bmo_scene_mesh_bvh, bmo_mesh_nearest_host).  Brute force is the same entry on
 the scene compiled with mesh_bvh=False (every face, Mesh.jl:244-267): t bits and face must agree for every ray."""
 import ctypes as C
-import math
 import time
 
 import numpy as np
@@ -13,10 +12,9 @@ from bmo_amd import abi
 
 from tests import mesh_scenes as ms
 from tests import scenes
+from tests.mesh_scenes import MESHES, _cuboid_grid, _fan, _rays, _slivers, _soup, _sphere  # noqa: F401  (shared with test_mesh_bvh_waves*.py)
 
 mm = 1e-3
-KEPS = 1e-9  # mt_keps of CompiledScene
-LEPS = 1e-9
 
 
 def _scene(mesh, mesh_bvh=True):
@@ -71,134 +69,6 @@ def test_blob_over_4_gib_is_refused():
         d.n_tris = n_tris
     assert rc == -1
     assert b"4 GiB" in lib.bmo_last_error()
-
-
-# ------------------------------------------------------------------ meshes
-def _sphere():
-    return ms.icosphere(3, 7 * mm, (1 * mm, -2 * mm, 3 * mm))  # 1 280 faces
-
-
-def _soup(rng, n=1000):
-    """Random triangles of mixed scales (edges from 1 um to 10 mm) in a 20 mm box."""
-    c = rng.uniform(-10 * mm, 10 * mm, (n, 1, 3))
-    s = 10.0 ** rng.uniform(-6, -2, (n, 1, 1))
-    v = (c + s * rng.normal(size=(n, 3, 3))).reshape(-1, 3)
-    return v, np.arange(3 * n).reshape(n, 3)
-
-
-def _slivers(rng, n=600):
-    """Needle triangles: two vertices far apart, the third a hair off their line."""
-    a = rng.uniform(-10 * mm, 10 * mm, (n, 3))
-    b = a + rng.normal(size=(n, 3)) * 5 * mm
-    w = rng.uniform(0, 1, (n, 1))
-    c = a + w * (b - a) + rng.normal(size=(n, 3)) * 10.0 ** rng.uniform(-12, -7, (n, 1))
-    v = np.stack([a, b, c], axis=1).reshape(-1, 3)
-    return v, np.arange(3 * n).reshape(n, 3)
-
-
-def _cuboid_grid(k=8, size=(10 * mm, 6 * mm, 8 * mm)):
-    """A cuboid whose six sides are k x k grids of coplanar face pairs (6 * 2 k^2 faces) sharing edges and vertices."""
-    verts, faces = [], []
-    sx, sy, sz = size
-    for ax in range(3):
-        for side in (0.0, 1.0):
-            u, w = [a for a in range(3) if a != ax]
-            base = len(verts)
-            for i in range(k + 1):
-                for j in range(k + 1):
-                    p = [0.0, 0.0, 0.0]
-                    p[ax], p[u], p[w] = side, i / k, j / k
-                    verts.append([p[0] * sx, p[1] * sy, p[2] * sz])
-            for i in range(k):
-                for j in range(k):
-                    a, b, c, d = base + i * (k + 1) + j, base + (i + 1) * (k + 1) + j, base + (i + 1) * (k + 1) + j + 1, base + i * (k + 1) + j + 1
-                    faces += [[a, b, c], [a, c, d]]
-    return np.array(verts), np.array(faces)
-
-
-def _fan():
-    m = bmo.CircularFlatMesh(20 * mm, 2400)  # test_fuzz.py::test_scene_larger_than_lds's mirror
-    bmo.xrotate3d(m, math.radians(20))
-    bmo.translate3d(m, [0, 60 * mm, 0])
-    return m.vertices, m.faces
-
-
-# ------------------------------------------------------------------ rays
-def _unit(x):
-    return x / np.linalg.norm(x, axis=-1, keepdims=True)
-
-
-def _rays(rng, v, f, n):
-    """n rays in seven families: random, through vertices, through shared-edge midpoints, grazing (|Det| just above kϵ),
-    axis-parallel (origins on vertex coordinates, i.e. on slab planes), starting on a face (t around lϵ), starting inside the mesh's
-    leaf boxes (a face's centroid, a hair off)."""
-    tri = v[f]
-    lo, hi = v.min(axis=0), v.max(axis=0)
-    span = hi - lo
-    k = n // 7
-    P, D = [], []
-
-    def origins(m):
-        return lo - span + rng.uniform(0, 1, (m, 3)) * 3 * span
-
-    def face_points(m):
-        i = rng.integers(0, len(f), m)
-        w = rng.dirichlet([1, 1, 1], m)
-        return i, np.einsum("mk,mkj->mj", w, tri[i])
-
-    # random lines through random points of faces (hits)
-    o = origins(k)
-    _, q = face_points(k)
-    P.append(o), D.append(q - o)
-    # through vertices (every face around a vertex is hit at the same t)
-    o = origins(k)
-    P.append(o), D.append(v[rng.integers(0, len(v), k)] - o)
-    # through midpoints of edges (two faces share the edge)
-    o = origins(k)
-    i = rng.integers(0, len(f), k)
-    e = rng.integers(0, 3, k)
-    a, b = tri[i, e], tri[i, (e + 1) % 3]
-    P.append(o), D.append(0.5 * a + 0.5 * b - o)
-    # grazing: in the face's plane plus a normal part that puts |Det| just above (or at) kϵ
-    i, q = face_points(k)
-    E1, E2 = tri[i, 1] - tri[i, 0], tri[i, 2] - tri[i, 0]
-    N = np.cross(E1, E2)
-    nn = np.linalg.norm(N, axis=1)
-    ok = nn > 0
-    inplane = _unit(np.cross(N[ok], rng.normal(size=(ok.sum(), 3))))
-    alpha = (KEPS * rng.choice([0.999, 1.0, 1.0 + 1e-9, 1.001, 1.1, 2.0], ok.sum()) / nn[ok])[:, None]
-    d = inplane + alpha * (N[ok] / nn[ok, None])
-    P.append(q[ok] - d * rng.uniform(0.01, 1.0, (ok.sum(), 1)) * np.linalg.norm(span)), D.append(d)
-    # axis-parallel, origins with coordinates taken from vertices (on the faces' box planes)
-    o = origins(k)
-    vv = v[rng.integers(0, len(v), (k, 3))]
-    axis = rng.integers(0, 3, k)
-    for c in range(3):
-        m = axis != c
-        o[m, c] = vv[m, c, c]
-    d = np.zeros((k, 3))
-    d[np.arange(k), axis] = rng.choice([-1.0, 1.0], k)
-    P.append(o), D.append(d)
-    # starting on a face: t around lϵ for the face it starts on
-    i, q = face_points(k)
-    d = _unit(rng.normal(size=(k, 3)))
-    back = rng.choice([0.0, 0.5 * LEPS, LEPS, 1.5 * LEPS, 3 * LEPS, 1e-6], k)[:, None]
-    P.append(q - back * d), D.append(d)
-    # inside the leaf boxes
-    m = n - 6 * k
-    i = rng.integers(0, len(f), m)
-    o = tri[i].mean(axis=1) + rng.normal(size=(m, 3)) * 1e-9
-    P.append(o), D.append(_unit(rng.normal(size=(m, 3))))
-    return np.concatenate(P), np.concatenate(D)
-
-
-MESHES = {
-    "sphere": (lambda rng: _sphere(), 250_000),
-    "soup": (_soup, 200_000),
-    "slivers": (_slivers, 150_000),
-    "cuboid": (lambda rng: _cuboid_grid(), 250_000),
-    "fan": (lambda rng: _fan(), 150_000),
-}
 
 
 @pytest.mark.parametrize("name", list(MESHES))

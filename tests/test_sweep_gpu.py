@@ -203,6 +203,27 @@ def test_mesh_scenes_sweep(name, kind):
     _sweep_vs_separate(scenes, [bundle] * 3, 100, label="mesh %s %s" % (name, kind))
 
 
+@pytest.mark.parametrize("kind", ["ray", "gauss"])
+def test_light_trap_sweep(oracle, kind):
+    """The light trap of tests/mesh_scenes.py (four BVH meshes, rays in all directions) with the ball moved and turned differently in each
+    configuration — each configuration has its own tree over the ball — under ragged slices of the permuted bundle; every configuration against the oracle too."""
+    system, parts = ms.light_trap_scene()
+    bundle = ms.light_trap_bundle(kind, 130)
+    moves = [([0.0, 0.0, 0.0], 0.0), ([0.05 * mm, 0.1 * mm, 0.0], 0.3), ([-0.2 * mm, 0.0, 0.15 * mm], -7.0)]
+
+    def configure(c):
+        bmo.translate3d(parts["ball"], moves[c][0])
+        bmo.zrotate3d(parts["ball"], math.radians(moves[c][1]))
+
+    scenes = bmo.sweep_snapshots(system, bundle.lambdas, 3, configure)[0]
+    assert sum(v[0] > 0 for v in bmo.mesh_bvh_stats(scenes[0]).values()) == 4
+    ball = scenes[0].shape_id(parts["ball"].shape)
+    assert len({bmo.mesh_bvh_stats(s)[ball] for s in scenes}) == 3  # three different trees over the ball
+    sizes = [130, 65, 1]
+    _sweep_vs_separate(scenes, [bmo.RayBundle(bundle.kind, bundle.planes[:, :n].copy()) for n in sizes], 20, label="light trap " + kind,
+                       oracle=oracle, oracle_every=1)
+
+
 # ------------------------------------------------------------------------------------------------ detector-only sweeps
 def test_detector_only_sweep_spot_hits():
     system, rng = random_system(404, with_detectors=True)
