@@ -227,6 +227,46 @@ class _Beamlet:
         E = E * (self.proj if self.planted == "proj_not_sqrt" else mp.sqrt(self.proj))
         return E, dict(w=w, R=R, psi=psi, w0=w0, a=a, t3=t3, x=R * zz, x1=x1, E_kt=E_kt, H=H)
 
+    def _eps_point(self, eps_z, z, s, temp, point):
+        """2a: the error bound of point_on_beam's point from that of z."""
+        u = _mp().mpf(U)
+        eps_s = eps_z + u * (self.n_len * abs(temp) + abs(temp - z) + abs(s))
+        return eps_s + u * abs(s) + u * _norm(point)
+
+    @staticmethod
+    def _eps_height_slope(eps_pt, y, m, g):
+        """2a: (eps_y, eps_m) of one ray's height and slope from the point's error bound and height_slope's third result."""
+        mp = _mp()
+        u = mp.mpf(U)
+        ad = abs(g["denom"])
+        eps_y0 = eps_pt * (1 + 1 / ad) + u * (4 * g["q"] / ad + 5 * abs(g["il"]) + g["foot"] + y)
+        eps_m = (1 + m ** 2) * ((eps_y0 / y + 11 * u) / mp.sqrt(1 - g["arg"] ** 2) + u * (5 * mp.pi / 2 + abs(g["alpha"]))) + 2 * u * abs(m)
+        return eps_y0 + 3 * u * y, eps_m
+
+    def waist_at(self, z):
+        """The fourth result of gauss_parameters(gauss, z) (Gaussian.jl:298-353), the waist radius w0 a beamlet takes on at z, with a first-order
+        bound of what the same formulas give in doubles -> (w0, bound).  z = length(gauss) is what a splitter's children are built with
+        (ThinBeamsplitter.jl:123, :134).  w0 = H / (n F), F = sqrt(m_d^2 + m_w^2): the error model of m_d, m_w and H of section 2a; z itself is a
+        sum of n_len lengths (n_len u z); H carries the errors of the four heights and slopes and 3 u of its terms, or is the double of
+        lambda / pi (2 u) where it is NOT approximately that (Gaussian.jl:336-339); F 3 u, the product and the quotient 2 u."""
+        mp = _mp()
+        u = mp.mpf(U)
+        point, index, s, temp = self.point_on_beam(z)
+        seg = self.segs[index - 1]
+        y_d, m_d, gd = self.height_slope(point, seg["dir"], seg["dpos"], seg["ddir"])
+        y_w, m_w, gw = self.height_slope(point, seg["dir"], seg["wpos"], seg["wdir"])
+        n = seg["n"]
+        H = abs(n * (y_w * m_d - y_d * m_w))
+        eps_pt = self._eps_point(u * self.n_len * abs(z), z, s, temp, point)
+        (e_yd, e_md), (e_yw, e_mw) = self._eps_height_slope(eps_pt, y_d, m_d, gd), self._eps_height_slope(eps_pt, y_w, m_w, gw)
+        if not abs(H - self.lam / mp.pi) <= 1e-6:                              # Gaussian.jl:332-337, as closing() has it
+            H, eps_H = self.lam / mp.pi, 2 * u * self.lam / mp.pi
+        else:
+            eps_H = n * (abs(m_d) * e_yw + abs(y_w) * e_md + abs(m_w) * e_yd + abs(y_d) * e_mw) + 3 * u * n * (abs(y_w * m_d) + abs(y_d * m_w))
+        F = mp.sqrt(m_d ** 2 + m_w ** 2)
+        w0 = H / (n * F)
+        return w0, w0 * (eps_H / H + (abs(m_d) * e_md + abs(m_w) * e_mw) / F ** 2 + 5 * u)
+
     def at(self, p1, A, bound):
         """The field at detector point p1 -> (E, index, info); with `bound` also this beamlet's share of pd_oracle_bound (A: the |A| of 2a)."""
         mp = _mp()
@@ -250,14 +290,10 @@ class _Beamlet:
         # 2a: the error bounds of the intermediates
         eps_r = u * (6 * A + 4 * ndp + abs(l1) + _norm(p2) + 4 * r)
         eps_z = u * (self.n_len * self.length + abs(self.l0) + abs(z) + 3 * A + 4 * ndp)
-        eps_s = eps_z + u * (self.n_len * abs(temp) + abs(temp - z) + abs(s))
-        eps_pt = eps_s + u * abs(s) + u * _norm(point)
+        eps_pt = self._eps_point(eps_z, z, s, temp, point)
         eps = {"r": eps_r, "z": eps_z}
         for name, y, m, g in (("d", y_d, m_d, gd), ("w", y_w, m_w, gw)):
-            ad = abs(g["denom"])
-            eps_y0 = eps_pt * (1 + 1 / ad) + u * (4 * g["q"] / ad + 5 * abs(g["il"]) + g["foot"] + y)
-            eps["y_" + name] = eps_y0 + 3 * u * y
-            eps["m_" + name] = (1 + m ** 2) * ((eps_y0 / y + 11 * u) / mp.sqrt(1 - g["arg"] ** 2) + u * (5 * mp.pi / 2 + abs(g["alpha"]))) + 2 * u * abs(m)
+            eps["y_" + name], eps["m_" + name] = self._eps_height_slope(eps_pt, y, m, g)
         eps["E_kt"] = 2 * u * (abs(y_d * m_d) + abs(y_w * m_w))
         eps["H"] = 3 * u * n * (abs(y_w * m_d) + abs(y_d * m_w))
         eps["x1"] = (18 * u / c["x"] + u * abs(c["x1"])) if c["x1"] != mp.inf else mp.mpf(0)

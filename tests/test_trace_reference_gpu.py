@@ -44,8 +44,8 @@ def _sample(c):
     return (first + rest)[:SAMPLE]
 
 
-def _held(name, h):
-    print(h.line(name + " (engine)"))
+def _held(name, h, what="engine"):
+    print(h.line("%s (%s)" % (name, what)))
     assert h.bounces >= 2 * SAMPLE * 0.9
     assert h.excluded <= (0 if name in tc.NO_EXCLUSIONS else 0.02 * h.bounces), (h.excluded, h.bounces)
     assert not h.over, h.over[:5]
@@ -87,11 +87,14 @@ def test_engine_rows_end_to_end(name, stride, rows_min):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["ray", "pol"])
+@pytest.mark.parametrize("kind", ["ray", "pol", "plate-ray", "cube-pol"])
 def test_engine_retrace_after_a_move(oracle, kind):
-    """The lens translated by 0.3 mm and rotated by 0.5 degrees: the retraced records meet the per-bounce bounds of the MOVED prescription."""
+    """The lens (ray, pol: the singlet; else the plate or cube splitter of that scene) translated by 0.3 mm and rotated by 0.5 degrees: the
+    retraced records meet the per-bounce bounds of the MOVED prescription.  No beamlets through a moved splitter: there the reference computes
+    a child's w0 over a stale tail, which the exact evaluator does not model."""
     move = ([0.3 * tc.mm, 0, 0], math.radians(0.5))
-    c0, c1 = _wide("singlet-" + kind), _wide("singlet-" + kind, move=move)
+    scene = "singlet-" + kind if kind in ("ray", "pol") else kind
+    c0, c1 = _wide(scene), _wide(scene, move=move)
     assert not np.array_equal(np.asarray(c0.lens.position()), np.asarray(c1.lens.position()))
     g0, s0 = _solve(c0.scene, c0.bundle)
     try:
@@ -100,7 +103,7 @@ def test_engine_retrace_after_a_move(oracle, kind):
             a0, osol = oracle.trace(c0.scene, c0.bundle, tc.R_MAX, threads=16, keep=True)
             compare(g1, oracle.trace(c1.scene, c1.bundle, tc.R_MAX, threads=16, prev=osol), 0.0, "retrace")
             osol.free()
-            _held("singlet-%s retraced" % kind, tc.hold(g1, c1, c1.consts, nodes=tc.tree_nodes(g1, _sample(c1))))
+            _held(scene, tc.hold(g1, c1, c1.consts, nodes=tc.tree_nodes(g1, _sample(c1))), "retraced")
             assert g1.rec.shape != g0.rec.shape or not np.array_equal(g1.rec, g0.rec)  # the move shows in the records
         finally:
             s1.free()

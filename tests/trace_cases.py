@@ -540,7 +540,213 @@ def doublet(kind="ray", planted=None):
     return c
 
 
+# ------------------------------------------------------------------------------------------------ scene 10: plate and cube splitters
+PLATE = dict(w=30 * mm, h=25 * mm, l=3 * mm, d=25 * mm, n=1.5, refl=0.3)
+CUBE = dict(leg=20 * mm, n=1.5, refl=0.3)
+
+
+def _two_fans(at, kind, per_side=(16, 7, 1), back=15 * mm):
+    """Half of the rays come up +y and half down -y onto `at`: a disc of 6 mm, a ring of 2 mm sloped by 0.05, one ray on the axis, per side."""
+    P, D = [], []
+    for sgn in (1.0, -1.0):
+        for p, d in (disc(at, [0.02, sgn, -0.01], 6 * mm, per_side[0], back=back), ring(at, [0, sgn, 0], 2 * mm, per_side[1], back=back, slope=0.05),
+                     ring(at, [0, sgn, 0], 0.0, per_side[2], back=back)):
+            P.append(p)
+            D.append(d)
+    return gauss_bundle(P, D) if kind == "gauss" else bundle(kind, P, D)
+
+
+def _detector(kind, width):
+    """PSFDetector for Rays, Spotdetector for PolarizedRays, Photodetector for beamlets -> (object, the exact evaluator's kind)."""
+    return {"ray": lambda: (bmo.PSFDetector(width), "psf"), "pol": lambda: (bmo.Spotdetector(width), "spot"),
+            "gauss": lambda: (bmo.Photodetector(width, 8), "pd")}[kind]()
+
+
+def _four_arms(c, splitter, exact, kind, at, axis, extra=(), extra_exact=()):
+    """The splitter and a detector in each of its four arms: +y and -y (the transmitted arms of the two fans), and -axis / +axis (the reflected
+    ones; axis 'z' or 'x'), 50 mm from `at`."""
+    objs, ex = [splitter] + list(extra), [exact] + list(extra_exact)
+    for off, rot in (([0, 50 * mm, 0], None), ([0, -50 * mm, 0], None), (-50 * mm, axis), (50 * mm, axis)):
+        det, dk = _detector(kind, 40 * mm)
+        if rot == "z":
+            bmo.xrotate3d(det, math.radians(90))
+            off = [0, 0, off]
+        elif rot == "x":
+            bmo.zrotate3d(det, math.radians(90))
+            off = [off, 0, 0]
+        bmo.translate3d(det, np.asarray(at) + np.asarray(off))
+        objs.append(det)
+        ex.append(tr.ExactFlat(40 * mm, det.position(), det.orientation(), dk))
+    c.system, c.exact = bmo.System(objs), ex
+    return c
+
+
+def plate(kind="ray", planted=None, round_=False, move=None):
+    """RectangularPlateBeamsplitter(30 mm, 25 mm, 3 mm, 1.5; reflectance 0.3) (round_: RoundPlateBeamsplitter(25 mm, 3 mm, ...)) at 45 degrees,
+    rolled 2 degrees and decentred.  One fan meets the coated side (the coated-face tie of coating and substrate, both children start on the
+    substrate's surface), the other enters the substrate through its back and meets the coating from inside: both values of isentering.  A
+    detector in each of the four arms; 'pol': a singlet in the -y transmitted arm (the child of the fan that came through the substrate)."""
+    c = Case()
+    q = PLATE
+    if round_:
+        bs = bmo.RoundPlateBeamsplitter(q["d"], q["l"], lambda lam: q["n"], reflectance=q["refl"])
+    else:
+        bs = bmo.RectangularPlateBeamsplitter(q["w"], q["h"], q["l"], lambda lam: q["n"], reflectance=q["refl"])
+    bmo.xrotate3d(bs, math.radians(45))
+    bmo.zrotate3d(bs, math.radians(2))
+    bmo.translate3d(bs, [0.3 * mm, 40 * mm, -0.2 * mm])
+    if move is not None:
+        bmo.translate3d(bs, move[0])
+        bmo.zrotate3d(bs, move[1])
+    c.lens = bs
+    ex = tr.ExactPlateBS(q["d"] if round_ else q["w"], q["h"], q["l"], lambda lam: q["n"], q["refl"], bs.position(), bs.orientation(), round_=round_)
+    at = np.array([0.3 * mm, 40 * mm, -0.2 * mm])
+    extra, extra_exact = (), ()
+    if kind == "pol":
+        lt = bmo.SphericalLens(S1["r1"], S1["r2"], S1["l"], S1["d"], S1["n"])
+        bmo.xrotate3d(lt, math.radians(2))
+        bmo.translate3d(lt, [0.3 * mm, 12 * mm, 0])
+        extra = (lt,)
+        extra_exact = (tr.ExactLens(tr.Surface(S1["r1"]), tr.Surface(S1["r2"]), S1["l"], S1["d"], lambda lam: S1["n"], lt.position(), lt.orientation()),)
+    _four_arms(c, bs, ex, kind, at, "z", extra, extra_exact)
+    c.bundle = _two_fans(at, kind)
+    c.name = ("roundplate-" if round_ else "plate-") + kind
+    return c
+
+
+def cube(kind="ray", planted=None, move=None):
+    """CubeBeamsplitter(20 mm, 1.5; reflectance 0.3), rolled 2 / 1.5 degrees and decentred: one fan enters through the front prism, one through
+    the back prism; both prisms hint at the coating, both children start in glass on the face the two prisms share."""
+    c = Case()
+    q = CUBE
+    bs = bmo.CubeBeamsplitter(q["leg"], lambda lam: q["n"], reflectance=q["refl"])
+    bmo.zrotate3d(bs, math.radians(2))
+    bmo.xrotate3d(bs, math.radians(1.5))
+    bmo.translate3d(bs, [0.3 * mm, 40 * mm, -0.2 * mm])
+    if move is not None:
+        bmo.translate3d(bs, move[0])
+        bmo.zrotate3d(bs, move[1])
+    c.lens = bs
+    ex = tr.ExactCubeBS(q["leg"], lambda lam: q["n"], q["refl"], bs.position(), bs.orientation())
+    at = np.array([0.3 * mm, 40 * mm, -0.2 * mm])
+    _four_arms(c, bs, ex, kind, at, "x")
+    c.bundle = _two_fans(at, kind, back=25 * mm)
+    c.name = "cube-" + kind
+    return c
+
+
+def splitter_gauss(planted=None):
+    """GaussianBeamlets through the singlet of scene 1 (their waist changes: a child's w0 is not the root's) and two ThinBeamsplitters in a row,
+    reflectance 0.3 and 0.6: the first is met from behind its normal (phi = 0), the second, in the transmitted arm, faces the beam
+    (phi = pi); its children are grandchildren whose length(gauss) runs over two parents.  A Photodetector in each of the three arms."""
+    c = Case()
+    lens = bmo.SphericalLens(S1["r1"], S1["r2"], S1["l"], S1["d"], S1["n"])
+    bmo.xrotate3d(lens, math.radians(2))
+    bmo.translate3d(lens, [0.3 * mm, 20 * mm, 0])
+    b1, b2 = bmo.ThinBeamsplitter(20 * mm, reflectance=0.3), bmo.ThinBeamsplitter(20 * mm, reflectance=0.6)
+    bmo.xrotate3d(b1, math.radians(45))
+    bmo.zrotate3d(b1, math.radians(1))
+    bmo.translate3d(b1, [0.2 * mm, 50 * mm, 0])
+    bmo.xrotate3d(b2, math.radians(135))
+    bmo.translate3d(b2, [0, 75 * mm, 0.2 * mm])
+    dets = []
+    for rot, at in ((90, [0, 50 * mm, -40 * mm]), (0, [0, 110 * mm, 0]), (90, [0, 75 * mm, 40 * mm])):
+        d = bmo.Photodetector(40 * mm, 8)
+        bmo.xrotate3d(d, math.radians(rot))
+        bmo.translate3d(d, at)
+        dets.append(d)
+    c.system, c.lens = bmo.System([lens, b1, b2] + dets), lens
+    c.exact = [tr.ExactLens(tr.Surface(S1["r1"]), tr.Surface(S1["r2"]), S1["l"], S1["d"], lambda lam: S1["n"], lens.position(), lens.orientation()),
+               tr.ExactFlat(20 * mm, b1.position(), b1.orientation(), "thin_bs", reflectance=0.3),
+               tr.ExactFlat(20 * mm, b2.position(), b2.orientation(), "thin_bs", reflectance=0.6)] + [
+        tr.ExactFlat(40 * mm, d.position(), d.orientation(), "pd") for d in dets]
+    at = np.array([0.3 * mm, 20 * mm, 0.0])
+    P, D = zip(disc(at, [0.01, 1.0, -0.005], 6 * mm, 38, back=15 * mm), ring(at, [0, 1, 0], 2 * mm, 9, back=15 * mm, slope=0.02), ring(at, [0, 1, 0], 0.0, 1, back=15 * mm))
+    c.bundle = gauss_bundle(P, D)
+    c.name = "splitter-gauss"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 11: polarization filters
+def pol_bundle(pos, dirs, E, lam=1.064e-6):
+    """PolarizedRays with the complex field E (one row per ray), made orthogonal to each ray's direction (PolarizedRays.jl:54)."""
+    b = bmo.RayBundle.rays(np.vstack(pos), np.vstack(dirs), lam)
+    d = b.planes[3:6].T
+    E = np.array(E, dtype=np.complex128)
+    for _ in range(3):
+        E = E - (E * d).sum(axis=1)[:, None] * d
+    P = np.zeros((14, b.n))
+    P[:8] = b.planes
+    P[8:14:2], P[9:14:2] = E.real.T, E.imag.T
+    return bmo.RayBundle(bmo.BEAM_POLARIZED, P)
+
+
+STATES = {"x": [1, 0, 0], "z": [0, 0, 1], "45": [math.sqrt(0.5), 0, math.sqrt(0.5)], "elliptical": [1.0, 0, 0.5 + 0.3j]}
+
+
+def polarizers(planted=None, roll=30.0, tilt=10.0, states=("x", "z", "45", "elliptical"), fan=True, roll1=1.5):
+    """Two PolarizationFilters in a row, the first rolled 1.5 degrees about the beam and decentred, the second rolled `roll` degrees about the
+    beam and tilted `tilt` degrees (a rolled filter shows a transposed rotation, oblique incidence a dropped projection), a Spotdetector
+    behind them.  Four input states: linear along x, along z, at 45 degrees, elliptical; per state a disc, a sloped ring and the axis ray.
+    Beside them eight identical rays onto a third filter whose cutoff is the norm they are transmitted with: they end BLOCKED.
+    fan=False, roll1, roll, tilt, states: the axis ray alone through two filters at the given rolls (the Malus cases of the tests)."""
+    c = Case()
+    f1, f2, f3 = bmo.PolarizationFilter(20 * mm), bmo.PolarizationFilter(20 * mm), None
+    bmo.yrotate3d(f1, math.radians(roll1))
+    bmo.translate3d(f1, [0.2 * mm, 20 * mm, -0.1 * mm])
+    bmo.yrotate3d(f2, math.radians(roll))
+    bmo.xrotate3d(f2, math.radians(tilt))
+    bmo.translate3d(f2, [-0.2 * mm, 40 * mm, 0.1 * mm])
+    det = bmo.Spotdetector(60 * mm)
+    bmo.translate3d(det, [0, 70 * mm, 0])
+    flt = lambda f: tr.ExactFlat(20 * mm, f.position(), f.orientation(), "polarizer", pre=math.pi, jones=f.jones, cutoff=f.cutoff)
+    at = np.array([0.0, 20 * mm, 0.0])
+    P, D, E = [], [], []
+    for s in states:
+        fans = (disc(at, [0.01, 1.0, -0.02], 6 * mm, 6), ring(at, [0, 1, 0], 2 * mm, 3, slope=0.05), ring(at, [0, 1, 0], 0.0, 1)) if fan else (ring(at, [0, 1, 0], 0.0, 1),)
+        for p, d in fans:
+            P.append(p)
+            D.append(d)
+            E += [STATES[s]] * len(p)
+    objs, exact = [f1, f2, det], None
+    if fan:  # the third filter, 40 mm beside the beam, tilted 5 degrees and rolled 20; its cutoff from the 50-digit evaluation of its own formula
+        side = np.array([40 * mm, 20 * mm, 0.0])
+        p8, d8 = np.tile(side - [0, 30 * mm, 0], (8, 1)), np.tile(_frame([0.03, 1.0, 0.02])[0], (8, 1))
+        P.append(p8)
+        D.append(d8)
+        E += [STATES["elliptical"]] * 8
+        b = pol_bundle(P, D, E)
+        probe = bmo.PolarizationFilter(20 * mm)
+        for f in (probe,):
+            bmo.yrotate3d(f, math.radians(20))
+            bmo.xrotate3d(f, math.radians(5))
+            bmo.translate3d(f, side)
+        mp = tr._mp()
+        with mp.workdps(50):
+            r = root_of(b, b.n - 1)
+            cut = float(tr.interact_polarizer(flt(probe), tr._v(r["dir"]), mp.mpf(1), tr._c(r["E0"]))[0]["norm"])
+        f3 = bmo.PolarizationFilter(20 * mm, cutoff_strength=cut)
+        bmo.yrotate3d(f3, math.radians(20))
+        bmo.xrotate3d(f3, math.radians(5))
+        bmo.translate3d(f3, side)
+        objs = [f1, f2, det, f3]
+    c.bundle = pol_bundle(P, D, E)
+    c.system = bmo.System(objs)
+    c.exact = [flt(f1), flt(f2), tr.ExactFlat(60 * mm, det.position(), det.orientation(), "spot")] + ([flt(f3)] if f3 is not None else [])
+    c.name = "polarizers"
+    return c
+
+
 SCENES = {
+    "plate-ray": lambda **kw: plate("ray", **kw),
+    "plate-pol": lambda **kw: plate("pol", **kw),
+    "roundplate-ray": lambda **kw: plate("ray", round_=True, **kw),
+    "cube-ray": lambda **kw: cube("ray", **kw),
+    "cube-pol": lambda **kw: cube("pol", **kw),
+    "plate-gauss": lambda **kw: plate("gauss", **kw),
+    "cube-gauss": lambda **kw: cube("gauss", **kw),
+    "splitter-gauss": splitter_gauss,
+    "polarizers": polarizers,
     "phone-l3": phone_l3,
     "prism-ray": lambda **kw: prism("ray", **kw),
     "prism-pol": lambda **kw: prism("pol", **kw),
@@ -570,7 +776,8 @@ SCENES = {
     "asphere-curved-first": lambda **kw: asphere(False, **kw),
     "asphere-plane-first": lambda **kw: asphere(True, **kw),
 }
-NO_EXCLUSIONS = ("phone-l3", "cylinders", "acylinders", "doublet", "doublet-gauss", "asphere-curved-first", "asphere-plane-first")  # the issue's scenes 3 - 5 allow none
+NO_EXCLUSIONS = ("phone-l3", "cylinders", "acylinders", "doublet", "doublet-gauss", "asphere-curved-first", "asphere-plane-first",  # the issue's scenes 3 - 5 allow none
+                 "plate-ray", "plate-pol", "plate-gauss", "roundplate-ray", "cube-ray", "cube-pol", "cube-gauss", "splitter-gauss", "polarizers")
 # Each planted mistake, and the scenes that exercise it.
 PLANTED_ON = [
     ("conic_sign", "phone-l3"),
@@ -590,11 +797,30 @@ PLANTED_ON = [
     ("tir_phase_conjugated", "rhomb"),
     ("tir_phase_conjugated", "prism-pol"),
     ("opl_next_medium", "singlet-ray"),
+    ("plate_no_refraction", "plate-ray"),
+    ("plate_no_refraction", "roundplate-ray"),
+    ("plate_normal_not_flipped", "plate-ray"),
+    ("plate_normal_not_flipped", "plate-gauss"),
+    ("plate_indices_swapped", "plate-ray"),
+    ("plate_indices_swapped", "plate-gauss"),
+    ("cube_children_in_air", "cube-ray"),
+    ("cube_children_in_air", "cube-pol"),
+    ("gauss_no_phase_flip", "cube-gauss"),
+    ("gauss_no_phase_flip", "splitter-gauss"),
+    ("gauss_flip_on_both_sides", "plate-gauss"),
+    ("gauss_flip_on_both_sides", "splitter-gauss"),
+    ("gauss_child_keeps_w0", "splitter-gauss"),
+    ("gauss_child_keeps_w0", "plate-gauss"),
+    ("gauss_w0_at_start", "splitter-gauss"),
+    ("polarizer_rotation_transposed", "polarizers"),
+    ("polarizer_not_projected", "polarizers"),
+    ("coating_loses_tie", "plate-ray"),
+    ("coating_loses_tie", "plate-pol"),
 ]
 
 
 # ------------------------------------------------------------------------------------------------ the comparison
-QUANT = ("t", "n", "pos", "dir", "index", "E0", "opl", "row_pos", "row_dir", "proj", "k")
+QUANT = ("t", "n", "pos", "dir", "index", "E0", "opl", "row_pos", "row_dir", "proj", "k", "w0", "E0_child")
 
 
 class Held:
@@ -603,7 +829,9 @@ class Held:
     def __init__(self):
         self.abs = {q: 0.0 for q in QUANT}
         self.ratio = {q: 0.0 for q in QUANT}
-        self.bounces = self.excluded = self.tir = self.barrel = self.leaving = self.children = 0
+        self.bounces = self.excluded = self.tir = self.barrel = self.leaving = self.children = self.ortho = self.blocked = self.ties = 0
+        self.facing = {True: 0, False: 0}  # coatings met with dot(dir, normal) < 0 / > 0
+        self.phase = {True: 0, False: 0}   # beamlets reflected with phi = pi / phi = 0
         self.over = []
 
     def note(self, q, diff, bound, where):
@@ -648,6 +876,9 @@ def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
                 where = (int(node), k, sub)
                 seg = dict(seg, opl=base + tr.exact_opl(segs, k))
                 obj = solid_of(case, case.exact, seg)
+                if sub and obj.kind == "plate_coating":  # waist and divergence ray take n_t / n_r by the CHIEF ray's isentering
+                    chief = tr.segments_of(res, node, 0)[k]
+                    seg["chief_entering"] = bool(tr.exact_step(chief, obj, consts)["hit"]["cos"] < 0)
                 if cache is not None and where in cache:
                     ex, b = cache[where]
                 else:
@@ -662,9 +893,31 @@ def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
                     continue
                 h.leaving += bool(ex["hit"]["leaving"])
                 h.barrel += ex["hit"]["piece"] == "barrel"
+                # where the reference's PolarizedRay constructor throws (PolarizedRays.jl:54-56) or a filter blocks, the record ends there with that status
+                status, last = int(res.node_status[node]), k == len(segs) - 1
+                assert (ex["end"] == "err_ortho") == bool(last and status & 256), (where, ex["end"], status)
+                assert (ex["end"] == "blocked") == bool(last and status & 128), (where, ex["end"], status)
+                h.ortho += ex["end"] == "err_ortho"
+                h.blocked += ex["end"] == "blocked"
+                if obj.kind in ("thin_bs", "plate_coating", "cube_coating") and sub == 0:
+                    h.facing[bool(ex["hit"]["cos"] < 0)] += 1
+                    if obj.kind == "plate_coating" and (cache is None or ("tie", where) not in cache):
+                        # the coated-face tie: the substrate's exact length is approximately the coating's (PlateBeamsplitter.jl:176)
+                        s = tr.exact_hit(case.exact[seg["obj"]].parts[0], tr._v(seg["pos"]), tr._v(seg["dir"]), consts)
+                        tie = s is not None and abs(s["t"] - ex["t"]) <= 2.0 ** -26 * max(abs(s["t"]), abs(ex["t"]))
+                        if cache is not None:
+                            cache[("tie", where)] = tie
+                    if obj.kind == "plate_coating":
+                        h.ties += bool(cache[("tie", where)] if cache is not None else tie)
                 cmp_ = ex
                 if planted is not None:
-                    cmp_ = tr.exact_step(dict(seg, opl=base + tr.exact_opl(segs, k, planted)), solid_of(case, wrong, seg), consts, planted)
+                    solid = solid_of(case, wrong, seg)
+                    if planted == "coating_loses_tie" and obj.kind == "plate_coating":
+                        # the evaluator that lets the substrate win the tie of the coated face meets the substrate where the record has the coating
+                        at_sub = tr.exact_step(seg, wrong[seg["obj"]].parts[0], consts)
+                        if at_sub is not None and abs(at_sub["t"] - ex["t"]) <= 2.0 ** -26 * max(abs(at_sub["t"]), abs(ex["t"])):
+                            solid = wrong[seg["obj"]].parts[0]
+                    cmp_ = tr.exact_step(dict(seg, opl=base + tr.exact_opl(segs, k, planted)), solid, consts, planted)
                     if cmp_ is None or (cmp_["next"] is None) != (ex["next"] is None):
                         h.note("t", math.inf, 1.0, where)
                         continue
@@ -683,15 +936,30 @@ def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
                 if cmp_["children"] is not None:  # the first rays of the two beams a splitter spawns, transmitted first (Beamsplitters.jl:16-19)
                     first = int(res.node_first_child[node])
                     assert first >= 0, where
-                    h.children += 1
+                    h.children += sub == 0
                     for i, o in enumerate(cmp_["children"]):
-                        s2 = tr.segments_of(res, first + i)[0]
+                        s2 = tr.segments_of(res, first + i, sub)[0]  # the child's chief, waist or divergence ray: each is split as a Ray of its own
                         assert int(res.node_parent[first + i]) == node
                         h.note("pos", tr.fdiff(s2["pos"], o["pos"]), b["pos"], where)
                         h.note("dir", tr.fdiff(s2["dir"], o["dir"]), b["outs"][i]["dir"], where)
                         h.note("index", tr.fdiff(s2["n"], o["n"]), 0.0, where)
                         if o["E0"] is not None:
                             h.note("E0", tr.fdiff(s2["E0"], o["E0"]), b["outs"][i]["E0"], where)
+                    if res.rec_planes == 33 and sub == 0:  # once per split: the waist and the field the two child beamlets are built with
+                        facing = bool(ex["hit"]["cos"] < 0)
+                        key = ("gauss", int(node))
+                        if cache is not None and key in cache:
+                            right = cache[key]
+                        else:
+                            right = tr.exact_gauss_children(tr.gauss_record(res, node), obj, facing)
+                            if cache is not None:
+                                cache[key] = right
+                        g = right if planted is None else tr.exact_gauss_children(tr.gauss_record(res, node), obj, facing, planted)
+                        h.phase[facing] += 1
+                        for i, E in enumerate((g["E_t"], g["E_r"])):
+                            aux = res.node_aux[first + i]
+                            h.note("w0", tr.fdiff(float(aux[0]), g["w0"]), right["b_w0"], where)
+                            h.note("E0_child", tr.fdiff(complex(aux[1], aux[2]), E), right["b_E"][i], where)
                 if cmp_["row"] is not None:
                     row = det_row[int(node)]
                     x = cmp_["row"]
@@ -718,7 +986,9 @@ def compile_case(c):
     """The compiled scene of a case, the march constants, and which part of a doublet every shape id of the record means."""
     c.scene = bmo.CompiledScene(c.system, c.bundle.lambdas)
     c.consts = tr.consts_of(c.scene)
-    c.shape_part = {c.scene.shape_id(s): i for o in c.system.objects() if isinstance(o, bmo.DoubletLens) for i, s in enumerate(o.parts())}
+    # a plate splitter's parts are substrate 0 / coating 1, a cube's front 0 / back 1 / coating 2 (shape(pbs), shape(cbs))
+    multi = (bmo.DoubletLens, bmo.RectangularPlateBeamsplitter, bmo.CubeBeamsplitter)
+    c.shape_part = {c.scene.shape_id(s): i for o in c.system.objects() if isinstance(o, multi) for i, s in enumerate(o.parts())}
     return c
 
 
@@ -754,7 +1024,7 @@ def sequence(res, node, case):
 
 def exact_sequence(trace, case):
     objs = [(s["obj"], s["part"]) for s in trace]
-    detected = trace[-1]["ex"] is not None and getattr(case.exact[trace[-1]["obj"]], "kind", None) in ("psf", "spot")
+    detected = trace[-1]["ex"] is not None and getattr(case.exact[trace[-1]["obj"]], "kind", None) in ("psf", "spot", "pd")
     return objs, detected
 
 
@@ -766,6 +1036,8 @@ def left_out(trace):
 def same_tree(trace, res, node, case):
     """The exact trace and the recorded beam tree below `node`: the same objects in the same order, the same end, the same children."""
     assert exact_sequence(trace, case) == sequence(res, node, case), node
+    end = trace[-1]["ex"]["end"] if trace[-1]["ex"] is not None else None
+    assert (end == "err_ortho", end == "blocked") == (bool(res.node_status[node] & 256), bool(res.node_status[node] & 128)), (node, end)
     kids = trace[-1].get("children")
     first = int(res.node_first_child[node])
     assert (kids is None) == (first < 0), node

@@ -111,8 +111,35 @@
    and the reference's doublet has no method for PolarizedRays, DoubletLenses.jl:66).  The tests show both halves: on the doublet scene the switch changes no
    direction beyond 50-digit rounding, and beyond the critical angle glass -> air it turns a refraction into a reflection.
 
-Not covered yet (no pieces for them here): a concave aspheric front or convex aspheric back in a lens with rings; GaussianBeamlets beyond
-their three rays' bounces (no read-out of a beamlet's field here: tests/pd_ref.py has that).
+4. Composite interactions.
+   Plate splitter (ExactPlateBS, parts substrate 0 / coating 1; PlateBeamsplitter.jl:160-228): both parts are tested and the coating wins where
+   the two lengths are approximately equal (rtol sqrt(eps)) or it is nearer; their exact faces coincide, so at the coated face that tie is the
+   rule (like the interface of a doublet: no tie exclusion inside one object).  At the substrate the lens interaction, then a hint at the
+   coating; at the coating the thin splitter's children, the transmitted one's direction replaced by refraction3d(ray, n2) with the normal
+   flipped by the ray's own isentering, the indices (n_optics, 1) entering and (1, n_optics) leaving - for a beamlet by the CHIEF ray's
+   isentering.  The transmitted child's E0 stays that of the straight-through direction.  The round plate's coating is a 30-gon mesh
+   (Mesh.jl:322-348): its triangles are slivers, and the doubles of its world vertices turn a sliver's normal by 2 (8 u M) / (R sin(2 pi / 30)).
+   Cube splitter (ExactCubeBS, front 0 / back 1 / coating 2; CubeBeamsplitter.jl:49-92): both prisms hint at the coating, both children keep
+   their directions and start in glass, on the face the two prisms share.
+   Children start ON surfaces, and exact_hit gives the reference's answer there (AbstractSDF.jl:166-181): within eps_srf of a solid and heading
+   outwards nothing is found on it, heading inwards the inside march runs; a mesh met below mt_leps is no hit.
+   Every new Ray and PolarizedRay is normalised by its constructor (Rays.jl:32-42, PolarizedRays.jl:80-95): a child's direction is
+   normalize(dir), 4 u (this shows inside the cube, where the parent's direction is a refracted one of length 1 to a few u).
+   Polarization filter (interact_polarizer; PolarizationFilter.jl:31-48, JonesCalculus.jl:29-45): E' = Q (R J R^T) Q E0 with R the filter's
+   orientation doubles and Q = I - d d^T, direction and index kept, blocked when norm(E') is approximately the cutoff; a Ray or a beamlet stops
+   there.  Bound of E': four 3 x 3 products and a matrix-vector product at 3 u |A| |B| each, Q's entries 2 u twice, the moduli of Q, R, R^T, Q
+   with 2-norms up to sqrt(3): 171 u |J| |E0|; nothing of it depends on the normal.  An outcome whose exact norm lies within that bound
+   (+ 4 u for the norm) of the threshold is the one the evaluator does not predict (excluded()).
+   The PolarizedRay constructor's check (PolarizedRays.jl:54-56: |dot(dir, E0)| <= 1e-14) runs wherever the reference builds one; where it fails
+   the reference throws and the record ends with BMO_NODE_ERR_ORTHO | BMO_NODE_STOPPED: exact_step's 'end'.  This is what ends the child a
+   plate transmits, at its next refraction.
+   GaussianBeamlet children (exact_gauss_children; ThinBeamsplitter.jl:117-168): w0 = gauss_parameters(gauss, length(gauss))[4], evaluated by
+   tests/pd_ref.py's one 50-digit gauss_parameters (waist_at, with the error model of its section 2a for the bound), E_t = T E0 (w0_g / w0),
+   E_r = R E0 (w0_g / w0) exp(i phi), phi = pi where the chief ray faces the normal; the bound adds 10 u and, for phi = pi, |sin(fl(pi))| = 1.3e-16.
+
+Not covered yet (no pieces for them here): a concave aspheric front or convex aspheric back in a lens with rings; the read-out of a
+beamlet's field (tests/pd_ref.py has that); a RETRACE of beamlets through a moved splitter, where the reference computes the children's w0 over
+a stale tail.
 
 The perimeter with which the reference closes an INFLECTED aspheric leaf (element L3 of the phone objective) enters through ExactRingLens: the
 convex leaf ends at the plane of its largest sag and the mid cylinder starts there, the concave leaf at the plane of its edge height
@@ -127,7 +154,12 @@ import numpy as np
 
 U = 2.0 ** -53
 PLANTED = ("conic_sign", "coef_shift", "back_vertex_edge_sag", "cylinder_extruded_along_z", "exit_normal_not_flipped", "n2_glass_on_exit", "ts_tp_swapped",
-           "tir_phase_conjugated", "opl_next_medium")
+           "tir_phase_conjugated", "opl_next_medium", "plate_no_refraction", "plate_normal_not_flipped", "plate_indices_swapped", "cube_children_in_air",
+           "gauss_no_phase_flip", "gauss_flip_on_both_sides", "gauss_child_keeps_w0", "gauss_w0_at_start", "polarizer_rotation_transposed",
+           "polarizer_not_projected", "coating_loses_tie")
+# The planted mistakes that show only in something held EXACTLY - a child's refractive index, or which part of a plate splitter is met at all -
+# and the quantity whose mismatch shows them: its bound is zero, so the ratio is infinite, not a number of bounds.
+PLANTED_EXACT = {"plate_indices_swapped": "index", "cube_children_in_air": "index", "coating_loses_tie": "t"}
 VIA_AIR = "doublet_via_air"  # not a mistake a Ray's direction can show (n sin(theta) is kept), except beyond the critical angle glass -> air
 SEAM = 1e-8       # a bounce whose exact hit lies this close to a seam between two pieces or to an aperture edge is left out
 TIE = 1e-9        # ... or whose two nearest objects' exact t* differ by less than this
@@ -227,10 +259,14 @@ def _precise(cls):
 
 @_precise
 class _Solid:
-    def __init__(self, position, orientation):
+    def __init__(self, position, orientation, pre=None):
         o = np.asarray(orientation, dtype=np.float64).reshape(3, 3)
         self.pos = _v(position)                      # doubles, or 50-digit numbers derived from doubles
         self.cols = [_v(o[:, k]) for k in range(3)]  # local axis k in world coordinates
+        if pre is not None:  # the solid was turned about z by the DOUBLE angle `pre` before the pose applied: orientation Rz(pre), in 50 digits
+            c, s = _mp().cos(_f(pre)), _mp().sin(_f(pre))
+            c0, c1 = self.cols[0], self.cols[1]
+            self.cols = [_add(_scale(c, c0), _scale(s, c1)), _sub(_scale(c, c1), _scale(s, c0)), self.cols[2]]
         self.pos_mag = float(_norm(self.pos))
 
     def to_local(self, p):
@@ -710,8 +746,8 @@ class ExactBox(_Solid):
 
     kind = "lens"
 
-    def __init__(self, x, y, z, n, position, orientation):
-        super().__init__(position, orientation)
+    def __init__(self, x, y, z, n, position, orientation, pre=None):
+        super().__init__(position, orientation, pre)
         self.half, self.n = [_f(x) / 2, _f(y) / 2, _f(z) / 2], n
         self.size = float(max(x, y, z))
         assert self.size < 0.5
@@ -743,8 +779,8 @@ class ExactPrism(ExactBox):
     the plane x + y = 0: the two leg faces x = -leg / 2 and y = -leg / 2, the two triangular end faces, and the hypotenuse with the outward
     normal (1, 1, 0) / sqrt(2).  max(box, plane) is exact next to every face."""
 
-    def __init__(self, leg, height, n, position, orientation):
-        super().__init__(leg, leg, height, n, position, orientation)
+    def __init__(self, leg, height, n, position, orientation, pre=None):
+        super().__init__(leg, leg, height, n, position, orientation, pre)
 
     def crossings(self, o, v):
         mp = _mp()
@@ -787,10 +823,18 @@ class ExactFlat(_Solid):
     """A flat square mesh of width w (Mesh.jl:282-310) at a pose: a detector (kind 'psf' / 'spot'), an IntersectableObject ('stop'), a plane
     mirror ('mirror', Mirrors.jl:93-96) or a thin splitter ('thin_bs' with its reflectance, ThinBeamsplitter.jl:43-51)."""
 
-    def __init__(self, width, position, orientation, kind="psf", reflectance=None):
-        super().__init__(position, orientation)
+    def __init__(self, width, position, orientation, kind="psf", reflectance=None, height=None, pre=None, sides=None, n=None, jones=None, cutoff=None):
+        """height: a RectangularFlatMesh(width, height) (x by z, Mesh.jl:282-303).  pre: the mesh was turned about z by that double angle and
+        made its own origin (set_new_origin3d!, Mesh.jl:170-174) before the pose applied.  sides: a CircularFlatMesh of diameter `width`
+        (Mesh.jl:322-348): a regular polygon of that many sides inscribed in the circle, normal -y; what lies between the polygon's inscribed
+        circle and the circle is a seam.  n, jones, cutoff: the glass behind a plate's or cube's coating, a filter's Jones matrix and cutoff."""
+        super().__init__(position, orientation, pre)
         self.kind, self.w, self.reflectance = kind, _f(width), reflectance
-        self.size = float(width)
+        self.h = self.w if height is None else _f(height)
+        self.sides, self.n, self.jones, self.cutoff = sides, n, jones, cutoff
+        self.size = float(max(self.w, self.h))
+
+    index = ExactLens.index
 
     def crossings(self, o, v):
         mp = _mp()
@@ -798,12 +842,22 @@ class ExactFlat(_Solid):
             return []
         t = -o[1] / v[1]
         p = _axpy(o, t, v)
-        h = self.w / 2
-        if abs(p[0]) > h or abs(p[2]) > h:
+        if self.sides is not None:
+            r, R = mp.sqrt(p[0] ** 2 + p[2] ** 2), self.w / 2
+            if r > R:
+                return []
+            return [dict(t=t, piece="mesh", n=[mp.mpf(0), mp.mpf(-1), mp.mpf(0)], kappa=mp.mpf(0), f3=mp.mpf(0), S=float(self.w), central=False, exact_leaf=True,
+                         edge_dist=max(R * mp.cos(mp.pi / self.sides) - r, 0),
+                         # the world vertices are doubles, re-rounded by every kinematic step (2 u M each, four steps at the most here: 8 u M,
+                         # M = |position| + R); a triangle of the polygon is a sliver whose smallest altitude is R sin(2 pi / sides), and its
+                         # normal turns by 2 (vertex error) / altitude
+                         dn_vertices=16 * mp.mpf(U) * (self.pos_mag + R) / (R * mp.sin(2 * mp.pi / self.sides)))]
+        hx, hz = self.w / 2, self.h / 2
+        if abs(p[0]) > hx or abs(p[2]) > hz:
             return []
         diag = abs(p[0] + p[2]) / mp.sqrt(2)  # the seam between the two triangles (vertices 2 and 4, Mesh.jl:286-295) is no seam of the SURFACE
-        return [dict(t=t, piece="mesh", n=[mp.mpf(0), mp.mpf(1), mp.mpf(0)], kappa=mp.mpf(0), f3=mp.mpf(0), S=float(self.w), central=False, exact_leaf=True,
-                     edge_dist=min(h - abs(p[0]), h - abs(p[2])), diag=diag)]
+        return [dict(t=t, piece="mesh", n=[mp.mpf(0), mp.mpf(1), mp.mpf(0)], kappa=mp.mpf(0), f3=mp.mpf(0), S=self.size, central=False, exact_leaf=True,
+                     edge_dist=min(hx - abs(p[0]), hz - abs(p[2])), diag=diag)]
 
 
 @_precise
@@ -874,6 +928,44 @@ class ExactMesh(_Solid):
             out.append(dict(t=t, piece="mesh", face=fid, n=_scale(1 / area2, nrm), kappa=mp.mpf(0), f3=mp.mpf(0), S=self.size, central=False,
                             exact_leaf=True, edge_dist=edge))
         return sorted(out, key=lambda h: h["t"])
+
+
+@_precise
+class ExactPlateBS:
+    """RectangularPlateBeamsplitter(width, height, thickness, n; reflectance) / RoundPlateBeamsplitter(diameter, thickness, n; reflectance)
+    (PlateBeamsplitter.jl:89-104, :146-158): parts = [substrate, coating].  position() is the coating's, orientation() the substrate's (:38-40):
+    both parts are derived from these two alone.  The rectangular substrate is BoxSDF(width, thickness, height) centred thickness / 2 behind
+    the coating along the plate's +y; the round one PlanoSurfaceSDF(thickness, diameter), the cylinder 0 <= y <= thickness (a lens of two
+    flat faces).  The coating is a flat mesh at the position whose normal is the plate's -y (turned by the double pi about z; the round one
+    is built that way).  The exact faces of substrate and coating coincide by construction, like the parts of a doublet."""
+
+    kind = "plate_bs"
+
+    def __init__(self, width, height, thickness, n, reflectance, position, orientation, round_=False):
+        o = np.asarray(orientation, dtype=np.float64).reshape(3, 3)
+        if round_:
+            sub = ExactLens(Surface(math.inf), Surface(math.inf), thickness, width, n, position, orientation)
+            coat = ExactFlat(width, position, orientation, "plate_coating", reflectance, sides=30, n=n)
+        else:
+            centre = _axpy(_v(position), _f(thickness) / 2, _v(o[:, 1]))
+            sub = ExactBox(width, thickness, height, n, centre, orientation)
+            coat = ExactFlat(width, position, orientation, "plate_coating", reflectance, height=height, pre=math.pi, n=n)
+        self.parts = [sub, coat]
+
+
+@_precise
+class ExactCubeBS:
+    """CubeBeamsplitter(leg, n; reflectance) (CubeBeamsplitter.jl:49-61): parts = [front, back, coating], two RightAnglePrism(leg, leg, n) on
+    one position, the back one turned by the double deg2rad(180) about z, and a ThinBeamsplitter(sqrt(2) leg, leg) turned by the double
+    deg2rad(135) about z and made its own origin: its plane is the two prisms' common hypotenuse x + y = 0, its normal (-1, -1, 0) / sqrt(2)
+    points into the front prism.  position() / orientation() are the front prism's."""
+
+    kind = "cube_bs"
+
+    def __init__(self, leg, n, reflectance, position, orientation):
+        mp = _mp()
+        self.parts = [ExactPrism(leg, leg, n, position, orientation), ExactPrism(leg, leg, n, position, orientation, pre=math.radians(180)),
+                      ExactFlat(mp.sqrt(2) * _f(leg), position, orientation, "cube_coating", reflectance, height=leg, pre=math.radians(180 - 45), n=n)]
 
 
 # ------------------------------------------------------------------------------------------------ the hit
@@ -1023,17 +1115,135 @@ def interact_thin_bs(obj, dirv, normal, E0=None):
     R = mp.sqrt(_f(obj.reflectance))
     T = mp.sqrt(1 - R * R)
     nd = _sub(dirv, _scale(2 * _dot(dirv, normal), normal))
-    outs = [dict(role="transmitted", dir=dirv, n=mp.mpf(1), tir=False, rnd_dir=4 if E0 is not None else 0, E0=None),   # PolarizedRay(...) normalises dir
-            dict(role="reflected", dir=nd, n=mp.mpf(1), tir=True, rnd_dir=12 if E0 is not None else 8, E0=None)]
+    # Ray(...) and PolarizedRay(...) normalise dir (Rays.jl:32-42, PolarizedRays.jl:80-95): 4 u, which shows where the parent's direction is a
+    # refracted one whose length is 1 to a few u only (inside a cube splitter); a root's direction is returned unchanged
+    outs = [dict(role="transmitted", dir=dirv, n=mp.mpf(1), tir=False, rnd_dir=4, E0=None),
+            dict(role="reflected", dir=nd, n=mp.mpf(1), tir=True, rnd_dir=12, E0=None)]
     if E0 is not None:
         for o, (a, b) in zip(outs, ((T, T), (-R, R))):
             o["E0"], o["sin_dev"] = jones_global(dirv, o["dir"], normal, a, b, E0)
             o.update(j11=a, j22=b, j_rnd=4)  # the doubles of R and T: a root, a product, a difference, a root
+    for o in outs:
+        o["dir"] = _unit(o["dir"])           # the constructor's normalize, after E0 was made from the directions as they were
     return outs
 
 
-def interact(obj, dirv, normal, n_ray, lam, E0=None, planted=None):
-    """The rays that leave the bounce: [] on a detector or a stop, one 'next' ray on a lens or a mirror, two children on a thin splitter."""
+def interact_plate_coating(obj, dirv, normal, n_ray, lam, E0=None, planted=None, chief_entering=None):
+    """interact3d(system, ::AbstractPlateBeamsplitter, beam, ray) at the coating, PlateBeamsplitter.jl:203-225: the thin splitter's children,
+    then the transmitted child's direction is replaced by refraction3d(ray, n2) (AbstractRay.jl:244-253: n1 the ray's own index, the normal
+    flipped when the ray is not entering), n2 = n_optics entering, 1 leaving; the children's indices are (n_optics, 1) or (1, n_optics).  The
+    transmitted child's E0 stays the thin splitter's, that of the straight-through direction (:221-223 set index and direction alone).
+    chief_entering: a beamlet's waist and divergence ray take the indices by the CHIEF ray's isentering (:250-264) and flip the normal by
+    their own."""
+    mp = _mp()
+    outs = interact_thin_bs(obj, dirv, normal, E0)
+    entering = _dot(dirv, normal) < 0                                        # AbstractRay.jl:234-237
+    ent_n = entering if chief_entering is None else chief_entering
+    n_opt, one = obj.index(lam), mp.mpf(1)
+    nt, nr = (n_opt, one) if ent_n else (one, n_opt)
+    if planted == "plate_indices_swapped":
+        nt, nr = nr, nt
+    nf = normal if (entering or planted == "plate_normal_not_flipped") else _scale(-1, normal)
+    eta = n_ray / (n_opt if ent_n else one)                                  # OpticUtils.jl:31-45
+    cos_i = -_dot(nf, dirv)
+    st2 = eta * eta * (1 - cos_i * cos_i)
+    if st2 > 1:
+        nd = _sub(dirv, _scale(2 * _dot(dirv, nf), nf))
+    else:
+        nd = _add(_scale(eta, dirv), _scale(eta * cos_i - mp.sqrt(1 - st2), nf))
+    if planted != "plate_no_refraction":
+        outs[0].update(dir=_unit(nd), rnd_dir=18)                            # direction! normalises (AbstractRay.jl:83-86)
+    outs[0]["n"], outs[1]["n"] = nt, nr
+    return outs
+
+
+def interact_cube_coating(obj, dirv, normal, lam, E0=None, planted=None):
+    """interact3d(system, ::CubeBeamsplitter, beam, ray) at the coating, CubeBeamsplitter.jl:76-84: the thin splitter's children, both in glass."""
+    outs = interact_thin_bs(obj, dirv, normal, E0)
+    if planted != "cube_children_in_air":
+        outs[0]["n"] = outs[1]["n"] = obj.index(lam)
+    return outs
+
+
+def interact_polarizer(obj, dirv, n_ray, E0, planted=None):
+    """interact3d(system, ::PolarizationFilter, beam, ray) PolarizationFilter.jl:31-48 with _calculate_global_E0 JonesCalculus.jl:29-45:
+    E' = Q (R J R^T) Q E0, R = orientation(filter) (its doubles), Q = I - d d^T; direction and index are kept; the ray is blocked when
+    norm(E') is approximately the cutoff (isapprox: |a - b| <= sqrt(eps) max(|a|, |b|))."""
+    mp = _mp()
+    R = [[obj.cols[k][i] for k in range(3)] for i in range(3)]               # R[i][k]: component i of local axis k
+    if planted == "polarizer_rotation_transposed":
+        R = [[R[k][i] for k in range(3)] for i in range(3)]
+    J = [[mp.mpc(complex(z).real, complex(z).imag) for z in row] for row in obj.jones]
+    mul = lambda A, B: [[sum(A[i][k] * B[k][j] for k in range(3)) for j in range(3)] for i in range(3)]
+    P = mul(mul(R, J), [[R[j][i] for j in range(3)] for i in range(3)])
+    if planted != "polarizer_not_projected":
+        Q = [[(1 if i == j else 0) - dirv[i] * dirv[j] for j in range(3)] for i in range(3)]
+        P = mul(mul(Q, P), Q)
+    E = [sum(P[i][j] * E0[j] for j in range(3)) for i in range(3)]
+    nrm, cut = _norm(E), _f(obj.cutoff)
+    out = dict(role="next", dir=dirv, n=n_ray, tir=False, entering=False, rnd_dir=0, E0=E, norm=nrm, j11=mp.mpf(1), j22=mp.mpf(1), sin_dev=mp.mpf(0), j_rnd=0)
+    # four 3 x 3 products and a matrix-vector product, 3 u of |A| |B| each; Q's entries carry 2 u, twice; the moduli of Q, R, R^T, Q have
+    # 2-norms up to sqrt(3) each: (4 3 + 3 + 2 2) 9 u of |J| |E0|
+    out["E_rnd"] = 171 * max(abs(z) for row in J for z in row)
+    out["blocked"] = abs(nrm - cut) <= mp.sqrt(2.0 ** -52) * max(nrm, cut)
+    # how far the outcome is from turning over, less what the recorded norm may be off: E0's bound and 4 u for the norm (three squares, two
+    # sums, a root).  Negative: the one outcome this evaluator does not predict (excluded())
+    out["block_margin"] = abs(abs(nrm - cut) - mp.sqrt(2.0 ** -52) * max(nrm, cut)) - _norm(E0) * mp.mpf(U) * (out["E_rnd"] + 4)
+    return [out]
+
+
+def gauss_record(res, node):
+    """Beamlet `node` of a TraceResult as the record tests/pd_ref.py evaluates (its doubles): the three rays of every segment that ends on an
+    object, the (length, index) of every ray of every ancestor, beam_waist, E0 and lambda of node_aux."""
+    c, w, d = (segments_of(res, node, s) for s in range(3))
+    segs = [dict(pos=a["pos"], dir=a["dir"], n=a["n"], t=a["t"], wpos=b["pos"], wdir=b["dir"], dpos=e["pos"], ddir=e["dir"])
+            for a, b, e in zip(c, w, d) if math.isfinite(a["t"])]
+    parents, p = [], int(res.node_parent[node])
+    while p >= 0:
+        parents.append([(s["t"], s["n"]) for s in segments_of(res, p) if math.isfinite(s["t"])])
+        p = int(res.node_parent[p])
+    aux = res.node_aux[node]
+    return dict(segs=segs, parents=parents, w0=float(aux[0]), E0=complex(aux[1], aux[2]), lam=float(aux[3]), proj=1.0)
+
+
+def exact_gauss_children(rec, splitter, facing, planted=None):
+    """What a splitter's coating makes of a GaussianBeamlet beyond its three rays (ThinBeamsplitter.jl:117-168), rec = gauss_record(parent):
+    both children's w0 = gauss_parameters(gauss, length(gauss))[4] - the waist the beamlet has taken on where it is split, the parents' lengths
+    included (Beam.jl:177-205) -, E_t = T E0 (w0_g / w0), E_r = R E0 (w0_g / w0) exp(i phi) with phi = pi where the chief ray faces the normal
+    (dot(dir, normal) < 0: `facing`) and 0 where not; pi is pi, so exp(i pi) = -1.  -> dict(w0, E_t, E_r and their bounds b_w0, b_E): the
+    bound of w0 is pd_ref's (waist_at); E takes w0's relative bound, 4 u for the doubles of R and T, 6 u for two products and a quotient of
+    a complex number, and - reflected with phi = pi - |sin(fl(pi))| = 1.3e-16, the imaginary part the double of pi leaves in the factor."""
+    import pd_ref
+
+    mp = _mp()
+    bl = pd_ref._Beamlet(rec, None)
+    w0, b_w0 = bl.waist_at(bl.length)
+    if planted == "gauss_child_keeps_w0":
+        w0 = bl.w0
+    elif planted == "gauss_w0_at_start":  # on the beam's first ray (halfway along it: at its very start the divergence ray has no height)
+        w0 = bl.waist_at(bl.l_parent + bl.segs[0]["t"] / 2)[0]
+    R = mp.sqrt(_f(splitter.reflectance))
+    T = mp.sqrt(1 - R * R)
+    flip = {None: facing, "gauss_no_phase_flip": False, "gauss_flip_on_both_sides": True}.get(planted, facing)
+    E_t = T * bl.E0 * (bl.w0 / w0)
+    E_r = R * bl.E0 * (bl.w0 / w0) * (-1 if flip else 1)
+    rel = b_w0 / w0 + 10 * mp.mpf(U)
+    return dict(w0=w0, E_t=E_t, E_r=E_r, b_w0=b_w0, b_E=[abs(E_t) * rel, abs(E_r) * (rel + (mp.mpf("1.3e-16") if facing else 0))], flip=flip)
+
+
+ORTHO_ATOL = 1e-14
+
+
+def _not_orthogonal(dirv, E0):
+    """The check of the PolarizedRay constructor, PolarizedRays.jl:54-56: isorthogonal3d(dir, E0; atol = 1e-14) (LinearAlgebraUtils.jl:15-17)."""
+    return E0 is not None and abs(_dot(dirv, E0)) > _f(ORTHO_ATOL)
+
+
+def interact(obj, dirv, normal, n_ray, lam, E0=None, planted=None, chief_entering=None):
+    """The rays that leave the bounce: [] on a detector or a stop, one 'next' ray on a lens, a mirror or a polarization filter, two children on a
+    splitter's coating.  Where the reference would build a PolarizedRay whose E0 is not orthogonal to its direction the constructor throws
+    (PolarizedRays.jl:54-56): one entry of role 'err_ortho'; a filter that blocks the ray: one of role 'blocked'."""
+    outs = []
     if obj.kind == "lens":
         ia = interact_lens(dirv, normal, n_ray, obj.index(lam), E0, planted)
         ia.update(role="next", rnd_dir=8 if ia["tir"] else 14)
@@ -1041,12 +1251,25 @@ def interact(obj, dirv, normal, n_ray, lam, E0=None, planted=None):
             ia["j_rnd"] = 16 + 6 * ia["X"]
         else:
             ia["E0"] = None
-        return [ia]
-    if obj.kind == "mirror":
-        return [interact_mirror(dirv, normal, n_ray, E0)]
-    if obj.kind == "thin_bs":
-        return interact_thin_bs(obj, dirv, normal, E0)
-    return []
+        outs = [ia]
+    elif obj.kind == "mirror":
+        outs = [interact_mirror(dirv, normal, n_ray, E0)]
+    elif obj.kind == "thin_bs":
+        outs = interact_thin_bs(obj, dirv, normal, E0)
+    elif obj.kind == "plate_coating":
+        plain = interact_thin_bs(obj, dirv, normal, E0)                     # the constructor's check runs on the thin splitter's children, :205
+        if any(_not_orthogonal(o["dir"], o["E0"]) for o in plain):
+            return [dict(role="err_ortho")]
+        return interact_plate_coating(obj, dirv, normal, n_ray, lam, E0, planted, chief_entering)
+    elif obj.kind == "cube_coating":
+        outs = interact_cube_coating(obj, dirv, normal, lam, E0, planted)
+    elif obj.kind == "polarizer" and E0 is not None:                        # no method for a Ray or a beamlet: they stop (Intersectable.jl:15)
+        outs = interact_polarizer(obj, dirv, n_ray, E0, planted)
+        if outs[0]["blocked"]:
+            return [dict(role="blocked", norm=outs[0]["norm"], block_margin=outs[0]["block_margin"])]
+    if planted != "polarizer_not_projected" and any(_not_orthogonal(o["dir"], o["E0"]) for o in outs):  # (that mistake is to show in E0)
+        return [dict(role="err_ortho")]
+    return outs
 
 
 # ------------------------------------------------------------------------------------------------ one bounce
@@ -1061,7 +1284,10 @@ def exact_step(seg, obj, consts, planted=None):
         return None
     n_ray = _f(seg["n"])
     out = dict(t=hit["t"], point=hit["point"], normal=hit["n"], hit=hit, next=None, children=None, row=None)
-    out["outs"] = interact(obj, dirv, hit["n"], n_ray, seg["lam"], _c(seg.get("E0")), planted)
+    out["outs"] = interact(obj, dirv, hit["n"], n_ray, seg["lam"], _c(seg.get("E0")), planted, seg.get("chief_entering"))
+    out["end"] = None  # 'err_ortho': the reference throws here (the record: BMO_NODE_ERR_ORTHO | BMO_NODE_STOPPED); 'blocked': a filter ends the ray
+    if out["outs"] and out["outs"][0]["role"] in ("err_ortho", "blocked"):
+        out["end"], out["ended"], out["outs"] = out["outs"][0]["role"], out["outs"][0], []
     for o in out["outs"]:
         o["pos"] = hit["point"]
     if out["outs"] and out["outs"][0]["role"] == "next":
@@ -1094,7 +1320,7 @@ def step_bound(seg, ex, obj, consts, n_seg=1):
     if hit["piece"] == "mesh":
         M = pos_mag + obj.pos_mag + obj.size + t
         b["t_lo"] = b["t_hi"] = 32 * u * M / c
-        dn = 8 * u
+        dn = 8 * u + hit.get("dn_vertices", 0)
     else:
         eps, kappa = mp.mpf(consts["eps_ray"]), hit["kappa"]
         c2 = 2 * kappa * eps * (1 + tan * tan) / c
@@ -1126,7 +1352,7 @@ def step_bound(seg, ex, obj, consts, n_seg=1):
         D_dir, D_E = [mp.mpf(0)] * len(ex["outs"]), [mp.mpf(0)] * len(ex["outs"])
         for e in _tangents(hit["n"]):
             n2 = _axpy(hit["n"], step, e)  # its length changes in second order only
-            for i, (oa, ob) in enumerate(zip(ex["outs"], interact(obj, dirv, n2, n_ray, seg["lam"], Ein))):
+            for i, (oa, ob) in enumerate(zip(ex["outs"], interact(obj, dirv, n2, n_ray, seg["lam"], Ein, None, seg.get("chief_entering")))):
                 D_dir[i] += _norm(_sub(ob["dir"], oa["dir"])) / step
                 if Ein is not None:
                     D_E[i] += _norm(_sub(ob["E0"], oa["E0"])) / step
@@ -1137,6 +1363,8 @@ def step_bound(seg, ex, obj, consts, n_seg=1):
                 sd = oa["sin_dev"]
                 basis = 8 * u * abs(oa["j11"] - oa["j22"]) / sd if sd > 0 else mp.mpf(0)
                 bo["E0"] = D_E[i] * dn + _norm(Ein) * (u * (30 + oa["j_rnd"]) * jmax + basis)
+                if "E_rnd" in oa:  # a polarization filter: no basis of s and p, the matrix chain of interact_polarizer
+                    bo["E0"] = D_E[i] * dn + _norm(Ein) * u * oa["E_rnd"]
             b["outs"].append(bo)
         b["dir"], b["E0"] = b["outs"][0]["dir"], b["outs"][0]["E0"]
     return b
@@ -1169,6 +1397,7 @@ def exact_trace(root, objects, consts, r_max=30, planted=None, kick=None, depth=
             ex = exact_step(seg, solid, consts, planted)
             if ex is not None:
                 best = (hint[0], hint[1], ex)
+        searched = best is None
         if best is None:
             for k, p, solid in cands:
                 if _dot(_sub(solid.pos, seg["pos"]), seg["dir"]) < -2 * solid.size:
@@ -1185,6 +1414,13 @@ def exact_trace(root, objects, consts, r_max=30, planted=None, kick=None, depth=
             out.append(dict(obj=-1, part=0, piece=None, ex=None, seg=seg, tie=None))
             break
         k, p, ex = best
+        if searched and getattr(objects[k], "kind", None) == "plate_bs":
+            # PlateBeamsplitter.jl:160-187: both parts are tested; the coating wins where the two lengths are approximately equal (isapprox,
+            # rtol = sqrt(eps)) or it is nearer.  The nearest-first search above has taken care of 'nearer'.
+            other = exact_step(seg, objects[k].parts[1 - p], consts, planted)
+            if other is not None and abs(other["t"] - ex["t"]) <= _mp().sqrt(2.0 ** -52) * max(abs(other["t"]), abs(ex["t"])):
+                if p == (1 if planted == "coating_loses_tie" else 0):
+                    p, ex = 1 - p, other
         same_object = second is not None and hasattr(objects[k], "parts")    # the parts of a doublet meet at their interface by construction
         out.append(dict(obj=k, part=p, piece=ex["hit"]["piece"], ex=ex, seg=seg, tie=None if (second is None or same_object) else second - ex["t"]))
         if ex["children"] is not None and depth < 4:
@@ -1193,7 +1429,9 @@ def exact_trace(root, objects, consts, r_max=30, planted=None, kick=None, depth=
         if ex["next"] is None:
             break
         nx = ex["next"]
-        if hasattr(objects[k], "parts"):
+        if getattr(objects[k], "kind", None) in ("plate_bs", "cube_bs"):
+            hint = (k, len(objects[k].parts) - 1)                            # PlateBeamsplitter.jl:199, CubeBeamsplitter.jl:72, :89: at the coating
+        elif hasattr(objects[k], "parts"):
             hint = (k, 1 - p)
         elif objects[k].kind == "lens" and (nx["entering"] or nx["tir"]):
             hint = (k, 0)
@@ -1207,7 +1445,11 @@ def exact_trace(root, objects, consts, r_max=30, planted=None, kick=None, depth=
 
 
 def excluded(ex, second_gap=None):
-    """The only criterion by which a bounce may be left out, computed from the exact geometry alone."""
+    """The only criterion by which a bounce may be left out, computed from the exact geometry alone; at a polarization filter also an exact
+    norm(E') that lies within the bound of E0 of the threshold at which the filter blocks."""
+    pol = ex.get("ended") if ex.get("end") == "blocked" else (ex["next"] if ex.get("next") is not None else None)
+    if pol is not None and pol.get("block_margin", 1) < 0:
+        return True
     return ex["hit"]["seam"] < SEAM or (second_gap is not None and abs(second_gap) < TIE)
 
 
