@@ -1,11 +1,77 @@
 // bmo_trace_host.inc.hpp — host side of one trace (included by bmo_engine.hip inside its anonymous namespace; shares its pools, error helpers
-// and kernels).  run_trace at the end is the driver; everything above it is one phase of a solve, given what it needs as arguments:
+// and kernels).  run_trace at the end is the driver; everything above it is one phase of a solve, given what it needs as arguments, with the
+// helper kernels it launches right above it:
+//   build_retrace_tables  the OldSolution tables of the solution a retrace re-walks (old_obj_scatter_kernel, old_first_child_kernel)
 //   device_ctx            stream, events and pinned counters of a device, made once
 //   NodeTable             the node arrays of a solution: allocation, growth, the kernels' view of them
 //   ChunkArena            the segment log's storage: chunks bumped out of large blocks, rewound behind a launch
 //   select_step_kernels   the step kernels of a beam kind / scene level / fresh, retrace or sweep solve
 //   plan_launch, fill_step_params, tile_order_feedback, build_sweep_lane_map, print_timeline, launch_step: one launch of the step loop
 //   order_nodes, gather_detector_hits                the canonical node order and the detector tables behind the last launch
+
+// ---- the retrace tables of a finished solution (OldSolution), built when it is first retraced
+__global__ void old_obj_scatter_kernel(Chunk c, int32_t chunk_index, const int32_t* __restrict__ rec_start, int32_t* __restrict__ rec_obj,
+                                       int64_t* __restrict__ rec_loc) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= c.count) return;
+    const int32_t node = chunk_node(c, j);
+    if (node < 0) return;  // hole of a fused level
+    const int32_t k = c.i[I_K * c.cap + j];
+    rec_obj[(int64_t)rec_start[node] + k] = c.i[I_OBJ * c.cap + j];
+    rec_loc[(int64_t)rec_start[node] + k] = ((int64_t)chunk_index << OLD_LOC_SHIFT) | j;
+}
+__global__ void old_first_child_kernel(const int32_t* __restrict__ parent, const unsigned long long* __restrict__ key, int64_t n, int32_t* __restrict__ first_child) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n) return;
+    const int32_t p = parent[c];
+    if (p >= 0 && !(key[c] & 1ull)) first_child[p] = (int32_t)c;  // transmitted child (path bit 0); the reflected one is c + 1
+}
+// OldSolution tables of `prev` (device arrays keyed by prev's node ids), built once per solution.
+int build_retrace_tables(bmo_trace_result* prev, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(prev->rt_mu);
+    if (!prev->has_log) return fail(BMO_ERR_INVALID, "retrace: the previous solution was solved with record_segments = 0 (no segment log to re-walk)");
+    if (prev->rt_built) return BMO_OK;
+    const int64_t nn = prev->n_nodes, nr = prev->n_records;
+    if (nr >= (int64_t)1 << 31) return fail(BMO_ERR_UNSUPPORTED, "retrace: previous solution has more than 2^31 segments");
+    int rc;
+    if ((rc = prev->rt_rec_start.alloc((size_t)std::max<int64_t>(nn, 1) * 4)) || (rc = prev->rt_rec_obj.alloc((size_t)std::max<int64_t>(nr, 1) * 4)) ||
+        (rc = prev->rt_first_child.alloc((size_t)std::max<int64_t>(nn, 1) * 4)) || (rc = prev->rt_rec_loc.alloc((size_t)std::max<int64_t>(nr, 1) * 8)) ||
+        (rc = prev->rt_chunks.alloc(std::max<size_t>(prev->chunks.size(), 1) * sizeof(OldChunk))))
+        return rc;
+    if (prev->chunks.size() >= ((size_t)1 << (63 - OLD_LOC_SHIFT))) return fail(BMO_ERR_UNSUPPORTED, "retrace: previous solution has too many log chunks");
+    if (nn > 0) {
+        Temps tmp;
+        CUB_TRY(tmp, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)prev->n_nseg.p, (int32_t*)prev->rt_rec_start.p, (int)nn, stream));
+        std::vector<OldChunk> oc(prev->chunks.size());
+        for (size_t q = 0; q < prev->chunks.size(); ++q) oc[q] = OldChunk{prev->chunks[q].d, prev->chunks[q].cap};
+        if (!oc.empty()) HIP_TRY(hipMemcpyAsync(prev->rt_chunks.p, oc.data(), oc.size() * sizeof(OldChunk), hipMemcpyHostToDevice, stream));
+        for (size_t q = 0; q < prev->chunks.size(); ++q) {
+            const Chunk& c = prev->chunks[q];
+            if (c.count > 0)
+                hipLaunchKernelGGL(old_obj_scatter_kernel, dim3((unsigned)((c.count + 255) / 256)), dim3(256), 0, stream, c, (int32_t)q,
+                                   (const int32_t*)prev->rt_rec_start.p, (int32_t*)prev->rt_rec_obj.p, (int64_t*)prev->rt_rec_loc.p);
+        }
+        HIP_TRY(hipMemsetAsync(prev->rt_first_child.p, 0xFF, (size_t)nn * 4, stream));
+        hipLaunchKernelGGL(old_first_child_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, stream, (const int32_t*)prev->n_parent.p,
+                           (const unsigned long long*)prev->n_key.p, nn, (int32_t*)prev->rt_first_child.p);
+        HIP_TRY(hipStreamSynchronize(stream));  // tmp goes back to the pool
+        HIP_TRY(hipGetLastError());
+        if (dbg_on()) {
+            const int q = (int)std::min<int64_t>(nn, 6), qr = (int)std::min<int64_t>(nr, 24);
+            std::vector<int32_t> a(q), b(q), c(q), d(qr);
+            (void)hipMemcpy(a.data(), prev->n_nseg.p, q * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(b.data(), prev->rt_rec_start.p, q * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(c.data(), prev->rt_first_child.p, q * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(d.data(), prev->rt_rec_obj.p, qr * 4, hipMemcpyDeviceToHost);
+            for (int i = 0; i < q; ++i) DBG("retrace table node %d: nseg %d rec_start %d first_child %d", i, a[i], b[i], c[i]);
+            std::string line;
+            for (int i = 0; i < qr; ++i) line += std::to_string(d[i]) + " ";
+            DBG("retrace table rec_obj: %s", line.c_str());
+        }
+    }
+    prev->rt_built = true;
+    return BMO_OK;
+}
 
 // one trace stream + timing events per device, created once (hipStreamCreate costs ~1 ms)
 struct DevCtx {
@@ -220,6 +286,60 @@ int select_step_kernels(int ext, bool retrace, bool sweep, StepKernels& k) {
     return BMO_OK;
 }
 
+// Slot s of the first chunk holds root ray perm[s] (perm == nullptr: ray s); `slot_planes` are the batch's planes in slot order (the
+// batch itself when perm == nullptr, its binned copy otherwise), so every read and write here is coalesced.  Beam nodes keep the
+// bundle's numbering (root i is node i): everything downstream — result order, detector order, retrace — is independent of where a
+// ray sits in the chunk.  Thread i fills slot i of the chunk and node i of the node table.
+template <int KIND>
+__global__ void init_roots_kernel(const double* __restrict__ planes, const double* __restrict__ slot_planes, const int32_t* __restrict__ lambda_idx,
+                                  const int32_t* __restrict__ perm, int64_t n, Chunk c0, NodeArrays nodes, int32_t r_max, int32_t n_planes) {
+    using L = Layout<KIND>;
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int64_t cap = c0.cap;
+    const double* Q = slot_planes;
+    const bool cont = KIND == BMO_BEAM_GAUSSIAN && n_planes >= BMO_PLANES_GAUSSIAN_CONTINUED;
+    if (KIND == BMO_BEAM_GAUSSIAN) {
+        for (int b = 0; b < 3; ++b) {
+            for (int p = 0; p < 6; ++p) c0.d[(11 * b + p) * cap + j] = Q[(6 * b + p) * n + j];
+            c0.d[(11 * b + 6) * cap + j] = Q[19 * n + j];
+        }
+        // accumulated lengths: zero for a fresh beamlet; a batch that continues solved beamlets brings them along (include/bmo.h)
+        c0.d[33 * cap + j] = cont ? Q[25 * n + j] : 0.0;  // lenA
+        c0.d[34 * cap + j] = cont ? Q[26 * n + j] : 0.0;  // lenB
+        c0.d[35 * cap + j] = cont ? Q[28 * n + j] : 0.0;  // oplC
+        c0.d[36 * cap + j] = cont ? Q[29 * n + j] : 0.0;  // oplW
+        c0.d[37 * cap + j] = cont ? Q[30 * n + j] : 0.0;  // oplD
+    } else {
+        for (int p = 0; p < 6; ++p) c0.d[p * cap + j] = Q[p * n + j];
+        c0.d[6 * cap + j] = Q[7 * n + j];
+        if (KIND == BMO_BEAM_POLARIZED)
+            for (int p = 0; p < 6; ++p) c0.d[(11 + p) * cap + j] = Q[(8 + p) * n + j];
+        c0.d[L::OPL * cap + j] = 0.0;
+    }
+    c0.i[I_NODE * cap + j] = perm ? perm[j] : (int32_t)j;
+    c0.i[I_K * cap + j] = 0;
+    c0.i[I_HOBJ * cap + j] = -1;
+    c0.i[I_HSHAPE * cap + j] = -1;
+    c0.i[I_FLAGS * cap + j] = (1 < r_max) ? 0 : F_DEAD;
+    // node j = root ray j of the bundle
+    if (KIND == BMO_BEAM_GAUSSIAN) {
+        nodes.aux[j * 4 + 0] = cont ? planes[27 * n + j] : 0.0;  // l0
+        nodes.aux[j * 4 + 1] = planes[20 * n + j];
+        nodes.aux[j * 4 + 2] = planes[21 * n + j];
+        nodes.aux[j * 4 + 3] = planes[22 * n + j];
+    }
+    nodes.root[j] = (int32_t)j;
+    nodes.parent[j] = -1;
+    nodes.nseg[j] = 1;
+    nodes.status[j] = 0;
+    nodes.li[j] = lambda_idx[j];
+    nodes.lambda[j] = planes[(KIND == BMO_BEAM_GAUSSIAN ? 18 : 6) * n + j];
+    nodes.hit_det[j] = -1;
+    nodes.key[j] = 0;
+    if (nodes.tbits) nodes.tbits[j] = 1ull;  // the root itself: heap index 0
+}
+
 // What the driver needs of a beam kind: two plane counts, the sub-beams per node, and the kernels.
 struct KindInfo {
     int kind, nd, abi_planes, nsub;
@@ -345,6 +465,12 @@ void fill_step_params(StepParams& P, const KindInfo& K, const bmo_scene* scene, 
 #endif
 }
 
+// a[j] = j: tile ids here, node ids in order_nodes and run_trace, record numbers in bmo_result_view.inc.hpp
+__global__ void iota_kernel(int32_t* a, int64_t n) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) a[j] = (int32_t)j;
+}
+
 // Longest-processing-time-first (StepParams::tile_order / ::tile_cost) for the first launch of a solve: the batch keeps the time every tile
 // took, the next solve of the batch sorts its tiles by it.  A retrace with a freshly uploaded batch starts from the retraced solution's times.
 int tile_order_feedback(StepParams& P, bmo_device_batch* batch, const bmo_trace_result* prev, unsigned n_blocks, hipStream_t stream) {
@@ -375,6 +501,36 @@ int tile_order_feedback(StepParams& P, bmo_device_batch* batch, const bmo_trace_
     return BMO_OK;
 }
 
+// ---- lane map of a sweep launch (StepParams::sweep): key = configuration of every slot of the launch's chunk (node -> root -> root_cfg),
+// a stable sort by it, the runs padded to whole waves.  beg / end: first and one-past-last sorted position of every configuration.
+__global__ void sweep_key_kernel(Chunk c, const int32_t* __restrict__ root, const int32_t* __restrict__ root_cfg, int64_t m, uint32_t* __restrict__ key,
+                                 int32_t* __restrict__ slot) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    key[j] = (uint32_t)root_cfg[root[c.i[I_NODE * c.cap + j]]];
+    slot[j] = (int32_t)j;
+}
+__global__ void sweep_bounds_kernel(const uint32_t* __restrict__ key, int64_t m, int32_t* __restrict__ beg, int32_t* __restrict__ end) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t k = key[i];
+    if (i == 0 || key[i - 1] != k) beg[k] = (int32_t)i;
+    if (i == m - 1 || key[i + 1] != k) end[k] = (int32_t)(i + 1);
+}
+__global__ void sweep_pad_kernel(const int32_t* __restrict__ beg, const int32_t* __restrict__ end, int32_t n_configs, int32_t* __restrict__ padded) {
+    const int32_t c = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (c >= n_configs) return;
+    padded[c] = (end[c] - beg[c] + 63) & ~63;
+}
+__global__ void sweep_scatter_kernel(const uint32_t* __restrict__ key, const int32_t* __restrict__ slot, int64_t m, const int32_t* __restrict__ beg,
+                                     const int32_t* __restrict__ pstart, int64_t lanes, int32_t* __restrict__ map, unsigned long long* __restrict__ overflow) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t k = key[i];
+    const int64_t v = (int64_t)pstart[k] + (i - beg[k]);
+    if (v < lanes) map[v] = slot[i];
+    else atomicAdd(overflow, 1ull);
+}
 // Sweep lane map (StepParams::sweep) of a launch over the m records of `cur`: key = configuration of every slot, stable sort (slot order
 // within a configuration), runs padded to whole waves.
 int build_sweep_lane_map(const bmo_trace_result* R, const Chunk& cur, int64_t sweep_lanes, Counters* d_ctr, hipStream_t stream, DevBuf& sw_map) {
@@ -475,6 +631,89 @@ int launch_step(DevCtx& ctx, const StepKernels& kern, const LaunchPlan& plan, co
     return BMO_OK;
 }
 
+// (root, depth, path) keys packed into as few bits as this solve needs: the radix sort of the final ordering runs 3-4 passes over
+// 32-bit keys instead of 8 over 64-bit ones.  Trees of up to MAX_PATH_LEVELS levels.
+constexpr int MAX_PATH_LEVELS = 26;
+__global__ void pack_keys_kernel(const int32_t* __restrict__ root_of, const unsigned long long* __restrict__ key, int64_t n, int bits_depth, int bits_path,
+                                 uint32_t* __restrict__ k32, unsigned long long* __restrict__ k64) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long k = key[i];
+    const unsigned long long root = (unsigned long long)root_of[i], depth = k >> 32, path = k & ((1ull << bits_path) - 1ull);
+    const unsigned long long packed = (root << (bits_depth + bits_path)) | (depth << bits_path) | path;
+    if (k32) k32[i] = (uint32_t)packed;
+    else k64[i] = packed;
+}
+// ---- ordering of shallow trees (up to MAX_HEAP_LEVELS levels below the root: what one to five splitters in a row give) without a
+// sort: node (depth, path) sits at index 2^depth - 1 + path of its root's tree laid out as a heap, and heap order IS (depth, path)
+// order.  Every root collects the heap indices of its nodes in one 64-bit word; a node's position in the canonical order is then
+// (number of nodes of the roots before its own: one scan over the roots) + (number of set bits below its own).
+constexpr int MAX_HEAP_LEVELS = 5;
+__device__ __forceinline__ unsigned heap_index(unsigned long long key) {
+    const unsigned depth = (unsigned)(key >> 32);
+    return (1u << depth) - 1u + (unsigned)(key & ((1ull << depth) - 1ull));
+}
+__global__ void tree_bits_kernel(const int32_t* __restrict__ root_of, const unsigned long long* __restrict__ key, int64_t n, unsigned long long* __restrict__ bits) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    atomicOr(&bits[root_of[i]], 1ull << heap_index(key[i]));
+}
+__global__ void tree_count_kernel(const unsigned long long* __restrict__ bits, int64_t n_roots, int32_t* __restrict__ cnt) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n_roots) cnt[r] = __popcll(bits[r]);
+}
+__global__ void tree_rank_kernel(const int32_t* __restrict__ root_of, const unsigned long long* __restrict__ key, int64_t n, const unsigned long long* __restrict__ bits,
+                                 const int32_t* __restrict__ base, int32_t* __restrict__ order) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t r = root_of[i];
+    const unsigned h = heap_index(key[i]);
+    order[base[r] + __popcll(bits[r] & ((1ull << h) - 1ull))] = (int32_t)i;
+}
+// ---- ordering of beam trees deeper than MAX_PATH_LEVELS (cavities: a splitter facing a mirror): the path no longer fits a key, so
+// the rank of every node within its tree level is built level by level from its parent's rank (a splitting beam has exactly two
+// children, transmitted first): rank(child) = 2 * #(splitting parents of smaller rank) + w.
+__global__ void node_depth_kernel(const unsigned long long* __restrict__ key, int64_t n, uint32_t* __restrict__ depth) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) depth[i] = (uint32_t)(key[i] >> 32);
+}
+__global__ void level_starts_kernel(const uint32_t* __restrict__ sorted_depth, int64_t n, int64_t max_depth, int32_t* __restrict__ start) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t d = sorted_depth[i], dprev = i ? (int64_t)sorted_depth[i - 1] : -1;
+    for (int64_t x = dprev + 1; x <= d; ++x) start[x] = (int32_t)i;
+    if (i == n - 1)
+        for (int64_t x = d + 1; x <= max_depth + 1; ++x) start[x] = (int32_t)n;
+}
+__global__ void level_root_rank_kernel(const int32_t* __restrict__ ids, int32_t cnt, int32_t* __restrict__ rank) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cnt) rank[ids[i]] = i;  // level 0: the roots, in node id = bundle order (the depth sort is stable)
+}
+__global__ void level_flag_kernel(const int32_t* __restrict__ ids, int32_t cnt, const int32_t* __restrict__ parent, const unsigned long long* __restrict__ key,
+                                  const int32_t* __restrict__ rank, int32_t* __restrict__ flag) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const int32_t nd = ids[i];
+    if (!(key[nd] & 1ull)) flag[rank[parent[nd]]] = 1;
+}
+__global__ void level_rank_kernel(const int32_t* __restrict__ ids, int32_t cnt, const int32_t* __restrict__ parent, const unsigned long long* __restrict__ key,
+                                  const int32_t* __restrict__ scan, int32_t* __restrict__ rank) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const int32_t nd = ids[i];
+    rank[nd] = 2 * scan[rank[parent[nd]]] + (int32_t)(key[nd] & 1ull);
+}
+__global__ void gather_u32_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ src, int64_t n, uint32_t* __restrict__ dst) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = (uint32_t)src[idx[i]];
+}
+__global__ void root_depth_key_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ root_of, const unsigned long long* __restrict__ key, int64_t n,
+                                      int bits_depth, unsigned long long* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t nd = idx[i];
+    out[i] = ((unsigned long long)root_of[nd] << bits_depth) | (key[nd] >> 32);
+}
 // ---- canonical node order (bundle order x BFS order): sort by (root, depth, path).  Three paths by the depth of the deepest tree;
 // all leave the order in R->order, queued on the stream.
 inline int bits_for(unsigned long long v) {  // bits needed to hold values 0..v
@@ -586,6 +825,63 @@ int order_nodes(bmo_trace_result* R, int64_t n, int64_t n_nodes, unsigned long l
     return order_level_by_level(R, n_nodes, (int64_t)max_depth, bits_root, bits_depth, stream);
 }
 
+// flags[d*n + i] = 1 if canonical node i recorded a hit on detector d
+__global__ void hit_flags_kernel(const int32_t* order, const int32_t* hit_det, int64_t n, int32_t n_det, int32_t nsub, int32_t* flags) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t d = hit_det[order[i]];
+    for (int32_t q = 0; q < n_det; ++q) flags[(int64_t)q * n + i] = (q == d) ? nsub : 0;
+}
+// offsets of every detector's segment in the compacted hit list + the total, in one small array (one read-back instead of nd + 2)
+__global__ void hit_offsets_kernel(const int32_t* __restrict__ offs, const int32_t* __restrict__ flags, int64_t n, int32_t n_det, int32_t* __restrict__ out) {
+    const int d = (int)threadIdx.x;
+    if (d < n_det) out[d] = offs[(int64_t)d * n];
+    if (d == n_det) out[d] = offs[(int64_t)n_det * n - 1] + flags[(int64_t)n_det * n - 1];
+}
+// A workgroup takes 256 consecutive canonical nodes: their (id, destination) pairs go to LDS once, then the 72-byte records are copied
+// as contiguous runs, one double per thread and turn (the first form of this kernel re-read the three index tables for each of
+// the 9 doubles: 152 us per C2 solve for 0.3 GB of traffic).
+__global__ void hit_gather_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ hit_det, const double* __restrict__ hit, int64_t n, int32_t nsub,
+                                  const int32_t* __restrict__ offs, int64_t cap, double* __restrict__ out, int32_t* __restrict__ out_node,
+                                  unsigned long long* __restrict__ overflow) {
+    __shared__ int32_t s_nd[256], s_pos[256];
+    const int64_t i0 = (int64_t)blockIdx.x * 256;
+    {
+        const int64_t i = i0 + threadIdx.x;
+        int32_t nd = -1, pos = -1;
+        if (i < n) {
+            nd = order[i];
+            const int32_t d = hit_det[nd];
+            if (d >= 0) {
+                pos = offs[(int64_t)d * n + i];
+                if ((int64_t)pos + nsub > cap) {
+                    atomicAdd(overflow, 1ull);
+                    pos = -1;
+                } else {
+                    for (int q = 0; q < nsub; ++q) out_node[pos + q] = (int32_t)i;
+                }
+            }
+        }
+        s_nd[threadIdx.x] = nd;
+        s_pos[threadIdx.x] = pos;
+    }
+    __syncthreads();
+    const int width = 9 * nsub;
+    // element t = e * width + k of the workgroup's 256 records; t advances by 256 per turn: (e, k) by (256 / width, 256 % width) with a
+    // carry, no division per element
+    const int de = 256 / width, dk = 256 % width;
+    int e = (int)threadIdx.x / width, k = (int)threadIdx.x % width;
+    for (int t = threadIdx.x; t < 256 * width; t += 256) {
+        const int32_t pos = s_pos[e];
+        if (pos >= 0) out[(int64_t)pos * 9 + k] = hit[(int64_t)s_nd[e] * width + k];
+        e += de;
+        k += dk;
+        if (k >= width) {
+            k -= width;
+            e += 1;
+        }
+    }
+}
 // ---- detector hits in reference push! order: flags -> exclusive scan -> gather.  Queued; the offsets of the nd detectors (and the total
 // behind them) arrive in h_off with the caller's synchronisation.
 int gather_detector_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, Counters* d_ctr, int32_t* h_off, hipStream_t stream, Temps& temps) {

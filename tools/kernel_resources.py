@@ -3,9 +3,11 @@
     python tools/kernel_resources.py --log <file>                 (reads the remarks of a build made with -Rpass-analysis=kernel-resource-usage)"""
 import os, re, subprocess, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-disable-machine-licm", "-mllvm", "-sink-insts-to-avoid-spills", "-Wno-unused-result",
-       "-I", os.path.join(ROOT, "include"), "-o", "/tmp/kr_lib.so", os.path.join(ROOT, "beamletoptics.jl_amd/csrc/bmo_engine.hip"),
-       "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
+sys.path.insert(0, ROOT)
+import __graft_entry__ as g  # the compiler, its flags and the sources are the build script's
+
+cmd = [g.HIPCC] + g.HIP_FLAGS + ["-I", os.path.join(ROOT, "include"), "-o", "/tmp/kr_lib.so", g.engine_sources()[0],
+                                 "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
 if sys.argv[1:2] == ["--log"]:
     out = open(sys.argv[2]).read()
 else:
