@@ -602,7 +602,10 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) { 
                     tk_last = t;
                 }
 #endif
-                const Hit X = tracing_step<EXT, RETR>(S, pos, dir, ho, hs, calls, cc, lm, rt.probe, rt.probe_obj, rt.fresh_allowed, &rt.missed);
+                // (single-shape marches in the specialised loop, BMO_LEAF_MARCH: every variant but the PolarizedRay in-wave kernel of the
+                //  plain-shapes level, which would hold 252 B of scratch with it instead of 240: DESIGN.md §4 "Round 6")
+                constexpr bool LEAF = !(KIND == BMO_BEAM_POLARIZED && EXT == 0 && !RETR && INW && !SWEEP);
+                const Hit X = tracing_step<EXT, RETR, LEAF>(S, pos, dir, ho, hs, calls, cc, lm, rt.probe, rt.probe_obj, rt.fresh_allowed, &rt.missed);
 #if defined(BMO_DEV_TIMELINE)
                 {
                     const unsigned long long t = wall_clock64();

@@ -45,6 +45,9 @@
 #if !defined(BMO_MARCH_FASTPATH)
 #define BMO_MARCH_FASTPATH 1  /* union fast path of tracing_step's outside march: 0 off, 1 fresh EXT = 0 kernels, 2 every kernel (tests) */
 #endif
+#if !defined(BMO_LEAF_MARCH)
+#define BMO_LEAF_MARCH 1  /* outside marches of a single plain shape (no union) in the same loop, in the kernels BMO_MARCH_FASTPATH selects: 0 off */
+#endif
 
 namespace bmo {
 
@@ -53,6 +56,9 @@ inline long g_emu_sdf_any = 0, g_emu_sdf_leaf = 0, g_emu_normal = 0, g_emu_norma
 // union evaluations, those decided by the one `others_lb` compare, and those of them taken in tracing_step's specialised loop
 // (tools/fastpath_stats.py)
 inline long g_emu_union = 0, g_emu_union_fast = 0, g_emu_union_loop = 0;
+// outside-march trips on a shape that is no union: those of the generic trip, those committed in the specialised loop, and those of
+// the latter that belong to a backward march
+inline long g_emu_leaf_outside = 0, g_emu_leaf_loop = 0, g_emu_leaf_loop_back = 0;
 #endif
 
 // Scalar scene access (device builds).  The scene tables (objects, shapes, children, triangles, n(lambda), candidate table) are
@@ -74,10 +80,17 @@ __device__ __forceinline__ bool bmo_same_id(int32_t u, int32_t id) {
     asm volatile("" : "+s"(u));
     return u == id;
 }
+// The opposite: an index that is the same in all lanes, but whose table entry is wanted in VECTOR registers (read once by vector loads
+// and held over a loop): through a vector register and an empty asm the optimiser cannot prove it uniform.
+__device__ __forceinline__ int32_t bmo_lane_id(int32_t id) {
+    asm volatile("" : "+v"(id));
+    return id;
+}
 #else
 #define BMO_UNIFORM(i) (i)
 #define BMO_KONST
 inline bool bmo_same_id(int32_t u, int32_t id) { return u == id; }
+inline int32_t bmo_lane_id(int32_t id) { return id; }
 #endif
 // BMO_WAVE_ALL(p) / BMO_WAVE_ANY(p): p holds in every / some lane of the wave that executes this statement (host: the lane itself)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1193,7 +1206,8 @@ BMO_HD bool cull_miss(double cx, double cy, double cz, double R, const d3& pos, 
 //     it by the 1e-6 margin; t0 only grows by positive steps until the final sub-tolerance step (DESIGN.md "nearest-hit prune").
 //   * the miss cull (file header).  `calls` counts the reference's intersect3d calls, culled or not.
 // Returns the winning hit; its normal is in lane memory 0..2 (X.n is filled from there).
-template <int EXT, bool RETR = false>
+// LEAF = false: the caller's kernel keeps single-shape marches on the generic trip (BMO_LEAF_MARCH: a variant whose scratch would grow).
+template <int EXT, bool RETR = false, bool LEAF = true>
 BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, int32_t hint_obj, int32_t hint_shape, uint32_t& calls, ChildCache& cc,
                         const LaneMem& lm, bool probe = false, int32_t probe_obj = -1, bool fresh_allowed = true, bool* probe_missed = nullptr) {
     enum { CLASSIFY = 0, INSIDE = 1, OUTSIDE = 2, FINAL = 3 };
@@ -1366,16 +1380,24 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                     // What a committed trip changes is what sdf_any's early return and the generic OUTSIDE branch change:
                                     // pos, cc.acc, dist, t0, it (prev_best, others_lb, v[] and bc stay as they are).  The leaf is
                                     // sdf_leaf itself with its class as a constant (equal bits by construction, -ffp-contract=off).
-                                    if (H.kind == BMO_SHAPE_UNION && phase == OUTSIDE) {
-                                        const int32_t fb = BMO_UNIFORM(cc.prev_best);
-                                        if (cc.prev_best == fb && fb < H.child_count) {
+                                    // ---- the same loop for a march on a single plain shape (BMO_LEAF_MARCH): the shape is its own
+                                    // "child", no other child exists (others_lb = +inf: the compare always holds for a finite value).
+                                    // Its entry is read through the lane's own id, like the child's, into vector registers.  sdf_any
+                                    // neither reads nor writes cc.acc for such a shape and leaves prev_best at child_cache_reset's 0,
+                                    // which is the child pre_v is handed over for.
+                                    const bool uni = H.kind == BMO_SHAPE_UNION;
+                                    if ((uni || (BMO_LEAF_MARCH != 0 && LEAF)) && phase == OUTSIDE) {
+                                        const int32_t fb = uni ? BMO_UNIFORM(cc.prev_best) : 0;
+                                        if (!uni || (cc.prev_best == fb && fb < H.child_count)) {
                                             // (the entry through the lane's own index — the same child in every lane here: it is read by
                                             //  vector loads into vector registers once per entry into the loop.  Through the wave-uniform
                                             //  index the scalar loads stay inside the loop, the kernel has no scalar registers to keep 33
                                             //  dwords in: c2s 2.84 ms against 2.80, SQ_INSTS_SMEM 4.0e7 against 3.2e7, DESIGN.md §4 "Round 5")
-                                            CShape& ch = S.shapes[(H.flags & BMO_SHAPE_FLAG_CONSECUTIVE) ? H.tri_begin + cc.prev_best
-                                                                                                         : S.children[H.child_begin + cc.prev_best]];
+                                            CShape& ch = S.shapes[!uni ? bmo_lane_id(sid)
+                                                                  : (H.flags & BMO_SHAPE_FLAG_CONSECUTIVE) ? H.tri_begin + cc.prev_best
+                                                                                                           : S.children[H.child_begin + cc.prev_best]];
                                             const int ck = ch.kind;
+                                            const double others_lb = uni ? cc.others_lb : kinf();
                                             auto fast_march = [&](auto cls_tag) {
                                                 constexpr int CLS = decltype(cls_tag)::value;
                                                 BMO_NOUNROLL
@@ -1387,7 +1409,7 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                                     const double bound = v > 0.0 ? v : 0.0;
                                                     const double t1 = t0 + v;
                                                     const int it1 = it + 1;
-                                                    bool go = (cc.others_lb - acc > bound + 1e-12) && !(v < S.eps_ray) && !(exact && !back && t1 > lim) &&
+                                                    bool go = (others_lb - acc > bound + 1e-12) && !(v < S.eps_ray) && !(exact && !back && t1 > lim) &&
                                                               (it1 <= S.march_iters);
                                                     if (go && v > dist) {  // the generic branch's receding test (only when the distance grew)
                                                         const double R = s.bs_radius;
@@ -1401,7 +1423,9 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                                         break;
                                                     }
 #if defined(BMO_EMU_STATS)
-                                                    ++g_emu_sdf_any, ++g_emu_sdf_leaf, ++g_emu_union, ++g_emu_union_fast, ++g_emu_union_loop;
+                                                    ++g_emu_sdf_any, ++g_emu_sdf_leaf;
+                                                    if (uni) ++g_emu_union, ++g_emu_union_fast, ++g_emu_union_loop;
+                                                    else ++g_emu_leaf_loop, g_emu_leaf_loop_back += back;
 #endif
                                                     pos = np;
                                                     cc.acc = acc;
@@ -1433,6 +1457,9 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                 const double d = sdf_any<EXT>(S, H, s, pos, bc, cc, moved, has_pre, pre_v);
                                 has_pre = false;
                                 if (phase == OUTSIDE) {
+#if defined(BMO_EMU_STATS)
+                                    g_emu_leaf_outside += H.kind != BMO_SHAPE_UNION;
+#endif
                                     // (the receding test below only when the distance GREW with this step: outside the bounding ball and moving away
                                     //  from it an exact sdf grows with every step, and a march that is converging skips 16 instructions per trip;
                                     //  for the inexact leaves the test merely comes a step later — it proves misses, it never makes one.  Round 4:
