@@ -273,6 +273,22 @@ def check(lib, rc, what):
         raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
+def _psf_rows(hits, hits_device_ptr, n_hits):
+    """(pointer, row count, on_device, keep-alive) of the PSF rows of a single read-out."""
+    if hits_device_ptr is not None:
+        return C.c_void_p(int(hits_device_ptr)), int(n_hits), 1, None
+    h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
+    return h.ctypes.data_as(C.c_void_p), len(h), 0, h
+
+
+def _per_config(v, K1, cols):
+    """An optional per-configuration argument of a _sweep form as [K1, cols]: None stays None, one row counts for all."""
+    if v is None:
+        return None
+    v = np.asarray(v, dtype=np.float64)
+    return np.ascontiguousarray(np.tile(v, (K1, 1)) if v.ndim == 1 else v.reshape(K1, cols))
+
+
 def psf_intensity(hits, origin, e1, e2, xs, zs, device=0, hits_device_ptr=None, n_hits=None, want_field=False):
     """bmo_psf_intensity: returns (I[n, n] indexed [i, j], field or None, kernel_ms).  `hits` is a host [H, 9] array, or pass
     `hits_device_ptr` + `n_hits` for a buffer already resident on `device` (bmo_result_device_hits)."""
@@ -287,11 +303,7 @@ def psf_intensity(hits, origin, e1, e2, xs, zs, device=0, hits_device_ptr=None, 
     n = len(x)
     if len(z) != n:
         raise ValueError("xs and zs must have the same length")
-    if hits_device_ptr is None:
-        h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
-        hp, nh, on_dev = h.ctypes.data_as(C.c_void_p), len(h), 0
-    else:
-        hp, nh, on_dev = C.c_void_p(int(hits_device_ptr)), int(n_hits), 1
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
     out = np.zeros(n * n)
     fld = np.zeros(2 * n * n) if want_field else None
     ms = C.c_double()
@@ -355,8 +367,7 @@ def spot_image_sweep(res_handle, detector, n_configs, windows, nx, nz=None):
     lib = load_engine()
     K = int(n_configs)
     nz = nx if nz is None else nz
-    w = np.asarray(windows, dtype=np.float64)
-    w = np.ascontiguousarray(np.tile(w, (max(K, 1), 1)) if w.ndim == 1 else w.reshape(max(K, 1), 4))
+    w = _per_config(windows, max(K, 1), 4)
     img = np.zeros(max(K, 1) * max(int(nx) * int(nz), 0), dtype=np.int64)
     out = np.zeros(max(K, 1), dtype=np.int64)
     ms = C.c_double()
@@ -395,11 +406,7 @@ def psf_stats(hits, origin, e1, e2, ref=None, device=0, hits_device_ptr=None, n_
     dp = C.POINTER(C.c_double)
     o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
     r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
-    if hits_device_ptr is None:
-        h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
-        hp, nh, on_dev = h.ctypes.data_as(C.c_void_p), len(h), 0
-    else:
-        hp, nh, on_dev = C.c_void_p(int(hits_device_ptr)), int(n_hits), 1
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
     st = np.zeros(PSF_STAT_N)
     ms = C.c_double()
     check(lib, lib.bmo_psf_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
@@ -415,23 +422,12 @@ def psf_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, ref=None
     K = int(n_configs)
     K1 = max(K, 1)
     o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
-    r = None
-    if ref is not None:
-        r = np.asarray(ref, dtype=np.float64)
-        r = np.ascontiguousarray(np.tile(r, (K1, 1)) if r.ndim == 1 else r.reshape(K1, 2))
+    r = _per_config(ref, K1, 2)
     st = np.zeros((K1, PSF_STAT_N))
     ms = C.c_double()
     check(lib, lib.bmo_psf_stats_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                        None if r is None else r.ctypes.data_as(dp), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats_sweep")
     return st[:K], ms.value
-
-
-def _psf_rows(hits, hits_device_ptr, n_hits):
-    """(pointer, row count, on_device, keep-alive) of the PSF rows of a single read-out."""
-    if hits_device_ptr is not None:
-        return C.c_void_p(int(hits_device_ptr)), int(n_hits), 1, None
-    h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
-    return h.ctypes.data_as(C.c_void_p), len(h), 0, h
 
 
 def psf_through_focus(hits, origin, e1, e2, displacements, xs, zs, device=0, hits_device_ptr=None, n_hits=None, want_field=False):
@@ -488,11 +484,7 @@ def psf_zernike(hits, origin, e1, e2, order=4, ref=None, pupil=None, device=0, h
     o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
     r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
     q = None if pupil is None else np.ascontiguousarray(pupil, dtype=np.float64).reshape(3)
-    if hits_device_ptr is None:
-        h = np.ascontiguousarray(np.asarray(hits, dtype=np.float64).reshape(-1, 9))
-        hp, nh, on_dev = h.ctypes.data_as(C.c_void_p), len(h), 0
-    else:
-        hp, nh, on_dev = C.c_void_p(int(hits_device_ptr)), int(n_hits), 1
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
     J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
     coef, info = np.zeros(J), np.zeros(ZERN_INFO_N)
     gram = np.zeros(E) if want_gram else None
@@ -512,14 +504,7 @@ def psf_zernike_sweep(res_handle, detector, n_configs, origins, e1s, e2s, order=
     K = int(n_configs)
     K1 = max(K, 1)
     o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
-
-    def per_config(v, cols):
-        if v is None:
-            return None
-        v = np.asarray(v, dtype=np.float64)
-        return np.ascontiguousarray(np.tile(v, (K1, 1)) if v.ndim == 1 else v.reshape(K1, cols))
-
-    r, q = per_config(ref, 2), per_config(pupil, 3)
+    r, q = _per_config(ref, K1, 2), _per_config(pupil, K1, 3)
     J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
     coef, info = np.zeros((K1, J)), np.zeros((K1, ZERN_INFO_N))
     gram = np.zeros((K1, E)) if want_gram else None

@@ -348,6 +348,16 @@ static int slot_check(const char* who, const bmo_trace_result* res, int32_t dete
     return BMO_OK;
 }
 
+// What the _sweep read-outs of resident rows end on, once the entry has made its checks and answered an empty slot: the result's device, the
+// ranges of the slot's H > 0 rows over the n_configs configurations, and the rows themselves [H][9].
+static int resident_rows(const char* who, bmo_trace_result* res, int32_t detector, int64_t H, int32_t n_configs, Ranges& R, const double*& rows) {
+    HIP_TRY(hipSetDevice(res->device));
+    const std::string refusal = std::string(who) + ": rows out of configuration order";
+    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, refusal.c_str(), 0, R)) return rc;
+    rows = (const double*)res->det_data.p + 9 * res->det_offset[detector];
+    return BMO_OK;
+}
+
 // K rows of N columns as a configuration without rows reads: 0 in column 0 (the row count), NaN elsewhere
 static void fill_empty_stats(double* out, size_t K, size_t N) {
     std::fill(out, out + K * N, std::nan(""));
@@ -416,10 +426,10 @@ extern "C" int bmo_psf_intensity_sweep(bmo_trace_result* res, int32_t detector, 
         if (out_field) std::fill(out_field, out_field + (size_t)n_configs * n_pts * 2, 0.0);
         return BMO_OK;
     }
-    HIP_TRY(hipSetDevice(res->device));
     Ranges R;
-    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_intensity_sweep: rows out of configuration order", 0, R)) return rc;
-    return psf_read((const double*)res->det_data.p + 9 * res->det_offset[detector], R, origins, e1s, e2s, xs, zs, n, out_intensity, out_field, kernel_ms);
+    const double* hits;
+    if (int rc = resident_rows("bmo_psf_intensity_sweep", res, detector, H, n_configs, R, hits)) return rc;
+    return psf_read(hits, R, origins, e1s, e2s, xs, zs, n, out_intensity, out_field, kernel_ms);
 }
 
 // ====================================================================================================================
@@ -812,8 +822,8 @@ extern "C" int bmo_photodetector_field_sweep(bmo_trace_result* res, int32_t dete
 //   * statistics: two accumulate kernels with a per-configuration reduce each, queued behind one synchronisation; the centroid stays on
 //     the device for the second pass.  Lane l of a workgroup sums rows h0 + l, h0 + l + 256, ... sequentially, a fixed tree runs over the
 //     lanes of a wave and the four waves, the splits are summed in split order: deterministic for a given row count.  The sums of a pass
-//     are a sum record (below), which the wavefront, Zernike and focus statistics share with this read-out, as they do rows_plan,
-//     rows_items and single_rows.
+//     are a sum record (below), which the wavefront, Zernike and focus statistics share with this read-out, as they do the walk over a
+//     work item's rows (sum_pass_strided, sum_pass_staged), the host side of the passes (RowPasses) and single_rows.
 namespace {
 
 constexpr int SPOT_MIN_SPLIT = 2048;   // rows: shorter splits would spend their time on the histogram, not on rows
@@ -1000,6 +1010,37 @@ static void sum_reduce(unsigned n, hipStream_t st, const SplitCfg* cfg, const De
     hipLaunchKernelGGL((sum_reduce_kernel<R, Finish>), dim3(n), dim3(256), 0, st, cfg, (const R*)partial.p, finish);
 }
 
+// How a statistics pass walks the rows W.h0 .. W.h1 - 1 of its work item, written once; the kernels are their bodies.
+// Tile-staged, for passes that use all nine columns: tiles of PSF_TILE rows go through LDS with coalesced loads (psf_stage_rows) and lane l
+// then reads row l of the tile (a 72-byte stride: the lanes of a half-wave fall on distinct even banks).  body(r, h): r the staged row, h
+// its index.  Every lane of the workgroup calls it (it syncs).
+template <class Body>
+__device__ __forceinline__ void rows_staged(const double* __restrict__ hits, const SplitWork& W, Body&& body) {
+    __shared__ double tile[PSF_TILE * 9];
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);
+        if ((int)threadIdx.x < cnt) body(tile + 9 * threadIdx.x, base + threadIdx.x);
+    }
+}
+// A pass of work item blockIdx.x that keeps one record per lane: every lane starts from the identity, the body adds the lane's rows in the
+// order of the walk, the workgroup's record goes to partial[blockIdx.x].  Staged: body(record, r, h).
+template <class R, class Body>
+__device__ __forceinline__ void sum_pass_staged(const double* __restrict__ hits, const SplitWork& W, R* __restrict__ partial, Body&& body) {
+    R a = sum_identity<R>();
+    rows_staged(hits, W, [&](const double* r, int64_t h) { body(a, r, h); });
+    a = sum_wg_reduce(a);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+// Strided, for passes that read a few columns straight from memory: lane l visits rows h0 + l, h0 + l + 256, ...; body(record, h).
+template <class R, class Body>
+__device__ __forceinline__ void sum_pass_strided(const SplitWork& W, R* __restrict__ partial, Body&& body) {
+    R a = sum_identity<R>();
+    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) body(a, h);
+    a = sum_wg_reduce(a);
+    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+
 // --------------------------------------------------------------------------------------------------------------------
 // Spot statistics
 #define SPOT_SUM1(F) F(sx, SumAdd) F(sz, SumAdd) F(x_min, SumMin) F(x_max, SumMax) F(z_min, SumMin) F(z_max, SumMax)
@@ -1011,8 +1052,7 @@ SUM_RECORD(SpotSum2, SPOT_SUM2);
 __global__ __launch_bounds__(256) void spot_centroid_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
                                                             SpotSum1* __restrict__ partial) {
     const SplitWork W = work[blockIdx.x];
-    SpotSum1 a = sum_identity<SpotSum1>();
-    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+    sum_pass_strided(W, partial, [&](SpotSum1& a, int64_t h) {
         const double* r = rows + h * cols;
         const double x = r[0], z = r[1];
         a.sx += x;
@@ -1021,9 +1061,7 @@ __global__ __launch_bounds__(256) void spot_centroid_kernel(const double* __rest
         a.x_max = x > a.x_max ? x : a.x_max;
         a.z_min = z < a.z_min ? z : a.z_min;
         a.z_max = z > a.z_max ? z : a.z_max;
-    }
-    a = sum_wg_reduce(a);
-    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+    });
 }
 
 // N, the centroid and the extrema go to stats[c], the centroid to cent[c] for the second pass
@@ -1057,8 +1095,7 @@ __global__ __launch_bounds__(256) void spot_moments_kernel(const double* __restr
                                                            const double2* __restrict__ cent, SpotSum2* __restrict__ partial) {
     const SplitWork W = work[blockIdx.x];
     const double2 c = cent[W.cfg];
-    SpotSum2 a = sum_identity<SpotSum2>();
-    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+    sum_pass_strided(W, partial, [&](SpotSum2& a, int64_t h) {
         const double* r = rows + h * cols;
         const double dx = r[0] - c.x, dz = r[1] - c.y;
         const double xx = dx * dx, zz = dz * dz;
@@ -1067,9 +1104,7 @@ __global__ __launch_bounds__(256) void spot_moments_kernel(const double* __restr
         a.xz += dx * dz;
         const double q = xx + zz;
         a.r2 = q > a.r2 ? q : a.r2;
-    }
-    a = sum_wg_reduce(a);
-    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+    });
 }
 
 struct SpotMomentsFinish {
@@ -1118,6 +1153,49 @@ static int rows_items(const SplitPlan& plan, const char* who, unsigned& n_items)
     return BMO_OK;
 }
 
+// The host side of a read-out that walks its rows in statistics passes, each an accumulate kernel and the reduce of its records: the plan,
+// the upload, the stream, the timer and the records.  A read-out makes one, checks items(), adds to `up` what its kernels read besides the
+// work list, allocates its own buffers, calls begin(), pass() per pass and end(); everything queues behind one synchronisation.
+struct RowPasses {
+    SplitPlan plan;
+    // What a reduce folds and hands to the Finish: range i is records first_work .. first_work + n_splits - 1.  The configurations' work
+    // items, unless the read-out lays its records out otherwise before begin() (the focus statistics: [plane][item]).
+    std::vector<SplitCfg> ranges;
+    unsigned n_items = 0;
+    dim3 grid;  // of an accumulate kernel: the work items on x; y and z are the read-out's to use
+    Packed up;
+    hipStream_t st = 0;
+    EventTimer timer;
+    DevBuf records;  // one buffer for every pass: the passes run in stream order, a pass's reduce has read it before the next pass writes
+    size_t o_work = 0, o_ranges = 0;
+
+    explicit RowPasses(const Ranges& R) : plan(rows_plan(R)), ranges(plan.cfg) {}
+    int items(const char* who) {
+        const int rc = rows_items(plan, who, n_items);
+        grid = dim3(n_items);
+        return rc;
+    }
+    // uploads, sizes `records` for the largest of the passes' records Recs, starts the timer
+    template <class... Recs>
+    int begin() {
+        o_work = up.add(plan.work), o_ranges = up.add(ranges);
+        size_t cells = 0;
+        for (const SplitCfg& c : ranges) cells += (size_t)c.n_splits;
+        int rc;
+        if ((rc = up.upload(st)) || (rc = records.alloc(cells * std::max({sizeof(Recs)...})))) return rc;
+        return timer.start(st);
+    }
+    const SplitWork* work() const { return up.at<SplitWork>(o_work); }
+    const SplitCfg* cfg() const { return up.at<SplitCfg>(o_ranges); }
+    // kernel(args..., records) on `grid`, when there is a work item at all; the reduce hands the record of every range to `finish`
+    template <class Rec, class Kernel, class Finish, class... Args>
+    void pass(Kernel kernel, Finish finish, Args... args) {
+        if (n_items > 0) hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, args..., (Rec*)records.p);
+        sum_reduce<Rec>((unsigned)ranges.size(), st, cfg(), records, finish);
+    }
+    int end(double* kernel_ms) { return timer.stop(kernel_ms); }
+};
+
 // window c as the kernels read it, or why it is refused
 static bool spot_window(const double* w, int32_t nx, int32_t nz, SpotWindow& W) {
     for (int q = 0; q < 4; ++q)
@@ -1162,29 +1240,19 @@ static int spot_image_read(const double* rows, int32_t cols, const Ranges& R, co
 // The statistics [K][BMO_SPOT_STAT_N] of the K configurations from the device rows `rows` [..][cols].
 static int spot_stats_read(const double* rows, int32_t cols, const Ranges& R, double* stats, double* kernel_ms, const char* who) {
     const size_t K = R.count.size();
-    hipStream_t st = 0;
-    const SplitPlan plan = rows_plan(R);
-    unsigned n_items = 0;
-    if (int rc = rows_items(plan, who, n_items)) return rc;
-    Packed up;
-    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count);
-    DevBuf p1, p2, d_stats, d_cent;
+    RowPasses P(R);
+    if (int rc = P.items(who)) return rc;
+    const size_t o_count = P.up.add(R.count);
+    DevBuf d_stats, d_cent;
     int rc;
-    if ((rc = up.upload(st)) || (rc = p1.alloc((size_t)n_items * sizeof(SpotSum1))) || (rc = p2.alloc((size_t)n_items * sizeof(SpotSum2))) ||
-        (rc = d_stats.alloc(K * BMO_SPOT_STAT_N * 8)) || (rc = d_cent.alloc(K * sizeof(double2))))
-        return rc;
-    EventTimer timer;
-    if ((rc = timer.start(st))) return rc;
-    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
-    const int64_t* d_count = up.at<int64_t>(o_count);
-    if (n_items > 0)
-        hipLaunchKernelGGL(spot_centroid_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (SpotSum1*)p1.p);
-    sum_reduce<SpotSum1>((unsigned)K, st, d_cfg, p1, SpotCentroidFinish{d_count, (double*)d_stats.p, (double2*)d_cent.p});
-    if (n_items > 0)
-        hipLaunchKernelGGL(spot_moments_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), (const double2*)d_cent.p, (SpotSum2*)p2.p);
-    sum_reduce<SpotSum2>((unsigned)K, st, d_cfg, p2, SpotMomentsFinish{d_count, (double*)d_stats.p});
-    if ((rc = timer.stop(kernel_ms))) return rc;
-    HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_SPOT_STAT_N * 8, hipMemcpyDeviceToHost));
+    if ((rc = d_stats.alloc(K * BMO_SPOT_STAT_N * 8)) || (rc = d_cent.alloc(K * sizeof(double2))) || (rc = P.begin<SpotSum1, SpotSum2>())) return rc;
+    const int64_t* d_count = P.up.at<int64_t>(o_count);
+    double* const g_stats = (double*)d_stats.p;
+    double2* const g_cent = (double2*)d_cent.p;
+    P.pass<SpotSum1>(spot_centroid_kernel, SpotCentroidFinish{d_count, g_stats, g_cent}, rows, cols, P.work());
+    P.pass<SpotSum2>(spot_moments_kernel, SpotMomentsFinish{d_count, g_stats}, rows, cols, P.work(), g_cent);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, g_stats, K * BMO_SPOT_STAT_N * 8, hipMemcpyDeviceToHost));
     return BMO_OK;
 }
 
@@ -1218,10 +1286,10 @@ extern "C" int bmo_spot_image_sweep(bmo_trace_result* res, int32_t detector, int
         std::fill(outside, outside + n_configs, (int64_t)0);
         return BMO_OK;
     }
-    HIP_TRY(hipSetDevice(res->device));
     Ranges R;
-    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_spot_image_sweep: rows out of configuration order", 0, R)) return rc;
-    return spot_image_read((const double*)res->det_data.p + 9 * res->det_offset[detector], 9, R, win, nx, nz, image, outside, kernel_ms, "bmo_spot_image_sweep");
+    const double* rows;
+    if (int rc = resident_rows("bmo_spot_image_sweep", res, detector, H, n_configs, R, rows)) return rc;
+    return spot_image_read(rows, 9, R, win, nx, nz, image, outside, kernel_ms, "bmo_spot_image_sweep");
 }
 
 extern "C" int bmo_spot_stats(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, int32_t device, double* stats, double* kernel_ms) {
@@ -1242,10 +1310,10 @@ extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int
         fill_empty_stats(stats, (size_t)n_configs, BMO_SPOT_STAT_N);
         return BMO_OK;
     }
-    HIP_TRY(hipSetDevice(res->device));
     Ranges R;
-    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_spot_stats_sweep: rows out of configuration order", 0, R)) return rc;
-    return spot_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], 9, R, stats, kernel_ms, "bmo_spot_stats_sweep");
+    const double* rows;
+    if (int rc = resident_rows("bmo_spot_stats_sweep", res, detector, H, n_configs, R, rows)) return rc;
+    return spot_stats_read(rows, 9, R, stats, kernel_ms, "bmo_spot_stats_sweep");
 }
 
 // ====================================================================================================================
@@ -1258,8 +1326,7 @@ extern "C" int bmo_spot_stats_sweep(bmo_trace_result* res, int32_t detector, int
 //   C  sum proj (W - W_MEAN)^2 and the extrema of W - W_MEAN, from the 16-byte scratch rows instead of the 72-byte rows
 // A reduce is sum_reduce_kernel with the pass's Finish: one workgroup per configuration stages the configuration's partial sums through LDS
 // and thread 0 folds them in split order (sum_fold).
-// Passes A and B use all nine columns: they stage tiles of 256 rows through LDS with coalesced loads (psf_stage_rows) and lane l then
-// reads row l of the tile (a 72-byte stride: the lanes of a half-wave fall on distinct even banks).
+// Passes A and B use all nine columns and are tile-staged (rows_staged); pass C is strided.
 namespace {
 
 #define PSF_STAT_SUM_A(F) \
@@ -1280,33 +1347,56 @@ __device__ __forceinline__ double psf_local(const double* r, const d3& o, const 
     return ((r[0] - o.x) * e.x + (r[1] - o.y) * e.y) + (r[2] - o.z) * e.z;
 }
 
+// The terms that the wavefront statistics and the Zernike fit have in common, one definition each, over the sum record of either: run in
+// the same lane / wave / split order they make S, X_REF, Z_REF and W_MEAN of the two read-outs equal bit for bit.
+// pass A: the proj-weighted centroid sums of row r at local (x, z)
+template <class R>
+__device__ __forceinline__ void wave_centroid_add(R& a, const double* r, double x, double z) {
+    const double w = r[7];
+    a.s += w;
+    a.sx += w * x;
+    a.sz += w * z;
+}
+// its reduce: the centroid, the reference point (ref_xz: nullptr for the centroid, or [K][2]) and that point in world coordinates
+struct WaveRef {
+    double cx, cz, x_ref, z_ref;
+    d3 p;
+};
+template <class R>
+__device__ __forceinline__ WaveRef wave_ref(const R& a, const PsfPose& P, const double* ref_xz, int32_t c) {
+    const double cx = a.sx / a.s, cz = a.sz / a.s;
+    const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+    return WaveRef{cx, cz, x_ref, z_ref, psf_point(P.origin, P.e1, P.e2, x_ref, z_ref)};
+}
+// pass B: W of row r seen from the reference point p, added to sum proj W
+template <class R>
+__device__ __forceinline__ double wave_path_add(R& b, const d3& p, const double* r) {
+    const double path = psf_path(p, r);
+    b.sw += r[7] * path;
+    return path;
+}
+// its reduce: W_MEAN over the S of pass A
+template <class R>
+__device__ __forceinline__ double wave_mean(const R& b, double s) {
+    return b.sw / s;
+}
+
 // pass A of work item blockIdx.x
 __global__ __launch_bounds__(256) void psf_stats_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                              PsfStatSumA* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
-    PsfStatSumA a = sum_identity<PsfStatSumA>();
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
-            const double w = r[7], k = r[8];
-            a.s += w;
-            a.sx += w * x;
-            a.sz += w * z;
-            a.x_min = x < a.x_min ? x : a.x_min;
-            a.x_max = x > a.x_max ? x : a.x_max;
-            a.z_min = z < a.z_min ? z : a.z_min;
-            a.z_max = z > a.z_max ? z : a.z_max;
-            a.k_min = k < a.k_min ? k : a.k_min;
-            a.k_max = k > a.k_max ? k : a.k_max;
-        }
-    }
-    a = sum_wg_reduce(a);
-    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+    sum_pass_staged(hits, W, partial, [&](PsfStatSumA& a, const double* r, int64_t) {
+        const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
+        const double k = r[8];
+        wave_centroid_add(a, r, x, z);
+        a.x_min = x < a.x_min ? x : a.x_min;
+        a.x_max = x > a.x_max ? x : a.x_max;
+        a.z_min = z < a.z_min ? z : a.z_min;
+        a.z_max = z > a.z_max ? z : a.z_max;
+        a.k_min = k < a.k_min ? k : a.k_min;
+        a.k_max = k > a.k_max ? k : a.k_max;
+    });
 }
 
 // N, S, the centroid, the extrema and the reference point go to stats[c], what the later passes need to mid[c].  ref_xz: nullptr (the
@@ -1326,53 +1416,41 @@ struct PsfStatSumsFinish {
     __device__ void operator()(int32_t c, const PsfStatSumA& a) const {
         double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
         out[BMO_PSF_STAT_N_ROWS] = (double)count[c];
-        const double cx = a.sx / a.s, cz = a.sz / a.s;
-        const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+        const WaveRef ref = wave_ref(a, pose[c], ref_xz, c);
         out[BMO_PSF_STAT_S] = a.s;
-        out[BMO_PSF_STAT_CX] = cx;
-        out[BMO_PSF_STAT_CZ] = cz;
+        out[BMO_PSF_STAT_CX] = ref.cx;
+        out[BMO_PSF_STAT_CZ] = ref.cz;
         out[BMO_PSF_STAT_X_MIN] = a.x_min;
         out[BMO_PSF_STAT_X_MAX] = a.x_max;
         out[BMO_PSF_STAT_Z_MIN] = a.z_min;
         out[BMO_PSF_STAT_Z_MAX] = a.z_max;
-        out[BMO_PSF_STAT_X_REF] = x_ref;
-        out[BMO_PSF_STAT_Z_REF] = z_ref;
+        out[BMO_PSF_STAT_X_REF] = ref.x_ref;
+        out[BMO_PSF_STAT_Z_REF] = ref.z_ref;
         out[BMO_PSF_STAT_K_MIN] = a.k_min;
         out[BMO_PSF_STAT_K_MAX] = a.k_max;
-        const PsfPose P = pose[c];
-        mid[c] = PsfStatMid{cx, cz, 0.0, psf_point(P.origin, P.e1, P.e2, x_ref, z_ref)};
+        mid[c] = PsfStatMid{ref.cx, ref.cz, 0.0, ref.p};
     }
 };
 
 // pass B of work item blockIdx.x; pw[h] = (proj, W) of row h for pass C
 __global__ __launch_bounds__(256) void psf_stats_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                              const PsfStatMid* __restrict__ mid, double2* __restrict__ pw, PsfStatSumB* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
     const PsfStatMid M = mid[W.cfg];
-    PsfStatSumB b = sum_identity<PsfStatSumB>();
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double ax = fabs(psf_local(r, C.origin, C.e1) - M.cx), az = fabs(psf_local(r, C.origin, C.e2) - M.cz);
-            b.hwx = ax > b.hwx ? ax : b.hwx;
-            b.hwz = az > b.hwz ? az : b.hwz;
-            const double w = r[7];
-            const double path = psf_path(M.p, r);
-            const double phase = r[8] * path;
-            double sn, cs;
-            sincos(phase, &sn, &cs);
-            b.sw += w * path;
-            b.re += w * cs;
-            b.im += w * sn;
-            pw[base + threadIdx.x] = make_double2(w, path);
-        }
-    }
-    b = sum_wg_reduce(b);
-    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+    sum_pass_staged(hits, W, partial, [&](PsfStatSumB& b, const double* r, int64_t h) {
+        const double ax = fabs(psf_local(r, C.origin, C.e1) - M.cx), az = fabs(psf_local(r, C.origin, C.e2) - M.cz);
+        b.hwx = ax > b.hwx ? ax : b.hwx;
+        b.hwz = az > b.hwz ? az : b.hwz;
+        const double w = r[7];
+        const double path = wave_path_add(b, M.p, r);
+        const double phase = r[8] * path;
+        double sn, cs;
+        sincos(phase, &sn, &cs);
+        b.re += w * cs;
+        b.im += w * sn;
+        pw[h] = make_double2(w, path);
+    });
 }
 
 struct PsfStatWaveFinish {
@@ -1382,7 +1460,7 @@ struct PsfStatWaveFinish {
     __device__ void operator()(int32_t c, const PsfStatSumB& b) const {
         double* out = stats + (int64_t)c * BMO_PSF_STAT_N;
         const double s = out[BMO_PSF_STAT_S];
-        const double w_mean = b.sw / s;
+        const double w_mean = wave_mean(b, s);
         out[BMO_PSF_STAT_HWX] = b.hwx;
         out[BMO_PSF_STAT_HWZ] = b.hwz;
         out[BMO_PSF_STAT_W_MEAN] = w_mean;
@@ -1398,16 +1476,13 @@ __global__ __launch_bounds__(256) void psf_stats_spread_kernel(const double2* __
                                                                PsfStatSumC* __restrict__ partial) {
     const SplitWork W = work[blockIdx.x];
     const double w_mean = mid[W.cfg].w_mean;
-    PsfStatSumC s = sum_identity<PsfStatSumC>();
-    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+    sum_pass_strided(W, partial, [&](PsfStatSumC& s, int64_t h) {
         const double2 v = pw[h];
         const double d = v.y - w_mean;
         s.var += v.x * (d * d);
         s.lo = d < s.lo ? d : s.lo;
         s.hi = d > s.hi ? d : s.hi;
-    }
-    s = sum_wg_reduce(s);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    });
 }
 
 struct PsfStatSpreadFinish {
@@ -1427,37 +1502,25 @@ struct PsfStatSpreadFinish {
 static int psf_stats_read(const double* hits, int64_t n_rows, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* ref_xz,
                           double* stats, double* kernel_ms, const char* who) {
     const size_t K = R.count.size();
-    hipStream_t st = 0;
-    const SplitPlan plan = rows_plan(R);
-    unsigned n_items = 0;
-    if (int rc = rows_items(plan, who, n_items)) return rc;
-    Packed up;
-    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(psf_poses(K, origins, e1s, e2s));
-    const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0;
-    DevBuf pa, pb, pc, d_stats, d_mid, d_pw;
+    RowPasses P(R);
+    if (int rc = P.items(who)) return rc;
+    const size_t o_count = P.up.add(R.count), o_pose = P.up.add(psf_poses(K, origins, e1s, e2s)), o_ref = ref_xz ? P.up.add(ref_xz, 2 * K) : 0;
+    DevBuf d_stats, d_mid, d_pw;
     int rc;
-    if ((rc = up.upload(st)) || (rc = pa.alloc((size_t)n_items * sizeof(PsfStatSumA))) || (rc = pb.alloc((size_t)n_items * sizeof(PsfStatSumB))) ||
-        (rc = pc.alloc((size_t)n_items * sizeof(PsfStatSumC))) || (rc = d_stats.alloc(K * BMO_PSF_STAT_N * 8)) || (rc = d_mid.alloc(K * sizeof(PsfStatMid))) ||
-        (rc = d_pw.alloc((size_t)n_rows * sizeof(double2))))
+    if ((rc = d_stats.alloc(K * BMO_PSF_STAT_N * 8)) || (rc = d_mid.alloc(K * sizeof(PsfStatMid))) || (rc = d_pw.alloc((size_t)n_rows * sizeof(double2))) ||
+        (rc = P.begin<PsfStatSumA, PsfStatSumB, PsfStatSumC>()))
         return rc;
-    EventTimer timer;
-    if ((rc = timer.start(st))) return rc;
-    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
-    const SplitWork* d_work = up.at<SplitWork>(o_work);
-    const PsfPose* d_pose = up.at<PsfPose>(o_pose);
+    const PsfPose* d_pose = P.up.at<PsfPose>(o_pose);
     double* const g_stats = (double*)d_stats.p;
     PsfStatMid* const g_mid = (PsfStatMid*)d_mid.p;
-    if (n_items > 0) hipLaunchKernelGGL(psf_stats_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (PsfStatSumA*)pa.p);
-    sum_reduce<PsfStatSumA>((unsigned)K, st, d_cfg, pa,
-                            PsfStatSumsFinish{up.at<int64_t>(o_count), d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, g_stats, g_mid});
-    if (n_items > 0)
-        hipLaunchKernelGGL(psf_stats_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const PsfStatMid*)g_mid, (double2*)d_pw.p, (PsfStatSumB*)pb.p);
-    sum_reduce<PsfStatSumB>((unsigned)K, st, d_cfg, pb, PsfStatWaveFinish{g_stats, g_mid});
-    if (n_items > 0)
-        hipLaunchKernelGGL(psf_stats_spread_kernel, dim3(n_items), dim3(256), 0, st, (const double2*)d_pw.p, d_work, (const PsfStatMid*)g_mid, (PsfStatSumC*)pc.p);
-    sum_reduce<PsfStatSumC>((unsigned)K, st, d_cfg, pc, PsfStatSpreadFinish{g_stats});
-    if ((rc = timer.stop(kernel_ms))) return rc;
-    HIP_TRY(hipMemcpy(stats, d_stats.p, K * BMO_PSF_STAT_N * 8, hipMemcpyDeviceToHost));
+    double2* const g_pw = (double2*)d_pw.p;
+    P.pass<PsfStatSumA>(psf_stats_sums_kernel,
+                        PsfStatSumsFinish{P.up.at<int64_t>(o_count), d_pose, ref_xz ? P.up.at<double>(o_ref) : (const double*)nullptr, g_stats, g_mid}, hits, P.work(),
+                        d_pose);
+    P.pass<PsfStatSumB>(psf_stats_wave_kernel, PsfStatWaveFinish{g_stats, g_mid}, hits, P.work(), d_pose, g_mid, g_pw);
+    P.pass<PsfStatSumC>(psf_stats_spread_kernel, PsfStatSpreadFinish{g_stats}, g_pw, P.work(), g_mid);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, g_stats, K * BMO_PSF_STAT_N * 8, hipMemcpyDeviceToHost));
     return BMO_OK;
 }
 
@@ -1480,16 +1543,17 @@ extern "C" int bmo_psf_stats_sweep(bmo_trace_result* res, int32_t detector, int3
         fill_empty_stats(stats, (size_t)n_configs, BMO_PSF_STAT_N);
         return BMO_OK;
     }
-    HIP_TRY(hipSetDevice(res->device));
     Ranges R;
-    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_stats_sweep: rows out of configuration order", 0, R)) return rc;
-    return psf_stats_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, stats, kernel_ms, "bmo_psf_stats_sweep");
+    const double* hits;
+    if (int rc = resident_rows("bmo_psf_stats_sweep", res, detector, H, n_configs, R, hits)) return rc;
+    return psf_stats_read(hits, H, R, origins, e1s, e2s, ref_xz, stats, kernel_ms, "bmo_psf_stats_sweep");
 }
 
 // ====================================================================================================================
 // Zernike read-out: the least-squares Zernike coefficients of a PSFDetector's wavefront (include/bmo.h "Zernike read-out").  The plumbing
-// and the first two passes are those of the wavefront statistics (same expressions, same lane / wave / split order: S, X_REF, Z_REF and
-// W_MEAN are that call's bit for bit); four accumulate passes with a per-configuration reduce each, queued behind one synchronisation:
+// and the first two passes are those of the wavefront statistics: both read-outs call wave_centroid_add, wave_ref, wave_path_add and
+// wave_mean in the same lane / wave / split order, so S, X_REF, Z_REF and W_MEAN are that call's bit for bit by construction.  Four accumulate
+// passes with a per-configuration reduce each, queued behind one synchronisation:
 //   A  S, sum proj x, sum proj z, sum proj u, sum proj v over the 9-column rows; its reduce leaves p, U0, V0
 //   B  sum proj W and the largest squared pupil radius; writes (proj, W, u, v) of every row to a 32-byte scratch column; its reduce
 //      leaves W_MEAN and RHO
@@ -1597,26 +1661,13 @@ __device__ __forceinline__ double zern_cosine(const double* r, const d3& e) { re
 // pass A of work item blockIdx.x
 __global__ __launch_bounds__(256) void psf_zernike_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                                ZernSumA* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
-    ZernSumA a = sum_identity<ZernSumA>();
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double x = psf_local(r, C.origin, C.e1), z = psf_local(r, C.origin, C.e2);
-            const double w = r[7];
-            a.s += w;
-            a.sx += w * x;
-            a.sz += w * z;
-            a.su += w * zern_cosine(r, C.e1);
-            a.sv += w * zern_cosine(r, C.e2);
-        }
-    }
-    a = sum_wg_reduce(a);
-    if (threadIdx.x == 0) partial[blockIdx.x] = a;
+    sum_pass_staged(hits, W, partial, [&](ZernSumA& a, const double* r, int64_t) {
+        wave_centroid_add(a, r, psf_local(r, C.origin, C.e1), psf_local(r, C.origin, C.e2));
+        a.su += r[7] * zern_cosine(r, C.e1);
+        a.sv += r[7] * zern_cosine(r, C.e2);
+    });
 }
 
 // ref_xz: nullptr (the centroid) or [K][2]; pupil: nullptr or [K][3].  A configuration without rows gets its whole answer here: N = 0,
@@ -1636,45 +1687,32 @@ struct ZernSumsFinish {
     }
     __device__ void operator()(int32_t c, const ZernSumA& a) const {
         double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
-        const double cx = a.sx / a.s, cz = a.sz / a.s;
-        const double x_ref = ref_xz ? ref_xz[2 * c] : cx, z_ref = ref_xz ? ref_xz[2 * c + 1] : cz;
+        const WaveRef ref = wave_ref(a, pose[c], ref_xz, c);
         const double u0 = pupil ? pupil[3 * c] : a.su / a.s, v0 = pupil ? pupil[3 * c + 1] : a.sv / a.s;
         out[BMO_ZERNIKE_N_ROWS] = (double)count[c];
         out[BMO_ZERNIKE_STATUS] = 0.0;
         out[BMO_ZERNIKE_S] = a.s;
-        out[BMO_ZERNIKE_X_REF] = x_ref;
-        out[BMO_ZERNIKE_Z_REF] = z_ref;
+        out[BMO_ZERNIKE_X_REF] = ref.x_ref;
+        out[BMO_ZERNIKE_Z_REF] = ref.z_ref;
         out[BMO_ZERNIKE_U0] = u0;
         out[BMO_ZERNIKE_V0] = v0;
-        const PsfPose P = pose[c];
-        mid[c] = ZernMid{psf_point(P.origin, P.e1, P.e2, x_ref, z_ref), u0, v0, 0.0, 0.0};
+        mid[c] = ZernMid{ref.p, u0, v0, 0.0, 0.0};
     }
 };
 
 // pass B of work item blockIdx.x; col[h] = (proj, W, u, v) of row h for passes C and D
 __global__ __launch_bounds__(256) void psf_zernike_wave_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, const PsfPose* __restrict__ pose,
                                                                const ZernMid* __restrict__ mid, double4* __restrict__ col, ZernSumB* __restrict__ partial) {
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const PsfPose C = pose[W.cfg];
     const ZernMid M = mid[W.cfg];
-    ZernSumB b = sum_identity<ZernSumB>();
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double w = r[7];
-            const double path = psf_path(M.p, r);
-            const double u = zern_cosine(r, C.e1), v = zern_cosine(r, C.e2);
-            b.sw += w * path;
-            const double q = (u - M.u0) * (u - M.u0) + (v - M.v0) * (v - M.v0);
-            b.r2 = q > b.r2 ? q : b.r2;
-            col[base + threadIdx.x] = make_double4(w, path, u, v);
-        }
-    }
-    b = sum_wg_reduce(b);
-    if (threadIdx.x == 0) partial[blockIdx.x] = b;
+    sum_pass_staged(hits, W, partial, [&](ZernSumB& b, const double* r, int64_t h) {
+        const double path = wave_path_add(b, M.p, r);
+        const double u = zern_cosine(r, C.e1), v = zern_cosine(r, C.e2);
+        const double q = (u - M.u0) * (u - M.u0) + (v - M.v0) * (v - M.v0);
+        b.r2 = q > b.r2 ? q : b.r2;
+        col[h] = make_double4(r[7], path, u, v);
+    });
 }
 
 struct ZernWaveFinish {
@@ -1684,7 +1722,7 @@ struct ZernWaveFinish {
     __device__ void empty(int32_t) const {}  // answered already
     __device__ void operator()(int32_t c, const ZernSumB& b) const {
         double* out = info + (int64_t)c * BMO_ZERNIKE_INFO_N;
-        const double w_mean = b.sw / out[BMO_ZERNIKE_S];
+        const double w_mean = wave_mean(b, out[BMO_ZERNIKE_S]);
         const double rho = pupil ? pupil[3 * c + 2] : sqrt(b.r2);
         out[BMO_ZERNIKE_W_MEAN] = w_mean;
         out[BMO_ZERNIKE_RHO] = rho;
@@ -1858,8 +1896,7 @@ __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4
     double cf[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
-    ZernSumD s = sum_identity<ZernSumD>();
-    for (int64_t h = W.h0 + threadIdx.x; h < W.h1; h += 256) {
+    sum_pass_strided(W, partial, [&](ZernSumD& s, int64_t h) {
         const double4 q = col[h];
         const double x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
         const double t = x * x + y * y;
@@ -1870,9 +1907,7 @@ __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4
         s.lo = e < s.lo ? e : s.lo;
         s.hi = e > s.hi ? e : s.hi;
         s.n_out += t > 1.0 ? 1.0 : 0.0;
-    }
-    s = sum_wg_reduce(s);
-    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+    });
 }
 
 struct ZernResidualFinish {
@@ -1887,15 +1922,6 @@ struct ZernResidualFinish {
         out[BMO_ZERNIKE_N_OUT] = s.n_out;
     }
 };
-
-template <int ORDER>
-static void zern_launch_gram(unsigned n_items, hipStream_t st, const double4* col, const SplitWork* work, const ZernMid* mid, double* partial) {
-    hipLaunchKernelGGL(psf_zernike_gram_kernel<ORDER>, dim3(n_items), dim3(256), 0, st, col, work, mid, partial);
-}
-template <int ORDER>
-static void zern_launch_residual(unsigned n_items, hipStream_t st, const double4* col, const SplitWork* work, const ZernMid* mid, const double* coef, ZernSumD* partial) {
-    hipLaunchKernelGGL(psf_zernike_residual_kernel<ORDER>, dim3(n_items), dim3(256), 0, st, col, work, mid, coef, partial);
-}
 
 }  // namespace
 
@@ -1925,50 +1951,37 @@ static int psf_zernike_read(const double* hits, int64_t n_rows, const Ranges& R,
     const size_t K = R.count.size();
     const int32_t J = zern_terms_of(order);
     const size_t E = (size_t)(J + 1) * (J + 2) / 2;
-    hipStream_t st = 0;
-    const SplitPlan plan = rows_plan(R);
-    unsigned n_items = 0;
-    if (int rc = rows_items(plan, who, n_items)) return rc;
-    Packed up;
-    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_count = up.add(R.count), o_pose = up.add(psf_poses(K, origins, e1s, e2s));
-    const size_t o_ref = ref_xz ? up.add(ref_xz, 2 * K) : 0, o_pupil = pupil ? up.add(pupil, 3 * K) : 0;
-    DevBuf pa, pb, pc, pd, d_info, d_coef, d_gram, d_mid, d_col;
+    RowPasses P(R);
+    if (int rc = P.items(who)) return rc;
+    const size_t o_count = P.up.add(R.count), o_pose = P.up.add(psf_poses(K, origins, e1s, e2s));
+    const size_t o_ref = ref_xz ? P.up.add(ref_xz, 2 * K) : 0, o_pupil = pupil ? P.up.add(pupil, 3 * K) : 0;
+    DevBuf d_gram_parts, d_info, d_coef, d_gram, d_mid, d_col;
     int rc;
-    if ((rc = up.upload(st)) || (rc = pa.alloc((size_t)n_items * sizeof(ZernSumA))) || (rc = pb.alloc((size_t)n_items * sizeof(ZernSumB))) ||
-        (rc = pc.alloc((size_t)n_items * E * 8)) || (rc = pd.alloc((size_t)n_items * sizeof(ZernSumD))) || (rc = d_info.alloc(K * BMO_ZERNIKE_INFO_N * 8)) ||
-        (rc = d_coef.alloc(K * (size_t)J * 8)) || (gram && (rc = d_gram.alloc(K * E * 8))) || (rc = d_mid.alloc(K * sizeof(ZernMid))) ||
-        (rc = d_col.alloc((size_t)n_rows * sizeof(double4))))
+    if ((rc = d_gram_parts.alloc((size_t)P.n_items * E * 8)) || (rc = d_info.alloc(K * BMO_ZERNIKE_INFO_N * 8)) || (rc = d_coef.alloc(K * (size_t)J * 8)) ||
+        (gram && (rc = d_gram.alloc(K * E * 8))) || (rc = d_mid.alloc(K * sizeof(ZernMid))) || (rc = d_col.alloc((size_t)n_rows * sizeof(double4))) ||
+        (rc = P.begin<ZernSumA, ZernSumB, ZernSumD>()))
         return rc;
-    EventTimer timer;
-    if ((rc = timer.start(st))) return rc;
-    const dim3 kb((unsigned)K);  // the reduces: one workgroup per configuration
-    const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
-    const SplitWork* d_work = up.at<SplitWork>(o_work);
-    const int64_t* d_count = up.at<int64_t>(o_count);
-    const PsfPose* d_pose = up.at<PsfPose>(o_pose);
-    const double* d_pupil = pupil ? up.at<double>(o_pupil) : (const double*)nullptr;
+    const int64_t* d_count = P.up.at<int64_t>(o_count);
+    const PsfPose* d_pose = P.up.at<PsfPose>(o_pose);
+    const double* d_pupil = pupil ? P.up.at<double>(o_pupil) : (const double*)nullptr;
     double* const g_info = (double*)d_info.p;
     ZernMid* const g_mid = (ZernMid*)d_mid.p;
     double4* const g_col = (double4*)d_col.p;
-    if (n_items > 0) hipLaunchKernelGGL(psf_zernike_sums_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (ZernSumA*)pa.p);
-    sum_reduce<ZernSumA>((unsigned)K, st, d_cfg, pa, ZernSumsFinish{d_count, d_pose, ref_xz ? up.at<double>(o_ref) : (const double*)nullptr, d_pupil, g_info, g_mid});
-    if (n_items > 0) hipLaunchKernelGGL(psf_zernike_wave_kernel, dim3(n_items), dim3(256), 0, st, hits, d_work, d_pose, (const ZernMid*)g_mid, g_col, (ZernSumB*)pb.p);
-    sum_reduce<ZernSumB>((unsigned)K, st, d_cfg, pb, ZernWaveFinish{d_pupil, g_info, g_mid});
-    if (n_items > 0) {
-        void (*const launch[])(unsigned, hipStream_t, const double4*, const SplitWork*, const ZernMid*, double*) = {
-            zern_launch_gram<0>, zern_launch_gram<1>, zern_launch_gram<2>, zern_launch_gram<3>, zern_launch_gram<4>, zern_launch_gram<5>, zern_launch_gram<6>};
-        launch[order](n_items, st, g_col, d_work, g_mid, (double*)pc.p);
-    }
-    hipLaunchKernelGGL(psf_zernike_gram_reduce_kernel, kb, dim3(256), 0, st, d_cfg, d_count, J, (const double*)pc.p, g_info, (double*)d_coef.p,
-                       gram ? (double*)d_gram.p : (double*)nullptr);
-    if (n_items > 0) {
-        void (*const launch[])(unsigned, hipStream_t, const double4*, const SplitWork*, const ZernMid*, const double*, ZernSumD*) = {
-            zern_launch_residual<0>, zern_launch_residual<1>, zern_launch_residual<2>, zern_launch_residual<3>,
-            zern_launch_residual<4>, zern_launch_residual<5>, zern_launch_residual<6>};
-        launch[order](n_items, st, g_col, d_work, g_mid, (const double*)d_coef.p, (ZernSumD*)pd.p);
-    }
-    sum_reduce<ZernSumD>((unsigned)K, st, d_cfg, pd, ZernResidualFinish{g_info});
-    if ((rc = timer.stop(kernel_ms))) return rc;
+    P.pass<ZernSumA>(psf_zernike_sums_kernel, ZernSumsFinish{d_count, d_pose, ref_xz ? P.up.at<double>(o_ref) : (const double*)nullptr, d_pupil, g_info, g_mid}, hits,
+                     P.work(), d_pose);
+    P.pass<ZernSumB>(psf_zernike_wave_kernel, ZernWaveFinish{d_pupil, g_info, g_mid}, hits, P.work(), d_pose, g_mid, g_col);
+    // pass C keeps no sum record: the Gram entries have a kernel and a reduce of their own
+    void (*const gram_pass[])(const double4*, const SplitWork*, const ZernMid*, double*) = {
+        psf_zernike_gram_kernel<0>, psf_zernike_gram_kernel<1>, psf_zernike_gram_kernel<2>, psf_zernike_gram_kernel<3>,
+        psf_zernike_gram_kernel<4>, psf_zernike_gram_kernel<5>, psf_zernike_gram_kernel<6>};
+    if (P.n_items > 0) hipLaunchKernelGGL(gram_pass[order], P.grid, dim3(256), 0, P.st, g_col, P.work(), g_mid, (double*)d_gram_parts.p);
+    hipLaunchKernelGGL(psf_zernike_gram_reduce_kernel, dim3((unsigned)K), dim3(256), 0, P.st, P.cfg(), d_count, J, (const double*)d_gram_parts.p, g_info,
+                       (double*)d_coef.p, gram ? (double*)d_gram.p : (double*)nullptr);
+    void (*const residual[])(const double4*, const SplitWork*, const ZernMid*, const double*, ZernSumD*) = {
+        psf_zernike_residual_kernel<0>, psf_zernike_residual_kernel<1>, psf_zernike_residual_kernel<2>, psf_zernike_residual_kernel<3>,
+        psf_zernike_residual_kernel<4>, psf_zernike_residual_kernel<5>, psf_zernike_residual_kernel<6>};
+    P.pass<ZernSumD>(residual[order], ZernResidualFinish{g_info}, g_col, P.work(), g_mid, (const double*)d_coef.p);
+    if ((rc = P.end(kernel_ms))) return rc;
     HIP_TRY(hipMemcpy(info, d_info.p, K * BMO_ZERNIKE_INFO_N * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(coef, d_coef.p, K * (size_t)J * 8, hipMemcpyDeviceToHost));
     if (gram) HIP_TRY(hipMemcpy(gram, d_gram.p, K * E * 8, hipMemcpyDeviceToHost));
@@ -2000,11 +2013,10 @@ extern "C" int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, in
         psf_zernike_empty(n_configs, zern_terms_of(order), coef, info, gram);
         return BMO_OK;
     }
-    HIP_TRY(hipSetDevice(res->device));
     Ranges R;
-    if (int rc = slot_ranges(res, detector, 1, H, n_configs, res->n_configs > 0, "bmo_psf_zernike_sweep: rows out of configuration order", 0, R)) return rc;
-    return psf_zernike_read((const double*)res->det_data.p + 9 * res->det_offset[detector], H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, info, gram, kernel_ms,
-                            "bmo_psf_zernike_sweep");
+    const double* hits;
+    if (int rc = resident_rows("bmo_psf_zernike_sweep", res, detector, H, n_configs, R, hits)) return rc;
+    return psf_zernike_read(hits, H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, info, gram, kernel_ms, "bmo_psf_zernike_sweep");
 }
 
 // ====================================================================================================================
@@ -2191,7 +2203,6 @@ __device__ __forceinline__ double focus_den(const double* r, const FocusFrame& F
 __global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
                                                              const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
     constexpr int MP = FOCUS_STAT_MP;
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
@@ -2202,27 +2213,22 @@ __global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __res
         o[m] = focus_origin(F, offsets[m0 + (m < mcnt ? m : 0)]);
         a[m] = sum_identity<FocusSumA>();
     }
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double w = r[7], den = focus_den(r, F);
-            a[0].s += w;  // the two sums that every plane shares are kept once
-            a[0].bad += den == 0.0 ? 1.0 : 0.0;
+    rows_staged(hits, W, [&](const double* r, int64_t) {
+        const double w = r[7], den = focus_den(r, F);
+        a[0].s += w;  // the two sums that every plane shares are kept once
+        a[0].bad += den == 0.0 ? 1.0 : 0.0;
 #pragma unroll
-            for (int m = 0; m < MP; ++m) {
-                double x, z;
-                focus_local(r, F, o[m], den, x, z);
-                a[m].sx += w * x;
-                a[m].sz += w * z;
-                a[m].x_min = x < a[m].x_min ? x : a[m].x_min;
-                a[m].x_max = x > a[m].x_max ? x : a[m].x_max;
-                a[m].z_min = z < a[m].z_min ? z : a[m].z_min;
-                a[m].z_max = z > a[m].z_max ? z : a[m].z_max;
-            }
+        for (int m = 0; m < MP; ++m) {
+            double x, z;
+            focus_local(r, F, o[m], den, x, z);
+            a[m].sx += w * x;
+            a[m].sz += w * z;
+            a[m].x_min = x < a[m].x_min ? x : a[m].x_min;
+            a[m].x_max = x > a[m].x_max ? x : a[m].x_max;
+            a[m].z_min = z < a[m].z_min ? z : a[m].z_min;
+            a[m].z_max = z > a[m].z_max ? z : a[m].z_max;
         }
-    }
+    });
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
         a[m].s = a[0].s, a[m].bad = a[0].bad;
@@ -2262,7 +2268,6 @@ __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __r
                                                                const double* __restrict__ offsets, int32_t n_planes, const double2* __restrict__ mid,
                                                                FocusSumC* __restrict__ partial) {
     constexpr int MP = FOCUS_STAT_MP;
-    __shared__ double tile[PSF_TILE * 9];
     const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
@@ -2276,26 +2281,21 @@ __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __r
         c[m] = mid[mm];
         v[m] = sum_identity<FocusSumC>();
     }
-    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
-        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
-        psf_stage_rows(hits, base, cnt, tile);
-        if ((int)threadIdx.x < cnt) {
-            const double* r = tile + 9 * threadIdx.x;
-            const double w = r[7], den = focus_den(r, F);
+    rows_staged(hits, W, [&](const double* r, int64_t) {
+        const double w = r[7], den = focus_den(r, F);
 #pragma unroll
-            for (int m = 0; m < MP; ++m) {
-                double x, z;
-                focus_local(r, F, o[m], den, x, z);
-                const double ax = x - c[m].x, az = z - c[m].y;
-                const double fx = fabs(ax), fz = fabs(az);
-                const double r2 = ax * ax + az * az;
-                v[m].hwx = fx > v[m].hwx ? fx : v[m].hwx;
-                v[m].hwz = fz > v[m].hwz ? fz : v[m].hwz;
-                v[m].sr2 += w * r2;
-                v[m].r2_max = r2 > v[m].r2_max ? r2 : v[m].r2_max;
-            }
+        for (int m = 0; m < MP; ++m) {
+            double x, z;
+            focus_local(r, F, o[m], den, x, z);
+            const double ax = x - c[m].x, az = z - c[m].y;
+            const double fx = fabs(ax), fz = fabs(az);
+            const double r2 = ax * ax + az * az;
+            v[m].hwx = fx > v[m].hwx ? fx : v[m].hwx;
+            v[m].hwz = fz > v[m].hwz ? fz : v[m].hwz;
+            v[m].sr2 += w * r2;
+            v[m].r2_max = r2 > v[m].r2_max ? r2 : v[m].r2_max;
         }
-    }
+    });
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
         const FocusSumC s = sum_wg_reduce(v[m]);
@@ -2322,6 +2322,34 @@ struct FocusSpreadFinish {
 
 }  // namespace
 
+// The statistics [n_planes][BMO_FOCUS_STAT_N] of the n_hits > 0 device rows `hits` [..][9] on the planes at offsets[m] * axis.
+static int psf_focus_stats_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* axis, const double* offsets,
+                                int32_t n_planes, double* stats, double* kernel_ms, const char* who) {
+    RowPasses P(Ranges{{0}, {n_hits}});
+    if (int rc = P.items(who)) return rc;
+    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
+    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
+    if (chunks > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
+    // the partial sums are [plane][item]: to the reduces a plane is a range of n_items records like a configuration's
+    P.ranges.resize((size_t)n_planes);
+    for (int32_t m = 0; m < n_planes; ++m) P.ranges[(size_t)m] = SplitCfg{(int64_t)m * P.n_items, (int32_t)P.n_items, 0};
+    const size_t o_off = P.up.add(offsets, (size_t)n_planes);
+    DevBuf d_stats, d_mid;
+    int rc;
+    if ((rc = d_stats.alloc((size_t)n_planes * BMO_FOCUS_STAT_N * 8)) || (rc = d_mid.alloc((size_t)n_planes * sizeof(double2))) || (rc = P.begin<FocusSumA, FocusSumC>()))
+        return rc;
+    P.grid.y = chunks;  // a workgroup per work item and chunk of planes
+    const double* d_off = P.up.at<double>(o_off);
+    double* const g_stats = (double*)d_stats.p;
+    double2* const g_mid = (double2*)d_mid.p;
+    P.pass<FocusSumA>(psf_focus_sums_kernel, FocusSumsFinish{n_hits, g_stats, g_mid}, hits, P.work(), F, d_off, n_planes);
+    P.pass<FocusSumC>(psf_focus_spread_kernel, FocusSpreadFinish{g_stats}, hits, P.work(), F, d_off, n_planes, g_mid);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(stats, g_stats, (size_t)n_planes * BMO_FOCUS_STAT_N * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
 extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
                                    const double axis[3], const double* offsets, int32_t n_planes, int32_t device, double* stats, double* kernel_ms) {
     if (!origin || !e1 || !e2 || !axis || !offsets || !stats || n_planes <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
@@ -2333,37 +2361,7 @@ extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t h
         fill_empty_stats(stats, (size_t)n_planes, BMO_FOCUS_STAT_N);
         return BMO_OK;
     }
-    hipStream_t st = 0;
-    const SplitPlan plan = rows_plan(Ranges{{0}, {n_hits}});
-    unsigned n_items = 0;
-    if (int rc = rows_items(plan, "bmo_psf_focus_stats", n_items)) return rc;
-    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
-    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
-    const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
-    if (chunks > 65535) return fail(BMO_ERR_LIMIT, "bmo_psf_focus_stats: more planes than one launch holds");
-    // the partial sums are [plane][item]: to the reduces a plane is a range of n_items records like a configuration's
-    std::vector<SplitCfg> planes((size_t)n_planes);
-    for (int32_t m = 0; m < n_planes; ++m) planes[(size_t)m] = SplitCfg{(int64_t)m * n_items, (int32_t)n_items, 0};
-    Packed up;
-    const size_t o_work = up.add(plan.work), o_off = up.add(offsets, (size_t)n_planes), o_planes = up.add(planes);
-    DevBuf pa, pc, d_stats, d_mid;
-    int rc;
-    const size_t cells = (size_t)n_planes * n_items;
-    if ((rc = up.upload(st)) || (rc = pa.alloc(cells * sizeof(FocusSumA))) || (rc = pc.alloc(cells * sizeof(FocusSumC))) ||
-        (rc = d_stats.alloc((size_t)n_planes * BMO_FOCUS_STAT_N * 8)) || (rc = d_mid.alloc((size_t)n_planes * sizeof(double2))))
-        return rc;
-    EventTimer timer;
-    if ((rc = timer.start(st))) return rc;
-    const SplitWork* d_work = up.at<SplitWork>(o_work);
-    const double* d_off = up.at<double>(o_off);
-    const SplitCfg* d_planes = up.at<SplitCfg>(o_planes);
-    hipLaunchKernelGGL(psf_focus_sums_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (FocusSumA*)pa.p);
-    sum_reduce<FocusSumA>((unsigned)n_planes, st, d_planes, pa, FocusSumsFinish{n_hits, (double*)d_stats.p, (double2*)d_mid.p});
-    hipLaunchKernelGGL(psf_focus_spread_kernel, dim3(n_items, chunks), dim3(256), 0, st, hits, d_work, F, d_off, n_planes, (const double2*)d_mid.p, (FocusSumC*)pc.p);
-    sum_reduce<FocusSumC>((unsigned)n_planes, st, d_planes, pc, FocusSpreadFinish{(double*)d_stats.p});
-    if ((rc = timer.stop(kernel_ms))) return rc;
-    HIP_TRY(hipMemcpy(stats, d_stats.p, (size_t)n_planes * BMO_FOCUS_STAT_N * 8, hipMemcpyDeviceToHost));
-    return BMO_OK;
+    return psf_focus_stats_read(hits, n_hits, origin, e1, e2, axis, offsets, n_planes, stats, kernel_ms, "bmo_psf_focus_stats");
 }
 
 // the resident PSF rows of slot `detector`, for the single-call read-outs that take a device pointer: bmo_result_device_hits with the checks
