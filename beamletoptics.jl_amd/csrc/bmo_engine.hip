@@ -104,7 +104,13 @@ struct Layout<BMO_BEAM_POLARIZED> {
 template <>
 struct Layout<BMO_BEAM_GAUSSIAN> {
     static constexpr int ABI = 33, ND = 38, OPL = 35;
+    static constexpr int RAY_STRIDE = 11;  // planes per sub-ray (chief, waist, divergence): ray r starts at plane RAY_STRIDE * r
+    static constexpr int LEN_A = 33, LEN_B = 34, OPL_C = 35, OPL_W = 36, OPL_D = 37;
+    // staging planes of a reflected child (StepParams::gstage, ::gkeep): its three rays without their hits, planes STAGE_STRIDE * r + c;
+    // a kept child (gkeep) has three more planes behind them
+    static constexpr int STAGE_STRIDE = 7, STAGE_PLANES = 3 * STAGE_STRIDE, KEEP_L0 = 21, KEEP_OPLC = 22, KEEP_FLAGS = 23, KEEP_PLANES = 24;
 };
+using LG = Layout<BMO_BEAM_GAUSSIAN>;
 constexpr int NI = 7;
 enum { I_NODE = 0, I_K = 1, I_HOBJ = 2, I_HSHAPE = 3, I_OBJ = 4, I_SHAPE = 5, I_FLAGS = 6 };
 enum { F_DEAD = 1 };
@@ -946,8 +952,8 @@ struct GaussRecDev {
     int64_t cap, j;
     int32_t node;
     double* N;     // the next level's record planes (same slot j): the rays the step produces for the beamlet that goes on are written
-    int64_t ncap;  // straight into their record, planes 11 r + c
-    double* G;     // staging of the reflected child's rays: [21][gcap], planes 7 r + c
+    int64_t ncap;  // straight into their record, planes RAY_STRIDE r + c
+    double* G;     // staging of the reflected child's rays: [STAGE_PLANES][gcap], planes STAGE_STRIDE r + c
     int64_t gcap;
     // wavelength index and wavelength of the beamlet: constant along a lane (children included), carried in the lane memory from the level
     // that loaded them — the node tables are indexed by beam, and with the roots in coherence order neighbouring lanes hold beams far apart:
@@ -955,7 +961,7 @@ struct GaussRecDev {
     int32_t li;
     double lambda;
     __device__ void put_next(int r, const RayS& x) const {
-        const int64_t b = 11 * (int64_t)r;
+        const int64_t b = LG::RAY_STRIDE * (int64_t)r;
         N[(b + 0) * ncap + j] = x.pos.x;
         N[(b + 1) * ncap + j] = x.pos.y;
         N[(b + 2) * ncap + j] = x.pos.z;
@@ -965,7 +971,7 @@ struct GaussRecDev {
         N[(b + 6) * ncap + j] = x.n;
     }
     __device__ void put_refl(int r, const RayS& x) const {
-        const int64_t b = 7 * (int64_t)r;
+        const int64_t b = LG::STAGE_STRIDE * (int64_t)r;
         G[(b + 0) * gcap + j] = x.pos.x;
         G[(b + 1) * gcap + j] = x.pos.y;
         G[(b + 2) * gcap + j] = x.pos.z;
@@ -975,7 +981,7 @@ struct GaussRecDev {
         G[(b + 6) * gcap + j] = x.n;
     }
     __device__ RayS ray(int r) const {
-        const int64_t b = 11 * (int64_t)r;
+        const int64_t b = LG::RAY_STRIDE * (int64_t)r;
         RayS x;
         x.pos = {D[(b + 0) * cap + j], D[(b + 1) * cap + j], D[(b + 2) * cap + j]};
         x.dir = {D[(b + 3) * cap + j], D[(b + 4) * cap + j], D[(b + 5) * cap + j]};
@@ -983,14 +989,14 @@ struct GaussRecDev {
         return x;
     }
     __device__ void put_hit(int r, const Hit& X) const {
-        const int64_t b = 11 * (int64_t)r;
+        const int64_t b = LG::RAY_STRIDE * (int64_t)r;
         D[(b + 7) * cap + j] = X.t;
         D[(b + 8) * cap + j] = X.n.x;
         D[(b + 9) * cap + j] = X.n.y;
         D[(b + 10) * cap + j] = X.n.z;
     }
     __device__ Hit hit(int r) const {
-        const int64_t b = 11 * (int64_t)r;
+        const int64_t b = LG::RAY_STRIDE * (int64_t)r;
         Hit X;
         X.t = D[(b + 7) * cap + j];
         X.n = {D[(b + 8) * cap + j], D[(b + 9) * cap + j], D[(b + 10) * cap + j]};
@@ -1007,11 +1013,11 @@ struct GaussRecDev {
     __device__ int32_t hint_shape() const { return I[I_HSHAPE * cap + j]; }
     __device__ GaussAcc acc() const {
         GaussAcc a;
-        a.lenA = D[33 * cap + j];
-        a.lenB = D[34 * cap + j];
-        a.oplC = D[35 * cap + j];
-        a.oplW = D[36 * cap + j];
-        a.oplD = D[37 * cap + j];
+        a.lenA = D[LG::LEN_A * cap + j];
+        a.lenB = D[LG::LEN_B * cap + j];
+        a.oplC = D[LG::OPL_C * cap + j];
+        a.oplW = D[LG::OPL_W * cap + j];
+        a.oplD = D[LG::OPL_D * cap + j];
         a.li = li;
         a.lambda = lambda;
         a.l0 = a.w0 = 0.0;  // (the splitter branch takes l0, w0, E0 from load(); nothing else reads them)
@@ -1024,11 +1030,11 @@ struct GaussRecDev {
         g.w = ray(1);
         g.d = ray(2);
         g.hint_obj = g.hint_shape = -1;  // consumed before the marches
-        g.lenA = D[33 * cap + j];
-        g.lenB = D[34 * cap + j];
-        g.oplC = D[35 * cap + j];
-        g.oplW = D[36 * cap + j];
-        g.oplD = D[37 * cap + j];
+        g.lenA = D[LG::LEN_A * cap + j];
+        g.lenB = D[LG::LEN_B * cap + j];
+        g.oplC = D[LG::OPL_C * cap + j];
+        g.oplW = D[LG::OPL_W * cap + j];
+        g.oplD = D[LG::OPL_D * cap + j];
         g.li = li;
         g.lambda = lambda;
         g.l0 = nodes.aux[(int64_t)node * 4 + 0];
@@ -1051,7 +1057,7 @@ struct GaussTailDev {
     __device__ RayS ray(int q, int r) const {
         int64_t c, s;
         const double* D = old_record(O, old, k + 1 + q, c, s);
-        const int64_t b = 11 * (int64_t)r;
+        const int64_t b = LG::RAY_STRIDE * (int64_t)r;
         RayS x;
         x.pos = {D[(b + 0) * c + s], D[(b + 1) * c + s], D[(b + 2) * c + s]};
         x.dir = {D[(b + 3) * c + s], D[(b + 4) * c + s], D[(b + 5) * c + s]};
@@ -1175,7 +1181,7 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                         const double* H = old_record(Qa->old, oc + w, 0, hc, hs);
                         BMO_NOUNROLL
                         for (int r = 0; r < 3; ++r) {
-                            const int64_t b11 = 11 * (int64_t)r;
+                            const int64_t b11 = LG::RAY_STRIDE * (int64_t)r;
                             RayS x;
                             x.pos = {H[(b11 + 0) * hc + hs], H[(b11 + 1) * hc + hs], H[(b11 + 2) * hc + hs]};
                             x.dir = {H[(b11 + 3) * hc + hs], H[(b11 + 4) * hc + hs], H[(b11 + 5) * hc + hs]};
@@ -1218,11 +1224,11 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             const int64_t tcap = T->cap;
             double* D = T->d;
             int32_t* I = T->i;
-            D[33 * tcap + slot] = lenA;
-            D[34 * tcap + slot] = lenB;
-            D[35 * tcap + slot] = oplC;
-            D[36 * tcap + slot] = oplW;
-            D[37 * tcap + slot] = oplD;
+            D[LG::LEN_A * tcap + slot] = lenA;
+            D[LG::LEN_B * tcap + slot] = lenB;
+            D[LG::OPL_C * tcap + slot] = oplC;
+            D[LG::OPL_W * tcap + slot] = oplW;
+            D[LG::OPL_D * tcap + slot] = oplD;
             I[I_NODE * tcap + slot] = nd;
             I[I_K * tcap + slot] = kk;
             I[I_HOBJ * tcap + slot] = ho;
@@ -1239,7 +1245,7 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             double* D = Q->nxt.d;
             BMO_NOUNROLL
             for (int r = 0; r < 3; ++r)
-                for (int c = 0; c < 7; ++c) D[(11 * r + c) * ncap + slot] = src[(int64_t)(rstride * r + c) * scap + j];
+                for (int c = 0; c < 7; ++c) D[(LG::RAY_STRIDE * r + c) * ncap + slot] = src[(int64_t)(rstride * r + c) * scap + j];
             write_tail(&Q->nxt, slot, nd, kk, ho, hs, fl, lenA, lenB, oplC, oplW, oplD);
         };
         // header of the record that follows a surviving bounce
@@ -1300,17 +1306,17 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                     const int32_t fl = ((RETR && old_kids) || 1 < Q->r_max) ? 0 : F_DEAD;
                     // children: chief inherits the parent chain (parent! Gaussian.jl:113-117); waist/div beams have no parent
                     if (go_on) write_tail(Nq, j, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);  // (its rays are in place)
-                    else write_next((int64_t)r1 + 2 * r, Nq->d, Nq->cap, 11, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);
+                    else write_next((int64_t)r1 + 2 * r, Nq->d, Nq->cap, LG::RAY_STRIDE, (int32_t)cn, 0, -1, -1, fl, 0.0, o.child_l0, o.oplC, 0.0, 0.0);
                     if (go_on && keep && pend_node < 0) {  // the reflected child waits for this lane (the staging planes serve the next split)
                         const int64_t gc = Q->gstage_cap;
                         BMO_NOUNROLL
-                        for (int q = 0; q < 21; ++q) Q->gkeep[q * gc + j] = Q->gstage[q * gc + j];
-                        Q->gkeep[21 * gc + j] = o.child_l0;
-                        Q->gkeep[22 * gc + j] = o.oplC;
-                        Q->gkeep[23 * gc + j] = (double)fl;
+                        for (int q = 0; q < LG::STAGE_PLANES; ++q) Q->gkeep[q * gc + j] = Q->gstage[q * gc + j];
+                        Q->gkeep[LG::KEEP_L0 * gc + j] = o.child_l0;
+                        Q->gkeep[LG::KEEP_OPLC * gc + j] = o.oplC;
+                        Q->gkeep[LG::KEEP_FLAGS * gc + j] = (double)fl;
                         pend_node = (int32_t)(cn + 1);
                     } else {
-                        write_next(go_on ? (int64_t)r1 + prefix_rank<!SWEEP>(m_push) : (int64_t)r1 + 2 * r + 1, Q->gstage, Q->gstage_cap, 7, (int32_t)(cn + 1), 0, -1, -1, fl, 0.0,
+                        write_next(go_on ? (int64_t)r1 + prefix_rank<!SWEEP>(m_push) : (int64_t)r1 + 2 * r + 1, Q->gstage, Q->gstage_cap, LG::STAGE_STRIDE, (int32_t)(cn + 1), 0, -1, -1, fl, 0.0,
                                    o.child_l0, o.oplC, 0.0, 0.0);
                     }
                     kid_here = go_on;
@@ -1331,8 +1337,8 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
                     const int64_t gc = Q->gstage_cap, nc = Nq->cap;
                     BMO_NOUNROLL
                     for (int r = 0; r < 3; ++r)
-                        for (int c = 0; c < 7; ++c) Nq->d[(11 * r + c) * nc + j] = Q->gkeep[(int64_t)(7 * r + c) * gc + j];
-                    write_tail(Nq, j, pend_node, 0, -1, -1, (int32_t)Q->gkeep[23 * gc + j], 0.0, Q->gkeep[21 * gc + j], Q->gkeep[22 * gc + j], 0.0, 0.0);
+                        for (int c = 0; c < 7; ++c) Nq->d[(LG::RAY_STRIDE * r + c) * nc + j] = Q->gkeep[(int64_t)(LG::STAGE_STRIDE * r + c) * gc + j];
+                    write_tail(Nq, j, pend_node, 0, -1, -1, (int32_t)Q->gkeep[LG::KEEP_FLAGS * gc + j], 0.0, Q->gkeep[LG::KEEP_L0 * gc + j], Q->gkeep[LG::KEEP_OPLC * gc + j], 0.0, 0.0);
                     pend_node = -1;
                 } else if (!kid_here) {
                     Nq->i[I_NODE * Nq->cap + j] = -1;  // no record of this beamlet at this level
@@ -1353,14 +1359,16 @@ __global__ __launch_bounds__(BMO_BLOCK, BMO_MIN_WAVES_GAUSS) void step_kernel_ga
             const int64_t slot = (int64_t)al.surv_base + prefix_rank<!SWEEP>(al.m_surv);
             int32_t fl, ho, hs;
             next_header(fl, ho, hs);
-            write_next(slot, Nq->d, Nq->cap, 11, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
+            write_next(slot, Nq->d, Nq->cap, LG::RAY_STRIDE, node, k + 1, ho, hs, fl, o.lenA, o.lenB, o.oplC, o.oplW, o.oplD);
         }
         if (pend_node >= 0) {  // the reflected children their lanes did not get to
             const int64_t gc = Q->gstage_cap;
-            write_next((int64_t)al.child_base + prefix_rank<!SWEEP>(al.m_split), Q->gkeep, gc, 7, pend_node, 0, -1, -1, (int32_t)Q->gkeep[23 * gc + j], 0.0, Q->gkeep[21 * gc + j],
-                       Q->gkeep[22 * gc + j], 0.0, 0.0);
+            write_next((int64_t)al.child_base + prefix_rank<!SWEEP>(al.m_split), Q->gkeep, gc, LG::STAGE_STRIDE, pend_node, 0, -1, -1, (int32_t)Q->gkeep[LG::KEEP_FLAGS * gc + j], 0.0, Q->gkeep[LG::KEEP_L0 * gc + j],
+                       Q->gkeep[LG::KEEP_OPLC * gc + j], 0.0, 0.0);
         }
-        if (Q->tile_cost && step_tid<SWEEP>() == 0) Q->tile_cost[tile] = (uint32_t)wall_clock64() - Q->tile_cost[tile];
+#if !defined(BMO_NO_TILE_COST)
+        if (Q->tile_cost && step_tid<SWEEP>() == 0) Q->tile_cost[tile] = (uint32_t)wall_clock64() - Q->tile_cost[tile];  // (guarded like the start stamp and like step_kernel's)
+#endif
         return;
     }
 }

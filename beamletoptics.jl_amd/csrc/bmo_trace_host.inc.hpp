@@ -301,15 +301,15 @@ __global__ void init_roots_kernel(const double* __restrict__ planes, const doubl
     const bool cont = KIND == BMO_BEAM_GAUSSIAN && n_planes >= BMO_PLANES_GAUSSIAN_CONTINUED;
     if (KIND == BMO_BEAM_GAUSSIAN) {
         for (int b = 0; b < 3; ++b) {
-            for (int p = 0; p < 6; ++p) c0.d[(11 * b + p) * cap + j] = Q[(6 * b + p) * n + j];
-            c0.d[(11 * b + 6) * cap + j] = Q[19 * n + j];
+            for (int p = 0; p < 6; ++p) c0.d[(LG::RAY_STRIDE * b + p) * cap + j] = Q[(6 * b + p) * n + j];
+            c0.d[(LG::RAY_STRIDE * b + 6) * cap + j] = Q[19 * n + j];
         }
         // accumulated lengths: zero for a fresh beamlet; a batch that continues solved beamlets brings them along (include/bmo.h)
-        c0.d[33 * cap + j] = cont ? Q[25 * n + j] : 0.0;  // lenA
-        c0.d[34 * cap + j] = cont ? Q[26 * n + j] : 0.0;  // lenB
-        c0.d[35 * cap + j] = cont ? Q[28 * n + j] : 0.0;  // oplC
-        c0.d[36 * cap + j] = cont ? Q[29 * n + j] : 0.0;  // oplW
-        c0.d[37 * cap + j] = cont ? Q[30 * n + j] : 0.0;  // oplD
+        c0.d[LG::LEN_A * cap + j] = cont ? Q[25 * n + j] : 0.0;
+        c0.d[LG::LEN_B * cap + j] = cont ? Q[26 * n + j] : 0.0;
+        c0.d[LG::OPL_C * cap + j] = cont ? Q[28 * n + j] : 0.0;
+        c0.d[LG::OPL_W * cap + j] = cont ? Q[29 * n + j] : 0.0;
+        c0.d[LG::OPL_D * cap + j] = cont ? Q[30 * n + j] : 0.0;
     } else {
         for (int p = 0; p < 6; ++p) c0.d[p * cap + j] = Q[p * n + j];
         c0.d[6 * cap + j] = Q[7 * n + j];
@@ -411,7 +411,7 @@ struct LaunchBufs {
             gstage.release();
             gkeep.release();
             gstage_cap = ((m + m / 8 + 1) & ~(int64_t)1);
-            if ((rc = gstage.alloc((size_t)gstage_cap * 21 * 8)) || (rc = gkeep.alloc((size_t)gstage_cap * 24 * 8))) return rc;
+            if ((rc = gstage.alloc((size_t)gstage_cap * LG::STAGE_PLANES * 8)) || (rc = gkeep.alloc((size_t)gstage_cap * LG::KEEP_PLANES * 8))) return rc;
         }
         return BMO_OK;
     }

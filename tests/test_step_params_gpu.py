@@ -138,6 +138,40 @@ def test_second_launch_reads_its_own_parameters(chain, monkeypatch):
     compare(got, ref, 0.0, "splitter chain, BMO_FUSE=4")
 
 
+def test_gaussian_splitter_chain(oracle, monkeypatch):
+    """`step_kernel_gauss` through what the two cases above take `step_kernel` through, 96 GaussianBeamlets = 1.5 waves: in-loop splits, a kept
+    reflected child (`gkeep`), a second split while one waits (pushed to `nxt`), a lane that takes its kept child up, kept children compacted
+    at the end of a loop; then a launch that ends in the middle of the chain (the beamlet kernels take their fuse depth from `BMO_FUSE_GAUSS`);
+    then one retrace after the second splitter was tilted: children re-walk their stored beamlets and keep the stored waist."""
+    system = _chain(4)
+    bundle = chain_bundle("gauss", 96)
+    scene0 = bmo.CompiledScene(system, bundle.lambdas)
+    ref0, sol = oracle.trace(scene0, bundle, CHAIN_R_MAX, threads=8, keep=True)
+    assert ref0.n_nodes >= 9 * bundle.n
+    for name in ("BMO_FUSE", "BMO_FUSE_GAUSS"):
+        monkeypatch.delenv(name, raising=False)
+    compare(_trace(scene0, bundle, CHAIN_R_MAX), ref0, 0.0, "splitter chain, 96 beamlets")
+    monkeypatch.setenv("BMO_FUSE", "4")
+    monkeypatch.setenv("BMO_FUSE_GAUSS", "4")
+    got = _trace(scene0, bundle, CHAIN_R_MAX)
+    assert got.n_steps >= 2, got.n_steps
+    compare(got, ref0, 0.0, "splitter chain, 96 beamlets, fuse depth 4")
+    monkeypatch.delenv("BMO_FUSE")
+    monkeypatch.delenv("BMO_FUSE_GAUSS")
+    bmo.xrotate3d(system.objects_tree[2], math.radians(0.7))
+    scene1 = bmo.CompiledScene(system, bundle.lambdas)
+    ref1 = oracle.trace(scene1, bundle, CHAIN_R_MAX, threads=8, prev=sol)
+    g0, h0 = bmo.system._engine_solve(scene0, bundle, CHAIN_R_MAX, None)
+    try:
+        g1, h1 = bmo.system._engine_solve(scene1, bundle, CHAIN_R_MAX, h0)
+        try:
+            compare(g1, ref1, 0.0, "splitter chain, 96 beamlets, retrace")
+        finally:
+            h1.free()
+    finally:
+        h0.free()
+
+
 def test_fewer_records_per_wave_than_lanes():
     """`BMO_THIN_WAVES=8` spreads the 96 records over six waves of 16 (`lane_shift` = 4: the upper lanes idle).  The knob is read once per
     process, so the solve runs in a child process that compares with the oracle itself."""
