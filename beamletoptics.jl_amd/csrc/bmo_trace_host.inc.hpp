@@ -7,7 +7,8 @@
 //   ChunkArena            the segment log's storage: chunks bumped out of large blocks, rewound behind a launch
 //   select_step_kernels   the step kernels of a beam kind / scene level / fresh, retrace or sweep solve
 //   plan_launch, fill_step_params, tile_order_feedback, build_sweep_lane_map, print_timeline, launch_step: one launch of the step loop
-//   order_nodes, gather_detector_hits                the canonical node order and the detector tables behind the last launch
+//   order_nodes, count_and_gather_hits               the canonical node order, the segment count and the detector tables behind the last
+//                                                    launch (gather_detector_hits_legacy: the pass BMO_FINISH=legacy brings back)
 
 // ---- the retrace tables of a finished solution (OldSolution), built when it is first retraced
 __global__ void old_obj_scatter_kernel(Chunk c, int32_t chunk_index, const int32_t* __restrict__ rec_start, int32_t* __restrict__ rec_obj,
@@ -73,11 +74,26 @@ int build_retrace_tables(bmo_trace_result* prev, hipStream_t stream) {
     return BMO_OK;
 }
 
+// Everything a solve counts, in ONE device block: a solve sets it by one copy of the context's pinned image and reads it back by one copy
+// behind the finish pass.  `ctr` comes first (StepParams::ctr; the read-back behind every launch takes these bytes alone), the 64
+// call-counter shards lie 128 B apart (StepParams::call_shards), `det_off` holds the first row of every detector in the hit table and
+// the number of rows behind them (written by hit_gather_kernel).  Word 1 of every shard's line counts segments (hit_count_kernel; the
+// step kernels count calls in word 0).
+constexpr int MAX_DETECTORS = 1023;  // hit_count_kernel / hit_gather_kernel keep a count per detector and wave in LDS
+struct TailBlock {
+    alignas(128) Counters ctr;
+    alignas(128) unsigned long long shards[64 * 16];
+    int32_t det_off[MAX_DETECTORS + 1];
+};
+inline size_t tail_bytes(int n_det) { return offsetof(TailBlock, det_off) + (size_t)(n_det + 1) * 4; }
+
 // one trace stream + timing events per device, created once (hipStreamCreate costs ~1 ms)
 struct DevCtx {
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     Counters* pinned = nullptr;
+    TailBlock* tail_img = nullptr;   // pinned; all zero but ctr.node_count, which a solve sets to its root count before it copies the image
+    TailBlock* tail_back = nullptr;  // pinned; the block as read back behind the finish pass
     std::vector<hipEvent_t> step_ev;
     std::mutex busy;  // one trace at a time per device: the stream, events and pinned counters are shared
 };
@@ -96,6 +112,9 @@ int device_ctx(int device, DevCtx*& out) {
     HIP_TRY(hipStreamCreateWithFlags(&nc->stream, hipStreamNonBlocking));
     for (int q = 0; q < 4; ++q) HIP_TRY(hipEventCreate(&nc->ev[q]));
     HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nc->pinned), sizeof(Counters), hipHostMallocDefault));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nc->tail_img), 2 * sizeof(TailBlock), hipHostMallocDefault));
+    std::memset(nc->tail_img, 0, 2 * sizeof(TailBlock));
+    nc->tail_back = nc->tail_img + 1;
     out = nc.get();
     ctxs.emplace_back(device, std::move(nc));
     return BMO_OK;
@@ -496,6 +515,7 @@ int tile_order_feedback(StepParams& P, bmo_device_batch* batch, const bmo_trace_
                                                                                          (const int32_t*)batch->lpt_ids.p, (int32_t*)batch->tile_order.p, (int)n_blocks, 0, 32, stream));
         P.tile_order = (const int32_t*)batch->tile_order.p;
     }
+    DBG("step 0 tile order: %s", P.tile_order ? "by the cost of the batch's previous solve" : "as laid out (no costs yet)");
     P.tile_cost = (uint32_t*)batch->tile_cost.p;
     batch->cost_valid = true;  // (after this launch)
     return BMO_OK;
@@ -825,7 +845,54 @@ int order_nodes(bmo_trace_result* R, int64_t n, int64_t n_nodes, unsigned long l
     return order_level_by_level(R, n_nodes, (int64_t)max_depth, bits_root, bits_depth, stream);
 }
 
-// flags[d*n + i] = 1 if canonical node i recorded a hit on detector d
+// ---- detector hits in reference push! order.  The hit table holds the rows of detector 0, then detector 1 ..., each in canonical node
+// order, nsub rows per hit.  A workgroup takes 256 consecutive canonical nodes (a tile): hit_count_kernel counts every tile's rows per
+// detector, one exclusive scan over the nd x n_tiles counts (detector-major) gives every tile its first row per detector, and
+// hit_gather_kernel ranks a tile's hits among themselves.  Nothing here scales with nd x n_nodes.  (BMO_FINISH=legacy: the pass this
+// one replaced — a flag per detector and node, a scan over all of them — kept to compare the two; gather_detector_hits_legacy.)
+//
+// Ranks the lanes of a wave by detector: `rank` = lanes below this one with the same detector d (d < 0: no hit), and once per distinct
+// detector of the wave (on the first lane that has it) f(detector, lanes with it).  As many trips as the wave has distinct detectors.
+template <class F>
+__device__ __forceinline__ int wave_rank_by_detector(int32_t d, F&& f) {
+    const int lane = (int)(threadIdx.x & 63u);
+    int rank = 0;
+    unsigned long long todo = __ballot(d >= 0);
+    while (todo) {
+        const int lead = __ffsll((long long)todo) - 1;
+        const int32_t dd = __shfl(d, lead);
+        const unsigned long long same = __ballot(d == dd);
+        if (d == dd) rank = __popcll(same & ((1ull << lane) - 1ull));
+        if (lane == lead) f(dd, __popcll(same));
+        todo &= ~same;
+    }
+    return rank;
+}
+// cnt[d * n_tiles + tile] = rows of detector d in the tile (nsub per hit), cnt[n_det * n_tiles] = 0 (the scan leaves the total there);
+// seg_shards[16 (tile & 63) + 1] += the segment counts of nodes [256 tile, 256 tile + 256): a sum of integers, in any order, one atomic
+// per workgroup, spread over the 64 lines of the call-counter shards (12 000 workgroups adding to ONE word took 147 us per config-2
+// solve, 12 ns per add: profiles/finish_pass_ab.txt).  n_det == 0 (no detectors): the segment count alone.
+__global__ void __launch_bounds__(256) hit_count_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ hit_det, const int32_t* __restrict__ nseg, int64_t n,
+                                                        int32_t n_det, int32_t nsub, int32_t* __restrict__ cnt, unsigned long long* __restrict__ seg_shards) {
+    __shared__ int32_t s_cnt[MAX_DETECTORS + 1];
+    __shared__ long long s_seg[4];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int q = threadIdx.x; q < n_det; q += 256) s_cnt[q] = 0;
+    long long seg = i < n ? (long long)nseg[i] : 0;
+    for (int o = 32; o > 0; o >>= 1) seg += __shfl_xor(seg, o);
+    if ((threadIdx.x & 63u) == 0) s_seg[threadIdx.x >> 6] = seg;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&seg_shards[(blockIdx.x & 63u) * 16u + 1u], (unsigned long long)(s_seg[0] + s_seg[1] + s_seg[2] + s_seg[3]));
+    if (n_det == 0) return;
+    int32_t d = i < n ? hit_det[order[i]] : -1;
+    if (d >= n_det) d = -1;
+    wave_rank_by_detector(d, [&](int32_t dd, int lanes) { atomicAdd(&s_cnt[dd], lanes); });
+    __syncthreads();
+    for (int q = threadIdx.x; q < n_det; q += 256) cnt[(int64_t)q * gridDim.x + blockIdx.x] = s_cnt[q] * nsub;
+    if (blockIdx.x == 0 && threadIdx.x == 0) cnt[(int64_t)n_det * gridDim.x] = 0;
+}
+
+// (the legacy pass) flags[d*n + i] = 1 if canonical node i recorded a hit on detector d
 __global__ void hit_flags_kernel(const int32_t* order, const int32_t* hit_det, int64_t n, int32_t n_det, int32_t nsub, int32_t* flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -841,15 +908,46 @@ __global__ void hit_offsets_kernel(const int32_t* __restrict__ offs, const int32
 // A workgroup takes 256 consecutive canonical nodes: their (id, destination) pairs go to LDS once, then the 72-byte records are copied
 // as contiguous runs, one double per thread and turn (the first form of this kernel re-read the three index tables for each of
 // the 9 doubles: 152 us per C2 solve for 0.3 GB of traffic).
-__global__ void hit_gather_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ hit_det, const double* __restrict__ hit, int64_t n, int32_t nsub,
-                                  const int32_t* __restrict__ offs, int64_t cap, double* __restrict__ out, int32_t* __restrict__ out_node,
-                                  unsigned long long* __restrict__ overflow) {
+// TILES: a node's first row = its tile's first row for the node's detector (`offs`: the scanned counts of hit_count_kernel, n_det x
+// n_tiles + 1 of them) + nsub x the tile's earlier hits on that detector, counted per wave in LDS; the first workgroup also leaves every
+// detector's first row and the number of rows in det_off (TailBlock).  !TILES (legacy): `offs` holds the first row of every (detector, node).
+template <bool TILES>
+__global__ void __launch_bounds__(256) hit_gather_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ hit_det, const double* __restrict__ hit, int64_t n,
+                                                         int32_t nsub, const int32_t* __restrict__ offs, int64_t cap, double* __restrict__ out,
+                                                         int32_t* __restrict__ out_node, unsigned long long* __restrict__ overflow, int32_t n_det,
+                                                         int32_t* __restrict__ det_off) {
     __shared__ int32_t s_nd[256], s_pos[256];
+    __shared__ int32_t s_wave[TILES ? 4 : 1][TILES ? MAX_DETECTORS + 1 : 1];  // TILES: hits of every wave of the tile on every detector
     const int64_t i0 = (int64_t)blockIdx.x * 256;
     {
         const int64_t i = i0 + threadIdx.x;
         int32_t nd = -1, pos = -1;
-        if (i < n) {
+        if constexpr (TILES) {
+            if (blockIdx.x == 0)
+                for (int q = threadIdx.x; q <= n_det; q += 256) det_off[q] = offs[(int64_t)q * gridDim.x];
+            for (int q = threadIdx.x; q < 4 * n_det; q += 256) s_wave[q / n_det][q % n_det] = 0;
+            __syncthreads();
+            int32_t d = -1;
+            if (i < n) {
+                nd = order[i];
+                d = hit_det[nd];
+                if (d >= n_det) d = -1;
+            }
+            const int w = (int)(threadIdx.x >> 6);
+            const int rank = wave_rank_by_detector(d, [&](int32_t dd, int lanes) { s_wave[w][dd] = lanes; });
+            __syncthreads();
+            if (d >= 0) {
+                int before = rank;
+                for (int q = 0; q < w; ++q) before += s_wave[q][d];
+                pos = offs[(int64_t)d * gridDim.x + blockIdx.x] + before * nsub;
+                if ((int64_t)pos + nsub > cap) {
+                    atomicAdd(overflow, 1ull);
+                    pos = -1;
+                } else {
+                    for (int q = 0; q < nsub; ++q) out_node[pos + q] = (int32_t)i;
+                }
+            }
+        } else if (i < n) {
             nd = order[i];
             const int32_t d = hit_det[nd];
             if (d >= 0) {
@@ -882,9 +980,33 @@ __global__ void hit_gather_kernel(const int32_t* __restrict__ order, const int32
         }
     }
 }
-// ---- detector hits in reference push! order: flags -> exclusive scan -> gather.  Queued; the offsets of the nd detectors (and the total
-// behind them) arrive in h_off with the caller's synchronisation.
-int gather_detector_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, Counters* d_ctr, int32_t* h_off, hipStream_t stream, Temps& temps) {
+// Segment count and detector tables of a solve, queued: the counts per tile, their scan, the gather.  d_tail->shards (word 1) and
+// d_tail->det_off (the first row of every detector, the number of rows behind them) come back with the block's read-back.
+int count_and_gather_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, TailBlock* d_tail, hipStream_t stream, Temps& temps) {
+    int rc;
+    const int nd = R->n_detectors;
+    if (nd > MAX_DETECTORS) return fail(BMO_ERR_UNSUPPORTED, "more than 1023 detectors");
+    const unsigned nb = (unsigned)((n_nodes + 255) / 256);
+    const int64_t tot = (int64_t)nd * nb + 1;  // counts of every (detector, tile), detector-major, and one more for the total
+    // the hit table is sized before the counts are back on the host: a beam with a hit has ended and every splitting beam has two
+    // children, so there are at most (beams + roots) / 2 of them
+    const int64_t bound = (n_nodes + n) / 2 * nsub + nsub;
+    if (tot >= ((int64_t)1 << 31) || bound >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "detector rows exceed 2^31: split the batch");
+    DevBuf *cnt = nullptr, *offs = nullptr;
+    if (nd > 0 && (!(cnt = temps.take((size_t)tot * 4)) || !(offs = temps.take((size_t)tot * 4)))) return BMO_ERR_OOM;
+    hipLaunchKernelGGL(hit_count_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const int32_t*)R->n_nseg.p, n_nodes,
+                       nd, nsub, cnt ? (int32_t*)cnt->p : nullptr, d_tail->shards);
+    if (nd == 0) return BMO_OK;
+    CUB_TRY(temps, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)cnt->p, (int32_t*)offs->p, (int)tot, stream));
+    if ((rc = R->det_data.alloc((size_t)std::max<int64_t>(bound, 1) * 72)) || (rc = R->det_node.alloc((size_t)std::max<int64_t>(bound, 1) * 4))) return rc;
+    hipLaunchKernelGGL(hit_gather_kernel<true>, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
+                       n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p, &d_tail->ctr.overflow, nd, d_tail->det_off);
+    return BMO_OK;
+}
+
+// ---- the legacy pass (BMO_FINISH=legacy): flags -> exclusive scan over nd x n_nodes of them -> gather.  Queued; the offsets of the nd
+// detectors (and the total behind them) arrive in h_off with the caller's synchronisation.
+int gather_detector_hits_legacy(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, Counters* d_ctr, int32_t* h_off, hipStream_t stream, Temps& temps) {
     int rc;
     const int nd = R->n_detectors;
     const int64_t tot = (int64_t)nd * n_nodes;
@@ -899,12 +1021,10 @@ int gather_detector_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nod
     // per-detector offsets = scan value at the start of each detector's segment; total = last offs + last flag
     hipLaunchKernelGGL(hit_offsets_kernel, dim3(1), dim3(1024), 0, stream, (const int32_t*)offs->p, (const int32_t*)flags->p, n_nodes, nd, (int32_t*)d_off->p);
     HIP_TRY(hipMemcpyAsync(h_off, d_off->p, (size_t)(nd + 1) * 4, hipMemcpyDeviceToHost, stream));
-    // the hit table is sized before the counts are back on the host: a beam with a hit has ended and every splitting beam has two
-    // children, so there are at most (beams + roots) / 2 of them
-    const int64_t bound = (n_nodes + n) / 2 * nsub + nsub;
+    const int64_t bound = (n_nodes + n) / 2 * nsub + nsub;  // (as in count_and_gather_hits)
     if ((rc = R->det_data.alloc((size_t)std::max<int64_t>(bound, 1) * 72)) || (rc = R->det_node.alloc((size_t)std::max<int64_t>(bound, 1) * 4))) return rc;
-    hipLaunchKernelGGL(hit_gather_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
-                       n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p, &d_ctr->overflow);
+    hipLaunchKernelGGL(hit_gather_kernel<false>, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
+                       n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p, &d_ctr->overflow, nd, (int32_t*)nullptr);
     return BMO_OK;
 }
 
@@ -1026,13 +1146,16 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
     const size_t rec_bytes = (size_t)K.nd * 8 + (size_t)NI * 4;
     ChunkArena arena{R->arena, (size_t)K.nd * 8, rec_bytes, std::max<size_t>((size_t)n * rec_bytes * 6, (size_t)1 << 20), keep_log};
 
-    DevBuf ctr_buf, shard_buf;
-    if ((rc = ctr_buf.alloc(sizeof(Counters))) || (rc = shard_buf.alloc(64 * 128))) return rc;
-    HIP_TRY(hipMemsetAsync(shard_buf.p, 0, 64 * 128, stream));
-    Counters* d_ctr = static_cast<Counters*>(ctr_buf.p);
+    if (R->n_detectors > MAX_DETECTORS) return fail(BMO_ERR_UNSUPPORTED, "more than 1023 detectors");
+    // counters, call-counter shards, segment count and detector offsets: one block, set by one copy (the image is zero but for the node count)
+    DevBuf tail_buf;
+    if ((rc = tail_buf.alloc(sizeof(TailBlock)))) return rc;
+    TailBlock* const d_tail = static_cast<TailBlock*>(tail_buf.p);
+    Counters* d_ctr = &d_tail->ctr;
     Counters& h_ctr = *ctx.pinned;  // pinned: the per-step read-back does not go through a staging copy
     h_ctr = Counters{{0, 0}, (unsigned long long)n, 0, 0, {0, 0}};
-    HIP_TRY(hipMemcpyAsync(d_ctr, &h_ctr, sizeof h_ctr, hipMemcpyHostToDevice, stream));
+    ctx.tail_img->ctr.node_count = (unsigned long long)n;
+    HIP_TRY(hipMemcpyAsync(d_tail, ctx.tail_img, tail_bytes(R->n_detectors), hipMemcpyHostToDevice, stream));
 
     LaunchChunks C;
     if ((rc = arena.alloc(n, C.cur))) return rc;
@@ -1083,7 +1206,7 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
         if (has_split && (rc = nodes.grow(n_nodes + 2 * m + 2 * plan.inwave_cap, stream))) return rc;
         if ((rc = bufs.fit(K, plan, m, rec_bytes))) return rc;
         StepParams P;
-        fill_step_params(P, K, scene, dblob, opts, C, plan, bufs, nodes.arrays(tbits_buf), old_tab, d_ctr, shard_buf.p, steps, n_nodes);
+        fill_step_params(P, K, scene, dblob, opts, C, plan, bufs, nodes.arrays(tbits_buf), old_tab, d_ctr, d_tail->shards, steps, n_nodes);
         if (knobs().lpt && !sweep && steps == 0 && plan.lane_shift == 6 && plan.n_blocks >= 64 && (rc = tile_order_feedback(P, batch, prev, plan.n_blocks, stream))) return rc;
 #if defined(BMO_DEV_TIMELINE)
         DevBuf tl_buf;
@@ -1149,45 +1272,67 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
     // Everything below is queued behind ONE synchronisation at the end: temporaries stay alive until then (`temps`: a block that went
     // back to the pool could be handed to a view running on another stream), counts are read back last.
     Temps temps;
-    // pinned read-back area: [0..1023] call-counter shards (64 x 16 words), [1024] segment count, [1025..] hit offsets
-    static_assert(sizeof(unsigned long long) == 8, "");
-    HostBuf h_tail;
-    if ((rc = h_tail.alloc((1024 + 1 + 1025) * 8))) return rc;
-    unsigned long long* const h_sh = static_cast<unsigned long long*>(h_tail.p);
-    long long* const h_sum = reinterpret_cast<long long*>(h_sh + 1024);
-    int32_t* const h_off = reinterpret_cast<int32_t*>(h_sh + 1025);
-    *h_sum = 0;
-    HIP_TRY(hipMemcpyAsync(h_sh, shard_buf.p, 64 * 128, hipMemcpyDeviceToHost, stream));
-    if (n_nodes > 0) {  // segments = sum of the beams' segment counts (chunk counts include the holes of fused levels)
-        DevBuf* d_sum = temps.take(8);
-        if (!d_sum) return BMO_ERR_OOM;
-        CUB_TRY(temps, hipcub::DeviceReduce::Sum(cub_tmp, cub_bytes, (const int32_t*)R->n_nseg.p, (long long*)d_sum->p, (int)n_nodes, stream));
-        HIP_TRY(hipMemcpyAsync(h_sum, d_sum->p, 8, hipMemcpyDeviceToHost, stream));
-    }
-    if ((rc = order_nodes(R, n, n_nodes, h_ctr.max_depth, tbits_buf, stream, temps))) return rc;
-    lap("order");
+    const char* const finish_env = getenv("BMO_FINISH");  // (read per solve: the tests switch it between solves)
+    const bool legacy = finish_env && !strcmp(finish_env, "legacy");
+    DBG("finish pass: %s", legacy ? "legacy (a flag per detector and node)" : "counts per tile");
     const int nd = R->n_detectors;
     R->det_count.assign(nd, 0);
     R->det_offset.assign(nd, 0);
     const bool with_hits = nd > 0 && n_nodes > 0;
-    if (with_hits && (rc = gather_detector_hits(R, K.nsub, n, n_nodes, d_ctr, h_off, stream, temps))) return rc;
-    HIP_TRY(hipMemcpyAsync(&h_ctr, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(ev_t1, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    HIP_TRY(hipGetLastError());
-    lap("hits");
-    if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
-    {
+    if (!legacy) {
+        if ((rc = order_nodes(R, n, n_nodes, h_ctr.max_depth, tbits_buf, stream, temps))) return rc;
+        lap("order");
+        // segments = sum of the beams' segment counts (chunk counts include the holes of fused levels)
+        if (n_nodes > 0 && (rc = count_and_gather_hits(R, K.nsub, n, n_nodes, d_tail, stream, temps))) return rc;
+        TailBlock& h_tail = *ctx.tail_back;
+        HIP_TRY(hipMemcpyAsync(&h_tail, d_tail, tail_bytes(nd), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(ev_t1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        lap("hits");
+        if (h_tail.ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
+        unsigned long long tot = 0, seg = 0;
+        for (int q = 0; q < 64; ++q) tot += h_tail.shards[(size_t)q * 16], seg += h_tail.shards[(size_t)q * 16 + 1];
+        R->calls = tot;
+        R->n_records = (int64_t)seg;
+        for (int d = 0; d < nd && with_hits; ++d) {
+            R->det_offset[d] = h_tail.det_off[d];
+            R->det_count[d] = h_tail.det_off[d + 1] - h_tail.det_off[d];
+        }
+    } else {
+        // pinned read-back area: [0..1023] call-counter shards (64 x 16 words), [1024] segment count, [1025..] hit offsets
+        static_assert(sizeof(unsigned long long) == 8, "");
+        HostBuf h_tail;
+        if ((rc = h_tail.alloc((1024 + 1 + 1025) * 8))) return rc;
+        unsigned long long* const h_sh = static_cast<unsigned long long*>(h_tail.p);
+        long long* const h_sum = reinterpret_cast<long long*>(h_sh + 1024);
+        int32_t* const h_off = reinterpret_cast<int32_t*>(h_sh + 1025);
+        *h_sum = 0;
+        HIP_TRY(hipMemcpyAsync(h_sh, d_tail->shards, 64 * 128, hipMemcpyDeviceToHost, stream));
+        if (n_nodes > 0) {
+            DevBuf* d_sum = temps.take(8);
+            if (!d_sum) return BMO_ERR_OOM;
+            CUB_TRY(temps, hipcub::DeviceReduce::Sum(cub_tmp, cub_bytes, (const int32_t*)R->n_nseg.p, (long long*)d_sum->p, (int)n_nodes, stream));
+            HIP_TRY(hipMemcpyAsync(h_sum, d_sum->p, 8, hipMemcpyDeviceToHost, stream));
+        }
+        if ((rc = order_nodes(R, n, n_nodes, h_ctr.max_depth, tbits_buf, stream, temps))) return rc;
+        lap("order");
+        if (with_hits && (rc = gather_detector_hits_legacy(R, K.nsub, n, n_nodes, d_ctr, h_off, stream, temps))) return rc;
+        HIP_TRY(hipMemcpyAsync(&h_ctr, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(ev_t1, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipGetLastError());
+        lap("hits");
+        if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
         unsigned long long tot = 0;
         for (int q = 0; q < 64; ++q) tot += h_sh[(size_t)q * 16];
         R->calls = tot;
         R->n_records = (int64_t)*h_sum;
-    }
-    if (with_hits)
-        for (int d = 0; d < nd; ++d) {
+        for (int d = 0; d < nd && with_hits; ++d) {
             R->det_offset[d] = h_off[d];
             R->det_count[d] = h_off[d + 1] - h_off[d];
         }
+    }
     float tms = 0;
     HIP_TRY(hipEventElapsedTime(&tms, ev_t0, ev_t1));
     R->total_ms = tms;

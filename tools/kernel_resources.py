@@ -1,4 +1,5 @@
-"""Resource usage (VGPRs, SGPRs, scratch, LDS, occupancy, the compiler's SGPR / VGPR spill counts) of the step and read-out kernels:
+"""Resource usage (VGPRs, SGPRs, scratch, LDS, occupancy, the compiler's SGPR / VGPR spill counts) of the step and read-out kernels and of the
+ordering / finish-pass helpers (tree_*, hit_*):
     python tools/kernel_resources.py [extra hipcc flags]          (-DBMO_DEV_RAY_LDS_ONLY: the Ray kernels of the plain-shapes level only, ~2 min)
     python tools/kernel_resources.py --log <file>                 (reads the remarks of a build made with -Rpass-analysis=kernel-resource-usage)"""
 import os, re, subprocess, sys
@@ -25,7 +26,7 @@ for line in out.splitlines():
     if "error" in line:
         print(line)
 for k, v in rows.items():
-    if "step_kernel" in k or "psf" in k or "spot" in k or "sum_reduce" in k:
+    if "step_kernel" in k or "psf" in k or "spot" in k or "sum_reduce" in k or "hit_" in k or "tree_" in k:
         name = subprocess.run(["c++filt", k], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
         print("%-58s VGPR %3d SGPR %3d scratch %4d LDS %5d occ %d  spilled SGPR %3d VGPR %3d" % (name[:58], v.get("VGPRs", -1), v.get("TotalSGPRs", -1), v.get("ScratchSize", -1),
                                                                                                    v.get("LDS", -1), v.get("Occupancy", -1), v.get("SGPRspill", -1), v.get("VGPRspill", -1)))
