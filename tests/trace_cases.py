@@ -231,6 +231,93 @@ def phone_l3(planted=None, crest=False):
     return c
 
 
+L1 = dict(front=(1.054e-3, 1.333024e-3, -0.14294, [0, 0.038162 * _K ** 3, 0.06317 * _K ** 5, -0.020792 * _K ** 7, 0.18432 * _K ** 9, -0.04827 * _K ** 11,
+                                                   0.094529 * _K ** 13]),
+          back=(2.027e-3, 1.216472e-3, 8.0226, [0, 0.0074974 * _K ** 3, 0.064686 * _K ** 5, 0.19354 * _K ** 7, -0.50703 * _K ** 9, -0.34529 * _K ** 11,
+                                                5.9938 * _K ** 13]),
+          ct=0.72e-3, n=1.580200)
+L2 = dict(front=(-3.116e-3, 1.4e-3, -49.984, [0, -0.31608 * _K ** 3, 0.34755 * _K ** 5, -0.17102 * _K ** 7, -0.41506 * _K ** 9, -1.342 * _K ** 11,
+                                              5.0594 * _K ** 13, -2.7483 * _K ** 15]),
+          back=(-4.835e-3, 1.9e-3, 1.6674, [0, -0.079727 * _K ** 3, 0.13899 * _K ** 5, -0.044057 * _K ** 7, -0.019369 * _K ** 9, 0.016993 * _K ** 11,
+                                            0.093716 * _K ** 13, -0.080329 * _K ** 15]),
+          ct=0.55e-3, n=1.804700)  # elements L1 and L2 of the same objective (runtests.jl:1581-1696), as L3 above
+PHONE_FLATS = ((4.2e-3, 0.15e-3, 1.516800, 0.19e-3), (4.9e-3, 0.5e-3, 1.469200, 0.18e-3))  # filter, cover: diameter, thickness, n, the gap in front
+PHONE_GAPS = (0.39e-3, 0.63e-3)  # L1 - L2, L2 - L3
+
+
+def _ring_lens(q, obj, planted=None):
+    (r1, d1, k1, a1), (r2, d2, k2, a2) = q["front"], q["back"]
+    return tr.ExactRingLens(tr.Surface(r1, k1, a1), tr.Surface(r2, k2, a2), q["ct"], lambda lam: q["n"], d1, d2, d1, d2, obj.position(), obj.orientation(), planted)
+
+
+def _asphere_lens(q):
+    E = bmo.EvenAsphericalSurface
+    return bmo.Lens(E(*q["front"]), E(*q["back"]), q["ct"], lambda lam: q["n"])
+
+
+def phone_l12(which, planted=None, apex=False):
+    """Elements L1 and L2 of the phone objective, each alone as phone-l3 is: tilted 2 degrees and decentred, a PSFDetector behind.
+    L1: a convex aspheric front over 1.333 mm and a concave aspheric back (R > 0) over 1.216 mm; the step is levelled BEHIND, by a ring
+    that reaches up to the back edge (Lenses.jl:247-266).  L2: a concave aspheric front (R < 0, closed along its vertex plane,
+    AsphericalLensSDF.jl:285-305) over 1.4 mm and a convex aspheric back (R < 0 behind: the leaf between the plane of its edge height and the
+    profile) over 1.9 mm; the ring in FRONT starts at the front's negative edge sag (Lenses.jl:232-246).  No profile of the two is inflected.
+    Rays: a 2.5 degree oblique disc over 0.98 of the front aperture, one on the axis, and nine onto the ring's plane face - from behind on L1."""
+    c = Case()
+    q = (L1, L2)[which - 1]
+    lens = _asphere_lens(q)
+    bmo.xrotate3d(lens, math.radians(2))
+    at = np.array([0.05 * mm, 5 * mm, -0.03 * mm])
+    bmo.translate3d(lens, at)
+    det = bmo.PSFDetector(12 * mm)
+    bmo.translate3d(det, [0, 9 * mm, 0])
+    c.system, c.lens, c.det = bmo.System([lens, det]), lens, det
+    c.exact = [_ring_lens(q, lens, planted), tr.ExactFlat(12 * mm, det.position(), det.orientation(), "psf")]
+    ob = math.radians(2.5)
+    d1, d2 = q["front"][1], q["back"][1]
+    onto = ring(at + [0, q["ct"], 0], [0, -1, 0], (d1 + d2) / 4, 9, back=3 * mm, phase=0.2) if which == 1 else ring(at, [0, 1, 0], (d1 + d2) / 4, 9, back=3 * mm, phase=0.2)
+    # L2's concave aspheric apex is a seam (the leaf under it is thinner than the central-difference stencil out to 11 um): its 'axis' ray
+    # runs 50 um beside the apex; apex=True: eight rays along the lens's own axis ON the apex and 3, 6 and 9 um beside it
+    P, D = zip(disc(at, [0.0, math.cos(ob), math.sin(ob)], 0.98 * d1, 38, back=3 * mm), onto,
+               ring(at + ([0, 0, 0] if which == 1 else [50e-6, 0, 0]), [0, 1, 0], 0.0, 1, back=3 * mm))
+    if apex:
+        axis = np.asarray(lens.orientation())[:, 1]
+        P, D = zip(ring(at, axis, 0.0, 2, back=3 * mm), ring(at, axis, 3e-6, 2, back=3 * mm), ring(at, axis, 6e-6, 2, back=3 * mm), ring(at, axis, 9e-6, 2, back=3 * mm))
+    c.bundle = bundle("ray", P, D)
+    c.name = "phone-l%d" % which
+    return c
+
+
+def phone(planted=None, kat=False):
+    """The phone objective of the reference's test (runtests.jl:1581-1696; tests/test_asphere_system.py): L1, L2, L3, filter and cover glass at
+    their poses there, and a PSFDetector 0.12 mm behind the cover: ten refractions per ray.  The first three rays are the test's own, parallel
+    to the axis at z = -0.65 mm and 0.65 mm and - the apex of L2's concave aspheric front being a seam - 50 um beside it instead of on it
+    (kat=True: the test's three rays themselves); then a collimated disc over 0.9 of L1's aperture and two fields of 3 and 6 degrees."""
+    c = Case()
+    lenses = [_asphere_lens(q) for q in (L1, L2, L3)]
+    for (d, t, n, _) in PHONE_FLATS:
+        lenses.append(bmo.Lens(bmo.CircularFlatSurface(d), t, (lambda v: (lambda lam: v))(n)))
+    gaps = PHONE_GAPS + tuple(f[3] for f in PHONE_FLATS)
+    for prev, cur, gap in zip(lenses, lenses[1:], gaps):
+        bmo.translate_to3d(cur, prev.position())
+        bmo.translate3d(cur, [0, prev.thickness + gap, 0])
+    det = bmo.PSFDetector(6 * mm)
+    bmo.translate_to3d(det, lenses[-1].position())
+    bmo.translate3d(det, [0, lenses[-1].thickness + 0.12e-3, 0])
+    c.system, c.lens, c.det = bmo.System(lenses + [det]), lenses[0], det
+    c.exact = [_ring_lens(q, o, planted) for q, o in zip((L1, L2, L3), lenses)]
+    c.exact += [tr.ExactLens(tr.Surface(math.inf), tr.Surface(math.inf), t, d, (lambda v: (lambda lam: v))(n), o.position(), o.orientation())
+                for (d, t, n, _), o in zip(PHONE_FLATS, lenses[3:])]
+    c.exact.append(tr.ExactFlat(6 * mm, det.position(), det.orientation(), "psf"))
+    kat = (np.array([[0, -0.5e-3, z] for z in (-1.3e-3 / 2, 0.0 if kat else 50e-6, 1.3e-3 / 2)]), np.tile([0.0, 1.0, 0.0], (3, 1)))
+    at = np.zeros(3)
+    f3, f6 = math.radians(3), math.radians(6)
+    P, D = zip(kat, disc(at, [0, 1, 0], 0.9 * L1["front"][1], 25, back=0.5 * mm), disc(at, [0.0, math.cos(f3), math.sin(f3)], 0.7 * L1["front"][1], 10, back=0.5 * mm),
+               disc(at, [math.sin(f6), math.cos(f6), 0.0], 0.6 * L1["front"][1], 10, back=0.5 * mm))
+    c.bundle = bundle("ray", P, D, lam=0.5876e-6)
+    c.name = "phone"
+    return c
+
+
 # ------------------------------------------------------------------------------------------------ scene 5: cylinder and acylinder lenses
 AYL = dict(R=15.538 * mm, D=25 * mm, H=50 * mm, K=-1.0, CT=7.5 * mm, N=1.777,
            A=[0, 1.1926075e-5 * (1e3) ** 3, -2.9323497e-9 * (1e3) ** 5, -1.8718889e-11 * (1e3) ** 7, -1.7009961e-14 * (1e3) ** 9,
@@ -737,7 +824,308 @@ def polarizers(planted=None, roll=30.0, tilt=10.0, states=("x", "z", "45", "elli
     return c
 
 
+# ------------------------------------------------------------------------------------------------ scene 12: mirrors made of SDFs and of a cuboid mesh
+def _wall(kind, width, at, rot=None):
+    """A detector `width` wide at `at`, turned by rot = (axis, degrees) before it is moved there -> (object, its exact flat)."""
+    det, dk = _detector(kind, width)
+    if rot is not None:
+        {"x": bmo.xrotate3d, "z": bmo.zrotate3d}[rot[0]](det, math.radians(rot[1]))
+    bmo.translate3d(det, at)
+    return det, tr.ExactFlat(width, det.position(), det.orientation(), dk)
+
+
+def _local_rays(obj, hits, dirs, back=30 * mm):
+    """Rays given in an object's own frame: through the local points `hits` along the local directions `dirs`, started `back` before them."""
+    o, p0 = np.asarray(obj.orientation()), np.asarray(obj.position())
+    D = np.array([o @ (np.asarray(d, dtype=np.float64) / np.linalg.norm(d)) for d in dirs])
+    return np.array([p0 + o @ np.asarray(h, dtype=np.float64) for h in hits]) - back * D, D
+
+
+CM = dict(R=100 * mm, l=6 * mm, d=25.4 * mm)
+
+
+def concave_mirror(kind="ray", planted=None, tilt=4.0, decentre=(0.8 * mm, -0.5 * mm)):
+    """ConcaveSphericalMirror(100 mm, 6 mm, 25.4 mm) (Mirrors.jl:195-200: a concave leaf in front of a plano cylinder, the only curved sdf
+    that reflects from outside), tilted 4 degrees about x and decentred; the dish opens towards -y.  Rays: a collimated disc along +y over 0.95
+    of the aperture, two rays on the mirror's own axis, rays parallel to it 5 um and 24 um beside the apex (the wedge of DESIGN.md section 2,
+    rule ii), one ray onto the barrel and one onto the flat back (leaf and cylinder have one diameter: there is no flat annulus in front).  The
+    reflected bundle converges onto a detector BEHIND the rays' starting points; a second detector behind the mirror takes the ray its back
+    reflects.  tilt, decentre: the untilted mirror of the known-answer test."""
+    c = Case()
+    q = CM
+    m = bmo.ConcaveSphericalMirror(q["R"], q["l"], q["d"])
+    bmo.xrotate3d(m, math.radians(tilt))
+    p0 = np.array([decentre[0], 60 * mm, decentre[1]])
+    bmo.translate3d(m, p0)
+    front, xf = _wall(kind, 120 * mm, [0, 20 * mm, 0])
+    rear, xr = _wall(kind, 120 * mm, [0, 100 * mm, 0])
+    c.system, c.lens = bmo.System([m, front, rear]), m
+    # the sphere's centre lies R in FRONT of the vertex (ps = p + (0, R, 0), SphericalLensSDF.jl:167): a front surface of signed radius -R
+    c.exact = [tr.ExactLens(tr.Surface(q["R"] if planted == "mirror_centre_wrong_side" else -q["R"]), tr.Surface(math.inf), q["l"], q["d"], None,
+                            m.position(), m.orientation(), kind="mirror"), xf, xr]
+    axis = np.asarray(m.orientation())[:, 1]
+    P, D = zip(disc(p0, [0, 1, 0], 0.95 * q["d"], 36), ring(p0, axis, 0.0, 2), ring(p0, axis, 5e-6, 4), ring(p0, axis, 24e-6, 4, phase=0.5),
+               _local_rays(m, [[q["d"] / 2, 3 * mm, 1 * mm], [3 * mm, q["l"], -2 * mm]], [[-0.3, -1.0, 0.0], [0.02, -1.0, 0.05]], back=25 * mm))
+    c.bundle = bundle(kind, P, D)
+    c.name = "concave-mirror-" + kind
+    return c
+
+
+RM = dict(d=25.4 * mm, l=5 * mm)
+
+
+def round_mirror(kind="ray", planted=None):
+    """Two RoundPlanoMirror(25.4 mm, 5 mm) (Mirrors.jl:161-164: a bare PlanoSurfaceSDF, whose flat faces take central-difference normals),
+    70 mm apart, turned about x until the bundle along +y meets their front faces at 45 and at 80 degrees, rolled 1.5 degrees.  At 80
+    degrees the front face is 4.4 mm high as the bundle sees it and the barrel 4.9 mm: eight rays meet the barrel FIRST.  A detector down each
+    front-reflected beam, and one behind the rays' starting points for what the barrel sends back."""
+    c = Case()
+    q = RM
+    objs, exact, P, D = [], [], [], []
+    for ang, x0 in ((45.0, 0.0), (80.0, 70 * mm)):
+        m = bmo.RoundPlanoMirror(q["d"], q["l"])
+        th = math.radians(ang)
+        bmo.xrotate3d(m, th)
+        bmo.zrotate3d(m, math.radians(1.5))
+        p0 = np.array([x0 + 0.3 * mm, 40 * mm, -0.2 * mm])
+        bmo.translate3d(m, p0)
+        out = np.array([0.0, -math.cos(2 * th), -math.sin(2 * th)])
+        det, dk = _detector(kind, 60 * mm)
+        bmo.xrotate3d(det, math.atan2(out[2], out[1]))
+        bmo.translate3d(det, p0 + 50 * mm * out)
+        objs += [m, det]
+        exact += [tr.ExactLens(tr.Surface(math.inf), tr.Surface(math.inf), q["l"], q["d"], None, m.position(), m.orientation(), kind="mirror"),
+                  tr.ExactFlat(60 * mm, det.position(), det.orientation(), dk)]
+        if ang < 80:
+            fans = (disc(p0, [0.01, 1.0, 0.005], 14 * mm, 20), ring(p0, [0, 1, 0], 1 * mm, 4, slope=0.02))
+        else:
+            fans = (disc(p0, [0.0, 1.0, 0.0], 3.5 * mm, 14), ring(p0, [0, 1, 0], 0.0, 2), disc(p0 + [0, 0, 4.6 * mm], [0.0, 1.0, 0.0], 3 * mm, 8))
+        for p, d in fans:
+            P.append(p)
+            D.append(d)
+    wall, xw = _wall(kind, 300 * mm, [35 * mm, -40 * mm, 0])
+    c.system, c.exact = bmo.System(objs + [wall]), exact + [xw]
+    c.bundle = bundle(kind, P, D)
+    c.name = "round-mirror-" + kind
+    return c
+
+
+PM = dict(leg=10 * mm, h=10 * mm)
+
+
+def prism_mirror(planted=None):
+    """Two RightAnglePrismMirror(10 mm, 10 mm) (Mirrors.jl:226-230: a RightAnglePrismSDF turned by the double deg2rad(45 + 180) about z, so
+    that the hypotenuse faces -y and the two legs form a roof towards +y).  The first is tilted 2 degrees about x; rays along -y fold once on
+    its left leg (towards -x, onto a detector) and once on its right leg (towards +x).  A convex solid cannot be met twice, so the paths of
+    TWO bounces go on to the second prism, which is turned upside down 40 mm to the right and rolled 1 degree: its leg folds them down onto
+    the detector below.  A fan from below folds on the first prism's hypotenuse, and one ray meets each of its triangular end faces.  The
+    evaluator gets the pose WITHOUT the builder's rotation (the orientation of a twin that made the scene's moves alone) and applies the
+    double angle itself, in 50 digits (ExactPrism's pre)."""
+    c = Case()
+    q = PM
+    pre = math.radians(45 if planted == "prism_mirror_pre_45" else 45 + 180)
+    moves = ([(bmo.xrotate3d, math.radians(2))], [(bmo.zrotate3d, math.radians(180)), (bmo.zrotate3d, math.radians(1))])
+    at = ([0.2 * mm, 40 * mm, -0.1 * mm], [40 * mm, 40 * mm + q["leg"] / math.sqrt(2), 0.0])
+    objs, exact = [], []
+    for mv, p in zip(moves, at):
+        m, twin = bmo.RightAnglePrismMirror(q["leg"], q["h"]), bmo.RoundPlanoMirror(1 * mm, 1 * mm)
+        for f, a in mv:
+            f(m, a)
+            f(twin, a)
+        bmo.translate3d(m, p)
+        objs.append(m)
+        exact.append(tr.ExactPrism(q["leg"], q["h"], None, m.position(), twin.orientation(), pre=pre, kind="mirror"))
+    for w, p, rot in ((100 * mm, [-50 * mm, 43 * mm, 0], ("z", 90)), (300 * mm, [20 * mm, -20 * mm, 0], None)):
+        det, x = _wall("ray", w, p, rot)
+        objs.append(det)
+        exact.append(x)
+    c.system, c.exact, c.lens = bmo.System(objs), exact, objs[0]
+    p1 = np.asarray(at[0])
+    top = p1 + [0, 3.5 * mm, 0]
+    ends = [(p1 + [0.5 * mm, 3 * mm, s * q["h"] / 2], np.array([0.0, -0.5, -s])) for s in (1.0, -1.0)]
+    P, D = zip(disc(top + [-3.5 * mm, 0, 0], [0, -1, 0], 4 * mm, 16), disc(top + [3.5 * mm, 0, 0], [0, -1, 0], 4 * mm, 16),
+               disc(p1, [0.3, 1.0, 0.02], 6 * mm, 14),
+               (np.array([h - 30 * mm * d / np.linalg.norm(d) for h, d in ends]), np.array([d / np.linalg.norm(d) for _, d in ends])))
+    c.bundle = bundle("ray", P, D)
+    c.name = "prism-mirror-ray"
+    return c
+
+
+RECT = dict(w=30 * mm, h=20 * mm, l=5 * mm)
+
+
+def rect_mirror(planted=None):
+    """RectangularPlanoMirror(30 mm, 20 mm, 5 mm) (Mirrors.jl:110-119: CuboidMesh(width, thickness, height) moved by (-width / 2, 0,
+    -height / 2) and made its own origin), turned 45 degrees about x, rolled 1.5 degrees and decentred: four kinematic steps have re-rounded
+    its vertex table.  The exact mesh derives the twelve triangles from the three lengths, that translation and the pose.  Rays along +y onto
+    the front face, ten onto the side face z = +height / 2 beside it, four oblique ones onto the side face x = +width / 2; a detector in
+    each of the three reflected directions."""
+    c = Case()
+    q = RECT
+    m = bmo.RectangularPlanoMirror(q["w"], q["h"], q["l"])
+    bmo.xrotate3d(m, math.radians(45))
+    bmo.zrotate3d(m, math.radians(1.5))
+    p0 = np.array([0.3 * mm, 40 * mm, -0.2 * mm])
+    bmo.translate3d(m, p0)
+    walls = [_wall("ray", 120 * mm, p0 + [0, 0, -50 * mm], ("x", 90)), _wall("ray", 120 * mm, p0 + [0, 0, 50 * mm], ("x", 90)),
+             _wall("ray", 300 * mm, [20 * mm, 100 * mm, 0])]
+    c.system, c.lens = bmo.System([m] + [w[0] for w in walls]), m
+    c.exact = [tr.ExactMesh.cuboid(q["w"], q["l"], q["h"], math.pi / 2, [-q["w"] / 2, 0, -q["h"] / 2], m.position(), m.orientation(), None,
+                                   kind="mirror", steps=4)] + [w[1] for w in walls]
+    side = _local_rays(m, [[q["w"] / 2, 1.5 * mm + 0.6 * mm * k, (-3 + 2 * k) * mm] for k in range(4)], [np.asarray(m.orientation()).T @ np.array([-0.5, 1.0, 0.0])] * 4)
+    P, D = zip(disc(p0, [0.01, 1.0, 0.005], 12 * mm, 30), ring(p0, [0, 1, 0], 1 * mm, 4, slope=0.02), disc(p0 + [0, 0, 8.8 * mm], [0, 1, 0], 2 * mm, 10), side)
+    c.bundle = bundle("ray", P, D)
+    c.name = "rect-mirror-ray"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 13: plano and thin spherical lenses
+FUSED_SILICA = (0.6961663, 0.4079426, 0.8974794, 0.0684043 ** 2, 0.1162414 ** 2, 9.896161 ** 2)  # the coefficients of tests/test_oracle_kat.py
+PCX = dict(r=38.6 * mm, ct=4.1 * mm, d=25.4 * mm, lams=[486e-9, 588e-9, 1064e-9])
+
+
+def plano_convex(planted=None):
+    """One plano-convex prescription (r = 38.6 mm, 4.1 mm thick, 25.4 mm) built twice: Lens(SphericalSurface(r, d), ct, n), the
+    three-argument path (Lenses.jl:293-301), met curved side first, and Lens(PlanoConvexLensSDF(r, ct, d), n) (SphericalLensSDF.jl:338-347)
+    turned round and met plane side first, 20 mm behind it.  The glass is a SellmeierEquation with fused silica's coefficients under three
+    wavelengths: the host evaluates it in doubles, the exact lenses in 50 digits from the coefficient doubles (trace_ref.sellmeier)."""
+    c = Case()
+    q = PCX
+    n_host = bmo.SellmeierEquation(*FUSED_SILICA)
+    a = bmo.Lens(bmo.SphericalSurface(q["r"], q["d"]), q["ct"], n_host)
+    bmo.xrotate3d(a, math.radians(3))
+    bmo.translate3d(a, [0.4 * mm, 20 * mm, -0.2 * mm])
+    b = bmo.Lens(bmo.PlanoConvexLensSDF(q["r"], q["ct"], q["d"]), n_host)
+    bmo.xrotate3d(b, math.radians(180))
+    bmo.translate3d(b, [0, q["ct"], 0])
+    bmo.zrotate3d(b, math.radians(-2))
+    bmo.translate3d(b, [-0.3 * mm, 40 * mm, 0.3 * mm])
+    det = bmo.PSFDetector(90 * mm)
+    bmo.translate3d(det, [0, 100 * mm, 0])
+    c.system, c.lens = bmo.System([a, b, det]), a
+    n = tr.sellmeier(*FUSED_SILICA, planted=planted if planted == "sellmeier_metres" else None)
+    lens = lambda o: tr.ExactLens(tr.Surface(q["r"]), tr.Surface(math.inf), q["ct"], q["d"], n, o.position(), o.orientation())
+    c.exact = [lens(a), lens(b), tr.ExactFlat(90 * mm, det.position(), det.orientation(), "psf")]
+    ob = math.radians(2)
+    P, D = disc([0.4 * mm, 22 * mm, -0.2 * mm], [math.sin(ob), math.cos(ob), 0.0], 0.9 * q["d"], 48)
+    c.bundle = bundle("ray", [P], [D], lam=np.tile(q["lams"], 16))
+    c.name = "plano-convex"
+    return c
+
+
+PCV = dict(r=40 * mm, l=3 * mm, d=25.4 * mm, md=30 * mm, n=1.5)
+
+
+def plano_concave(kind="ray", planted=None, axial=False):
+    """Lens(PlanoConcaveLensSDF(40 mm, 3 mm, 25.4 mm, 30 mm), 1.5) (SphericalLensSDF.jl:349-381): a plano cylinder, a concave leaf behind it
+    and a mechanical ring as thick as the lens at its edge, _l = l + sag, centred on _l / 2 (the biconcave one's ring sits at l / 2, :315-325),
+    tilted 3 degrees.  Rays: a 2 degree oblique disc over 0.85 of the aperture, rings along the lens's own axis 1 mm beside it and at 14 mm - on
+    the ring's plane faces - and two skew rays that enter through the ring's barrel, cross the air pocket of the concave face and re-enter.
+    PolarizedRays take the two rings 0.004 off the axis' direction: ALONG it they meet the plane face along its normal and end there (axial=True:
+    the fans of test_normal_incidence_on_a_flat_face_ends_a_polarized_ray)."""
+    c = Case()
+    q = PCV
+    off = 0.0 if (kind == "ray" or axial) else 0.004
+    lens = bmo.Lens(bmo.PlanoConcaveLensSDF(q["r"], q["l"], q["d"], q["md"]), lambda lam: q["n"])
+    bmo.xrotate3d(lens, math.radians(3))
+    bmo.translate3d(lens, [0.4 * mm, 20 * mm, 0])
+    det = bmo.PSFDetector(90 * mm) if kind == "ray" else bmo.Spotdetector(90 * mm)
+    bmo.translate3d(det, [0, 80 * mm, 0])
+    c.system, c.lens = bmo.System([lens, det]), lens
+    c.exact = [tr.ExactRingLens(tr.Surface(math.inf), tr.Surface(q["r"]), q["l"], lambda lam: q["n"], q["d"], q["d"], q["md"], q["md"], lens.position(),
+                                lens.orientation(), planted),
+               tr.ExactFlat(90 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    p0, axis = np.asarray(lens.position()), np.asarray(lens.orientation())[:, 1]
+    P, D = zip(disc(p0 + 1.5 * mm * axis, [math.sin(math.radians(2)), math.cos(math.radians(2)), 0.0], 0.85 * q["d"], 34),
+               ring(p0, axis, 1 * mm, 4, phase=0.9, slope=off), ring(p0, axis, 14 * mm, 8, phase=0.3, slope=off),
+               _local_rays(lens, [[-q["md"] / 2, 4.0 * mm, 1 * mm], [-q["md"] / 2, 4.5 * mm, 1 * mm]], [[1.0, 0.01, 0.03], [1.0, -0.005, -0.02]], back=5 * mm))
+    c.bundle = bundle(kind, P, D)
+    c.name = "plano-concave-" + kind
+    return c
+
+
+TL = dict(R1=80 * mm, R2=120 * mm, d=25.4 * mm, n=1.5)
+
+
+def thin_lens(planted=None):
+    """SphericalLens(80 mm, 120 mm, 0, 25.4 mm, 1.5): a centre thickness of zero dispatches to ThinLens / ThinLensSDF (SphericalLenses.jl:20-45;
+    both radii positive there, the back surface's signed radius is -120 mm): two caps, no barrel, a sharp rim.  Tilted 5 / -3 degrees and
+    decentred.  Rays: a 2 degree oblique disc over 0.9 of the aperture and rings along the lens's own axis at 0.5 and at 0.98 of it (the
+    lens is 66 um thick there)."""
+    c = Case()
+    q = TL
+    lens = bmo.SphericalLens(q["R1"], q["R2"], 0, q["d"], q["n"])
+    bmo.xrotate3d(lens, math.radians(5))
+    bmo.zrotate3d(lens, math.radians(-3))
+    bmo.translate3d(lens, [0.5 * mm, 20 * mm, -0.4 * mm])
+    det = bmo.PSFDetector(90 * mm)
+    bmo.translate3d(det, [0, 80 * mm, 0])
+    c.system, c.lens = bmo.System([lens, det]), lens
+    c.exact = [tr.ExactThinLens(q["R1"], q["R2"], q["d"], lambda lam: q["n"], lens.position(), lens.orientation(), planted),
+               tr.ExactFlat(90 * mm, det.position(), det.orientation(), "psf")]
+    p0, axis = np.asarray(lens.position()), np.asarray(lens.orientation())[:, 1]
+    ob = math.radians(2)
+    P, D = zip(disc(p0 + 0.8 * mm * axis, [math.sin(ob), math.cos(ob), 0.0], 0.9 * q["d"], 36), ring(p0, axis, 0.5 * q["d"] / 2, 4),
+               ring(p0, axis, 0.98 * q["d"] / 2, 8, phase=0.37))
+    c.bundle = bundle("ray", P, D)
+    c.name = "thin-lens"
+    return c
+
+
+# ------------------------------------------------------------------------------------------------ scene 14: stand-alone primitive bodies
+PRIM = dict(cyl=(5 * mm, 3 * mm), cut=(10 * mm, 4 * mm), ball=6 * mm, n=(1.52, 1.5, 1.6))
+
+
+def primitives(kind="ray", planted=None):
+    """Three bodies as Lens(shape, n), in a row along +y: CylinderSDF(5 mm, 3 mm) - the second number is the HALF height (PrimitiveSDF.jl:71-76)
+    - tilted 20 / 5 degrees so that the bundle meets an end cap and, beside it, the barrel; CutSphereSDF(10 mm, 4 mm), the part of the ball above
+    the plane y = 4 mm (:112-124), tilted -4 degrees, entered through the cut and left through the cap; SphereSDF(6 mm), whose orientation is
+    fixed (SphericalLensSDF.jl:82-84), decentred.  A detector close behind the ball takes what it focuses.  Four rays run along the cylinder's
+    own axis; PolarizedRays 0.004 off it (see plano_concave)."""
+    c = Case()
+    q = PRIM
+    cyl = bmo.Lens(bmo.CylinderSDF(*q["cyl"]), lambda lam: q["n"][0])
+    bmo.xrotate3d(cyl, math.radians(20))
+    bmo.zrotate3d(cyl, math.radians(5))
+    pc = np.array([0.2 * mm, 20 * mm, -0.1 * mm])
+    bmo.translate3d(cyl, pc)
+    cut = bmo.Lens(bmo.CutSphereSDF(*q["cut"]), lambda lam: q["n"][1])
+    bmo.xrotate3d(cut, math.radians(-4))
+    bmo.translate3d(cut, [-0.1 * mm, 36 * mm, 0.3 * mm])
+    ball = bmo.Lens(bmo.SphereSDF(q["ball"]), lambda lam: q["n"][2])
+    bmo.translate3d(ball, [0.15 * mm, 58 * mm, -0.1 * mm])
+    det = bmo.PSFDetector(300 * mm) if kind == "ray" else bmo.Spotdetector(300 * mm)
+    bmo.translate3d(det, [0, 72 * mm, 0])
+    c.system, c.lens = bmo.System([cyl, cut, ball, det]), cyl
+    mist = lambda *names: planted if planted in names else None
+    c.exact = [tr.ExactCylinder(q["cyl"][0], q["cyl"][1], lambda lam: q["n"][0], cyl.position(), cyl.orientation(), mist("cylinder_axis_x")),
+               tr.ExactCutSphere(q["cut"][0], q["cut"][1], lambda lam: q["n"][1], cut.position(), cut.orientation(), mist("cut_height_negated")),
+               tr.ExactBall(q["ball"], lambda lam: q["n"][2], ball.position(), ball.orientation()),
+               tr.ExactFlat(300 * mm, det.position(), det.orientation(), "psf" if kind == "ray" else "spot")]
+    axis = np.asarray(cyl.orientation())[:, 1]
+    P, D = zip(disc(pc + [0, 0, -1 * mm], [0.01, 1.0, 0.005], 7 * mm, 28, back=15 * mm), disc(pc + [0, 0, 4.7 * mm], [0, 1, 0], 1.6 * mm, 8, back=15 * mm),
+               ring(pc, axis, 2 * mm, 4, back=15 * mm, slope=0.0 if kind == "ray" else 0.004), ring(pc + [0, 0, -1 * mm], [0, 1, 0], 3 * mm, 8, back=15 * mm, phase=0.4, slope=0.03))
+    c.bundle = bundle(kind, P, D)
+    c.name = "primitives-" + kind
+    return c
+
+
 SCENES = {
+    "concave-mirror-ray": lambda **kw: concave_mirror("ray", **kw),
+    "concave-mirror-pol": lambda **kw: concave_mirror("pol", **kw),
+    "round-mirror-ray": lambda **kw: round_mirror("ray", **kw),
+    "round-mirror-pol": lambda **kw: round_mirror("pol", **kw),
+    "prism-mirror-ray": prism_mirror,
+    "rect-mirror-ray": rect_mirror,
+    "plano-convex": plano_convex,
+    "plano-concave-ray": lambda **kw: plano_concave("ray", **kw),
+    "plano-concave-pol": lambda **kw: plano_concave("pol", **kw),
+    "thin-lens": thin_lens,
+    "primitives-ray": lambda **kw: primitives("ray", **kw),
+    "primitives-pol": lambda **kw: primitives("pol", **kw),
+    "phone-l1": lambda **kw: phone_l12(1, **kw),
+    "phone-l2": lambda **kw: phone_l12(2, **kw),
+    "phone": phone,
     "plate-ray": lambda **kw: plate("ray", **kw),
     "plate-pol": lambda **kw: plate("pol", **kw),
     "roundplate-ray": lambda **kw: plate("ray", round_=True, **kw),
@@ -777,7 +1165,9 @@ SCENES = {
     "asphere-plane-first": lambda **kw: asphere(True, **kw),
 }
 NO_EXCLUSIONS = ("phone-l3", "cylinders", "acylinders", "doublet", "doublet-gauss", "asphere-curved-first", "asphere-plane-first",  # the issue's scenes 3 - 5 allow none
-                 "plate-ray", "plate-pol", "plate-gauss", "roundplate-ray", "cube-ray", "cube-pol", "cube-gauss", "splitter-gauss", "polarizers")
+                 "plate-ray", "plate-pol", "plate-gauss", "roundplate-ray", "cube-ray", "cube-pol", "cube-gauss", "splitter-gauss", "polarizers",
+                 "concave-mirror-ray", "concave-mirror-pol", "round-mirror-ray", "round-mirror-pol", "prism-mirror-ray", "rect-mirror-ray", "plano-convex",
+                 "phone-l1", "phone-l2", "phone")
 # Each planted mistake, and the scenes that exercise it.
 PLANTED_ON = [
     ("conic_sign", "phone-l3"),
@@ -816,6 +1206,14 @@ PLANTED_ON = [
     ("polarizer_not_projected", "polarizers"),
     ("coating_loses_tie", "plate-ray"),
     ("coating_loses_tie", "plate-pol"),
+    ("mirror_centre_wrong_side", "concave-mirror-ray"),
+    ("prism_mirror_pre_45", "prism-mirror-ray"),
+    ("ring_centred_half_l", "plano-concave-ray"),
+    ("thin_back_not_shifted", "thin-lens"),
+    ("cut_height_negated", "primitives-ray"),
+    ("cylinder_axis_x", "primitives-ray"),
+    ("sellmeier_metres", "plano-convex"),
+    ("aspheric_edge_sag_unsigned", "phone-l2"),
 ]
 
 
@@ -832,6 +1230,7 @@ class Held:
         self.bounces = self.excluded = self.tir = self.barrel = self.leaving = self.children = self.ortho = self.blocked = self.ties = 0
         self.facing = {True: 0, False: 0}  # coatings met with dot(dir, normal) < 0 / > 0
         self.phase = {True: 0, False: 0}   # beamlets reflected with phi = pi / phi = 0
+        self.pieces = {}                   # held bounces per (object, piece of its exact boundary, 'in' / 'out'); a mesh's piece is 'face<k>'
         self.over = []
 
     def note(self, q, diff, bound, where):
@@ -893,6 +1292,9 @@ def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
                     continue
                 h.leaving += bool(ex["hit"]["leaving"])
                 h.barrel += ex["hit"]["piece"] == "barrel"
+                if sub == 0:
+                    key = (seg["obj"], "face%d" % ex["hit"]["face"] if "face" in ex["hit"] else ex["hit"]["piece"], "out" if ex["hit"]["leaving"] else "in")
+                    h.pieces[key] = h.pieces.get(key, 0) + 1
                 # where the reference's PolarizedRay constructor throws (PolarizedRays.jl:54-56) or a filter blocks, the record ends there with that status
                 status, last = int(res.node_status[node]), k == len(segs) - 1
                 assert (ex["end"] == "err_ortho") == bool(last and status & 256), (where, ex["end"], status)
@@ -930,7 +1332,7 @@ def hold(res, case, consts, nodes=None, wrong=None, planted=None, cache=None):
                     s2 = segs[k + 1]
                     h.note("pos", tr.fdiff(s2["pos"], nx["pos"]), b["pos"], where)
                     h.note("dir", tr.fdiff(s2["dir"], nx["dir"]), b["dir"], where)
-                    h.note("index", tr.fdiff(s2["n"], nx["n"]), 0.0, where)
+                    h.note("index", tr.fdiff(s2["n"], nx["n"]), b.get("index", 0.0), where)
                     if nx["E0"] is not None:
                         h.note("E0", tr.fdiff(s2["E0"], nx["E0"]), b["E0"], where)
                 if cmp_["children"] is not None:  # the first rays of the two beams a splitter spawns, transmitted first (Beamsplitters.jl:16-19)
