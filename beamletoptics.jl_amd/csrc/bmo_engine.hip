@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <cmath>
 #include <chrono>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -47,20 +48,42 @@ using namespace bmo;
 namespace {
 
 thread_local std::string g_err;
-// The switches read ONCE per process.  (Read at every launch: BMO_WIDE_MIN_WAVES; at every solve: BMO_FUSE / BMO_FUSE_GAUSS,
-// BMO_FORCE_SORT_ORDER, BMO_FORCE_DEEP_ORDER, BMO_GAPS, BMO_TIMELINE; at every upload: BMO_ROOT_ORDER — tests change those.)
-struct Knobs {
+// The switches of the engine, all read from the environment by read_switches below and nowhere else (DESIGN.md §3 "Switches" is the
+// table of them: when each is read, its default, what it selects, who sets it).  Three groups by WHEN the value counts:
+struct Knobs {  // once per process (knobs())
     bool debug;          // BMO_DEBUG: phase and step log on stderr
     bool keep_kids;      // BMO_KEEP_KIDS=0: no kept reflected children (StepParams::pend / ::gkeep)
     int64_t thin_waves;  // BMO_THIN_WAVES=<n>: a launch of fewer than n waves spreads its records over more waves (plan_launch)
     bool lpt;            // BMO_LPT=0: no tile-order feedback (tile_order_feedback)
     int reverse;         // BMO_REVERSE=<0|1|2>: StepParams::reverse (-1: the default)
 };
-const Knobs& knobs() {
-    static const Knobs k = [] {
-        auto num = [](const char* name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
-        return Knobs{getenv("BMO_DEBUG") != nullptr, num("BMO_KEEP_KIDS", 1) != 0, num("BMO_THIN_WAVES", 0), num("BMO_LPT", 1) != 0, (int)num("BMO_REVERSE", -1)};
-    }();
+struct SolveSwitches {  // at the start of every solve (run_trace): the tests change these between solves
+    int fuse, fuse_gauss;     // BMO_FUSE / BMO_FUSE_GAUSS=<n>: at most n bounce levels per launch (unset: INT_MAX, what the kernels take)
+    int64_t wide_min_waves;   // BMO_WIDE_MIN_WAVES=<n>: the 4-waves-per-SIMD build from n waves per launch (launch_step)
+    bool force_sort_order;    // BMO_FORCE_SORT_ORDER: test hook, no tree is ordered by heap index (order_nodes)
+    bool force_deep_order;    // BMO_FORCE_DEEP_ORDER: test hook, every tree is ordered level by level (order_nodes)
+    bool gaps;                // BMO_GAPS: device idle time between two launches on stderr
+    bool timeline;            // BMO_TIMELINE: wave timeline of every launch (developer builds with BMO_DEV_TIMELINE)
+};
+struct Switches {
+    Knobs process;
+    SolveSwitches solve;
+    const char* root_order;  // at every upload: BMO_ROOT_ORDER = chord | mask | none (nullptr: unset, auto; root_order_wanted)
+};
+Switches read_switches() {
+    auto set = [](const char* name) { return getenv(name) != nullptr; };
+    auto num = [](const char* name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
+    auto small = [](const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
+    static const Knobs process{set("BMO_DEBUG"), num("BMO_KEEP_KIDS", 1) != 0, num("BMO_THIN_WAVES", 0), num("BMO_LPT", 1) != 0, (int)num("BMO_REVERSE", -1)};
+    Switches s;
+    s.process = process;  // (the first call's values: a solve does not pay for them again)
+    s.solve = SolveSwitches{small("BMO_FUSE", INT_MAX), small("BMO_FUSE_GAUSS", INT_MAX), num("BMO_WIDE_MIN_WAVES", 4096), set("BMO_FORCE_SORT_ORDER"),
+                            set("BMO_FORCE_DEEP_ORDER"), set("BMO_GAPS"), set("BMO_TIMELINE")};
+    s.root_order = getenv("BMO_ROOT_ORDER");
+    return s;
+}
+const Knobs& knobs() {  // (asked at every launch and DBG line: it keeps the group, read_switches would read the per-solve names again)
+    static const Knobs k = read_switches().process;
     return k;
 }
 bool dbg_on() { return knobs().debug; }

@@ -36,9 +36,13 @@ struct BlobHeader {
     uint32_t off_objects, off_shapes, off_children, off_tris, off_ntable, total;
     uint32_t has_splitter, off_coefs;
     uint32_t has_asphere, off_cands;
-    int32_t n_cands, has_meniscus, pad[2];  // pad[0]: has_bvh (some mesh has a BVH: the kernels of level 3)
+    int32_t n_cands, has_meniscus, pad[2];  // pad[0] is has_bvh() below, the one spelling in use; the member keeps the name and type
+                                            // that every earlier revision of tests/emu/scene_check.cpp compiles against
     uint32_t off_bvh_nodes, off_bvh_faces;  // mesh BVHs (bmo_lane.hpp BvhNode; face ids, int32)
+    BMO_BLOB_HD int32_t has_bvh() const { return pad[0]; }  // 1: some mesh has a BVH (the kernels of level 3)
+    BMO_BLOB_HD int32_t& has_bvh() { return pad[0]; }
 };
+static_assert(sizeof(BlobHeader) == 144, "BlobHeader travels in the step kernels' arguments (StepParams::hdr): its layout is part of their builds");
 
 // `h`: the blob's header; the kernels read it from their arguments (scalar loads the compiler may repeat instead of holding the
 // values in registers — read from the LDS copy they would sit in vector registers for the whole kernel)
@@ -62,7 +66,7 @@ BMO_BLOB_HD SceneView view_of(CharPtr blob, const BlobHeader* h) {
     S.mt_leps = h->mt_leps;
     S.grad_h = h->grad_h;
     S.march_iters = h->march_iters;
-    if (h->pad[0]) {
+    if (h->has_bvh()) {
         S.bvh_nodes = (const BMO_KONST BvhNode*)(blob + h->off_bvh_nodes);
         S.bvh_faces = (CInt*)(blob + h->off_bvh_faces);
     }
@@ -432,7 +436,7 @@ inline int build_scene_image(const bmo_scene_desc* d, SceneImage& img, std::stri
     // the list with empty BVH tables is a lower bound: a description that is too large is refused here, before any triangle is read
     if (!lay_out_blob(blob_regions(d, img.hdr, B), img.hdr)) return refuse(err, BMO_ERR_INVALID, too_big);
     if (int rc = build_bvhs(d, B, img.bvh, err)) return rc;
-    img.hdr.pad[0] = B.nodes.empty() ? 0 : 1;  // has_bvh
+    img.hdr.has_bvh() = B.nodes.empty() ? 0 : 1;
     const std::vector<BlobRegion> regions = blob_regions(d, img.hdr, B);  // (its sources live as long as `d` and `B`: this function)
     if (!lay_out_blob(regions, img.hdr)) return refuse(err, BMO_ERR_INVALID, too_big);
     fill_blob(img, d, regions);
@@ -510,7 +514,7 @@ inline int merge_sweep_images(const bmo_scene_desc* descs, int32_t n_configs, Sc
     for (size_t r = 0; r < regions.size(); ++r) regions[r] = BlobRegion{regions[r].off, cfg[0].region_bytes[r], nullptr};
     for (int32_t c = 0; c < n_configs; ++c) {
         const BlobHeader& h = cfg[(size_t)c].hdr;
-        if (h.n_cands != h0.n_cands || h.pad[0] != h0.pad[0] || h.off_bvh_nodes != h0.off_bvh_nodes || h.has_splitter != h0.has_splitter) {
+        if (h.n_cands != h0.n_cands || h.has_bvh() != h0.has_bvh() || h.off_bvh_nodes != h0.off_bvh_nodes || h.has_splitter != h0.has_splitter) {
             err = "bmo_scene_create_sweep: configuration " + std::to_string(c) + " differs from configuration 0 in its candidate table or BVHs";
             return BMO_ERR_INVALID;
         }

@@ -6,9 +6,9 @@
 //   NodeTable             the node arrays of a solution: allocation, growth, the kernels' view of them
 //   ChunkArena            the segment log's storage: chunks bumped out of large blocks, rewound behind a launch
 //   select_step_kernels   the step kernels of a beam kind / scene level / fresh, retrace or sweep solve
-//   plan_launch, fill_step_params, tile_order_feedback, build_sweep_lane_map, print_timeline, launch_step: one launch of the step loop
-//   order_nodes, count_and_gather_hits               the canonical node order, the segment count and the detector tables behind the last
-//                                                    launch (gather_detector_hits_legacy: the pass BMO_FINISH=legacy brings back)
+//   plan_launch, fill_step_params, tile_order_feedback, build_sweep_lane_map, print_timeline, launch_step: the parts of one launch
+//   order_nodes, count_and_gather_hits               the canonical node order, the segment count and the detector tables behind the last launch
+//   step_once, finish_solve                          one turn of the step loop; everything behind the loop, behind ONE synchronisation
 
 // ---- the retrace tables of a finished solution (OldSolution), built when it is first retraced
 __global__ void old_obj_scatter_kernel(Chunk c, int32_t chunk_index, const int32_t* __restrict__ rec_start, int32_t* __restrict__ rec_obj,
@@ -627,7 +627,7 @@ int print_timeline(const unsigned long long* tl, size_t nw, int steps) {
 
 // Queues the launch between its two timing events (one pair per step out of the context's pool, read after the loop: nothing but the counter
 // read-back sits between two launches), reads the counters back and waits.
-int launch_step(DevCtx& ctx, const StepKernels& kern, const LaunchPlan& plan, const StepParams& P, int step, Counters* d_ctr) {
+int launch_step(DevCtx& ctx, const StepKernels& kern, const LaunchPlan& plan, const StepParams& P, int step, Counters* d_ctr, int64_t wide_min_waves) {
     hipStream_t stream = ctx.stream;
     while ((int)ctx.step_ev.size() < 2 * (step + 1)) {
         hipEvent_t e;
@@ -637,8 +637,6 @@ int launch_step(DevCtx& ctx, const StepKernels& kern, const LaunchPlan& plan, co
     HIP_TRY(hipEventRecord(ctx.step_ev[2 * step], stream));
     // (the 4-waves-per-SIMD build for a launch that fills the device at that occupancy — 256 CUs x 16 waves —, the 3-waves one below: step_waves.
     //  Between 4 096 and ~10 000 waves the two scenes measured disagree — config 5 - 13 % / - 6 %, config 2 + 2 % / + 3 % — and the larger effect decides.)
-    const char* const wide_env = getenv("BMO_WIDE_MIN_WAVES");  // (read per launch: the tests switch it between solves)
-    const int64_t wide_min_waves = wide_env ? atoll(wide_env) : 4096;
     const bool wide = kern.plain_wide && plan.n_waves >= wide_min_waves;
     const StepKernel k = (plan.inwave_cap > 0 && kern.inw) ? (wide ? kern.inw_wide : kern.inw) : (wide ? kern.plain_wide : kern.plain);
     if (!k) return fail(BMO_ERR_INTERNAL, "no step kernel selected for this beam kind / scene level");
@@ -829,27 +827,27 @@ int order_level_by_level(bmo_trace_result* R, int64_t n_nodes, int64_t md, int b
     return BMO_OK;
 }
 
-// max_depth: Counters::max_depth as read back after the last launch.
-int order_nodes(bmo_trace_result* R, int64_t n, int64_t n_nodes, unsigned long long max_depth, const DevBuf& tbits, hipStream_t stream, Temps& temps) {
+// max_depth: Counters::max_depth as read back after the last launch.  force_sort / force_deep (test hooks, SolveSwitches): the radix-sort /
+// level-by-level path for any tree.  Says which path ran, once per solve.
+int order_nodes(bmo_trace_result* R, int64_t n, int64_t n_nodes, unsigned long long max_depth, const DevBuf& tbits, bool force_sort, bool force_deep,
+                hipStream_t stream, Temps& temps) {
     int rc;
     if ((rc = R->order.alloc((size_t)std::max<int64_t>(n_nodes, 1) * 4))) return rc;
-    // test hooks: BMO_FORCE_SORT_ORDER / BMO_FORCE_DEEP_ORDER take the radix-sort / level-by-level path for any tree
-    const bool force_deep = std::getenv("BMO_FORCE_DEEP_ORDER") != nullptr;
-    if (n_nodes > n && max_depth <= (unsigned long long)MAX_HEAP_LEVELS && !std::getenv("BMO_FORCE_SORT_ORDER") && !force_deep)
-        return order_by_heap_index(R, n, n_nodes, tbits, stream, temps);
+    const bool roots_only = n_nodes <= n, heap = !roots_only && max_depth <= (unsigned long long)MAX_HEAP_LEVELS && !force_sort && !force_deep;
+    const bool packed = max_depth <= (unsigned long long)MAX_PATH_LEVELS && !force_deep;
+    DBG("node order: %s", roots_only ? "bundle order" : (heap ? "heap index" : (packed ? "packed keys" : "level by level")));
+    if (heap) return order_by_heap_index(R, n, n_nodes, tbits, stream, temps);
     if (n_nodes > 0) hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, stream, (int32_t*)R->order.p, n_nodes);
-    if (n_nodes <= n) return BMO_OK;  // roots only: bundle order
+    if (roots_only) return BMO_OK;
     const int bits_depth = bits_for(max_depth), bits_root = bits_for((unsigned long long)std::max<int64_t>(n - 1, 0));
-    if (max_depth <= (unsigned long long)MAX_PATH_LEVELS && !force_deep)
-        return order_by_packed_keys(R, n_nodes, bits_root, bits_depth, (int)max_depth /* one bit per level */, stream, temps);
+    if (packed) return order_by_packed_keys(R, n_nodes, bits_root, bits_depth, (int)max_depth /* one bit per level */, stream, temps);
     return order_level_by_level(R, n_nodes, (int64_t)max_depth, bits_root, bits_depth, stream);
 }
 
 // ---- detector hits in reference push! order.  The hit table holds the rows of detector 0, then detector 1 ..., each in canonical node
 // order, nsub rows per hit.  A workgroup takes 256 consecutive canonical nodes (a tile): hit_count_kernel counts every tile's rows per
 // detector, one exclusive scan over the nd x n_tiles counts (detector-major) gives every tile its first row per detector, and
-// hit_gather_kernel ranks a tile's hits among themselves.  Nothing here scales with nd x n_nodes.  (BMO_FINISH=legacy: the pass this
-// one replaced — a flag per detector and node, a scan over all of them — kept to compare the two; gather_detector_hits_legacy.)
+// hit_gather_kernel ranks a tile's hits among themselves.  Nothing here scales with nd x n_nodes.
 //
 // Ranks the lanes of a wave by detector: `rank` = lanes below this one with the same detector d (d < 0: no hit), and once per distinct
 // detector of the wave (on the first lane that has it) f(detector, lanes with it).  As many trips as the wave has distinct detectors.
@@ -892,72 +890,44 @@ __global__ void __launch_bounds__(256) hit_count_kernel(const int32_t* __restric
     if (blockIdx.x == 0 && threadIdx.x == 0) cnt[(int64_t)n_det * gridDim.x] = 0;
 }
 
-// (the legacy pass) flags[d*n + i] = 1 if canonical node i recorded a hit on detector d
-__global__ void hit_flags_kernel(const int32_t* order, const int32_t* hit_det, int64_t n, int32_t n_det, int32_t nsub, int32_t* flags) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t d = hit_det[order[i]];
-    for (int32_t q = 0; q < n_det; ++q) flags[(int64_t)q * n + i] = (q == d) ? nsub : 0;
-}
-// offsets of every detector's segment in the compacted hit list + the total, in one small array (one read-back instead of nd + 2)
-__global__ void hit_offsets_kernel(const int32_t* __restrict__ offs, const int32_t* __restrict__ flags, int64_t n, int32_t n_det, int32_t* __restrict__ out) {
-    const int d = (int)threadIdx.x;
-    if (d < n_det) out[d] = offs[(int64_t)d * n];
-    if (d == n_det) out[d] = offs[(int64_t)n_det * n - 1] + flags[(int64_t)n_det * n - 1];
-}
 // A workgroup takes 256 consecutive canonical nodes: their (id, destination) pairs go to LDS once, then the 72-byte records are copied
 // as contiguous runs, one double per thread and turn (the first form of this kernel re-read the three index tables for each of
 // the 9 doubles: 152 us per C2 solve for 0.3 GB of traffic).
-// TILES: a node's first row = its tile's first row for the node's detector (`offs`: the scanned counts of hit_count_kernel, n_det x
+// A node's first row = its tile's first row for the node's detector (`offs`: the scanned counts of hit_count_kernel, n_det x
 // n_tiles + 1 of them) + nsub x the tile's earlier hits on that detector, counted per wave in LDS; the first workgroup also leaves every
-// detector's first row and the number of rows in det_off (TailBlock).  !TILES (legacy): `offs` holds the first row of every (detector, node).
-template <bool TILES>
+// detector's first row and the number of rows in det_off (TailBlock).
 __global__ void __launch_bounds__(256) hit_gather_kernel(const int32_t* __restrict__ order, const int32_t* __restrict__ hit_det, const double* __restrict__ hit, int64_t n,
                                                          int32_t nsub, const int32_t* __restrict__ offs, int64_t cap, double* __restrict__ out,
                                                          int32_t* __restrict__ out_node, unsigned long long* __restrict__ overflow, int32_t n_det,
                                                          int32_t* __restrict__ det_off) {
     __shared__ int32_t s_nd[256], s_pos[256];
-    __shared__ int32_t s_wave[TILES ? 4 : 1][TILES ? MAX_DETECTORS + 1 : 1];  // TILES: hits of every wave of the tile on every detector
+    __shared__ int32_t s_wave[4][MAX_DETECTORS + 1];  // hits of every wave of the tile on every detector
     const int64_t i0 = (int64_t)blockIdx.x * 256;
     {
         const int64_t i = i0 + threadIdx.x;
         int32_t nd = -1, pos = -1;
-        if constexpr (TILES) {
-            if (blockIdx.x == 0)
-                for (int q = threadIdx.x; q <= n_det; q += 256) det_off[q] = offs[(int64_t)q * gridDim.x];
-            for (int q = threadIdx.x; q < 4 * n_det; q += 256) s_wave[q / n_det][q % n_det] = 0;
-            __syncthreads();
-            int32_t d = -1;
-            if (i < n) {
-                nd = order[i];
-                d = hit_det[nd];
-                if (d >= n_det) d = -1;
-            }
-            const int w = (int)(threadIdx.x >> 6);
-            const int rank = wave_rank_by_detector(d, [&](int32_t dd, int lanes) { s_wave[w][dd] = lanes; });
-            __syncthreads();
-            if (d >= 0) {
-                int before = rank;
-                for (int q = 0; q < w; ++q) before += s_wave[q][d];
-                pos = offs[(int64_t)d * gridDim.x + blockIdx.x] + before * nsub;
-                if ((int64_t)pos + nsub > cap) {
-                    atomicAdd(overflow, 1ull);
-                    pos = -1;
-                } else {
-                    for (int q = 0; q < nsub; ++q) out_node[pos + q] = (int32_t)i;
-                }
-            }
-        } else if (i < n) {
+        if (blockIdx.x == 0)
+            for (int q = threadIdx.x; q <= n_det; q += 256) det_off[q] = offs[(int64_t)q * gridDim.x];
+        for (int q = threadIdx.x; q < 4 * n_det; q += 256) s_wave[q / n_det][q % n_det] = 0;
+        __syncthreads();
+        int32_t d = -1;
+        if (i < n) {
             nd = order[i];
-            const int32_t d = hit_det[nd];
-            if (d >= 0) {
-                pos = offs[(int64_t)d * n + i];
-                if ((int64_t)pos + nsub > cap) {
-                    atomicAdd(overflow, 1ull);
-                    pos = -1;
-                } else {
-                    for (int q = 0; q < nsub; ++q) out_node[pos + q] = (int32_t)i;
-                }
+            d = hit_det[nd];
+            if (d >= n_det) d = -1;
+        }
+        const int w = (int)(threadIdx.x >> 6);
+        const int rank = wave_rank_by_detector(d, [&](int32_t dd, int lanes) { s_wave[w][dd] = lanes; });
+        __syncthreads();
+        if (d >= 0) {
+            int before = rank;
+            for (int q = 0; q < w; ++q) before += s_wave[q][d];
+            pos = offs[(int64_t)d * gridDim.x + blockIdx.x] + before * nsub;
+            if ((int64_t)pos + nsub > cap) {
+                atomicAdd(overflow, 1ull);
+                pos = -1;
+            } else {
+                for (int q = 0; q < nsub; ++q) out_node[pos + q] = (int32_t)i;
             }
         }
         s_nd[threadIdx.x] = nd;
@@ -984,8 +954,7 @@ __global__ void __launch_bounds__(256) hit_gather_kernel(const int32_t* __restri
 // d_tail->det_off (the first row of every detector, the number of rows behind them) come back with the block's read-back.
 int count_and_gather_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, TailBlock* d_tail, hipStream_t stream, Temps& temps) {
     int rc;
-    const int nd = R->n_detectors;
-    if (nd > MAX_DETECTORS) return fail(BMO_ERR_UNSUPPORTED, "more than 1023 detectors");
+    const int nd = R->n_detectors;  // (at most MAX_DETECTORS: run_trace refuses more before it sizes the tail block)
     const unsigned nb = (unsigned)((n_nodes + 255) / 256);
     const int64_t tot = (int64_t)nd * nb + 1;  // counts of every (detector, tile), detector-major, and one more for the total
     // the hit table is sized before the counts are back on the host: a beam with a hit has ended and every splitting beam has two
@@ -999,32 +968,8 @@ int count_and_gather_hits(bmo_trace_result* R, int nsub, int64_t n, int64_t n_no
     if (nd == 0) return BMO_OK;
     CUB_TRY(temps, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)cnt->p, (int32_t*)offs->p, (int)tot, stream));
     if ((rc = R->det_data.alloc((size_t)std::max<int64_t>(bound, 1) * 72)) || (rc = R->det_node.alloc((size_t)std::max<int64_t>(bound, 1) * 4))) return rc;
-    hipLaunchKernelGGL(hit_gather_kernel<true>, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
+    hipLaunchKernelGGL(hit_gather_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
                        n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p, &d_tail->ctr.overflow, nd, d_tail->det_off);
-    return BMO_OK;
-}
-
-// ---- the legacy pass (BMO_FINISH=legacy): flags -> exclusive scan over nd x n_nodes of them -> gather.  Queued; the offsets of the nd
-// detectors (and the total behind them) arrive in h_off with the caller's synchronisation.
-int gather_detector_hits_legacy(bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, Counters* d_ctr, int32_t* h_off, hipStream_t stream, Temps& temps) {
-    int rc;
-    const int nd = R->n_detectors;
-    const int64_t tot = (int64_t)nd * n_nodes;
-    if (tot >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "detectors x beams exceeds 2^31: split the batch");
-    if (nd + 1 > 1024) return fail(BMO_ERR_UNSUPPORTED, "more than 1023 detectors");
-    DevBuf *flags = temps.take((size_t)tot * 4), *offs = temps.take((size_t)tot * 4), *d_off = temps.take((size_t)(nd + 1) * 4);
-    if (!flags || !offs || !d_off) return BMO_ERR_OOM;
-    const unsigned nb = (unsigned)((n_nodes + 255) / 256);
-    hipLaunchKernelGGL(hit_flags_kernel, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, n_nodes, nd, nsub,
-                       (int32_t*)flags->p);
-    CUB_TRY(temps, hipcub::DeviceScan::ExclusiveSum(cub_tmp, cub_bytes, (const int32_t*)flags->p, (int32_t*)offs->p, (int)tot, stream));
-    // per-detector offsets = scan value at the start of each detector's segment; total = last offs + last flag
-    hipLaunchKernelGGL(hit_offsets_kernel, dim3(1), dim3(1024), 0, stream, (const int32_t*)offs->p, (const int32_t*)flags->p, n_nodes, nd, (int32_t*)d_off->p);
-    HIP_TRY(hipMemcpyAsync(h_off, d_off->p, (size_t)(nd + 1) * 4, hipMemcpyDeviceToHost, stream));
-    const int64_t bound = (n_nodes + n) / 2 * nsub + nsub;  // (as in count_and_gather_hits)
-    if ((rc = R->det_data.alloc((size_t)std::max<int64_t>(bound, 1) * 72)) || (rc = R->det_node.alloc((size_t)std::max<int64_t>(bound, 1) * 4))) return rc;
-    hipLaunchKernelGGL(hit_gather_kernel<false>, dim3(nb), dim3(256), 0, stream, (const int32_t*)R->order.p, (const int32_t*)R->n_hitdet.p, (const double*)R->n_hit.p,
-                       n_nodes, nsub, (const int32_t*)offs->p, bound, (double*)R->det_data.p, (int32_t*)R->det_node.p, &d_ctr->overflow, nd, (int32_t*)nullptr);
     return BMO_OK;
 }
 
@@ -1091,6 +1036,140 @@ int alloc_launch_chunks(const KindInfo& K, ChunkArena& arena, bmo_trace_result* 
     return BMO_OK;
 }
 
+// wall-clock laps of a solve's phases on stderr (BMO_DEBUG)
+struct PhaseClock {
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    void lap(const char* what) {
+        if (!dbg_on()) return;
+        const auto t = std::chrono::steady_clock::now();
+        DBG("phase %-10s %.3f ms", what, std::chrono::duration<double, std::milli>(t - t0).count());
+        t0 = t;
+    }
+};
+
+// One turn of the step loop: plans the launch over C.cur, gives it its chunks, node slots and buffers, launches it and waits, then books
+// what it made: the log's chunks (or their room back to the pool), C.cur = the next launch's records, R->n_nodes, R->n_steps.
+int step_once(DevCtx& ctx, const KindInfo& K, bmo_scene* scene, const char* dblob, bmo_device_batch* batch, const bmo_trace_opts* opts, const SolveSwitches& sw,
+              bmo_trace_result* R, bmo_trace_result* prev, const StepKernels& kern, ChunkArena& arena, NodeTable& nodes, const DevBuf& tbits, LaunchBufs& bufs,
+              TailBlock* d_tail, LaunchChunks& C) {
+    int rc;
+    // bounces per launch: fewer launches and host round trips; holes instead of compaction inside a launch.  BMO_FUSE=1 (BMO_FUSE_GAUSS=1)
+    // restores one launch per bounce level.
+    // measured on C1-C5: 8 levels per launch beat 4 by 1-4 % at 10^6 beams and by 8-10 % below 10^5; with per-wave loops 16 beat 8 by
+    // another 1-3 %, and 32 beat 16 by 1-2.5 % (config C2 reaches its splitter, level 17, in the first launch: 2 launches instead of 3).
+    // The GaussianBeamlet kernels need one in-place chunk more than they fuse levels (step_kernel_gauss): one level fewer.
+    const int fuse_max = std::max(1, std::min(K.gauss ? MAX_FUSE - 1 : MAX_FUSE, K.gauss ? sw.fuse_gauss : sw.fuse));
+    const int steps = R->n_steps;  // launches so far = the number of this one
+    const int64_t n_nodes = R->n_nodes;
+    hipStream_t stream = ctx.stream;
+    const Counters& h_ctr = *ctx.pinned;
+    // a sweep (bmo_trace_sweep): R->n_configs configurations, R->d_root_cfg the configuration of every root; lanes find their slots through
+    // the map built before the launch (StepParams::sweep)
+    const bool has_split = scene->hdr.has_splitter != 0, sweep = R->n_configs > 0, keep_log = arena.keep_log;
+    const int64_t m = C.cur.count;
+    LaunchPlan plan = plan_launch(m, fuse_max, keep_log, arena.rec_bytes, has_split, kern.inw || K.gauss, R->n_configs);
+    if (plan.sweep_lanes >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "sweep launch of more than 2^31 lanes: fewer roots per call");
+    ChunkArena::Mark marks[MAX_FUSE];  // arena state behind nxt [0] and behind every in-place level [q + 1]
+    if ((rc = alloc_launch_chunks(K, arena, R, plan, has_split, C, marks))) return rc;
+    if (has_split && (rc = nodes.grow(n_nodes + 2 * m + 2 * plan.inwave_cap, stream))) return rc;
+    if ((rc = bufs.fit(K, plan, m, arena.rec_bytes))) return rc;
+    StepParams P;
+    fill_step_params(P, K, scene, dblob, opts, C, plan, bufs, nodes.arrays(tbits), prev ? old_solution_of(prev) : OldSolution{}, &d_tail->ctr, d_tail->shards, steps, n_nodes);
+    if (knobs().lpt && !sweep && steps == 0 && plan.lane_shift == 6 && plan.n_blocks >= 64 && (rc = tile_order_feedback(P, batch, prev, plan.n_blocks, stream))) return rc;
+#if defined(BMO_DEV_TIMELINE)
+    DevBuf tl_buf;
+    if (sw.timeline && !sweep) {
+        if ((rc = tl_buf.alloc((size_t)plan.n_waves * 16 + 64))) return rc;
+        HIP_TRY(hipMemsetAsync(tl_buf.p, 0, tl_buf.bytes, stream));
+        P.tl = (unsigned long long*)tl_buf.p;
+    }
+#endif
+    DevBuf sw_map;  // (P.sweep shares its room with P.old: set for sweeps only)
+    if (sweep) {
+        if ((rc = build_sweep_lane_map(R, C.cur, plan.sweep_lanes, &d_tail->ctr, stream, sw_map))) return rc;
+        P.sweep = SweepLanes{(const int32_t*)sw_map.p, (const int32_t*)R->d_root_cfg.p, scene->stride};
+    }
+    DBG("step %d launching m=%lld, %d records per wave", steps, (long long)m, 1 << plan.lane_shift);
+    if ((rc = launch_step(ctx, kern, plan, P, steps, &d_tail->ctr, sw.wide_min_waves))) return rc;
+#if defined(BMO_DEV_TIMELINE)
+    if (P.tl && (rc = print_timeline(P.tl, (size_t)plan.n_waves, steps))) return rc;
+#endif
+    const unsigned long long produced = h_ctr.next_count[steps & 1];
+    DBG("step %d done next=%llu nodes=%llu deepest in-place level %llu of %d", steps, produced, h_ctr.node_count, h_ctr.max_level[steps & 1], plan.n_fuse);
+    R->n_steps = steps + 1;
+    if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "queue overflow (internal capacity bound violated)");
+    if (h_ctr.sweep_mixed) return fail(BMO_ERR_INTERNAL, "sweep: a wave held records of more than one configuration (lane map violated)");
+    if (keep_log) {
+        const int used = (int)std::min<unsigned long long>(h_ctr.max_level[steps & 1], (unsigned long long)(plan.n_fuse - 1));  // in-place levels reached
+        R->chunks.push_back(C.cur);
+        for (int q = 0; q < used; ++q) R->chunks.push_back(C.inner[q]);
+        // the levels behind them were never touched: their room goes back to the arena
+        // (the GaussianBeamlet kernels' extra level is always given back; the launch has completed: nothing in flight touches these blocks)
+        if (used < C.n_inner) arena.rewind(marks[used]);
+    } else {  // the launch above has completed (counter read-back): its input and in-place levels are dead
+        arena.drop(C.cur);
+        if (K.gauss || plan.n_fuse > 1) arena.drop(C.inner[0]);
+        if (K.gauss && plan.n_fuse > 1) arena.drop(C.inner[1]);
+    }
+    C.nxt.count = (int64_t)produced;  // (planes are strided by cap, so the chunk keeps its footprint)
+    R->n_nodes = (int64_t)h_ctr.node_count;
+    if (opts->max_beams > 0 && R->n_nodes > (int64_t)opts->max_beams)
+        return fail(BMO_ERR_LIMIT, "beam tree exceeds bmo_trace_opts.max_beams (" + std::to_string(R->n_nodes) + " beams after " + std::to_string(R->n_steps) +
+                                       " launches): a splitter facing a mirror?");
+    C.cur = C.nxt;
+    return BMO_OK;
+}
+
+// the step kernels' time of a solve, from the event pair around every launch
+int sum_step_times(const DevCtx& ctx, int steps, bool gaps, double& kernel_ms) {
+    kernel_ms = 0;
+    for (int q = 0; q < steps; ++q) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx.step_ev[2 * q], ctx.step_ev[2 * q + 1]));
+        kernel_ms += ms;
+        DBG("step %d kernel %.3f ms", q, ms);
+        if (q + 1 < steps && gaps) {  // diagnosis: device idle time between two step launches (host round trip)
+            float gap = 0;
+            (void)hipEventElapsedTime(&gap, ctx.step_ev[2 * q + 1], ctx.step_ev[2 * q + 2]);
+            fprintf(stderr, "[bmo] step %d kernel %.3f ms, gap to the next launch %.3f ms\n", q, ms, gap);
+        }
+    }
+    return BMO_OK;
+}
+
+// Everything behind the last launch: the canonical order, the segment count and the detector tables, all queued behind ONE
+// synchronisation at the end.  The temporaries stay alive until then (`temps`: a block that went back to the pool could be handed to a
+// view running on another stream); the tail block is read back last and unpacked into R.  Records ctx.ev[3] behind the queued work.
+int finish_solve(DevCtx& ctx, bmo_trace_result* R, int nsub, int64_t n, int64_t n_nodes, const DevBuf& tbits, const SolveSwitches& sw, TailBlock* d_tail,
+                 PhaseClock& clock) {
+    int rc;
+    hipStream_t stream = ctx.stream;
+    Temps temps;
+    const int nd = R->n_detectors;
+    R->det_count.assign(nd, 0);
+    R->det_offset.assign(nd, 0);
+    if ((rc = order_nodes(R, n, n_nodes, ctx.pinned->max_depth, tbits, sw.force_sort_order, sw.force_deep_order, stream, temps))) return rc;
+    clock.lap("order");
+    // segments = sum of the beams' segment counts (chunk counts include the holes of fused levels)
+    if (n_nodes > 0 && (rc = count_and_gather_hits(R, nsub, n, n_nodes, d_tail, stream, temps))) return rc;
+    TailBlock& h_tail = *ctx.tail_back;
+    HIP_TRY(hipMemcpyAsync(&h_tail, d_tail, tail_bytes(nd), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(ctx.ev[3], stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipGetLastError());
+    clock.lap("hits");
+    if (h_tail.ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
+    unsigned long long tot = 0, seg = 0;
+    for (int q = 0; q < 64; ++q) tot += h_tail.shards[(size_t)q * 16], seg += h_tail.shards[(size_t)q * 16 + 1];
+    R->calls = tot;
+    R->n_records = (int64_t)seg;
+    for (int d = 0; d < nd && n_nodes > 0; ++d) {
+        R->det_offset[d] = h_tail.det_off[d];
+        R->det_count[d] = h_tail.det_off[d + 1] - h_tail.det_off[d];
+    }
+    return BMO_OK;
+}
+
 int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, const bmo_trace_opts* opts, bmo_trace_result* R, bmo_trace_result* prev) {
     const int device = batch->device;
     if (prev) {
@@ -1099,6 +1178,7 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
             return fail(BMO_ERR_INVALID, "retrace: batch does not match the previous solution (root count / beam kind)");
     }
     HIP_TRY(hipSetDevice(device));
+    const SolveSwitches sw = read_switches().solve;  // (read at the start of every solve: the tests switch these between solves)
     int rc = BMO_OK;
     const char* dblob = scene->device_blob(device, rc);
     if (rc) return rc;
@@ -1112,20 +1192,13 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
     R->nd = K.nd;
     R->abi_planes = K.abi_planes;
 
-    auto wall0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!dbg_on()) return;
-        auto t = std::chrono::steady_clock::now();
-        DBG("phase %-10s %.3f ms", what, std::chrono::duration<double, std::milli>(t - wall0).count());
-        wall0 = t;
-    };
+    PhaseClock clock;
     DevCtx* ctxp = nullptr;
     if ((rc = device_ctx(device, ctxp))) return rc;
     DevCtx& ctx = *ctxp;
     std::lock_guard<std::mutex> one_trace_per_device(ctx.busy);
     hipStream_t stream = ctx.stream;
-    hipEvent_t ev_t0 = ctx.ev[2], ev_t1 = ctx.ev[3];
-    HIP_TRY(hipEventRecord(ev_t0, stream));
+    HIP_TRY(hipEventRecord(ctx.ev[2], stream));
     // Every exit path — the error returns too — waits for what has been queued BEFORE the temporaries of this function go back to the
     // shared pools: a kernel or copy still in flight must not write into a block another host thread has been handed.
     // While `hold` lives, blocks released on this thread are parked in it; its destructor (it is declared before every temporary, so it
@@ -1151,20 +1224,14 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
     DevBuf tail_buf;
     if ((rc = tail_buf.alloc(sizeof(TailBlock)))) return rc;
     TailBlock* const d_tail = static_cast<TailBlock*>(tail_buf.p);
-    Counters* d_ctr = &d_tail->ctr;
-    Counters& h_ctr = *ctx.pinned;  // pinned: the per-step read-back does not go through a staging copy
-    h_ctr = Counters{{0, 0}, (unsigned long long)n, 0, 0, {0, 0}};
+    *ctx.pinned = Counters{{0, 0}, (unsigned long long)n, 0, 0, {0, 0}};  // pinned: the per-step read-back does not go through a staging copy
     ctx.tail_img->ctr.node_count = (unsigned long long)n;
     HIP_TRY(hipMemcpyAsync(d_tail, ctx.tail_img, tail_bytes(R->n_detectors), hipMemcpyHostToDevice, stream));
 
     LaunchChunks C;
     if ((rc = arena.alloc(n, C.cur))) return rc;
     C.cur.count = n;
-    OldSolution old_tab{};
-    if (prev) {
-        if ((rc = build_retrace_tables(prev, stream))) return rc;
-        old_tab = old_solution_of(prev);
-    }
+    if (prev && (rc = build_retrace_tables(prev, stream))) return rc;  // (step_once hands them to the kernels: old_solution_of)
     if (has_split && n > 0 && (rc = tbits_buf.alloc((size_t)n * 8))) return rc;
     if (n > 0) {
         // a retrace re-walks the stored first ray whatever r_max says (System.jl:197); root j re-walks old node j
@@ -1173,168 +1240,30 @@ int run_trace(const KindInfo& K, bmo_scene* scene, bmo_device_batch* batch, cons
                            nodes.arrays(tbits_buf), prev ? 0x7fffffff : opts->r_max, (int32_t)batch->n_planes);
         if (prev) hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (int32_t*)R->n_old.p, n);
     }
-    lap("setup");
-    DBG("roots initialised n=%lld blob=%u use_lds=%d", (long long)n, (uint32_t)scene->blob.size(), 0);
+    clock.lap("setup");
+    DBG("roots initialised n=%lld blob=%u", (long long)n, (uint32_t)scene->blob.size());
     if (dbg_on()) {
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipGetLastError());
         DBG("init kernel done");
     }
-    // a sweep (bmo_trace_sweep): R->n_configs configurations, R->d_root_cfg the configuration of every root; lanes find their slots through
-    // the map built before every launch (StepParams::sweep)
-    const bool sweep = R->n_configs > 0;
     StepKernels kern;
-    const int ext = scene->hdr.pad[0] ? 3 : (scene->hdr.has_asphere ? 2 : (scene->hdr.has_meniscus ? 1 : 0));
-    if ((rc = K.select(ext, prev != nullptr, sweep, kern))) return rc;
+    const int ext = scene->hdr.has_bvh() ? 3 : (scene->hdr.has_asphere ? 2 : (scene->hdr.has_meniscus ? 1 : 0));
+    if ((rc = K.select(ext, prev != nullptr, R->n_configs > 0, kern))) return rc;
 
-    int64_t n_nodes = n;
-    int steps = 0;
-    // bounces per launch: fewer launches and host round trips; holes instead of compaction inside a launch.  BMO_FUSE=1 (BMO_FUSE_GAUSS=1)
-    // restores one launch per bounce level.
-    // measured on C1-C5: 8 levels per launch beat 4 by 1-4 % at 10^6 beams and by 8-10 % below 10^5; with per-wave loops 16 beat 8 by
-    // another 1-3 %, and 32 beat 16 by 1-2.5 % (config C2 reaches its splitter, level 17, in the first launch: 2 launches instead of 3).
-    // The GaussianBeamlet kernels need one in-place chunk more than they fuse levels (step_kernel_gauss): one level fewer.
-    int fuse_max = K.gauss ? MAX_FUSE - 1 : MAX_FUSE;
-    if (const char* e = getenv(K.gauss ? "BMO_FUSE_GAUSS" : "BMO_FUSE")) fuse_max = std::max(1, std::min(fuse_max, atoi(e)));
+    R->n_nodes = n;
+    R->n_steps = 0;
     LaunchBufs bufs;
-    while (C.cur.count > 0) {
-        const int64_t m = C.cur.count;
-        LaunchPlan plan = plan_launch(m, fuse_max, keep_log, rec_bytes, has_split, kern.inw || K.gauss, R->n_configs);
-        if (plan.sweep_lanes >= ((int64_t)1 << 31)) return fail(BMO_ERR_UNSUPPORTED, "sweep launch of more than 2^31 lanes: fewer roots per call");
-        ChunkArena::Mark marks[MAX_FUSE];  // arena state behind nxt [0] and behind every in-place level [q + 1]
-        if ((rc = alloc_launch_chunks(K, arena, R, plan, has_split, C, marks))) return rc;
-        if (has_split && (rc = nodes.grow(n_nodes + 2 * m + 2 * plan.inwave_cap, stream))) return rc;
-        if ((rc = bufs.fit(K, plan, m, rec_bytes))) return rc;
-        StepParams P;
-        fill_step_params(P, K, scene, dblob, opts, C, plan, bufs, nodes.arrays(tbits_buf), old_tab, d_ctr, d_tail->shards, steps, n_nodes);
-        if (knobs().lpt && !sweep && steps == 0 && plan.lane_shift == 6 && plan.n_blocks >= 64 && (rc = tile_order_feedback(P, batch, prev, plan.n_blocks, stream))) return rc;
-#if defined(BMO_DEV_TIMELINE)
-        DevBuf tl_buf;
-        if (getenv("BMO_TIMELINE") && !sweep) {
-            if ((rc = tl_buf.alloc((size_t)plan.n_waves * 16 + 64))) return rc;
-            HIP_TRY(hipMemsetAsync(tl_buf.p, 0, tl_buf.bytes, stream));
-            P.tl = (unsigned long long*)tl_buf.p;
-        }
-#endif
-        DevBuf sw_map;  // (P.sweep shares its room with P.old: set for sweeps only)
-        if (sweep) {
-            if ((rc = build_sweep_lane_map(R, C.cur, plan.sweep_lanes, d_ctr, stream, sw_map))) return rc;
-            P.sweep = SweepLanes{(const int32_t*)sw_map.p, (const int32_t*)R->d_root_cfg.p, scene->stride};
-        }
-        DBG("step %d launching m=%lld, %d records per wave", steps, (long long)m, 1 << plan.lane_shift);
-        if ((rc = launch_step(ctx, kern, plan, P, steps, d_ctr))) return rc;
-#if defined(BMO_DEV_TIMELINE)
-        if (P.tl && (rc = print_timeline(P.tl, (size_t)plan.n_waves, steps))) return rc;
-#endif
-        const unsigned long long produced = h_ctr.next_count[steps & 1];
-        DBG("step %d done next=%llu nodes=%llu deepest in-place level %llu of %d", steps, produced, h_ctr.node_count, h_ctr.max_level[steps & 1], plan.n_fuse);
-        steps += 1;
-        if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "queue overflow (internal capacity bound violated)");
-        if (h_ctr.sweep_mixed) return fail(BMO_ERR_INTERNAL, "sweep: a wave held records of more than one configuration (lane map violated)");
-        if (keep_log) {
-            const int used = (int)std::min<unsigned long long>(h_ctr.max_level[(steps - 1) & 1], (unsigned long long)(plan.n_fuse - 1));  // in-place levels reached
-            R->chunks.push_back(C.cur);
-            for (int q = 0; q < used; ++q) R->chunks.push_back(C.inner[q]);
-            // the levels behind them were never touched: their room goes back to the arena
-            // (the GaussianBeamlet kernels' extra level is always given back; the launch has completed: nothing in flight touches these blocks)
-            if (used < C.n_inner) arena.rewind(marks[used]);
-        } else {  // the launch above has completed (counter read-back): its input and in-place levels are dead
-            arena.drop(C.cur);
-            if (K.gauss || plan.n_fuse > 1) arena.drop(C.inner[0]);
-            if (K.gauss && plan.n_fuse > 1) arena.drop(C.inner[1]);
-        }
-        C.nxt.count = (int64_t)produced;  // (planes are strided by cap, so the chunk keeps its footprint)
-        n_nodes = (int64_t)h_ctr.node_count;
-        if (opts->max_beams > 0 && n_nodes > (int64_t)opts->max_beams)
-            return fail(BMO_ERR_LIMIT, "beam tree exceeds bmo_trace_opts.max_beams (" + std::to_string(n_nodes) + " beams after " + std::to_string(steps) +
-                                           " launches): a splitter facing a mirror?");
-        C.cur = C.nxt;
-    }
-    double kernel_ms = 0;
-    for (int q = 0; q < steps; ++q) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx.step_ev[2 * q], ctx.step_ev[2 * q + 1]));
-        kernel_ms += ms;
-        DBG("step %d kernel %.3f ms", q, ms);
-        if (q + 1 < steps && getenv("BMO_GAPS")) {  // diagnosis: device idle time between two step launches (host round trip)
-            float gap = 0;
-            (void)hipEventElapsedTime(&gap, ctx.step_ev[2 * q + 1], ctx.step_ev[2 * q + 2]);
-            fprintf(stderr, "[bmo] step %d kernel %.3f ms, gap to the next launch %.3f ms\n", q, ms, gap);
-        }
-    }
-    lap("steps");
-    R->n_nodes = n_nodes;
-    R->n_steps = steps;
-    R->kernel_ms = kernel_ms;
+    while (C.cur.count > 0)
+        if ((rc = step_once(ctx, K, scene, dblob, batch, opts, sw, R, prev, kern, arena, nodes, tbits_buf, bufs, d_tail, C))) return rc;
+    if ((rc = sum_step_times(ctx, R->n_steps, sw.gaps, R->kernel_ms))) return rc;
+    clock.lap("steps");
     if (batch->cost_valid && batch->tile_n > 0 && batch->tile_cost.p && !R->tile_cost.alloc((size_t)batch->tile_n * 4)) {  // (best effort)
         if (hipMemcpyAsync(R->tile_cost.p, batch->tile_cost.p, (size_t)batch->tile_n * 4, hipMemcpyDeviceToDevice, stream) == hipSuccess) R->tile_n = batch->tile_n;
     }
-    // Everything below is queued behind ONE synchronisation at the end: temporaries stay alive until then (`temps`: a block that went
-    // back to the pool could be handed to a view running on another stream), counts are read back last.
-    Temps temps;
-    const char* const finish_env = getenv("BMO_FINISH");  // (read per solve: the tests switch it between solves)
-    const bool legacy = finish_env && !strcmp(finish_env, "legacy");
-    DBG("finish pass: %s", legacy ? "legacy (a flag per detector and node)" : "counts per tile");
-    const int nd = R->n_detectors;
-    R->det_count.assign(nd, 0);
-    R->det_offset.assign(nd, 0);
-    const bool with_hits = nd > 0 && n_nodes > 0;
-    if (!legacy) {
-        if ((rc = order_nodes(R, n, n_nodes, h_ctr.max_depth, tbits_buf, stream, temps))) return rc;
-        lap("order");
-        // segments = sum of the beams' segment counts (chunk counts include the holes of fused levels)
-        if (n_nodes > 0 && (rc = count_and_gather_hits(R, K.nsub, n, n_nodes, d_tail, stream, temps))) return rc;
-        TailBlock& h_tail = *ctx.tail_back;
-        HIP_TRY(hipMemcpyAsync(&h_tail, d_tail, tail_bytes(nd), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(ev_t1, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-        lap("hits");
-        if (h_tail.ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
-        unsigned long long tot = 0, seg = 0;
-        for (int q = 0; q < 64; ++q) tot += h_tail.shards[(size_t)q * 16], seg += h_tail.shards[(size_t)q * 16 + 1];
-        R->calls = tot;
-        R->n_records = (int64_t)seg;
-        for (int d = 0; d < nd && with_hits; ++d) {
-            R->det_offset[d] = h_tail.det_off[d];
-            R->det_count[d] = h_tail.det_off[d + 1] - h_tail.det_off[d];
-        }
-    } else {
-        // pinned read-back area: [0..1023] call-counter shards (64 x 16 words), [1024] segment count, [1025..] hit offsets
-        static_assert(sizeof(unsigned long long) == 8, "");
-        HostBuf h_tail;
-        if ((rc = h_tail.alloc((1024 + 1 + 1025) * 8))) return rc;
-        unsigned long long* const h_sh = static_cast<unsigned long long*>(h_tail.p);
-        long long* const h_sum = reinterpret_cast<long long*>(h_sh + 1024);
-        int32_t* const h_off = reinterpret_cast<int32_t*>(h_sh + 1025);
-        *h_sum = 0;
-        HIP_TRY(hipMemcpyAsync(h_sh, d_tail->shards, 64 * 128, hipMemcpyDeviceToHost, stream));
-        if (n_nodes > 0) {
-            DevBuf* d_sum = temps.take(8);
-            if (!d_sum) return BMO_ERR_OOM;
-            CUB_TRY(temps, hipcub::DeviceReduce::Sum(cub_tmp, cub_bytes, (const int32_t*)R->n_nseg.p, (long long*)d_sum->p, (int)n_nodes, stream));
-            HIP_TRY(hipMemcpyAsync(h_sum, d_sum->p, 8, hipMemcpyDeviceToHost, stream));
-        }
-        if ((rc = order_nodes(R, n, n_nodes, h_ctr.max_depth, tbits_buf, stream, temps))) return rc;
-        lap("order");
-        if (with_hits && (rc = gather_detector_hits_legacy(R, K.nsub, n, n_nodes, d_ctr, h_off, stream, temps))) return rc;
-        HIP_TRY(hipMemcpyAsync(&h_ctr, d_ctr, sizeof h_ctr, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(ev_t1, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipGetLastError());
-        lap("hits");
-        if (h_ctr.overflow) return fail(BMO_ERR_INTERNAL, "hit table overflow (internal capacity bound violated)");
-        unsigned long long tot = 0;
-        for (int q = 0; q < 64; ++q) tot += h_sh[(size_t)q * 16];
-        R->calls = tot;
-        R->n_records = (int64_t)*h_sum;
-        for (int d = 0; d < nd && with_hits; ++d) {
-            R->det_offset[d] = h_off[d];
-            R->det_count[d] = h_off[d + 1] - h_off[d];
-        }
-    }
+    if ((rc = finish_solve(ctx, R, K.nsub, n, R->n_nodes, tbits_buf, sw, d_tail, clock))) return rc;
     float tms = 0;
-    HIP_TRY(hipEventElapsedTime(&tms, ev_t0, ev_t1));
+    HIP_TRY(hipEventElapsedTime(&tms, ctx.ev[2], ctx.ev[3]));
     R->total_ms = tms;
     return BMO_OK;
 }

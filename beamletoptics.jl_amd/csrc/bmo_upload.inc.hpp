@@ -4,7 +4,7 @@
 //   root_key_kernel, root_chord_kernel, root_order_key_kernel, root_ring_jump_kernel, bin_planes_kernel
 //   check_batch, copy_batch               the batch's shape, its planes and wavelength indices on the device
 //   RootKeys, sort_roots, bin_planes      the permutation of the roots by their keys, the planes in that order
-//   root_order_wanted                     the order BMO_ROOT_ORDER asks for
+//   root_order_wanted                     the order asked for (Switches::root_order)
 //   order_by_chords, order_by_masks       the two kinds of keys (and auto's test of the bundle's own order)
 
 // Coherence key of a root ray: the set of candidates (first 64 of the candidate table) whose bounding sphere the ray's line meets —
@@ -175,8 +175,7 @@ int bin_planes(bmo_device_batch* b) {
 
 // ---- choose the order.  BMO_ROOT_ORDER = chord (root_order_key_kernel) | mask (round 3's candidate-set keys) | none; unset: auto, which is
 // chord unless the bundle's own numbering turns out coherent (order_by_chords), and mask where the scene has no bound to take chords through.
-std::string root_order_wanted(bool order_roots) {
-    const char* order_env = getenv("BMO_ROOT_ORDER");
+std::string root_order_wanted(bool order_roots, const char* order_env) {
     return !order_roots ? "none" : (order_env ? order_env : "auto");
 }
 
@@ -252,7 +251,7 @@ int batch_upload(bmo_scene* scene, const bmo_ray_batch* in, int32_t device, bmo_
     HIP_TRY(hipSetDevice(device));
     auto b = std::make_unique<bmo_device_batch>();
     if ((rc = copy_batch(in, device, b.get()))) return rc;
-    std::string root_order = root_order_wanted(order_roots);
+    std::string root_order = root_order_wanted(order_roots, read_switches().root_order);  // (read at every upload, with the per-solve names: one reader, and an upload is no hot path)
     const bool large = in->n >= 4096 && scene->hdr.n_cands > 0;
     if (large && scene->bound[3] > 0.0 && (root_order == "chord" || root_order == "auto")) {
         if ((rc = order_by_chords(scene, b.get(), root_order))) return rc;  // (leaves "chord", or "mask": auto kept the bundle's own order)

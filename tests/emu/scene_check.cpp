@@ -209,7 +209,7 @@ void check_valid_scenes() {
     const SceneView S = view_of(lens.blob.data(), &lens.hdr);
     CHECK((S.shapes[3].flags & BMO_SHAPE_FLAG_CONSECUTIVE) && S.shapes[3].tri_begin == 0, "consecutive union: flags %d", S.shapes[3].flags);
     CHECK(!(S.shapes[6].flags & BMO_SHAPE_FLAG_CONSECUTIVE), "union of shapes 5, 4: flags %d", S.shapes[6].flags);
-    CHECK(S.n_cands == 3 && S.children[3] == 5 && S.n_table[1] == 1.5 && !lens.hdr.pad[0] && !lens.hdr.has_splitter, "two lenses: tables");
+    CHECK(S.n_cands == 3 && S.children[3] == 5 && S.n_table[1] == 1.5 && !lens.hdr.has_bvh() && !lens.hdr.has_splitter, "two lenses: tables");
     CHECK(lens.bound[3] > 0.05 && lens.bound[3] < 0.2, "two lenses: bounding sphere of radius %g", lens.bound[3]);
     Desc A = asphere_scene();
     const SceneImage asph = build("asphere", A);
@@ -219,17 +219,17 @@ void check_valid_scenes() {
     Desc M64 = mesh_scene(sphere_mesh(5, 8, 0.02, c, 0.0));
     CHECK(M64.tris.size() == 64 * 9, "%zu faces", M64.tris.size() / 9);
     const SceneImage m64 = build("sphere mesh, 64 faces", M64);
-    CHECK(m64.bvh[0].n_nodes > 0 && m64.hdr.pad[0] == 1, "64 faces: %d BVH nodes", m64.bvh[0].n_nodes);
+    CHECK(m64.bvh[0].n_nodes > 0 && m64.hdr.has_bvh() == 1, "64 faces: %d BVH nodes", m64.bvh[0].n_nodes);
     bvh_against_brute_force("64 faces", m64.blob.data(), m64.hdr, true);
     std::vector<double> t63 = sphere_mesh(5, 8, 0.02, c, 0.0);
     t63.resize(63 * 9);
     Desc M63 = mesh_scene(t63);
     const SceneImage m63 = build("sphere mesh, 63 faces", M63);
-    CHECK(m63.bvh[0].n_nodes == 0 && m63.hdr.pad[0] == 0, "63 faces: %d BVH nodes", m63.bvh[0].n_nodes);
+    CHECK(m63.bvh[0].n_nodes == 0 && m63.hdr.has_bvh() == 0, "63 faces: %d BVH nodes", m63.bvh[0].n_nodes);
     bvh_against_brute_force("63 faces", m63.blob.data(), m63.hdr, false);
     Desc MN = mesh_scene(sphere_mesh(12, 16, 0.02, c, 0.2), BMO_SHAPE_FLAG_NO_BVH);
     const SceneImage mn = build("sphere mesh, NO_BVH", MN);
-    CHECK(mn.bvh[0].n_nodes == 0 && mn.hdr.pad[0] == 0, "NO_BVH: %d BVH nodes", mn.bvh[0].n_nodes);
+    CHECK(mn.bvh[0].n_nodes == 0 && mn.hdr.has_bvh() == 0, "NO_BVH: %d BVH nodes", mn.bvh[0].n_nodes);
     bvh_against_brute_force("NO_BVH", mn.blob.data(), mn.hdr, false);
     Desc MB = mesh_scene(sphere_mesh(12, 16, 0.02, c, 0.2), BMO_SHAPE_FLAG_BVH);  // (the output flag on input: ignored)
     const SceneImage mb = build("sphere mesh, 352 faces", MB);
@@ -292,13 +292,13 @@ void check_bvh_corner_cases() {
     CHECK(bvh_build(bad.data(), (int)(bad.size() / 9), 1e-9, nodes, faces, st) == -1 && nodes.empty() && faces.empty(), "a non-finite vertex: no BVH");
     Desc N = mesh_scene(bad);
     const SceneImage nan = build("mesh with a NaN vertex", N);
-    CHECK(nan.bvh[0].n_nodes == 0 && nan.hdr.pad[0] == 0, "NaN vertex: %d BVH nodes", nan.bvh[0].n_nodes);
+    CHECK(nan.bvh[0].n_nodes == 0 && nan.hdr.has_bvh() == 0, "NaN vertex: %d BVH nodes", nan.bvh[0].n_nodes);
     CHECK(!(view_of(nan.blob.data(), &nan.hdr).shapes[0].flags & BMO_SHAPE_FLAG_BVH), "NaN vertex: the mesh stays brute force");
     for (double keps : {0.0, -1e-9}) {
         Desc K = mesh_scene(sphere_mesh(12, 16, 0.02, c, 0.2));
         K.mt_keps = keps;
         const SceneImage k = build(keps == 0.0 ? "mt_keps = 0" : "mt_keps < 0", K);
-        CHECK(k.bvh[0].n_nodes == 0 && k.hdr.pad[0] == 0 && !(view_of(k.blob.data(), &k.hdr).shapes[0].flags & BMO_SHAPE_FLAG_BVH), "mt_keps = %g: no BVH", keps);
+        CHECK(k.bvh[0].n_nodes == 0 && k.hdr.has_bvh() == 0 && !(view_of(k.blob.data(), &k.hdr).shapes[0].flags & BMO_SHAPE_FLAG_BVH), "mt_keps = %g: no BVH", keps);
     }
 }
 

@@ -1,12 +1,10 @@
 """The finish pass of a solve (csrc/bmo_trace_host.inc.hpp `count_and_gather_hits`): behind the last launch the segment count and the
 detector tables come from counts per tile of 256 canonical nodes, one scan over detectors x tiles of them and a gather that ranks a
-tile's hits in LDS.  `BMO_FINISH=legacy` (read per solve) brings back the pass it replaced: a flag per detector and node, a scan over
-all of them, a separate reduce for the segment count.  Every case here solves once each way and asks for equal results: node tables in
-canonical order, segments, detector rows, `det_node`, `det_offset`, `det_count`, `n_records`, the call count (parity.compare at zero
-tolerance) — and, where it is cheap, for the oracle's solution too.  The cases are the smallest that reach each way the counts can go
-wrong: the edges of the 256-node tiling, trees with children behind each of the three orderings, three rows per hit, tiles and
-detectors without hits, a PSFDetector, solves without the log, a retrace, a sweep, and two solves of one batch in a row (the second
-sorts its tiles by the first one's times)."""
+tile's hits in LDS.  Every case here asks for the oracle's solution: node tables in canonical order, segments, detector rows, `det_node`,
+`det_offset`, `det_count`, `n_records`, the call count (parity.compare at zero tolerance).  The cases are the smallest that reach each
+way the counts can go wrong: the edges of the 256-node tiling, trees with children behind each of the three orderings (the engine's
+`node order:` debug line says which one ran), three rows per hit, tiles and detectors without hits, a PSFDetector, solves without the
+log, a retrace, a sweep, and two solves of one batch in a row (the second sorts its tiles by the first one's times)."""
 import os
 import subprocess
 import sys
@@ -38,30 +36,6 @@ def _trace(scene, bundle, r_max=100):
         eng.close()
 
 
-def _both_ways(solve, label, setenv=None, delenv=None):
-    """solve() with the tiled pass and with BMO_FINISH=legacy; the two results equal.  Returns the tiled one."""
-    setenv = setenv or (lambda k, v: os.environ.__setitem__(k, v))
-    delenv = delenv or (lambda k: os.environ.pop(k, None))
-    delenv("BMO_FINISH")
-    new = solve()
-    setenv("BMO_FINISH", "legacy")
-    try:
-        old = solve()
-    finally:
-        delenv("BMO_FINISH")
-    compare(new, old, 0.0, label + ", tiled against legacy")
-    assert new.n_detectors == old.n_detectors and new.n_steps == old.n_steps, label
-    return new
-
-
-@pytest.fixture
-def both(monkeypatch):
-    def run(solve, label):
-        return _both_ways(solve, label, monkeypatch.setenv, lambda k: monkeypatch.delenv(k, raising=False))
-
-    return run
-
-
 def _lens_and_detector():
     """one lens, one Spotdetector behind it: no splitter, every beam is a root"""
     lens = bmo.SphericalLens(120 * mm, -120 * mm, 4 * mm, 25.4 * mm, 1.5)
@@ -72,36 +46,36 @@ def _lens_and_detector():
 
 
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 513])
-def test_tile_edges_roots_only(oracle, both, n):
+def test_tile_edges_roots_only(oracle, n):
     """Roots only, at the edges of the 256-node tiling: config 4's three singlets (no detector: the segment count alone, summed per tile)
     and a lens in front of a Spotdetector (every node has a hit: a tile's count, its first row, the rank within the tile)."""
     bundle = scenes.c4_bundle(n)
     scene = bmo.CompiledScene(scenes.c4_scene()[0], bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "c4, %d rays" % n)
+    got = _trace(scene, bundle)
     assert got.n_nodes == n and got.n_detectors == 0
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "c4, %d rays, oracle" % n)
     bundle = chain_bundle("ray", n)
     scene = bmo.CompiledScene(_lens_and_detector(), bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "lens + detector, %d rays" % n)
+    got = _trace(scene, bundle)
     assert got.n_nodes == n and got.det_count.tolist() == [n] and np.array_equal(got.det_node, np.arange(n))
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "lens + detector, %d rays, oracle" % n)
 
 
-def test_two_detectors_hits_on_children(oracle, both):
+def test_two_detectors_hits_on_children(oracle):
     """Config 2 under the survey bundle, 2 048 rays = 32 waves: the splitter's children carry the hits, both detectors have rows, the heap ordering."""
     bundle = scenes.c2_survey_bundle(2048)
     scene = bmo.CompiledScene(scenes.c2_scene()[0], bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "c2 survey bundle")
+    got = _trace(scene, bundle)
     assert got.n_nodes > bundle.n and (got.det_count > 0).all() and got.det_node.max() >= bundle.n
     compare(got, oracle.trace(scene, bundle, 100, threads=16), 0.0, "c2 survey bundle, oracle")
 
 
 @pytest.mark.parametrize("kind,nsub", [("ray", 1), ("gauss", 3)])
-def test_splitter_chain_heap_ordering(oracle, both, kind, nsub):
+def test_splitter_chain_heap_ordering(oracle, kind, nsub):
     """Four splitters in a row under 96 beams: trees four levels deep; GaussianBeamlets have three rows per hit (nsub = 3)."""
     bundle = chain_bundle(kind, 96)
     scene = bmo.CompiledScene(_chain(4), bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle, CHAIN_R_MAX), "splitter chain, %s" % kind)
+    got = _trace(scene, bundle, CHAIN_R_MAX)
     assert got.n_nodes >= 9 * bundle.n and got.det_count.sum() % nsub == 0 and got.det_count.sum() >= nsub * bundle.n
     compare(got, oracle.trace(scene, bundle, CHAIN_R_MAX, threads=8), 0.0, "splitter chain, %s, oracle" % kind)
 
@@ -109,20 +83,29 @@ def test_splitter_chain_heap_ordering(oracle, both, kind, nsub):
 def _child(mode, **env):
     """This file as a child process (BMO_DEBUG and the ordering hooks are read by the engine as the child sets them); the child compares itself."""
     path = os.pathsep.join([ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")] + ([os.environ["PYTHONPATH"]] if os.environ.get("PYTHONPATH") else []))
-    env = dict(os.environ, BMO_DEBUG="1", PYTHONPATH=path, **env)
-    for name in ("BMO_FINISH", "BMO_LPT"):
-        env.pop(name, None)
+    base = {k: v for k, v in os.environ.items() if k not in ("BMO_LPT", "BMO_FORCE_SORT_ORDER", "BMO_FORCE_DEEP_ORDER")}
+    env = dict(base, BMO_DEBUG="1", PYTHONPATH=path, **env)
     r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + [os.path.abspath(__file__), mode], env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     return r.stderr
 
 
+def _node_orders(err):
+    return [line.split("node order: ")[1] for line in err.splitlines() if "node order: " in line]
+
+
 @pytest.mark.parametrize("hook", ["BMO_FORCE_SORT_ORDER", "BMO_FORCE_DEEP_ORDER"])
 def test_splitter_chain_behind_the_other_orderings(hook):
-    """The same chain with the canonical order made by the packed-key sort and level by level; the debug line names the pass of each solve."""
-    err = _child("chain", **{hook: "1"})
-    assert err.count("finish pass: counts per tile") == 1 and err.count("finish pass: legacy") == 1, err[-2000:]
+    """The same chain with the canonical order made by the packed-key sort and level by level (the child compares itself with the
+    oracle); the debug line says that the hook took effect."""
+    path = {"BMO_FORCE_SORT_ORDER": "packed keys", "BMO_FORCE_DEEP_ORDER": "level by level"}[hook]
+    assert _node_orders(_child("chain", **{hook: "1"})) == [path]
+
+
+def test_splitter_chain_heap_index_without_a_hook():
+    """A fresh process with neither hook set orders the chain's four-level trees by heap index."""
+    assert _node_orders(_child("chain")) == ["heap index"]
 
 
 def _two_detector_scene():
@@ -136,24 +119,24 @@ def _two_detector_scene():
     return bmo.System([aside, lens, det])
 
 
-def test_no_hits_at_all(oracle, both):
+def test_no_hits_at_all(oracle):
     """Every ray leaves config 2's scene backwards: all counts 0, all offsets equal."""
     bundle = scenes.disc_bundle(600, center=[0, 0, -0.77 * mm], direction=[0, 0, -1], diameter=1 * mm, e1=[1, 0, 0])
     scene = bmo.CompiledScene(scenes.c2_scene()[0], bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "no hits")
+    got = _trace(scene, bundle)
     assert got.n_nodes == 600 and got.det_count.tolist() == [0, 0] and got.det_offset.tolist() == [0, 0] and got.det_node.size == 0
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "no hits, oracle")
 
 
-def test_all_hits_on_the_second_detector(oracle, both):
+def test_all_hits_on_the_second_detector(oracle):
     bundle = chain_bundle("ray", 600)
     scene = bmo.CompiledScene(_two_detector_scene(), bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "second detector only")
+    got = _trace(scene, bundle)
     assert got.det_count.tolist() == [0, 600] and got.det_offset.tolist() == [0, 0]
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "second detector only, oracle")
 
 
-def test_tiles_without_hits_between_tiles_with_one(oracle, both):
+def test_tiles_without_hits_between_tiles_with_one(oracle):
     """Only every 300th root looks at the detector, the others away from it: tiles with one hit, tiles with none between them and at the end."""
     n = 2100
     b = chain_bundle("ray", n)
@@ -162,7 +145,7 @@ def test_tiles_without_hits_between_tiles_with_one(oracle, both):
     planes[3:6, away] *= -1.0
     bundle = bmo.RayBundle(b.kind, planes)
     scene = bmo.CompiledScene(_two_detector_scene(), bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "every 300th")
+    got = _trace(scene, bundle)
     want = np.arange(0, n, 300)
     assert got.det_count.tolist() == [0, want.size] and np.array_equal(got.det_node, want)
     tiles = set((want // TILE).tolist())
@@ -170,17 +153,17 @@ def test_tiles_without_hits_between_tiles_with_one(oracle, both):
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "every 300th, oracle")
 
 
-def test_psf_detector_rows(oracle, both):
+def test_psf_detector_rows(oracle):
     """The Airy scene of the read-out tests under 512 rays: a PSFDetector keeps all nine columns of a row."""
     system, _, _, lam, D = airy_setup(num_rays=8)
     bundle = scenes.disc_bundle(512, center=[0, -10e-3, 0], direction=[0, 1, 0], diameter=D, lam=lam, e1=[1, 0, 0], jitter=0.0)
     scene = bmo.CompiledScene(system, bundle.lambdas)
-    got = both(lambda: _trace(scene, bundle), "airy scene")
+    got = _trace(scene, bundle)
     assert got.det_count.tolist() == [512] and np.isfinite(got.det_data).all() and (np.abs(got.det_data) > 0).any(axis=0).sum() >= 8
     compare(got, oracle.trace(scene, bundle, 100, threads=4), 0.0, "airy scene, oracle")
 
 
-def test_without_the_segment_log(oracle, both):
+def test_without_the_segment_log(oracle):
     """record_segments = 0: nodes, counts and detector rows as with the log; the segment count is still that of the beams."""
     bundle = scenes.c2_survey_bundle(2048)
     scene = bmo.CompiledScene(scenes.c2_scene()[0], bundle.lambdas)
@@ -199,16 +182,16 @@ def test_without_the_segment_log(oracle, both):
         finally:
             eng.close()
 
-    got = both(solve, "no log")
+    got = solve()
     ref = oracle.trace(scene, bundle, 100, threads=16)
-    assert sizes[0] == sizes[1] == (ref.n_intersect_calls, ref.n_records, ref.n_nodes, int(ref.det_count.sum()))
+    assert sizes[0] == (ref.n_intersect_calls, ref.n_records, ref.n_nodes, int(ref.det_count.sum()))
     for name in ("node_root", "node_parent", "node_first_child", "node_nseg", "node_status", "det_count", "det_offset", "det_node"):
         assert np.array_equal(getattr(got, name), getattr(ref, name)), name
     assert np.array_equal(got.det_data.view(np.int64), ref.det_data.view(np.int64))
 
 
-def test_retrace(oracle, both):
-    """A retrace after the splitter was tilted (192 rays): first solve and retrace, each both ways."""
+def test_retrace(oracle):
+    """A retrace after the splitter was tilted (192 rays): first solve and retrace."""
     case = RETRACE_CASES[0]
     scene0, scene1, bundle = retrace_pair("ray", case, 192)
     first = []
@@ -223,29 +206,27 @@ def test_retrace(oracle, both):
         finally:
             h0.free()
 
-    got = both(solve, case + ", retrace")
-    compare(first[0], first[1], 0.0, case + ", first solve, tiled against legacy")
+    got = solve()
     a0, sol = oracle.trace(scene0, bundle, 20, threads=8, keep=True)
     compare(first[0], a0, 0.0, case + ", first solve, oracle")
     compare(got, oracle.trace(scene1, bundle, 20, threads=8, prev=sol), 0.0, case + ", retrace, oracle")
 
 
-def test_sweep(both):
-    """4 configurations x 64 rays in one sweep: each configuration's slice against its separate solve, and the sweep both ways."""
+def test_sweep(oracle):
+    """4 configurations x 64 rays in one sweep: each configuration's slice against its separate solve and against the oracle."""
     system, _ = scenes.c2_scene()
     bundle = scenes.c2_bundle(64)
     snaps = _perturbed_snapshots(system, bundle.lambdas, 4, 11)
-    got = both(lambda: _sweep_vs_separate(snaps, [bundle] * 4, 100, label="c2 sweep"), "c2 sweep")
+    got = _sweep_vs_separate(snaps, [bundle] * 4, 100, label="c2 sweep", oracle=oracle, oracle_every=1)
     assert got.n_roots == 4 * 64 and got.det_count.sum() > 0
 
 
 def test_two_solves_of_one_batch():
-    """4 096 rays = 64 tiles of the step kernel through config 2, two solves of the resident batch each way: the results are equal, the first
-    solve of the batch has no tile costs, the later ones sort their tiles by the previous solve's."""
+    """4 096 rays = 64 tiles of the step kernel through config 2, two solves of the resident batch: the first equals the oracle's solution
+    and the second equals the first (the child compares), the first has no tile costs, the second sorts its tiles by the first one's."""
     err = _child("twice")
     order = [line.split("tile order: ")[1] for line in err.splitlines() if "tile order: " in line]
-    assert len(order) == 4 and order[0].startswith("as laid out") and all(o.startswith("by the cost") for o in order[1:]), order
-    assert err.count("finish pass: counts per tile") == 2 and err.count("finish pass: legacy") == 2, err[-2000:]
+    assert len(order) == 2 and order[0].startswith("as laid out") and order[1].startswith("by the cost"), order
 
 
 if __name__ == "__main__":  # the child processes of _child
@@ -254,26 +235,21 @@ if __name__ == "__main__":  # the child processes of _child
 
         b = chain_bundle("ray", 96)
         s = bmo.CompiledScene(_chain(4), b.lambdas)
-        got = _both_ways(lambda: _trace(s, b, CHAIN_R_MAX), "splitter chain")
-        compare(got, pyoracle.trace(s, b, CHAIN_R_MAX, threads=8), 0.0, "splitter chain, oracle")
+        compare(_trace(s, b, CHAIN_R_MAX), pyoracle.trace(s, b, CHAIN_R_MAX, threads=8), 0.0, "splitter chain, oracle")
     elif sys.argv[1:] == ["twice"]:
+        import pyoracle
+
         b = scenes.c2_survey_bundle(4096)
         s = bmo.CompiledScene(scenes.c2_scene()[0], b.lambdas)
         eng = bmo.Engine(s, 0)
         dev = eng.upload(b)
         views = []
 
-        def solve():
+        for _ in range(2):
             res = eng.trace_device(dev, 100)
             views.append(eng.result_view(res))
             eng.free_result(res)
-            return views[-1]
-
-        def twice():
-            solve()
-            return solve()
-
-        _both_ways(twice, "two solves of one batch")
+        compare(views[0], pyoracle.trace(s, b, 100, threads=16), 0.0, "two solves of one batch, first against the oracle")
         for v in views[1:]:
             compare(views[0], v, 0.0, "two solves of one batch, first against a later one")
         eng.free_batch(dev)

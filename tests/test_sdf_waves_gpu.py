@@ -79,7 +79,7 @@ def test_mixed_waves_through_both_wave_builds(monkeypatch, name):
         compare(got, ref, 0.0, f"{name}, BMO_WIDE_MIN_WAVES={w}")
 
 
-VARIANTS = [{"BMO_NO_LDS": "1"}, {"BMO_FUSE": "1"}, {"BMO_FUSE": "3"}]  # (of tests/test_fuzz.py's VARIANTS)
+VARIANTS = [{"BMO_FUSE": "1"}, {"BMO_FUSE": "3"}]  # (of tests/test_fuzz.py's VARIANTS; both wave builds: the test above)
 
 
 @pytest.mark.parametrize("env", VARIANTS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))

@@ -1,6 +1,5 @@
 """What a solve costs outside its step kernels: total_ms - kernel_ms of Engine.result_timing (device time between the events around the
-whole solve and around the step launches) for one bench workload, min / median / max over the solves; library from BMO_ENGINE_LIB,
-finish pass from BMO_FINISH.
+whole solve and around the step launches) for one bench workload, min / median / max over the solves; library from BMO_ENGINE_LIB.
     python tools/finish_pass_times.py c2s [rays [solves]]"""
 import os, statistics, sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -26,4 +25,4 @@ eng.free_batch(dev); eng.close()
 o = [b - a for a, b in zip(k, t)]
 f = lambda v: "%.4f / %.4f / %.4f" % (min(v), statistics.median(v), max(v))
 print("%-20s %-4s rays %8d  kernel_ms %s  total_ms %s  total - kernel %s  (min / median / max of %d solves, %d launches)" % (
-    (os.environ.get("BMO_ENGINE_LIB", "default")[-20:] + (" legacy" if os.environ.get("BMO_FINISH") == "legacy" else "")), name, n, f(k), f(t), f(o), reps, nl), flush=True)
+    os.environ.get("BMO_ENGINE_LIB", "default")[-20:], name, n, f(k), f(t), f(o), reps, nl), flush=True)
