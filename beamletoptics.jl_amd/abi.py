@@ -263,6 +263,8 @@ def load_engine():
     lib.bmo_psf_through_focus.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, dp, dp]
     lib.bmo_psf_focus_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
     lib.bmo_result_psf_rows.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    lib.bmo_psf_geo_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -466,6 +468,54 @@ def psf_focus_stats(hits, origin, e1, e2, axis, offsets, device=0, hits_device_p
     check(lib, lib.bmo_psf_focus_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp),
                                        off.ctypes.data_as(dp), len(off), int(device), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_focus_stats")
     return st, ms.value
+
+
+def _freqs(freqs):
+    """Frequencies (fx, fz) in cycles per metre as a contiguous [nf, 2] array."""
+    return np.ascontiguousarray(np.asarray(freqs, dtype=np.float64).reshape(-1, 2))
+
+
+def psf_geo_otf(hits, origin, e1, e2, axis, offsets, freqs, centers=None, device=0, hits_device_ptr=None, n_hits=None):
+    """bmo_psf_geo_otf: the geometric transfer function T(f) = sum proj cis(-2 pi (fx x + fz z)) of the rows propagated to the detector plane
+    moved by offsets[m] * axis, at the frequencies `freqs` [nf, 2] (cycles per metre, local x and z); centers: None or [M, 2], the point of
+    each plane the phase is counted from.  Returns (mtf [M, nf], otf [M, nf] complex, sums [M], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2, ax = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2, axis))
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64).reshape(-1))
+    fq = _freqs(freqs)
+    M, nf = len(off), len(fq)
+    cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_geo_otf(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp), off.ctypes.data_as(dp),
+                                   None if cen is None else cen.ctypes.data_as(dp), M, fq.ctypes.data_as(dp), nf, int(device), otf.ctypes.data_as(dp),
+                                   mtf.ctypes.data_as(dp), sums.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_geo_otf")
+    return mtf, otf[..., 0] + 1j * otf[..., 1], sums, ms.value
+
+
+def psf_otf(hits, origin, e1, e2, displacements, xs, zs, freqs, device=0, hits_device_ptr=None, n_hits=None, want_intensity=False):
+    """bmo_psf_otf: the transform of the through-focus stack (psf_through_focus of the same arguments, kept on the device) at the frequencies
+    `freqs` [nf, 2] (cycles per metre).  Returns (mtf [M, nf], otf [M, nf] complex, sums [M], I[M, n, n] indexed [m, i, j] or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    d = np.ascontiguousarray(np.asarray(displacements, dtype=np.float64).reshape(-1, 3))
+    x, z = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(zs, dtype=np.float64)
+    fq = _freqs(freqs)
+    n, M, nf = len(x), len(d), len(fq)
+    if len(z) != n:
+        raise ValueError("xs and zs must have the same length")
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
+    img = np.zeros(M * n * n) if want_intensity else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_otf(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
+                               z.ctypes.data_as(dp), n, fq.ctypes.data_as(dp), nf, int(device), otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp),
+                               sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_otf")
+    I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
+    return mtf, otf[..., 0] + 1j * otf[..., 1], sums, I, ms.value
 
 
 def zernike_sizes(order):

@@ -488,12 +488,13 @@ def best_focus(offsets, values, kind="min"):
     return float(xv), float(y[i - 1] + d1 * (xv - x[i - 1]) + a * (xv - x[i - 1]) * (xv - x[i]))
 
 
-def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0):
+def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0, half_width=None):
     """The through-focus stack of PSF rows read through stats_fn(axis, offsets) -> focus statistics [M, 12] and stack_fn(displacements, xs, zs)
     -> I[M, n, n]: what PSFDetector.through_focus and EngineSolution.psf_through_focus share.  Plane m is the detector plane moved by
     offsets[m] along `axis` (None: the detector's local y).  The window is common to the stack: the half-widths of plane `window_plane`
-    (None: the plane of least RMS radius) times crop_factor, xs and zs running over -hw .. +hw about each plane's centre.  The centre of
-    plane m is its own centroid (follow="centroid": the grid follows the chief ray) or the centroid of the window plane (follow=None).
+    (None: the plane of least RMS radius) times crop_factor, or `half_width` (one number, or (hwx, hwz)) where it is given, xs and zs running
+    over -hw .. +hw about each plane's centre.  The centre of plane m is its own centroid (follow="centroid": the grid follows the chief
+    ray) or the centroid of the window plane (follow=None).
     Returns (xs, zs, displacements [M, 3], I[M, n, n], stats): the point (i, j) of plane m lies at origin + xs[i] e1 + zs[j] e2 + d_m."""
     from . import abi
 
@@ -512,10 +513,111 @@ def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None
         raise ValueError("through_focus: no plane has statistics (a row runs parallel to the detector plane)")
     w = int(np.nanargmin(st[:, abi.FOCUS_RMS_R])) if window_plane is None else int(window_plane)
     hwx, hwz = st[w, abi.FOCUS_HWX] * crop_factor, st[w, abi.FOCUS_HWZ] * crop_factor
+    if half_width is not None:
+        hwx, hwz = (float(v) for v in np.broadcast_to(np.asarray(half_width, dtype=np.float64), (2,)))
     xs, zs = la.linrange(-hwx, hwx, n), la.linrange(-hwz, hwz, n)
     centre = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]] if follow == "centroid" else np.tile(st[w, [abi.FOCUS_CX, abi.FOCUS_CZ]], (len(off), 1))
     d = off[:, None] * ax[None, :] + centre[:, 0:1] * e1[None, :] + centre[:, 1:2] * e2[None, :]
     return xs, zs, d, stack_fn(d, xs, zs), st
+
+
+# The MTF read-out (include/bmo.h "MTF read-out").  Frequencies are (fx, fz) in cycles per metre in the detector's local frame.
+def mtf_frequencies(f_max, n, azimuth_deg=0.0):
+    """[n, 2]: n frequencies from 0 to f_max along the direction at `azimuth_deg` from the local x axis (0: tangential x, 90: z)."""
+    a = math.radians(float(azimuth_deg))
+    f = float(f_max) * np.arange(int(n), dtype=np.float64) / max(int(n) - 1, 1)
+    return np.stack([f * math.cos(a), f * math.sin(a)], axis=1)
+
+
+def mtf_cutoff(k_max, rho):
+    """The incoherent cutoff 2 NA / lambda = rho k / pi in cycles per metre: rho the pupil radius in direction cosines (abi.ZERN_RHO of the
+    Zernike info), k the wave number (abi.PSF_K_MAX of the wavefront statistics)."""
+    return float(rho) * float(k_max) / math.pi
+
+
+def mtf_diffraction_limit(s):
+    """The MTF of an aberration-free circular pupil at s = |f| / cutoff: 2 / pi (acos s - s sqrt(1 - s^2)), and 0 beyond 1."""
+    s = np.abs(np.asarray(s, dtype=np.float64))
+    t = np.minimum(s, 1.0)
+    return np.where(s < 1.0, 2.0 / math.pi * (np.arccos(t) - t * np.sqrt(1.0 - t * t)), 0.0)
+
+
+def mtf_window(k_max, rho, n_rows, f_max, airy_radii=10):
+    """(half_width, n) of the image grid whose transform is the diffraction MTF up to f_max.  A sum of H plane waves repeats: a disc of H
+    directions has the spacing du = rho sqrt(pi / H), so the PSF has replicas at L = 2 pi / (k du), and a window wider than L transforms
+    them too.  The half-width is the smaller of `airy_radii` Airy radii (1.22 pi / (k rho) each) and 0.35 L; n makes the pitch
+    2 half_width / (n - 1) at most 0.75 of the Nyquist pitch 1 / (2 f_max)."""
+    k, rho, H = float(k_max), float(rho), int(n_rows)
+    if not (k > 0 and rho > 0 and H > 0 and math.isfinite(k) and math.isfinite(rho)):
+        raise ValueError("mtf_window: needs a wave number, a pupil radius and a row count above zero (give half_width and n instead)")
+    replica = 2 * math.pi / (k * rho * math.sqrt(math.pi / H))
+    hw = min(float(airy_radii) * 1.22 * math.pi / (k * rho), 0.35 * replica)
+    return hw, mtf_grid_points(hw, f_max)
+
+
+def mtf_grid_points(half_width, f_max):
+    """The least n at which the pitch 2 half_width / (n - 1) is at most 0.75 / (2 f_max); at least 2."""
+    hw = float(np.max(half_width))
+    if not float(f_max) > 0:
+        return 2
+    return max(2, int(math.ceil(2 * hw / (0.75 / (2 * float(f_max))) * (1 - 1e-12))) + 1)
+
+
+def mtf_check_pitch(xs, zs, freqs):
+    """Raises ValueError where the grid (xs, zs) samples too coarsely for `freqs`: a pitch above 1 / (2 max |f|) along its axis aliases."""
+    fq = np.abs(np.asarray(freqs, dtype=np.float64).reshape(-1, 2))
+    for name, ax, f in (("x", xs, fq[:, 0].max()), ("z", zs, fq[:, 1].max())):
+        if len(ax) > 1 and f > 0:
+            pitch = float(np.max(np.abs(np.diff(ax))))
+            if pitch > 1 / (2 * f):
+                raise ValueError("mtf: the %s pitch %.3e m exceeds 1 / (2 max |f%s|) = %.3e m: the image would alias (raise n or shrink the window)"
+                                 % (name, pitch, name, 1 / (2 * f)))
+
+
+def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.0,), kind="diffraction", n=None, half_width=None, axis=None,
+            follow="centroid"):
+    """The MTF of PSF rows on the detector plane moved by each of `offsets` along `axis` (None: local y), at `freqs` [nf, 2] in cycles per
+    metre: what PSFDetector.mtf and EngineSolution.psf_mtf share.  stats_fn(axis, offsets) -> focus statistics [M, 12];
+    geo_fn(axis, offsets, freqs, centers) and otf_fn(displacements, xs, zs, freqs) -> (mtf, otf, sums); window_fn() -> (k_max, rho, n_rows).
+    kind "geometric": the transform of the propagated rows, the phase counted from each plane's centroid (follow="centroid") or from the
+    centroid of the plane of least RMS radius (follow=None).  kind "diffraction": the transform of the through-focus stack on the grid of
+    psf_through_focus with the same `follow`; half_width None takes mtf_window's, n None the least n that mtf_window's pitch rule allows.
+    Returns (mtf [M, nf], otf [M, nf] complex, sums [M], stats [M, 12])."""
+    from . import abi
+
+    if kind not in ("diffraction", "geometric"):
+        raise ValueError('mtf: kind must be "diffraction" or "geometric"')
+    if follow not in ("centroid", None):
+        raise ValueError('mtf: follow must be "centroid" or None')
+    fq = np.asarray(freqs, dtype=np.float64).reshape(-1, 2)
+    if len(fq) == 0 or not np.isfinite(fq).all():
+        raise ValueError("mtf: needs at least one frequency, all finite")
+    if kind == "geometric":
+        o = np.asarray(orientation, dtype=np.float64)
+        ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
+        off = np.asarray(offsets, dtype=np.float64).reshape(-1)
+        if len(off) == 0:
+            raise ValueError("mtf: no offsets")
+        st = stats_fn(ax, off)
+        centers = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]]
+        if follow is None and not np.isnan(st[:, abi.FOCUS_RMS_R]).all():
+            centers = np.tile(centers[int(np.nanargmin(st[:, abi.FOCUS_RMS_R]))], (len(off), 1))
+        mtf, otf, sums = geo_fn(ax, off, fq, np.ascontiguousarray(centers))
+        return mtf, otf, sums, st
+    f_max = float(np.abs(fq).max())
+    if half_width is None:
+        half_width, n_rule = mtf_window(*window_fn(), f_max)
+    else:
+        n_rule = mtf_grid_points(half_width, f_max)
+    n = n_rule if n is None else int(n)
+    out = {}
+
+    def stack_fn(d, xs, zs):
+        mtf_check_pitch(xs, zs, fq)
+        out["r"] = otf_fn(d, xs, zs, fq)
+
+    _, _, _, _, st = psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=n, axis=axis, follow=follow, half_width=half_width)
+    return out["r"] + (st,)
 
 
 def zernike_terms(order):
@@ -618,6 +720,25 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
         return psf_through_focus(lambda ax, off: abi.psf_focus_stats(self.data, pos, o[:, 0], o[:, 2], ax, off, device=device)[0],
                                  lambda d, xs, zs: abi.psf_through_focus(self.data, pos, o[:, 0], o[:, 2], d, xs, zs, device=device)[0],
                                  o, offsets, n=n, axis=axis, follow=follow, window_plane=window_plane, crop_factor=crop_factor)
+
+    def mtf(self, freqs, offsets=(0.0,), kind="diffraction", n=None, half_width=None, axis=None, follow="centroid", device=0):
+        """The MTF of all rows accumulated so far at `freqs` [nf, 2] (cycles per metre, local x and z; mtf_frequencies makes a radial cut) on
+        the detector plane moved by each of `offsets` along `axis`: (mtf [M, nf], otf [M, nf] complex, sums [M], stats [M, 12]) as psf_mtf
+        describes them.  kind "diffraction": bmo_psf_otf, the transform of the through-focus stack; "geometric": bmo_psf_geo_otf."""
+        from . import abi
+
+        o, pos = self.orientation(), self.position()
+        e1, e2 = o[:, 0], o[:, 2]
+
+        def window_fn():
+            st = abi.psf_stats(self.data, pos, e1, e2, device=device)[0]
+            info = abi.psf_zernike(self.data, pos, e1, e2, order=0, device=device)[1]
+            return st[abi.PSF_K_MAX], info[abi.ZERN_RHO], int(st[abi.PSF_N])
+
+        return psf_mtf(lambda ax, off: abi.psf_focus_stats(self.data, pos, e1, e2, ax, off, device=device)[0],
+                       lambda ax, off, fq, cen: abi.psf_geo_otf(self.data, pos, e1, e2, ax, off, fq, centers=cen, device=device)[:3],
+                       lambda d, xs, zs, fq: abi.psf_otf(self.data, pos, e1, e2, d, xs, zs, fq, device=device)[:3],
+                       window_fn, o, freqs, offsets=offsets, kind=kind, n=n, half_width=half_width, axis=axis, follow=follow)
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

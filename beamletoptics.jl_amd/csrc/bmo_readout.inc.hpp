@@ -2112,9 +2112,10 @@ __global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double*
 
 }  // namespace
 
-// The stack of n_planes planes from the n_hits > 0 device rows `hits`.
-static int psf_focus_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* disp, int32_t n_planes,
-                          const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field, double* kernel_ms) {
+// The stack of n_planes planes from the n_hits > 0 device rows `hits`, left on the device: d_int [n_planes][n * n], and d_field likewise when
+// want_field.  `timer` runs from the first launch; the caller may queue more behind the stack on stream 0 and stop it again.
+static int psf_focus_stack(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* disp, int32_t n_planes,
+                           const double* xs, const double* zs, int32_t n, bool want_field, DevBuf& d_int, DevBuf& d_field, EventTimer& timer, double* kernel_ms) {
     const int64_t n_pts = (int64_t)n * n;
     const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
     const size_t n_out = (size_t)n_planes * (size_t)n_pts;
@@ -2124,13 +2125,11 @@ static int psf_focus_read(const double* hits, int64_t n_hits, const double* orig
     const PsfPose pose{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}};
     Packed up;
     const size_t o_cfg = up.add(plan.cfg), o_xs = up.add(xs, (size_t)n), o_zs = up.add(zs, (size_t)n), o_d = up.add(disp, (size_t)n_planes * 3);
-    DevBuf d_int, d_field;
     int rc;
-    if ((rc = up.upload(st)) || (rc = d_int.alloc(n_out * sizeof(double))) || (out_field && (rc = d_field.alloc(n_out * sizeof(double2))))) return rc;
+    if ((rc = up.upload(st)) || (rc = d_int.alloc(n_out * sizeof(double))) || (want_field && (rc = d_field.alloc(n_out * sizeof(double2))))) return rc;
     // planes per pass: whole chunks, partial sums of at most 1 GiB (one chunk if a single one needs more)
     const int64_t fit = ((int64_t)1 << 30) / (plan.max_nw * n_pts * (int64_t)sizeof(double2)) / PSF_FOCUS_MP * PSF_FOCUS_MP;
     const int32_t per_pass = (int32_t)std::min<int64_t>(std::max<int64_t>(fit, PSF_FOCUS_MP), (int64_t)65535 * PSF_FOCUS_MP);
-    EventTimer timer;
     for (int32_t m_pass = 0; m_pass < n_planes; m_pass += per_pass) {
         const int32_t pass_planes = std::min(per_pass, n_planes - m_pass);
         auto accumulate = [&](dim3, const SplitPlan::Launch& L, double2* partial) {
@@ -2147,9 +2146,19 @@ static int psf_focus_read(const double* hits, int64_t n_hits, const double* orig
             else if (rest > 1) launch(std::integral_constant<int, 2>{}, m_rest, 1);
             else if (rest > 0) launch(std::integral_constant<int, 1>{}, m_rest, 1);
         };
-        const PsfFinish finish{(double*)d_int.p + (int64_t)m_pass * n_pts, out_field ? (double2*)d_field.p + (int64_t)m_pass * n_pts : nullptr};
+        const PsfFinish finish{(double*)d_int.p + (int64_t)m_pass * n_pts, want_field ? (double2*)d_field.p + (int64_t)m_pass * n_pts : nullptr};
         if ((rc = split_reduce(plan, up.at<SplitCfg>(o_cfg), (int64_t)pass_planes * n_pts, st, timer, kernel_ms, accumulate, finish))) return rc;
     }
+    return BMO_OK;
+}
+
+// The stack copied to the caller.
+static int psf_focus_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* disp, int32_t n_planes,
+                          const double* xs, const double* zs, int32_t n, double* out_intensity, double* out_field, double* kernel_ms) {
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    DevBuf d_int, d_field;
+    EventTimer timer;
+    if (int rc = psf_focus_stack(hits, n_hits, origin, e1, e2, disp, n_planes, xs, zs, n, out_field != nullptr, d_int, d_field, timer, kernel_ms)) return rc;
     HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
     if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, n_out * sizeof(double2), hipMemcpyDeviceToHost));
     return BMO_OK;
@@ -2362,6 +2371,277 @@ extern "C" int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t h
         return BMO_OK;
     }
     return psf_focus_stats_read(hits, n_hits, origin, e1, e2, axis, offsets, n_planes, stats, kernel_ms, "bmo_psf_focus_stats");
+}
+
+// ====================================================================================================================
+// MTF read-out (include/bmo.h "MTF read-out"): the transfer function T(f) = sum w cis(-2 pi (fx x + fz z)) of the rows propagated to a stack
+// of planes (geometric), and of the images of the through-focus stack (diffraction).
+//
+// Geometric.  The PSF kernel's shape with a (plane, frequency) pair for a point: a workgroup owns one split of the rows (the splits of
+// spot_splits), one chunk of MP planes and 256 / MP frequencies; lane l holds the sum of pair (l / (256 / MP), l % (256 / MP)) of them.  Per
+// staged tile of 256 rows lane r propagates row r to the chunk's planes (focus_local: one division per row and plane, not per pair) and
+// writes (x - cx_m, z - cz_m) to LDS laid out [plane][row] (consecutive lanes, consecutive addresses); every lane then walks the tile, the
+// lanes of a plane reading one address (broadcast reads).  18 KB of row tile + MP * 4 KB: 50 KB at MP = 8, three workgroups per CU.  The
+// sum of a pair runs over the rows of a split in row order and the splits are folded in split order, whatever the chunking: the value
+// does not depend on the planes and frequencies asked for along with it.  S and the count of rows parallel to the planes are summed in the
+// order of the focus statistics (lane r adds the rows it propagates; sum_wg_reduce; sum_reduce_kernel): S equals BMO_FOCUS_STAT_S.
+namespace {
+
+constexpr int GEO_OTF_MP = 8;  // planes per chunk of a stack; a stack of fewer planes runs the next power of two
+
+#define GEO_OTF_SUM(F) F(s, SumAdd) F(bad, SumAdd)
+SUM_RECORD(GeoOtfSum, GEO_OTF_SUM);
+
+// split blockIdx.y (work item) of the rows, planes blockIdx.z * MP .., frequencies blockIdx.x * (256 / MP) ..; partial: [item][plane][freq]
+template <int MP>
+__global__ __launch_bounds__(256) void psf_geo_otf_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                          const double* __restrict__ offsets, const double2* __restrict__ centers, int32_t n_planes,
+                                                          const double2* __restrict__ freqs, int32_t n_freqs, double2* __restrict__ partial,
+                                                          GeoOtfSum* __restrict__ sums) {
+    constexpr int FB = 256 / MP;
+    static_assert(MP >= 1 && MP <= 8 && 256 % MP == 0, "a chunk of planes divides the workgroup");
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double2 xz[MP * PSF_TILE];
+    const SplitWork W = work[blockIdx.y];
+    const int32_t m0 = (int32_t)blockIdx.z * MP;
+    const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;  // planes of this chunk; the slots past them repeat its first and are not stored
+    d3 o[MP];
+    double2 c[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        const int32_t mm = m0 + (m < mcnt ? m : 0);
+        o[m] = focus_origin(F, offsets[mm]);
+        c[m] = centers ? centers[mm] : make_double2(0.0, 0.0);
+    }
+    const int ml = (int)threadIdx.x / FB;
+    const int32_t f = (int32_t)blockIdx.x * FB + (int)threadIdx.x % FB;
+    const bool live = ml < mcnt && f < n_freqs;
+    const double2 fq = live ? freqs[f] : make_double2(0.0, 0.0);
+    GeoOtfSum a = sum_identity<GeoOtfSum>();
+    double re = 0.0, im = 0.0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);  // its first sync: the walk over the tile before is done
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double den = focus_den(r, F);
+            a.s += r[7];
+            a.bad += den == 0.0 ? 1.0 : 0.0;
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                double x, z;
+                focus_local(r, F, o[m], den, x, z);
+                xz[m * PSF_TILE + threadIdx.x] = make_double2(x - c[m].x, z - c[m].y);
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const double2* p = xz + ml * PSF_TILE;
+            for (int h = 0; h < cnt; ++h) {
+                const double w = tile[9 * h + 7];
+                const double arg = fq.x * p[h].x + fq.y * p[h].y;
+                double s, cs;
+                sincospi(-2.0 * arg, &s, &cs);
+                re += w * cs;
+                im += w * s;
+            }
+        }
+    }
+    if (live) partial[((int64_t)blockIdx.y * n_planes + (m0 + ml)) * n_freqs + f] = make_double2(re, im);
+    if (blockIdx.x == 0 && blockIdx.z == 0) {  // uniform over the workgroup: one record per work item
+        a = sum_wg_reduce(a);
+        if (threadIdx.x == 0) sums[blockIdx.y] = a;
+    }
+}
+
+// S of the call, NaN when a row runs parallel to the planes
+struct GeoOtfSumFinish {
+    double* s;
+    __device__ void empty(int32_t) const {}  // a call with rows has work items
+    __device__ void operator()(int32_t, const GeoOtfSum& a) const { *s = a.bad != 0.0 ? knan() : a.s; }
+};
+
+// pair (plane, frequency) = blockIdx.x * 256 + threadIdx.x: its partial sums folded in split order; otf, mtf and, from the pairs of
+// frequency 0, sums
+__global__ void psf_geo_otf_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pairs, int32_t n_freqs, const double* __restrict__ s_all,
+                                          double2* __restrict__ otf, double* __restrict__ mtf, double* __restrict__ sums) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pairs) return;
+    double re = 0.0, im = 0.0;
+    for (int32_t s = 0; s < n_splits; ++s) {
+        const double2 v = partial[(int64_t)s * n_pairs + q];
+        re += v.x;
+        im += v.y;
+    }
+    const double S = *s_all;
+    if (S != S) re = im = knan();  // a row parallel to the planes (or a NaN proj): no transfer function
+    otf[q] = make_double2(re, im);
+    mtf[q] = sqrt(re * re + im * im) / S;
+    if (q % n_freqs == 0) sums[q / n_freqs] = S;
+}
+
+// Diffraction: the transform of the stack's images where they lie, separable.  Thread (plane m, slot f, row j) sums image row j against the
+// x factors of frequency f; slot n_freqs has the factor (1, 0), whose transform is the plane's sum.
+__global__ void psf_otf_rows_kernel(const double* __restrict__ img, const double* __restrict__ xs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
+                                    int64_t n_threads, double2* __restrict__ rowsum) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_threads) return;  // n_planes * (n_freqs + 1) * n
+    const int32_t j = (int32_t)(t % n), f = (int32_t)(t / n % (n_freqs + 1));
+    const int64_t m = t / n / (n_freqs + 1);
+    const double* row = img + (m * n + j) * n;
+    double re = 0.0, im = 0.0;
+    if (f == n_freqs) {
+        for (int32_t i = 0; i < n; ++i) {
+            re += row[i] * 1.0;
+            im += row[i] * 0.0;
+        }
+    } else {
+        const double fx = freqs[f].x;
+        for (int32_t i = 0; i < n; ++i) {
+            double s, c;
+            sincospi(-2.0 * (fx * xs[i]), &s, &c);
+            re += row[i] * c;
+            im += row[i] * s;
+        }
+    }
+    rowsum[t] = make_double2(re, im);  // [m][f][j]
+}
+
+// thread (plane m, frequency f): the row sums against the z factors, j ascending; the plane's sum the same way from slot n_freqs
+__global__ void psf_otf_cols_kernel(const double2* __restrict__ rowsum, const double* __restrict__ zs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
+                                    int64_t n_pairs, double2* __restrict__ otf, double* __restrict__ mtf, double* __restrict__ sums) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pairs) return;
+    const int64_t m = q / n_freqs;
+    const int32_t f = (int32_t)(q % n_freqs);
+    const double2* r = rowsum + (m * (n_freqs + 1) + f) * n;
+    const double2* r1 = rowsum + (m * (n_freqs + 1) + n_freqs) * n;
+    const double fz = freqs[f].y;
+    double re = 0.0, im = 0.0, S = 0.0;
+    for (int32_t j = 0; j < n; ++j) {
+        double s, c;
+        sincospi(-2.0 * (fz * zs[j]), &s, &c);
+        re += r[j].x * c - r[j].y * s;
+        im += r[j].x * s + r[j].y * c;
+        S += r1[j].x * 1.0 - r1[j].y * 0.0;
+    }
+    otf[q] = make_double2(re, im);
+    mtf[q] = sqrt(re * re + im * im) / S;
+    if (f == 0) sums[m] = S;
+}
+
+}  // namespace
+
+// what the two MTF entries refuse of their frequencies
+static bool otf_freqs_ok(const double* freqs, int32_t n_freqs) {
+    for (int64_t q = 0; q < 2 * (int64_t)n_freqs; ++q)
+        if (!std::isfinite(freqs[q])) return false;
+    return true;
+}
+// what a call without rows reads: zeros, and NaN (0 / 0) in mtf
+static void otf_fill_empty(size_t n_pairs, size_t n_planes, double* otf, double* mtf, double* sums) {
+    std::fill(otf, otf + 2 * n_pairs, 0.0);
+    std::fill(mtf, mtf + n_pairs, std::nan(""));
+    std::fill(sums, sums + n_planes, 0.0);
+}
+
+// The geometric transfer function of the n_hits > 0 device rows `hits` [..][9].
+static int psf_geo_otf_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* axis, const double* offsets,
+                            const double* centers, int32_t n_planes, const double* freqs, int32_t n_freqs, double* otf, double* mtf, double* sums, double* kernel_ms,
+                            const char* who) {
+    RowPasses P(Ranges{{0}, {n_hits}});  // the plan, the upload and the reduce of the statistics passes: S is one
+    if (int rc = P.items(who)) return rc;
+    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
+    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    int mp = 1;
+    while (mp < GEO_OTF_MP && mp < n_planes) mp *= 2;
+    const unsigned chunks = (unsigned)((n_planes + mp - 1) / mp), f_blocks = (unsigned)(((int64_t)n_freqs + 256 / mp - 1) / (256 / mp));
+    const int64_t n_pairs = (int64_t)n_planes * n_freqs;
+    if (chunks > 65535 || P.n_items > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
+    // a pair's value does not depend on the pairs asked for along with it: a caller with more of them splits the call
+    if ((int64_t)P.n_items * n_pairs > ((int64_t)1 << 32) / (int64_t)sizeof(double2))
+        return fail(BMO_ERR_LIMIT, std::string(who) + ": the partial sums of n_planes * n_freqs pairs pass 4 GiB; ask for them in several calls");
+    const size_t o_off = P.up.add(offsets, (size_t)n_planes), o_freq = P.up.add(freqs, (size_t)n_freqs * 2);
+    const size_t o_cen = centers ? P.up.add(centers, (size_t)n_planes * 2) : 0;
+    DevBuf d_partial, d_s, d_otf, d_mtf, d_sums;
+    int rc;
+    if ((rc = d_partial.alloc((size_t)P.n_items * (size_t)n_pairs * sizeof(double2))) || (rc = d_s.alloc(8)) || (rc = d_otf.alloc((size_t)n_pairs * sizeof(double2))) ||
+        (rc = d_mtf.alloc((size_t)n_pairs * 8)) || (rc = d_sums.alloc((size_t)n_planes * 8)) || (rc = P.begin<GeoOtfSum>()))
+        return rc;
+    const double2* d_cen = centers ? P.up.at<double2>(o_cen) : nullptr;
+    auto launch = [&](auto MP) {
+        hipLaunchKernelGGL(psf_geo_otf_kernel<decltype(MP)::value>, dim3(f_blocks, P.n_items, chunks), dim3(256), 0, P.st, hits, P.work(), F, P.up.at<double>(o_off), d_cen,
+                           n_planes, P.up.at<double2>(o_freq), n_freqs, (double2*)d_partial.p, (GeoOtfSum*)P.records.p);
+    };
+    if (mp == 1) launch(std::integral_constant<int, 1>{});
+    else if (mp == 2) launch(std::integral_constant<int, 2>{});
+    else if (mp == 4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, GEO_OTF_MP>{});
+    sum_reduce<GeoOtfSum>(1u, P.st, P.cfg(), P.records, GeoOtfSumFinish{(double*)d_s.p});
+    hipLaunchKernelGGL(psf_geo_otf_reduce_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, P.st, (const double2*)d_partial.p, (int32_t)P.n_items, n_pairs, n_freqs,
+                       (const double*)d_s.p, (double2*)d_otf.p, (double*)d_mtf.p, (double*)d_sums.p);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(otf, d_otf.p, (size_t)n_pairs * sizeof(double2), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mtf, d_mtf.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_geo_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                               const double axis[3], const double* offsets, const double* centers, int32_t n_planes, const double* freqs, int32_t n_freqs, int32_t device,
+                               double* otf, double* mtf, double* sums, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !axis || !offsets || !freqs || !otf || !mtf || !sums || n_planes <= 0 || n_freqs <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_geo_otf: bad argument (null pointer, n_planes <= 0, n_freqs <= 0, n_hits < 0)");
+    if (!otf_freqs_ok(freqs, n_freqs)) return fail(BMO_ERR_INVALID, "bmo_psf_geo_otf: a frequency is not finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_geo_otf", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (n_hits == 0) {
+        otf_fill_empty((size_t)n_planes * (size_t)n_freqs, (size_t)n_planes, otf, mtf, sums);
+        return BMO_OK;
+    }
+    return psf_geo_otf_read(hits, n_hits, origin, e1, e2, axis, offsets, centers, n_planes, freqs, n_freqs, otf, mtf, sums, kernel_ms, "bmo_psf_geo_otf");
+}
+
+extern "C" int bmo_psf_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                           const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* freqs, int32_t n_freqs,
+                           int32_t device, double* otf, double* mtf, double* sums, double* out_intensity, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !displacements || !xs || !zs || !freqs || !otf || !mtf || !sums || n <= 0 || n_planes <= 0 || n_freqs <= 0 || n_hits < 0 ||
+        (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_otf: bad argument (null pointer, n <= 0, n_planes <= 0, n_freqs <= 0, n_hits < 0)");
+    if (!otf_freqs_ok(freqs, n_freqs)) return fail(BMO_ERR_INVALID, "bmo_psf_otf: a frequency is not finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_otf", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    const int64_t n_pairs = (int64_t)n_planes * n_freqs;
+    if (n_hits == 0) {
+        otf_fill_empty((size_t)n_pairs, (size_t)n_planes, otf, mtf, sums);
+        if (out_intensity) std::fill(out_intensity, out_intensity + n_out, 0.0);
+        return BMO_OK;
+    }
+    const int64_t n_rowsums = (int64_t)n_planes * (n_freqs + 1) * n;
+    if ((n_rowsums + 255) / 256 > (int64_t)0x7fffffff) return fail(BMO_ERR_LIMIT, "bmo_psf_otf: more row sums than one launch holds");
+    hipStream_t st = 0;
+    DevBuf d_int, d_field, d_rowsum, d_otf, d_mtf, d_sums;
+    Packed up;
+    const size_t o_xs = up.add(xs, (size_t)n), o_zs = up.add(zs, (size_t)n), o_freq = up.add(freqs, (size_t)n_freqs * 2);
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_rowsum.alloc((size_t)n_rowsums * sizeof(double2))) || (rc = d_otf.alloc((size_t)n_pairs * sizeof(double2))) ||
+        (rc = d_mtf.alloc((size_t)n_pairs * 8)) || (rc = d_sums.alloc((size_t)n_planes * 8)))
+        return rc;
+    EventTimer timer;
+    if ((rc = psf_focus_stack(hits, n_hits, origin, e1, e2, displacements, n_planes, xs, zs, n, false, d_int, d_field, timer, kernel_ms))) return rc;
+    hipLaunchKernelGGL(psf_otf_rows_kernel, dim3((unsigned)((n_rowsums + 255) / 256)), dim3(256), 0, st, (const double*)d_int.p, up.at<double>(o_xs), n,
+                       up.at<double2>(o_freq), n_freqs, n_rowsums, (double2*)d_rowsum.p);
+    hipLaunchKernelGGL(psf_otf_cols_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, (const double2*)d_rowsum.p, up.at<double>(o_zs), n,
+                       up.at<double2>(o_freq), n_freqs, n_pairs, (double2*)d_otf.p, (double*)d_mtf.p, (double*)d_sums.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(otf, d_otf.p, (size_t)n_pairs * sizeof(double2), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mtf, d_mtf.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    if (out_intensity) HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return BMO_OK;
 }
 
 // the resident PSF rows of slot `detector`, for the single-call read-outs that take a device pointer: bmo_result_device_hits with the checks

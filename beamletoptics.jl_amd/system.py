@@ -522,6 +522,31 @@ class EngineSolution:
         self.readout_ms = ms[0] + ms[1]
         return out
 
+    def psf_mtf(self, slot, position, orientation, freqs, offsets=(0.0,), kind="diffraction", n=None, half_width=None, axis=None, follow="centroid"):
+        """The MTF of the resident rows of PSFDetector slot `slot` (bmo_psf_focus_stats, then bmo_psf_otf or bmo_psf_geo_otf on the device
+        pointer: no row and no image leaves the device): (mtf [M, nf], otf [M, nf] complex, sums [M], stats [M, 12]) as PSFDetector.mtf gives
+        them from host rows."""
+        o = np.asarray(orientation, dtype=np.float64)
+        e1, e2 = o[:, 0], o[:, 2]
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        rows = dict(device=dev, hits_device_ptr=ptr, n_hits=cnt)
+        ms = []
+
+        def timed(out):
+            ms.append(out[-1])
+            return out
+
+        def window_fn():
+            st, info = self.psf_stats(slot, position, o), self.psf_zernike(slot, position, o, order=0)[1]
+            return st[abi.PSF_K_MAX], info[abi.ZERN_RHO], int(st[abi.PSF_N])
+
+        out = cp.psf_mtf(lambda ax, off: timed(abi.psf_focus_stats(None, position, e1, e2, ax, off, **rows))[0],
+                         lambda ax, off, fq, cen: timed(abi.psf_geo_otf(None, position, e1, e2, ax, off, fq, centers=cen, **rows))[:3],
+                         lambda d, xs, zs, fq: timed(abi.psf_otf(None, position, e1, e2, d, xs, zs, fq, **rows))[:3],
+                         window_fn, o, freqs, offsets=offsets, kind=kind, n=n, half_width=half_width, axis=axis, follow=follow)
+        self.readout_ms = float(sum(ms))
+        return out
+
     def psf_intensity(self, slot, position, orientation, n=100, **window_kw):
         """intensity(psf; ...) of the resident rows of PSFDetector slot `slot`: (xs, zs, I[n, n]).  The window comes from psf_stats
         (components.psf_axes_from_stats takes window_kw), the image from bmo_psf_intensity_sweep: only the image leaves the device."""

@@ -733,6 +733,50 @@ int bmo_psf_focus_stats(const double* hits, int64_t n_hits, int32_t hits_on_devi
                         double* kernel_ms);
 int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, const double** data, int64_t* count, int32_t* device);
 
+/* ------------------------------------------------------------------------------------------------
+ * MTF read-out: the transfer function of a PSFDetector's rows on a stack of planes, computed on the device from the rows where they lie.
+ * Frequencies f = (fx, fz) are in cycles per metre in the detector's local (x, z) frame.  One sign and unit convention for both entries:
+ *   T(f) = sum w * cis(-2 pi (fx * x + fz * z)),      MTF(f) = |T(f)| / T(0)
+ * w the weight at the point (x, z): a row's proj at its intersection with the plane (geometric), or the intensity of an image sample
+ * (diffraction).  freqs: [n_freqs][2], host.  otf: [n_planes][n_freqs][2] as (re, im); mtf: [n_planes][n_freqs]; sums: [n_planes], T(0).
+ * Everything is FP64, each expression evaluated left to right as written, without contraction.  sincospi(t) = (sin(pi t), cos(pi t)) keeps
+ * the rounding of 2 pi out of the argument.
+ *
+ * bmo_psf_geo_otf: hits, origin, e1, e2, axis, offsets, n_planes, device, kernel_ms as for bmo_psf_focus_stats.  centers: NULL or
+ * [n_planes][2], (cx_m, cz_m), the point of plane m the phase is counted from ((0, 0) when NULL; the MTF does not depend on it).  Per row
+ * and plane m:
+ *   den, o_m, s, q, x, z: exactly the expressions of bmo_psf_focus_stats
+ *   ax = x - cx_m,   az = z - cz_m
+ *   a = fx * ax + fz * az,   (sn, cs) = sincospi(-2.0 * a)
+ *   re += proj * cs,   im += proj * sn
+ *   S = sum proj (equal to BMO_FOCUS_STAT_S bit for bit),   sums[m] = S,   mtf = sqrt(re * re + im * im) / S
+ * The sums of (re, im) run over the rows of a split in row order and the splits (those of bmo_spot_stats) are folded in split order: a
+ * fixed order that depends on n_hits only.  So the value at (plane, frequency) does not depend on which other planes or frequencies the
+ * call asks for, and resident rows equal host rows, both bit for bit.  No rows: zeros, and NaN in mtf.  A row with den = 0 (or a NaN proj):
+ * NaN everywhere.  BMO_ERR_LIMIT if the partial sums (16 bytes per split, plane and frequency; at most 2 048 splits) would pass 4 GiB: ask
+ * for the planes or frequencies in several calls.
+ *
+ * bmo_psf_otf: hits .. displacements, n_planes, xs, zs, n, device as for bmo_psf_through_focus.  The images I_m are those of
+ * bmo_psf_through_focus for the same arguments bit for bit (the same kernels and plan) and stay on the device; out_intensity: optional,
+ * host, [n_planes][n*n].  The sample (i, j) of plane m has the local coordinates (xs[i], zs[j]) of its own displaced grid.  Per plane and
+ * frequency:
+ *   (sx_i, cx_i) = sincospi(-2.0 * (fx * xs[i])),   (sz_j, cz_j) = sincospi(-2.0 * (fz * zs[j]))
+ *   row j:  r_re = sum_i I(i,j) * cx_i,   r_im = sum_i I(i,j) * sx_i                                                       (i ascending)
+ *   T_re = sum_j (r_re * cz_j - r_im * sz_j),   T_im = sum_j (r_re * sz_j + r_im * cz_j)                                 (j ascending)
+ *   sums[m]: the same two loops with the factor (1, 0) in place of both cis;   mtf = sqrt(T_re * T_re + T_im * T_im) / sums[m]
+ * n_hits = 0: zeros, and NaN in mtf.  An image samples the PSF at the pitch of xs and zs: a frequency beyond 1 / (2 pitch) aliases (the
+ * Python layer refuses it), and the window must hold the PSF without its replicas (components.mtf_window).
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than centers, out_intensity, kernel_ms; n_planes <= 0,
+ * n_freqs <= 0, n <= 0, n_hits < 0; a frequency that is not finite.  There is no _sweep form and no GaussianBeamlet form: resident rows come
+ * through bmo_result_psf_rows.                                                                                                          */
+int bmo_psf_geo_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                    const double e2[3], const double axis[3], const double* offsets, const double* centers, int32_t n_planes,
+                    const double* freqs, int32_t n_freqs, int32_t device, double* otf, double* mtf, double* sums, double* kernel_ms);
+int bmo_psf_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* freqs,
+                int32_t n_freqs, int32_t device, double* otf, double* mtf, double* sums, double* out_intensity, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
