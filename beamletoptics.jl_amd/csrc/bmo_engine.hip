@@ -634,7 +634,11 @@ __global__ __launch_bounds__(BMO_BLOCK, WAVES) void step_kernel(StepParams P) { 
                 // (single-shape marches in the specialised loop, BMO_LEAF_MARCH: every variant but the PolarizedRay in-wave kernel of the
                 //  plain-shapes level, which would hold 252 B of scratch with it instead of 240: DESIGN.md §4 "Round 6")
                 constexpr bool LEAF = !(KIND == BMO_BEAM_POLARIZED && EXT == 0 && !RETR && INW && !SWEEP);
-                const Hit X = tracing_step<EXT, RETR, LEAF>(S, pos, dir, ho, hs, calls, cc, lm, rt.probe, rt.probe_obj, rt.fresh_allowed, &rt.missed);
+                // (the box cull, BMO_BOX_CULL.  Of the variants that hold the specialised march loops — the fresh kernels of the plain-shapes
+                //  level — only the Ray kernel of the large launches runs it: with it the loops of the others take a scalar load per trip
+                //  or eight lane operations they did not hold, so those stay on the parent's form: DESIGN.md §4 "Round 7")
+                constexpr bool BOX = !(EXT == 0 && !RETR) || (KIND == BMO_BEAM_RAY && INW && WAVES == 4 && !SWEEP);
+                const Hit X = tracing_step<EXT, RETR, LEAF, BOX>(S, pos, dir, ho, hs, calls, cc, lm, rt.probe, rt.probe_obj, rt.fresh_allowed, &rt.missed);
 #if defined(BMO_DEV_TIMELINE)
                 {
                     const unsigned long long t = wall_clock64();

@@ -48,10 +48,21 @@
 #if !defined(BMO_LEAF_MARCH)
 #define BMO_LEAF_MARCH 1  /* outside marches of a single plain shape (no union) in the same loop, in the kernels BMO_MARCH_FASTPATH selects: 0 off */
 #endif
+#if !defined(BMO_BOX_CULL)
+#define BMO_BOX_CULL 1  /* slab test of a candidate's bounding box in front of its march (box_cull below, DESIGN.md §3 "box cull"): 0 off */
+#endif
 
 namespace bmo {
 
-#if defined(BMO_EMU_STATS)  // host-only instrumentation of the test emulator (tools/emu_stats.py)
+#if !defined(BMO_EMU_STATS)
+#define BMO_TALLY(w, shadow) ((void)0)
+#else  // host-only instrumentation of the test emulator (tools/emu_stats.py)
+// How the SDF marches of tracing_step ended (tools/fastpath_stats.py): [0] marches started, [1] a hit offered, [2] on the surface and
+// leaving, [3] t0 > lim at the first evaluation, [4] receded, [5] t0 > lim later, [6] iteration limit, [7] on the surface and entering
+// (not an end: the march goes on inside).  g_emu_box: [0] candidates the box cull took; with BMO_EMU_BOX_SHADOW (the tool's build)
+// those marches run all the same and [1..7] count how they ended — [1], [2] and [7] stay zero if the cull's proof holds.
+inline long g_emu_march[8] = {}, g_emu_box[8] = {};
+#define BMO_TALLY(w, shadow) (++g_emu_march[w], g_emu_box[w] += (w) != 0 && (shadow))
 inline long g_emu_sdf_any = 0, g_emu_sdf_leaf = 0, g_emu_normal = 0, g_emu_normal_fd = 0;
 // union evaluations, those decided by the one `others_lb` compare, and those of them taken in tracing_step's specialised loop
 // (tools/fastpath_stats.py)
@@ -121,6 +132,9 @@ struct SceneView {
     // traces every mesh by brute force)
     const BMO_KONST struct BvhNode* bvh_nodes = nullptr;
     CInt* bvh_faces = nullptr;
+    // bounding boxes of the shapes, six doubles per shape id (box_cull; built by bmo_scene_create, bmo_scene_blob.hpp).  Null in the
+    // emulator's SceneView: a host build of tracing_step then derives a candidate's box on the spot, by the same shape_box
+    CDouble* boxes = nullptr;
 };
 
 struct d3 {
@@ -1172,6 +1186,124 @@ BMO_HD bool cull_miss(double cx, double cy, double cz, double R, const d3& pos, 
     return (R >= 0.0) & (cc > R2) & ((b < 0.0) | (b * b - dd * (cc - R2) < 0.0));
 }
 
+// ------------------------------------------------------------------ box cull (DESIGN.md §3 "box cull")
+// An axis-aligned world box per SDF shape: lo[3], hi[3]; lo > hi means "no box" and is never culled.  Derived by the engine from kind,
+// p[], pos and tdir (shape_box, host code: the scene builder fills the table SceneView::boxes with it).  Rules, each from the
+// leaf's own formula in sdf_leaf (a solid that is a max() of parts lies inside each part, so the part's extents hold):
+//   PLANO      disc |r| <= p1/2, y in [0, p0]            CONVEX   |r| <= p1/2 (p0 if the cap passes its equator), y in [0, p0 - p3]
+//   CONCAVE    its cylinder: |r| <= p1/2, y in [-p2, 0]  CYLINDER |r| <= p0, |y| <= p1        RING  |r| <= p0 + p1, |y| <= p2
+//   BOX, PRISM |x|, |y|, |z| <= p0, p1, p2               SPHERE, CUTSPHERE  the ball of p0    POINT the origin
+//   MENISCUS   hull of its three children (their frames are relative to the meniscus);  UNION  hull of its children's boxes
+// No box: a mesh, a kind without a rule (the aspheric and cylinder lenses), BMO_SHAPE_FLAG_INEXACT (its slope bound is baked into the
+// sphere only), bs_radius < 0 (the description asks for no cull), a frame that is no rotation to 1e-9, anything not finite.
+// Every face is moved out by r * 1e-6 + 1 um (r: half the diagonal), the bounding sphere's margin for exact shapes.
+constexpr int BMO_BOX_DOUBLES = 6;
+struct ShapeBox {
+    double lo[3] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val()};
+    double hi[3] = {-__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
+    bool any() const { return lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]; }
+};
+// local extents of a leaf kind; false: no rule (or parameters that give none)
+inline bool box_local_extent(const bmo_shape& s, double lo[3], double hi[3]) {
+    const double* P = s.p;
+    double ra, y0, y1;
+    switch (s.kind) {
+        case BMO_SHAPE_PLANO: ra = P[1] / 2, y0 = 0.0, y1 = P[0]; break;
+        case BMO_SHAPE_CONVEX: ra = P[3] >= 0.0 ? P[1] / 2 : fmax(P[1] / 2, P[0]), y0 = 0.0, y1 = P[0] - P[3]; break;  // (the leaf cuts at q2 = p0 - y >= p3; it never reads p2)
+        case BMO_SHAPE_CONCAVE: ra = P[1] / 2, y0 = -P[2], y1 = 0.0; break;
+        case BMO_SHAPE_CYLINDER: ra = P[0], y0 = -P[1], y1 = P[1]; break;
+        case BMO_SHAPE_RING: ra = P[0] + P[1], y0 = -P[2], y1 = P[2]; break;
+        case BMO_SHAPE_SPHERE:
+        case BMO_SHAPE_CUTSPHERE: ra = P[0], y0 = -P[0], y1 = P[0]; break;
+        case BMO_SHAPE_POINT: ra = 0.0, y0 = 0.0, y1 = 0.0; break;
+        case BMO_SHAPE_BOX:
+        case BMO_SHAPE_PRISM:
+            for (int a = 0; a < 3; ++a) lo[a] = -P[a], hi[a] = P[a];
+            return P[0] >= 0.0 && P[1] >= 0.0 && P[2] >= 0.0 && __builtin_isfinite(P[0]) && __builtin_isfinite(P[1]) && __builtin_isfinite(P[2]);
+        default: return false;
+    }
+    lo[0] = lo[2] = -ra, hi[0] = hi[2] = ra, lo[1] = y0, hi[1] = y1;
+    return ra >= 0.0 && y0 <= y1 && __builtin_isfinite(ra) && __builtin_isfinite(y0) && __builtin_isfinite(y1);
+}
+// the frame the leaves evaluate in is p_local = tdir (p - pos) (to_local): its inverse is pos + tdir' p_local only for a rotation
+inline bool box_frame_ok(const bmo_shape& s) {
+    for (int i = 0; i < 3; ++i) {
+        if (!__builtin_isfinite(s.pos[i])) return false;
+        for (int j = 0; j < 3; ++j) {
+            double g = 0.0;
+            for (int k = 0; k < 3; ++k) g += s.tdir[3 * i + k] * s.tdir[3 * j + k];
+            if (!(fabs(g - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+        }
+    }
+    return true;
+}
+// the un-inflated box of shape `sid` (shapes / children: the description's tables); `outer`: the meniscus whose frame a leaf lives in
+inline ShapeBox shape_box_raw(const bmo_shape* shapes, const int32_t* children, int32_t sid, const bmo_shape* outer = nullptr) {
+    const bmo_shape& s = shapes[sid];
+    ShapeBox b;
+    if (s.kind == BMO_SHAPE_MESH || (s.flags & BMO_SHAPE_FLAG_INEXACT) || (!outer && !(s.bs_radius >= 0.0))) return ShapeBox{};
+    if (s.kind == BMO_SHAPE_UNION || s.kind == BMO_SHAPE_MENISCUS) {
+        const bool men = s.kind == BMO_SHAPE_MENISCUS;
+        if (outer || s.child_count < 1 || (men && !box_frame_ok(s))) return ShapeBox{};  // (a nested group: refused by the scene builder)
+        for (int c = 0; c < s.child_count; ++c) {
+            const int32_t ch = children[s.child_begin + c];
+            const int ck = shapes[ch].kind;
+            if (ck == BMO_SHAPE_UNION || (men && ck == BMO_SHAPE_MENISCUS)) return ShapeBox{};
+            const ShapeBox cb = shape_box_raw(shapes, children, ch, men ? &s : nullptr);
+            if (!cb.any()) return ShapeBox{};
+            for (int a = 0; a < 3; ++a) b.lo[a] = fmin(b.lo[a], cb.lo[a]), b.hi[a] = fmax(b.hi[a], cb.hi[a]);
+        }
+        return b;
+    }
+    double lo[3], hi[3];
+    if (!box_frame_ok(s) || !box_local_extent(s, lo, hi)) return ShapeBox{};
+    for (int q = 0; q < 8; ++q) {  // the hull of the 8 corners, taken to the world
+        double p[3] = {(q & 1) ? hi[0] : lo[0], (q & 2) ? hi[1] : lo[1], (q & 4) ? hi[2] : lo[2]};
+        for (int level = 0; level < 2; ++level) {
+            const bmo_shape* f = level == 0 ? &s : outer;
+            if (!f) continue;
+            double w[3];
+            for (int a = 0; a < 3; ++a) w[a] = f->pos[a] + ((f->tdir[a] * p[0] + f->tdir[3 + a] * p[1]) + f->tdir[6 + a] * p[2]);
+            for (int a = 0; a < 3; ++a) p[a] = w[a];
+        }
+        for (int a = 0; a < 3; ++a) b.lo[a] = fmin(b.lo[a], p[a]), b.hi[a] = fmax(b.hi[a], p[a]);
+    }
+    for (int a = 0; a < 3; ++a)
+        if (!__builtin_isfinite(b.lo[a]) || !__builtin_isfinite(b.hi[a])) return ShapeBox{};
+    return b;
+}
+// ... and the box the kernels test: every face moved out by the margin
+inline ShapeBox shape_box(const bmo_shape* shapes, const int32_t* children, int32_t sid) {
+    ShapeBox b = shape_box_raw(shapes, children, sid);
+    if (!b.any()) return ShapeBox{};
+    double d2 = 0.0;
+    for (int a = 0; a < 3; ++a) d2 += (b.hi[a] - b.lo[a]) * (b.hi[a] - b.lo[a]);
+    const double m = 0.5 * sqrt(d2) * 1e-6 + 1e-6;
+    for (int a = 0; a < 3; ++a) b.lo[a] -= m, b.hi[a] += m;
+    return b;
+}
+// The slab test.  true: the ray (origin o, direction d, t >= 0) misses the box `b` (six doubles) — the reference returns `nothing`
+// for the shape — or enters it beyond `lim`: a hit could only lose the nearest-hit selection (cull_entry's safety factors).
+// A direction component whose reciprocal is infinite only asks whether the origin lies in that slab (bvh_visit's rule: the slab
+// bounds would be NaN for an origin on the slab's plane).  fmin / fmax return the other operand for a NaN and every compare with a
+// NaN is false, so a NaN anywhere leaves the candidate alone.
+// (Measured against a form with v_rcp_f64 + one Newton step for the division and bare v_min_f64 / v_max_f64: this one is 0.4 % faster
+//  on the headline bundle — profiles/box_cull_ab.txt.  What the test costs is not what limits the gain.)
+BMO_HD bool box_cull(CDouble* b, const d3& o, const d3& d, double lim) {
+    const double ov[3] = {o.x, o.y, o.z}, dv[3] = {d.x, d.y, d.z};
+    double tn = -kinf(), tf = kinf();
+    bool outside = false;
+    for (int k = 0; k < 3; ++k) {
+        const double lo = b[k], hi = b[3 + k], iv = 1.0 / dv[k];
+        const bool par = fabs(iv) == kinf();
+        const double a = (lo - ov[k]) * iv, c = (hi - ov[k]) * iv;
+        tn = fmax(tn, par ? -kinf() : fmin(a, c));
+        tf = fmin(tf, par ? kinf() : fmax(a, c));
+        outside = outside | (par & ((ov[k] < lo) | (ov[k] > hi)));
+    }
+    return outside | (tn > tf) | (tf < 0.0) | (tn * (1.0 - 1e-9) - 1e-9 > lim);
+}
+
 // tracing_step! (System.jl:100-110) = trace_one (:74-85) falling back to trace_all (:57-72), with intersect3d of objects
 // (SingleShape / MultiShape AbstractRay.jl:118-155, plate splitter PlateBeamsplitter.jl:160-187, NonInteractable.jl:19), of meshes
 // (Mesh.jl:244-267) and of SDF shapes (AbstractSDF.jl:166-181 with _raymarch_outside :102-125 and _raymarch_inside :132-159) written as
@@ -1207,7 +1339,8 @@ BMO_HD bool cull_miss(double cx, double cy, double cz, double R, const d3& pos, 
 //   * the miss cull (file header).  `calls` counts the reference's intersect3d calls, culled or not.
 // Returns the winning hit; its normal is in lane memory 0..2 (X.n is filled from there).
 // LEAF = false: the caller's kernel keeps single-shape marches on the generic trip (BMO_LEAF_MARCH: a variant whose scratch would grow).
-template <int EXT, bool RETR = false, bool LEAF = true>
+// BOX = false: the caller's kernel runs no box cull (BMO_BOX_CULL: likewise).
+template <int EXT, bool RETR = false, bool LEAF = true, bool BOX = true>
 BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, int32_t hint_obj, int32_t hint_shape, uint32_t& calls, ChildCache& cc,
                         const LaneMem& lm, bool probe = false, int32_t probe_obj = -1, bool fresh_allowed = true, bool* probe_missed = nullptr) {
     enum { CLASSIFY = 0, INSIDE = 1, OUTSIDE = 2, FINAL = 3 };
@@ -1291,6 +1424,7 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                     const int32_t s_kind = s.kind, s_flags = s.flags;
                     double lim = kinf();
                     d3 pos{0, 0, 0};
+                    [[maybe_unused]] bool shadow = false;  // (stats builds with BMO_EMU_BOX_SHADOW: the box cull took this candidate, its march runs to be tallied)
                     if (pass != 2) {
                         pos = lm.get3(3);
                         if (slot < 0) {
@@ -1299,6 +1433,29 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                             lim = x_t + 1e-6 * (1.0 + x_t);
                             const double t_lb = cull_entry(s, pos, dir0);
                             if (t_lb * (1.0 - 1e-9) - 1e-9 > lim) active = false;  // provable loser of the nearest-hit selection
+                        }
+                        // the box cull (box_cull above): candidates the spheres let through, SDF shapes only; the hinted slot starts on
+                        // its shape and is left alone.  The table entry is wave-uniform (scalar loads), "no box" skips the test.
+                        if constexpr (BMO_BOX_CULL != 0 && BOX) {
+                            if (slot >= 0 && s_kind != BMO_SHAPE_MESH && BMO_WAVE_ANY(active)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                                CDouble* bx = S.boxes + BMO_BOX_DOUBLES * usid;
+#else
+                                ShapeBox own;
+                                if (!S.boxes) own = shape_box(S.shapes, S.children, usid);
+                                CDouble* bx = S.boxes ? S.boxes + BMO_BOX_DOUBLES * usid : own.lo;
+#endif
+                                if (bx[0] <= bx[3] && active && box_cull(bx, pos, dir0, lim)) {
+#if defined(BMO_EMU_STATS)
+                                    ++g_emu_box[0];
+#endif
+#if defined(BMO_EMU_STATS) && defined(BMO_EMU_BOX_SHADOW)
+                                    shadow = true;
+#else
+                                    active = false;
+#endif
+                                }
+                            }
                         }
                     }
                     // a hit of this part at t (end point of the march p, arg-min child / face a): the reference's selection rules
@@ -1354,6 +1511,7 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                         enum { ST_BACK = 4, ST_PENDING = 8, ST_ACTIVE = 16 };  // PENDING: the lane waits for the normal site
                         int st = (active ? ST_ACTIVE : 0) | (pass == 2 ? (FINAL | ST_PENDING) : CLASSIFY);
                         int32_t bc = 0;
+                        if (active && pass != 2) BMO_TALLY(0, shadow);
                         if (pass == 2) {
                             pos = lm.get3(0);
                             bc = x_aux;
@@ -1470,6 +1628,7 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                     it += 1;
                                     if (d < S.eps_ray) {
                                         offer((st & ST_BACK) ? t_in - t0 : t0, bc, pos);
+                                        BMO_TALLY(1, shadow);
                                         st = 0;
                                     } else {
                                         // outside the bounding sphere and receding (the backward march runs along -dir: dot(co, -dir) =
@@ -1482,8 +1641,10 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                         recede = R >= 0.0 && dot3(co, co) > R * R && ((st & ST_BACK) ? cd < 0.0 : cd > 0.0);
                                         }
                                         if (recede || (exact && !(st & ST_BACK) && t0 > lim)  // provable loser of the nearest-hit selection
-                                            || !(it <= S.march_iters))
+                                            || !(it <= S.march_iters)) {
+                                            BMO_TALLY(recede ? 4 : (it <= S.march_iters) ? 5 : 6, shadow);
                                             st = 0;
+                                        }
                                     }
                                 } else if (phase == CLASSIFY) {
                                     if (d > S.eps_srf) {
@@ -1491,7 +1652,10 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                         dist = d;
                                         t0 = d;
                                         it = 1;
-                                        if (!(it <= S.march_iters) || (exact && t0 > lim)) st = 0;  // the reference returns `nothing`
+                                        if (!(it <= S.march_iters) || (exact && t0 > lim)) {  // the reference returns `nothing`
+                                            BMO_TALLY((it <= S.march_iters) ? 3 : 6, shadow);
+                                            st = 0;
+                                        }
                                     } else {
                                         st |= ST_PENDING;
                                     }
@@ -1504,7 +1668,10 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                     } else {
                                         it += 1;
                                     }
-                                    if (!(it <= S.march_iters)) st = 0;
+                                    if (!(it <= S.march_iters)) {
+                                        BMO_TALLY(6, shadow);
+                                        st = 0;
+                                    }
                                 }
                             }
                             // nobody is marching: every lane still active waits for a normal (or nobody is left)
@@ -1518,7 +1685,9 @@ BMO_HD Hit tracing_step(const SceneView& S, const d3& pos_in, const d3& dir0, in
                                     st = 0;
                                 } else if (dot3(dir0, n) <= 0 && 1 <= S.march_iters) {  // entering
                                     st = ST_ACTIVE | INSIDE;
+                                    BMO_TALLY(7, shadow);
                                 } else {
+                                    BMO_TALLY(2, shadow);
                                     st = 0;  // on the surface and leaving: no intersection
                                 }
                             }

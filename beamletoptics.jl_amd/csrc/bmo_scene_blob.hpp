@@ -39,10 +39,11 @@ struct BlobHeader {
     int32_t n_cands, has_meniscus, pad[2];  // pad[0] is has_bvh() below, the one spelling in use; the member keeps the name and type
                                             // that every earlier revision of tests/emu/scene_check.cpp compiles against
     uint32_t off_bvh_nodes, off_bvh_faces;  // mesh BVHs (bmo_lane.hpp BvhNode; face ids, int32)
+    uint32_t off_boxes, pad2;               // the shapes' bounding boxes (bmo_lane.hpp box_cull), six doubles per shape id
     BMO_BLOB_HD int32_t has_bvh() const { return pad[0]; }  // 1: some mesh has a BVH (the kernels of level 3)
     BMO_BLOB_HD int32_t& has_bvh() { return pad[0]; }
 };
-static_assert(sizeof(BlobHeader) == 144, "BlobHeader travels in the step kernels' arguments (StepParams::hdr): its layout is part of their builds");
+static_assert(sizeof(BlobHeader) == 152, "BlobHeader travels in the step kernels' arguments (StepParams::hdr): its layout is part of their builds");
 
 // `h`: the blob's header; the kernels read it from their arguments (scalar loads the compiler may repeat instead of holding the
 // values in registers — read from the LDS copy they would sit in vector registers for the whole kernel)
@@ -56,6 +57,7 @@ BMO_BLOB_HD SceneView view_of(CharPtr blob, const BlobHeader* h) {
     S.n_table = (CDouble*)(blob + h->off_ntable);
     S.coefs = (CDouble*)(blob + h->off_coefs);
     S.cands = (const BMO_KONST Cand*)(blob + h->off_cands);
+    S.boxes = (CDouble*)(blob + h->off_boxes);
     S.n_cands = h->n_cands;
     S.n_objects = h->n_objects;
     S.n_lambda = h->n_lambda;
@@ -362,10 +364,12 @@ inline std::vector<BlobRegion> blob_regions(const bmo_scene_desc* d, const BlobH
         {&H::off_cands, sizeof(Cand) * (size_t)(std::max(1, h.n_cands) + 3), nullptr},
         {&H::off_bvh_nodes, sizeof(BvhNode) * B.nodes.size(), B.nodes.data()},
         {&H::off_bvh_faces, 4 * B.faces.size(), B.faces.data()},
+        // filled by fill_blob from the shape table (shape_box)
+        {&H::off_boxes, 8 * (size_t)BMO_BOX_DOUBLES * (size_t)std::max(1, d->n_shapes), nullptr},
     };
 }
 
-// the header, every region that has a source, the candidate table (trace_all's flat slot list)
+// the header, every region that has a source, the candidate table (trace_all's flat slot list), the shapes' boxes
 inline void fill_blob(SceneImage& img, const bmo_scene_desc* d, const std::vector<BlobRegion>& regions) {
     const BlobHeader& h = img.hdr;
     img.blob.assign(h.total, 0);
@@ -376,6 +380,12 @@ inline void fill_blob(SceneImage& img, const bmo_scene_desc* d, const std::vecto
         img.region_bytes.push_back(r.bytes);
     }
     fill_candidates(d->objects, d->n_objects, d->shapes, reinterpret_cast<Cand*>(img.blob.data() + h.off_cands));
+    for (int i = 0; i < d->n_shapes; ++i) {
+        const ShapeBox b = shape_box(d->shapes, d->children, i);
+        char* at = img.blob.data() + h.off_boxes + 8 * (size_t)BMO_BOX_DOUBLES * (size_t)i;
+        std::memcpy(at, b.lo, sizeof b.lo);
+        std::memcpy(at + sizeof b.lo, b.hi, sizeof b.hi);
+    }
 }
 
 // The blob's shape flags are the builder's, whatever the description's say.  Unions whose children sit back to back in the shape
