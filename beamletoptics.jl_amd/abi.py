@@ -265,6 +265,10 @@ def load_engine():
     lib.bmo_result_psf_rows.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.bmo_psf_geo_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
     lib.bmo_psf_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp]
+    lib.bmo_spot_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_int32, ip, dp]
+    lib.bmo_spot_ee_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, dp]
+    lib.bmo_psf_geo_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, ip, dp, dp]
+    lib.bmo_psf_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -516,6 +520,103 @@ def psf_otf(hits, origin, e1, e2, displacements, xs, zs, freqs, device=0, hits_d
                                sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_otf")
     I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
     return mtf, otf[..., 0] + 1j * otf[..., 1], sums, I, ms.value
+
+
+EE_SHAPES = {"circle": 0, "square": 1}
+
+
+def _ee_shape(shape):
+    """The shape code of the encircled-energy entries: "circle" / 0, "square" / 1 (another integer goes through for the library to refuse)."""
+    if isinstance(shape, str):
+        if shape not in EE_SHAPES:
+            raise ValueError('encircled energy: shape must be "circle" or "square"')
+        return EE_SHAPES[shape]
+    return int(shape)
+
+
+def _radii(radii):
+    return np.ascontiguousarray(np.asarray(radii, dtype=np.float64).reshape(-1))
+
+
+def spot_ee(rows, center, radii, shape="circle", device=0, rows_device_ptr=None, n_rows=None, row_cols=9):
+    """bmo_spot_ee: the number of rows [n, 2..9] (x in column 0, z in column 1) inside a circle (r2 <= R * R) or a square (|ax| <= R and
+    |az| <= R) of half-size R about `center`, for every R of `radii` (any order).  Returns (inside int64 [n_radii], kernel_ms).  `rows` is
+    a host array, or pass `rows_device_ptr` + `n_rows` + `row_cols` for rows already resident on `device`."""
+    lib = load_engine()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(2)
+    r = _radii(radii)
+    inside = np.zeros(len(r), dtype=np.int64)
+    ms = C.c_double()
+    check(lib, lib.bmo_spot_ee(rp, n, cols, on_dev, c.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), len(r), int(device), inside.ctypes.data_as(ip),
+                               C.byref(ms)), "bmo_spot_ee")
+    return inside, ms.value
+
+
+def spot_ee_sweep(res_handle, detector, n_configs, centers, radii, shape="circle"):
+    """bmo_spot_ee_sweep on the result handle `res_handle`: centers [K, 2] (or one centre for all).  Returns (inside int64 [K, n_radii],
+    n_rows int64 [K], kernel_ms); configuration c equals spot_ee on its rows."""
+    lib = load_engine()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    c = _per_config(centers, K1, 2)
+    r = _radii(radii)
+    inside, n_rows = np.zeros((K1, len(r)), dtype=np.int64), np.zeros(K1, dtype=np.int64)
+    ms = C.c_double()
+    check(lib, lib.bmo_spot_ee_sweep(res_handle, int(detector), K, c.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), len(r), inside.ctypes.data_as(ip),
+                                     n_rows.ctypes.data_as(ip), C.byref(ms)), "bmo_spot_ee_sweep")
+    return inside[:K], n_rows[:K], ms.value
+
+
+def psf_geo_ee(hits, origin, e1, e2, axis, offsets, radii, centers=None, shape="circle", device=0, hits_device_ptr=None, n_hits=None, want_count=True):
+    """bmo_psf_geo_ee: the proj-weighted share of the rows, propagated to the detector plane moved by offsets[m] * axis, inside a circle or a
+    square of half-size R about centers[m] ([M, 2]; None: the plane's origin), for every R of `radii`.  Returns (ee [M, nr], energy [M, nr],
+    count int64 [M, nr] or None, sums [M], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2, ax = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2, axis))
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64).reshape(-1))
+    r = _radii(radii)
+    M, nr = len(off), len(r)
+    cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    ee, energy, sums = np.zeros((M, nr)), np.zeros((M, nr)), np.zeros(M)
+    count = np.zeros((M, nr), dtype=np.int64) if want_count else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_geo_ee(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp), off.ctypes.data_as(dp),
+                                  None if cen is None else cen.ctypes.data_as(dp), M, _ee_shape(shape), r.ctypes.data_as(dp), nr, int(device), ee.ctypes.data_as(dp),
+                                  energy.ctypes.data_as(dp), count.ctypes.data_as(C.POINTER(C.c_int64)) if want_count else None, sums.ctypes.data_as(dp),
+                                  C.byref(ms)), "bmo_psf_geo_ee")
+    return ee, energy, count, sums, ms.value
+
+
+def psf_ee(hits, origin, e1, e2, displacements, xs, zs, radii, centers=None, shape="circle", device=0, hits_device_ptr=None, n_hits=None, want_intensity=False):
+    """bmo_psf_ee: the share of the pixel sums of the through-focus stack (psf_through_focus of the same arguments, kept on the device) inside
+    a circle or a square of half-size R about centers[m] ([M, 2] in the coordinates of xs and zs; None: each image's intensity centroid),
+    for every R of `radii`.  Returns (ee [M, nr], energy [M, nr], sums [M], centers [M, 2] as used, I[M, n, n] indexed [m, i, j] or None,
+    kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    d = np.ascontiguousarray(np.asarray(displacements, dtype=np.float64).reshape(-1, 3))
+    x, z = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(zs, dtype=np.float64)
+    r = _radii(radii)
+    n, M, nr = len(x), len(d), len(r)
+    if len(z) != n:
+        raise ValueError("xs and zs must have the same length")
+    cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    ee, energy, sums, cout = np.zeros((M, nr)), np.zeros((M, nr)), np.zeros(M), np.zeros((M, 2))
+    img = np.zeros(M * n * n) if want_intensity else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_ee(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
+                              z.ctypes.data_as(dp), n, None if cen is None else cen.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), nr, int(device),
+                              ee.ctypes.data_as(dp), energy.ctypes.data_as(dp), sums.ctypes.data_as(dp), cout.ctypes.data_as(dp),
+                              img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_ee")
+    I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
+    return ee, energy, sums, cout, I, ms.value
 
 
 def zernike_sizes(order):

@@ -386,6 +386,30 @@ class Spotdetector(AbstractObject):  # Detectors/Spotdetector.jl:21-45
         counts, outside, _ = abi.spot_image(self.data, window, nx, nz, device=device)
         return la.linrange(window[0], window[1], nx + 1), la.linrange(window[2], window[3], nz + 1), counts, outside
 
+    def encircled_energy(self, radii, center=None, shape="circle", device=0):
+        """The share of all rows accumulated so far inside a circle (shape "circle": r2 <= R * R) or a square ("square": |ax| <= R and
+        |az| <= R) of half-size R about `center` = (x, z), for every R of `radii` (bmo_spot_ee): (fraction [nr], inside int64 [nr], n_rows).
+        center None: the centroid CX, CZ of stats().  Without rows the fraction is NaN."""
+        from . import abi
+
+        if center is None:
+            center = spot_ee_centers(self.stats(device))
+        inside, _ = abi.spot_ee(self.data, center, radii, shape=shape, device=device)
+        return spot_ee_fraction(inside, len(self.data)), inside, len(self.data)
+
+
+def spot_ee_centers(stats):
+    """The centroid (CX, CZ) of spot statistics ([12] or [K, 12]) as the centre of an encircled-energy curve; (0, 0) where there is no row."""
+    st = np.asarray(stats, dtype=np.float64)
+    return np.where(st[..., 0:1] > 0, st[..., 1:3], 0.0)
+
+
+def spot_ee_fraction(inside, n_rows):
+    """inside / n_rows ([nr] with one count, [K, nr] with [K]); NaN where there is no row."""
+    n = np.asarray(n_rows, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(n[..., None] > 0, np.asarray(inside, dtype=np.float64) / n[..., None], np.nan)
+
 
 def spot_extent_window(stats, who):
     """The window X_MIN .. Z_MAX of spot statistics [12]; ValueError (starting with `who`) without rows or with a zero extent."""
@@ -620,6 +644,118 @@ def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.
     return out["r"] + (st,)
 
 
+# The encircled-energy read-out (include/bmo.h "Encircled-energy read-out").  Radii are half-sizes in metres in the detector's local frame.
+def ee_radii(r_max, n):
+    """[n]: n radii from 0 to r_max in equal steps (the first is 0: only the points at the centre itself)."""
+    return float(r_max) * np.arange(int(n), dtype=np.float64) / max(int(n) - 1, 1)
+
+
+def ee_radius_at(radii, ee, fraction):
+    """The radius at which an energy curve first reaches `fraction`: `radii` ascending, `ee` [n] the curve on them ([..., n]: one answer per
+    curve); linear interpolation between the last sample below and the first at or above, the first radius if the curve starts there, NaN
+    if the curve never reaches it (or is NaN)."""
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    e = np.asarray(ee, dtype=np.float64)
+    if e.shape[-1] != len(r) or len(r) == 0 or np.any(np.diff(r) < 0):
+        raise ValueError("ee_radius_at: radii must be ascending and ee must hold one value per radius")
+    f = float(fraction)
+    out = np.full(e.shape[:-1], np.nan)
+    for idx in np.ndindex(*e.shape[:-1]):
+        curve = e[idx]
+        hit = np.nonzero(curve >= f)[0]
+        if len(hit) == 0:
+            continue
+        q = int(hit[0])
+        if q == 0 or curve[q] == curve[q - 1] or not np.isfinite(curve[q - 1]):
+            out[idx] = r[q]
+        else:
+            out[idx] = r[q - 1] + (f - curve[q - 1]) / (curve[q] - curve[q - 1]) * (r[q] - r[q - 1])
+    return float(out) if out.ndim == 0 else out
+
+
+def _bessel_j01(v):
+    """(J0(v), J1(v)) from Bessel's integral J_n(v) = 1 / (2 pi) int_0^2pi cos(n t - v sin t) dt by the trapezoid rule on N points: the
+    integrand is periodic and entire, so the rule's error is the aliased orders J_(n + m N)(v), below 1e-20 with N >= |v| + 48."""
+    v = np.asarray(v, dtype=np.float64)
+    N = max(64, int(math.ceil(float(np.max(np.abs(v), initial=0.0)))) + 48)
+    t = 2.0 * math.pi * np.arange(N, dtype=np.float64) / N
+    arg = v[..., None] * np.sin(t)
+    return np.cos(arg).mean(axis=-1), np.cos(t - arg).mean(axis=-1)
+
+
+def ee_diffraction_limit(v):
+    """The encircled energy of an aberration-free circular pupil (the Airy pattern) inside the radius r: 1 - J0(v)^2 - J1(v)^2 at
+    v = k_max rho r, with the k_max and rho of mtf_cutoff (v = pi r cutoff)."""
+    j0, j1 = _bessel_j01(v)
+    return np.clip(1.0 - j0 * j0 - j1 * j1, 0.0, 1.0)  # a share: the rounding at v = 0 must not leave -1e-33
+
+
+def psf_encircled_energy(stats_fn, geo_fn, ee_fn, window_fn, orientation, radii, offsets=(0.0,), kind="geometric", shape="circle", n=None, half_width=None,
+                         axis=None, follow="centroid"):
+    """The encircled (shape "circle") or ensquared ("square") energy of PSF rows on the detector plane moved by each of `offsets` along `axis`
+    (None: local y), inside every half-size of `radii`: what PSFDetector.encircled_energy and EngineSolution.psf_encircled_energy share.
+    stats_fn(axis, offsets) -> focus statistics [M, 12]; geo_fn(axis, offsets, radii, centers, shape) -> (ee, energy, sums);
+    ee_fn(displacements, xs, zs, radii, shape) -> (ee, energy, sums, centers of the grid's coordinates); window_fn() -> (k_max, rho, n_rows).
+    kind "geometric": the proj-weighted share of the propagated rows about each plane's centroid (follow="centroid") or about the centroid
+    of the plane of least RMS radius (follow=None).  kind "diffraction": the share of the pixel sums of the through-focus stack on the grid
+    of psf_through_focus with the same `follow`, about each image's intensity centroid; half_width None takes mtf_window's at the cutoff
+    frequency (the band limit of the intensity), n None the least n that mtf_window's pitch rule allows there.  The curve is normalised by
+    the energy inside the window, so a radius whose circle or square leaves the window is refused (ValueError).
+    Returns (ee [M, nr], energy [M, nr], sums [M], centers [M, 2] in the plane's local coordinates, stats [M, 12])."""
+    from . import abi
+
+    if kind not in ("diffraction", "geometric"):
+        raise ValueError('encircled_energy: kind must be "diffraction" or "geometric"')
+    if shape not in abi.EE_SHAPES:
+        raise ValueError('encircled_energy: shape must be "circle" or "square"')
+    if follow not in ("centroid", None):
+        raise ValueError('encircled_energy: follow must be "centroid" or None')
+    r = np.asarray(radii, dtype=np.float64).reshape(-1)
+    if len(r) == 0 or not np.isfinite(r).all() or (r < 0).any():
+        raise ValueError("encircled_energy: needs at least one radius, all finite and not negative")
+    off = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    if len(off) == 0:
+        raise ValueError("encircled_energy: no offsets")
+    if kind == "geometric":
+        o = np.asarray(orientation, dtype=np.float64)
+        ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
+        st = stats_fn(ax, off)
+        centers = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]]
+        if follow is None and not np.isnan(st[:, abi.FOCUS_RMS_R]).all():
+            centers = np.tile(centers[int(np.nanargmin(st[:, abi.FOCUS_RMS_R]))], (len(off), 1))
+        centers = np.ascontiguousarray(centers)
+        if st[0, abi.FOCUS_N] == 0 or not np.isfinite(centers).all():
+            raise ValueError("encircled_energy: no plane has a centroid (no hit, or a row runs parallel to the detector plane)")
+        ee, energy, sums = geo_fn(ax, off, r, centers, shape)
+        return ee, energy, sums, centers, st
+    if half_width is None or n is None:
+        k_max, rho, n_rows = window_fn()
+        if half_width is None:
+            half_width, n_rule = mtf_window(k_max, rho, n_rows, mtf_cutoff(k_max, rho))
+        else:
+            n_rule = mtf_grid_points(half_width, mtf_cutoff(k_max, rho))
+        n = n_rule if n is None else int(n)
+    hw = np.broadcast_to(np.asarray(half_width, dtype=np.float64), (2,))
+    if r.max() > hw.min():
+        raise ValueError("encircled_energy: the radius %.3e m leaves the sampled window of half-width %.3e m (shrink the radii or give half_width)"
+                         % (r.max(), hw.min()))
+    out = {}
+
+    def stack_fn(d, xs, zs):
+        out["d"], out["r"] = d, ee_fn(d, xs, zs, r, shape)
+
+    _, _, d, _, st = psf_through_focus(stats_fn, stack_fn, orientation, off, n=int(n), axis=axis, follow=follow, half_width=half_width)
+    ee, energy, sums, cen = out["r"]
+    reach = np.abs(cen) + r.max()
+    if np.any(reach > hw[None, :]):  # a NaN centre (an image without energy) compares false
+        m = int(np.argmax(np.any(reach > hw[None, :], axis=1)))
+        raise ValueError("encircled_energy: about the centroid of plane %d the radius %.3e m leaves the sampled window of half-width %.3e m" % (m, r.max(), hw.min()))
+    grid = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]]
+    if follow is None:
+        grid = np.tile(grid[int(np.nanargmin(st[:, abi.FOCUS_RMS_R]))], (len(off), 1))
+    return ee, energy, sums, cen + grid, st
+
+
 def zernike_terms(order):
     """The (n, m) of the Zernike terms up to radial order `order` in OSA/ANSI order: j = (n (n + 2) + m) / 2."""
     return [(n, m) for n in range(int(order) + 1) for m in range(-n, n + 1, 2)]
@@ -739,6 +875,29 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
                        lambda ax, off, fq, cen: abi.psf_geo_otf(self.data, pos, e1, e2, ax, off, fq, centers=cen, device=device)[:3],
                        lambda d, xs, zs, fq: abi.psf_otf(self.data, pos, e1, e2, d, xs, zs, fq, device=device)[:3],
                        window_fn, o, freqs, offsets=offsets, kind=kind, n=n, half_width=half_width, axis=axis, follow=follow)
+
+    def encircled_energy(self, radii, offsets=(0.0,), kind="geometric", shape="circle", n=None, half_width=None, axis=None, follow="centroid", device=0):
+        """The encircled (shape "circle") or ensquared ("square") energy of all rows accumulated so far inside every half-size of `radii`
+        (metres; ee_radii makes an even list) on the detector plane moved by each of `offsets` along `axis`: (ee [M, nr], energy [M, nr],
+        sums [M], centers [M, 2], stats [M, 12]) as psf_encircled_energy describes them.  kind "geometric": bmo_psf_geo_ee, the proj-weighted
+        share of the propagated rows; "diffraction": bmo_psf_ee, the share of the pixel sums of the through-focus stack."""
+        from . import abi
+
+        o, pos = self.orientation(), self.position()
+        e1, e2 = o[:, 0], o[:, 2]
+
+        def window_fn():
+            st = abi.psf_stats(self.data, pos, e1, e2, device=device)[0]
+            info = abi.psf_zernike(self.data, pos, e1, e2, order=0, device=device)[1]
+            return st[abi.PSF_K_MAX], info[abi.ZERN_RHO], int(st[abi.PSF_N])
+
+        def geo_fn(ax, off, r, cen, sh_):
+            ee, energy, _, sums, _ = abi.psf_geo_ee(self.data, pos, e1, e2, ax, off, r, centers=cen, shape=sh_, device=device, want_count=False)
+            return ee, energy, sums
+
+        return psf_encircled_energy(lambda ax, off: abi.psf_focus_stats(self.data, pos, e1, e2, ax, off, device=device)[0], geo_fn,
+                                    lambda d, xs, zs, r, sh_: abi.psf_ee(self.data, pos, e1, e2, d, xs, zs, r, shape=sh_, device=device)[:4],
+                                    window_fn, o, radii, offsets=offsets, kind=kind, shape=shape, n=n, half_width=half_width, axis=axis, follow=follow)
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

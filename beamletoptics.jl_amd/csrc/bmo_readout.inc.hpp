@@ -2655,3 +2655,445 @@ extern "C" int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, cons
     if (device) *device = res->device;
     return BMO_OK;
 }
+
+// ====================================================================================================================
+// Encircled-energy read-out (include/bmo.h "Encircled-energy read-out"): the share of the light inside a circle or a square of half-size R
+// about a centre, for a list of R.  A point has one key: r2 = ax * ax + az * az (circle) or max(|ax|, |az|) (square), and it is inside
+// radius k iff key <= thr_k, thr_k = R_k * R_k or R_k, computed once on the host.  A NaN key compares false: outside every radius.
+//
+// Geometric (bmo_psf_geo_ee).  psf_geo_otf_kernel's shape with a (plane, radius) pair for a (plane, frequency) pair: a workgroup owns one
+// split of the rows (spot_splits), one chunk of MP planes and 256 / MP radii; per staged tile lane r propagates row r to the chunk's planes
+// and writes ONE double per (plane, row), its key, to LDS laid out [plane][row]; every lane then walks the tile with broadcast reads, a
+// compare, a masked add of proj and a masked count: no division, root or transcendental inside the walk.  18 KB of row tile + MP * 2 KB:
+// 34 KB at MP = 8, four workgroups per CU.  A pair's sum runs over the rows of a split in row order (a row outside adds +0.0 to a sum
+// that started at +0.0: the same number as adding nothing), the splits are folded in split order.  S is GeoOtfSum's, summed as the focus
+// statistics sum it.
+//
+// Diffraction (bmo_psf_ee).  psf_focus_stack's images summed where they lie, in the row / column shape of psf_otf_rows_kernel /
+// psf_otf_cols_kernel, twice: the moments (S and the centroid), then the energies about the centre.
+//
+// Spot (bmo_spot_ee, bmo_spot_ee_sweep).  spot_image_kernel's shape with a radial key for a bin: the thresholds sorted on the host, a
+// row's bin the number of thresholds below its key (a binary search; K for a NaN), counted into a per-workgroup LDS histogram of K + 1
+// bins by spot_add and added to the configuration's with 64-bit atomics; a cumulative pass per configuration turns bins into counts (a
+// row is inside sorted radius s iff its bin is <= s) and writes them in the caller's order.
+namespace {
+
+constexpr int GEO_EE_MP = 8;  // planes per chunk of a stack; a stack of fewer planes runs the next power of two
+
+struct EePartial {
+    double e;
+    long long n;
+};
+static_assert(sizeof(EePartial) == 16, "16 bytes per split, plane and radius");
+
+// the key of a point at (ax, az) from the centre.  The square's is the larger of |ax| and |az| and NaN if either is
+__device__ __forceinline__ double ee_key(double ax, double az, int32_t shape) {
+    if (shape == 0) return ax * ax + az * az;
+    const double fx = fabs(ax), fz = fabs(az);
+    return (fx >= fz || fx != fx) ? fx : fz;
+}
+
+// split blockIdx.y (work item) of the rows, planes blockIdx.z * MP .., radii blockIdx.x * (256 / MP) ..; partial: [item][plane][radius]
+template <int MP>
+__global__ __launch_bounds__(256) void psf_geo_ee_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                         const double* __restrict__ offsets, const double2* __restrict__ centers, int32_t n_planes,
+                                                         int32_t shape, const double* __restrict__ thr, int32_t n_radii, EePartial* __restrict__ partial,
+                                                         GeoOtfSum* __restrict__ sums) {
+    constexpr int RB = 256 / MP;
+    static_assert(MP >= 1 && MP <= 8 && 256 % MP == 0, "a chunk of planes divides the workgroup");
+    __shared__ double tile[PSF_TILE * 9];
+    __shared__ double key[MP * PSF_TILE];
+    const SplitWork W = work[blockIdx.y];
+    const int32_t m0 = (int32_t)blockIdx.z * MP;
+    const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;  // planes of this chunk; the slots past them repeat its first and are not stored
+    d3 o[MP];
+    double2 c[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        const int32_t mm = m0 + (m < mcnt ? m : 0);
+        o[m] = focus_origin(F, offsets[mm]);
+        c[m] = centers ? centers[mm] : make_double2(0.0, 0.0);
+    }
+    const int ml = (int)threadIdx.x / RB;
+    const int32_t k = (int32_t)blockIdx.x * RB + (int)threadIdx.x % RB;
+    const bool live = ml < mcnt && k < n_radii;
+    const double t = live ? thr[k] : 0.0;
+    GeoOtfSum a = sum_identity<GeoOtfSum>();
+    double e = 0.0;
+    long long n = 0;
+    for (int64_t base = W.h0; base < W.h1; base += PSF_TILE) {
+        const int cnt = (int)(W.h1 - base < PSF_TILE ? W.h1 - base : PSF_TILE);
+        psf_stage_rows(hits, base, cnt, tile);  // its first sync: the walk over the tile before is done
+        if ((int)threadIdx.x < cnt) {
+            const double* r = tile + 9 * threadIdx.x;
+            const double den = focus_den(r, F);
+            a.s += r[7];
+            a.bad += den == 0.0 ? 1.0 : 0.0;
+#pragma unroll
+            for (int m = 0; m < MP; ++m) {
+                double x, z;
+                focus_local(r, F, o[m], den, x, z);
+                key[m * PSF_TILE + threadIdx.x] = ee_key(x - c[m].x, z - c[m].y, shape);
+            }
+        }
+        __syncthreads();
+        if (live) {
+            const double* p = key + ml * PSF_TILE;
+            for (int h = 0; h < cnt; ++h) {
+                const bool in = p[h] <= t;
+                e += in ? tile[9 * h + 7] : 0.0;
+                n += in ? 1 : 0;
+            }
+        }
+    }
+    if (live) partial[((int64_t)blockIdx.y * n_planes + (m0 + ml)) * n_radii + k] = EePartial{e, n};
+    if (blockIdx.x == 0 && blockIdx.z == 0) {  // uniform over the workgroup: one record per work item
+        a = sum_wg_reduce(a);
+        if (threadIdx.x == 0) sums[blockIdx.y] = a;
+    }
+}
+
+// pair (plane, radius) = blockIdx.x * 256 + threadIdx.x: its partial sums folded in split order; energy, ee, count (optional) and, from
+// the pairs of radius 0, sums
+__global__ void psf_geo_ee_reduce_kernel(const EePartial* __restrict__ partial, int32_t n_splits, int64_t n_pairs, int32_t n_radii, const double* __restrict__ s_all,
+                                         double* __restrict__ ee, double* __restrict__ energy, long long* __restrict__ count, double* __restrict__ sums) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pairs) return;
+    double e = 0.0;
+    long long n = 0;
+    for (int32_t s = 0; s < n_splits; ++s) {
+        const EePartial v = partial[(int64_t)s * n_pairs + q];
+        e += v.e;
+        n += v.n;
+    }
+    const double S = *s_all;
+    if (S != S) e = knan();  // a row parallel to the planes (or a NaN proj): no energy
+    energy[q] = e;
+    ee[q] = e / S;
+    if (count) count[q] = n;
+    if (q % n_radii == 0) sums[q / n_radii] = S;
+}
+
+// Diffraction, the moments: thread (plane m, row j) sums image row j and its first x moment, i ascending
+__global__ void psf_ee_moment_rows_kernel(const double* __restrict__ img, const double* __restrict__ xs, int32_t n, int64_t n_threads, double2* __restrict__ rowmom) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_threads) return;  // n_planes * n
+    const double* row = img + t * n;
+    double s = 0.0, sx = 0.0;
+    for (int32_t i = 0; i < n; ++i) {
+        s += row[i];
+        sx += row[i] * xs[i];
+    }
+    rowmom[t] = make_double2(s, sx);  // [m][j]
+}
+
+// thread (plane m): the row moments summed, j ascending; sums and the centre used (the given one, or the intensity centroid)
+__global__ void psf_ee_moment_cols_kernel(const double2* __restrict__ rowmom, const double* __restrict__ zs, int32_t n, int32_t n_planes,
+                                          const double2* __restrict__ centers, double* __restrict__ sums, double2* __restrict__ centers_out) {
+    const int32_t m = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (m >= n_planes) return;
+    const double2* r = rowmom + (int64_t)m * n;
+    double S = 0.0, sx = 0.0, sz = 0.0;
+    for (int32_t j = 0; j < n; ++j) {
+        S += r[j].x;
+        sx += r[j].y;
+        sz += r[j].x * zs[j];
+    }
+    sums[m] = S;
+    centers_out[m] = centers ? centers[m] : make_double2(sx / S, sz / S);
+}
+
+// thread (plane m, radius k, row j): the samples of image row j inside radius k about the plane's centre, i ascending
+__global__ void psf_ee_rows_kernel(const double* __restrict__ img, const double* __restrict__ xs, const double* __restrict__ zs, int32_t n,
+                                   const double2* __restrict__ cen, int32_t shape, const double* __restrict__ thr, int32_t n_radii, int64_t n_threads,
+                                   double* __restrict__ rowsum) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_threads) return;  // n_planes * n_radii * n
+    const int32_t j = (int32_t)(t % n), k = (int32_t)(t / n % n_radii);
+    const int64_t m = t / n / n_radii;
+    const double* row = img + (m * n + j) * n;
+    const double2 c = cen[m];
+    const double az = zs[j] - c.y, th = thr[k];
+    double e = 0.0;
+    for (int32_t i = 0; i < n; ++i) e += ee_key(xs[i] - c.x, az, shape) <= th ? row[i] : 0.0;
+    rowsum[t] = e;  // [m][k][j]
+}
+
+// thread (plane m, radius k): the row sums added, j ascending
+__global__ void psf_ee_cols_kernel(const double* __restrict__ rowsum, int32_t n, int32_t n_radii, int64_t n_pairs, const double* __restrict__ sums,
+                                   double* __restrict__ ee, double* __restrict__ energy) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pairs) return;
+    const double* r = rowsum + q * n;
+    double e = 0.0;
+    for (int32_t j = 0; j < n; ++j) e += r[j];
+    energy[q] = e;
+    ee[q] = e / sums[q / n_radii];
+}
+
+constexpr int SPOT_EE_MAX_RADII = 4096;
+
+// work item blockIdx.x: the bins of its rows (the number of sorted thresholds below the row's key; n_radii for a NaN) added to hist[cfg],
+// [n_radii + 1] each.  LDS: the thresholds, then the counters.
+__global__ __launch_bounds__(256) void spot_ee_kernel(const double* __restrict__ rows, int32_t cols, const SplitWork* __restrict__ work,
+                                                      const double2* __restrict__ centers, int32_t shape, const double* __restrict__ thr, int32_t n_radii,
+                                                      unsigned long long* __restrict__ hist) {
+    __shared__ double sh_thr[SPOT_EE_MAX_RADII];
+    __shared__ uint32_t sh_hist[SPOT_EE_MAX_RADII + 1];
+    const SplitWork W = work[blockIdx.x];
+    const double2 c = centers[W.cfg];
+    for (int32_t b = threadIdx.x; b < n_radii; b += 256) sh_thr[b] = thr[b];
+    for (int32_t b = threadIdx.x; b <= n_radii; b += 256) sh_hist[b] = 0;
+    __syncthreads();
+    for (int64_t base = W.h0; base < W.h1; base += 256) {  // workgroup-uniform trips: spot_add needs whole waves
+        const int64_t h = base + threadIdx.x;
+        const bool live = h < W.h1;
+        int32_t bin = n_radii;
+        if (live) {
+            const double* r = rows + h * cols;
+            const double v = ee_key(r[0] - c.x, r[1] - c.y, shape);
+            if (v == v) {
+                int32_t lo = 0, hi = n_radii;  // the first threshold that is not below v
+                while (lo < hi) {
+                    const int32_t mid = (lo + hi) >> 1;
+                    if (sh_thr[mid] < v) lo = mid + 1;
+                    else hi = mid;
+                }
+                bin = lo;
+            }
+        }
+        spot_add(sh_hist, bin, live);
+    }
+    __syncthreads();
+    unsigned long long* out = hist + (int64_t)W.cfg * (n_radii + 1);
+    for (int32_t b = threadIdx.x; b <= n_radii; b += 256) {
+        const uint32_t v = sh_hist[b];
+        if (v) atomicAdd(&out[b], (unsigned long long)v);
+    }
+}
+
+// configuration blockIdx.x: inside[cfg][perm[s]] = hist[cfg][0] + .. + hist[cfg][s].  Lane l sums bins l * per .. in order, a scan over the
+// lanes' totals gives each its start.
+__global__ __launch_bounds__(256) void spot_ee_cumulate_kernel(const unsigned long long* __restrict__ hist, const int32_t* __restrict__ perm, int32_t n_radii,
+                                                               long long* __restrict__ inside) {
+    __shared__ unsigned long long tot[256];
+    const unsigned long long* h = hist + (int64_t)blockIdx.x * (n_radii + 1);
+    long long* out = inside + (int64_t)blockIdx.x * n_radii;
+    const int32_t per = (n_radii + 255) / 256, b0 = (int32_t)threadIdx.x * per, b1 = b0 + per < n_radii ? b0 + per : n_radii;
+    unsigned long long s = 0;
+    for (int32_t b = b0; b < b1; ++b) s += h[b];
+    tot[threadIdx.x] = s;
+    __syncthreads();
+    unsigned long long run = 0;
+    for (int l = 0; l < (int)threadIdx.x; ++l) run += tot[l];
+    for (int32_t b = b0; b < b1; ++b) {
+        run += h[b];
+        out[perm[b]] = (long long)run;
+    }
+}
+
+}  // namespace
+
+// what the encircled-energy entries refuse of their shape, radii and centres; thr: the thresholds the kernels compare with
+static bool ee_args_ok(int32_t shape, const double* radii, int32_t n_radii, const double* centers, int64_t n_centers, std::vector<double>& thr) {
+    if (shape < 0 || shape > 1) return false;
+    thr.resize((size_t)n_radii);
+    for (int32_t k = 0; k < n_radii; ++k) {
+        if (!std::isfinite(radii[k]) || radii[k] < 0) return false;
+        thr[(size_t)k] = shape == 0 ? radii[k] * radii[k] : radii[k];
+    }
+    for (int64_t q = 0; centers && q < 2 * n_centers; ++q)
+        if (!std::isfinite(centers[q])) return false;
+    return true;
+}
+
+// The geometric encircled energy of the n_hits > 0 device rows `hits` [..][9].
+static int psf_geo_ee_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* axis, const double* offsets,
+                           const double* centers, int32_t n_planes, int32_t shape, const std::vector<double>& thr, double* ee, double* energy, int64_t* count,
+                           double* sums, double* kernel_ms, const char* who) {
+    const int32_t n_radii = (int32_t)thr.size();
+    RowPasses P(Ranges{{0}, {n_hits}});  // the plan, the upload and the reduce of the statistics passes: S is one
+    if (int rc = P.items(who)) return rc;
+    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
+    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    int mp = 1;
+    while (mp < GEO_EE_MP && mp < n_planes) mp *= 2;
+    const unsigned chunks = (unsigned)((n_planes + mp - 1) / mp), r_blocks = (unsigned)(((int64_t)n_radii + 256 / mp - 1) / (256 / mp));
+    const int64_t n_pairs = (int64_t)n_planes * n_radii;
+    if (chunks > 65535 || P.n_items > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
+    // a pair's value does not depend on the pairs asked for along with it: a caller with more of them splits the call
+    if ((int64_t)P.n_items * n_pairs > ((int64_t)1 << 32) / (int64_t)sizeof(EePartial))
+        return fail(BMO_ERR_LIMIT, std::string(who) + ": the partial sums of n_planes * n_radii pairs pass 4 GiB; ask for them in several calls");
+    const size_t o_off = P.up.add(offsets, (size_t)n_planes), o_thr = P.up.add(thr);
+    const size_t o_cen = centers ? P.up.add(centers, (size_t)n_planes * 2) : 0;
+    DevBuf d_partial, d_s, d_ee, d_energy, d_count, d_sums;
+    int rc;
+    if ((rc = d_partial.alloc((size_t)P.n_items * (size_t)n_pairs * sizeof(EePartial))) || (rc = d_s.alloc(8)) || (rc = d_ee.alloc((size_t)n_pairs * 8)) ||
+        (rc = d_energy.alloc((size_t)n_pairs * 8)) || (count && (rc = d_count.alloc((size_t)n_pairs * 8))) || (rc = d_sums.alloc((size_t)n_planes * 8)) ||
+        (rc = P.begin<GeoOtfSum>()))
+        return rc;
+    const double2* d_cen = centers ? P.up.at<double2>(o_cen) : nullptr;
+    auto launch = [&](auto MP) {
+        hipLaunchKernelGGL(psf_geo_ee_kernel<decltype(MP)::value>, dim3(r_blocks, P.n_items, chunks), dim3(256), 0, P.st, hits, P.work(), F, P.up.at<double>(o_off), d_cen,
+                           n_planes, shape, P.up.at<double>(o_thr), n_radii, (EePartial*)d_partial.p, (GeoOtfSum*)P.records.p);
+    };
+    if (mp == 1) launch(std::integral_constant<int, 1>{});
+    else if (mp == 2) launch(std::integral_constant<int, 2>{});
+    else if (mp == 4) launch(std::integral_constant<int, 4>{});
+    else launch(std::integral_constant<int, GEO_EE_MP>{});
+    sum_reduce<GeoOtfSum>(1u, P.st, P.cfg(), P.records, GeoOtfSumFinish{(double*)d_s.p});
+    hipLaunchKernelGGL(psf_geo_ee_reduce_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, P.st, (const EePartial*)d_partial.p, (int32_t)P.n_items, n_pairs,
+                       n_radii, (const double*)d_s.p, (double*)d_ee.p, (double*)d_energy.p, count ? (long long*)d_count.p : nullptr, (double*)d_sums.p);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(ee, d_ee.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(energy, d_energy.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(hipMemcpy(count, d_count.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_geo_ee(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                              const double axis[3], const double* offsets, const double* centers, int32_t n_planes, int32_t shape, const double* radii, int32_t n_radii,
+                              int32_t device, double* ee, double* energy, int64_t* count, double* sums, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !axis || !offsets || !radii || !ee || !energy || !sums || n_planes <= 0 || n_radii <= 0 || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_geo_ee: bad argument (null pointer, n_planes <= 0, n_radii <= 0, n_hits < 0)");
+    std::vector<double> thr;
+    if (!ee_args_ok(shape, radii, n_radii, centers, n_planes, thr))
+        return fail(BMO_ERR_INVALID, "bmo_psf_geo_ee: shape must be 0 or 1, every radius finite and >= 0, every centre finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_geo_ee", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    if (n_hits == 0) {
+        const size_t n_pairs = (size_t)n_planes * (size_t)n_radii;
+        std::fill(ee, ee + n_pairs, std::nan(""));
+        std::fill(energy, energy + n_pairs, 0.0);
+        if (count) std::fill(count, count + n_pairs, (int64_t)0);
+        std::fill(sums, sums + n_planes, 0.0);
+        return BMO_OK;
+    }
+    return psf_geo_ee_read(hits, n_hits, origin, e1, e2, axis, offsets, centers, n_planes, shape, thr, ee, energy, count, sums, kernel_ms, "bmo_psf_geo_ee");
+}
+
+extern "C" int bmo_psf_ee(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                          const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* centers, int32_t shape,
+                          const double* radii, int32_t n_radii, int32_t device, double* ee, double* energy, double* sums, double* centers_out, double* out_intensity,
+                          double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !displacements || !xs || !zs || !radii || !ee || !energy || !sums || !centers_out || n <= 0 || n_planes <= 0 || n_radii <= 0 ||
+        n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_ee: bad argument (null pointer, n <= 0, n_planes <= 0, n_radii <= 0, n_hits < 0)");
+    std::vector<double> thr;
+    if (!ee_args_ok(shape, radii, n_radii, centers, n_planes, thr))
+        return fail(BMO_ERR_INVALID, "bmo_psf_ee: shape must be 0 or 1, every radius finite and >= 0, every centre finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_ee", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    const int64_t n_pairs = (int64_t)n_planes * n_radii;
+    if (n_hits == 0) {  // the sums of an image of zeros: the centroid is 0 / 0
+        std::fill(ee, ee + n_pairs, std::nan(""));
+        std::fill(energy, energy + n_pairs, 0.0);
+        std::fill(sums, sums + n_planes, 0.0);
+        for (int64_t q = 0; q < 2 * (int64_t)n_planes; ++q) centers_out[q] = centers ? centers[q] : std::nan("");
+        if (out_intensity) std::fill(out_intensity, out_intensity + n_out, 0.0);
+        return BMO_OK;
+    }
+    const int64_t n_rowsums = n_pairs * n, n_rowmoms = (int64_t)n_planes * n;
+    if ((n_rowsums + 255) / 256 > (int64_t)0x7fffffff) return fail(BMO_ERR_LIMIT, "bmo_psf_ee: more row sums than one launch holds");
+    hipStream_t st = 0;
+    DevBuf d_int, d_field, d_rowmom, d_rowsum, d_cen, d_ee, d_energy, d_sums;
+    Packed up;
+    const size_t o_xs = up.add(xs, (size_t)n), o_zs = up.add(zs, (size_t)n), o_thr = up.add(thr);
+    const size_t o_cen = centers ? up.add(centers, (size_t)n_planes * 2) : 0;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_rowmom.alloc((size_t)n_rowmoms * sizeof(double2))) || (rc = d_rowsum.alloc((size_t)n_rowsums * 8)) ||
+        (rc = d_cen.alloc((size_t)n_planes * sizeof(double2))) || (rc = d_ee.alloc((size_t)n_pairs * 8)) || (rc = d_energy.alloc((size_t)n_pairs * 8)) ||
+        (rc = d_sums.alloc((size_t)n_planes * 8)))
+        return rc;
+    EventTimer timer;
+    if ((rc = psf_focus_stack(hits, n_hits, origin, e1, e2, displacements, n_planes, xs, zs, n, false, d_int, d_field, timer, kernel_ms))) return rc;
+    hipLaunchKernelGGL(psf_ee_moment_rows_kernel, dim3((unsigned)((n_rowmoms + 255) / 256)), dim3(256), 0, st, (const double*)d_int.p, up.at<double>(o_xs), n, n_rowmoms,
+                       (double2*)d_rowmom.p);
+    hipLaunchKernelGGL(psf_ee_moment_cols_kernel, dim3((unsigned)((n_planes + 255) / 256)), dim3(256), 0, st, (const double2*)d_rowmom.p, up.at<double>(o_zs), n, n_planes,
+                       centers ? up.at<double2>(o_cen) : nullptr, (double*)d_sums.p, (double2*)d_cen.p);
+    hipLaunchKernelGGL(psf_ee_rows_kernel, dim3((unsigned)((n_rowsums + 255) / 256)), dim3(256), 0, st, (const double*)d_int.p, up.at<double>(o_xs), up.at<double>(o_zs), n,
+                       (const double2*)d_cen.p, shape, up.at<double>(o_thr), n_radii, n_rowsums, (double*)d_rowsum.p);
+    hipLaunchKernelGGL(psf_ee_cols_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, (const double*)d_rowsum.p, n, n_radii, n_pairs, (const double*)d_sums.p,
+                       (double*)d_ee.p, (double*)d_energy.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(ee, d_ee.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(energy, d_energy.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(centers_out, d_cen.p, (size_t)n_planes * sizeof(double2), hipMemcpyDeviceToHost));
+    if (out_intensity) HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// The counts [K][n_radii] of the K = R.count.size() configurations from the device rows `rows` [..][cols]: centers [K][2].
+static int spot_ee_read(const double* rows, int32_t cols, const Ranges& R, const double* centers, int32_t shape, const std::vector<double>& thr, int64_t* inside,
+                        double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    const int32_t n_radii = (int32_t)thr.size();
+    hipStream_t st = 0;
+    const SplitPlan plan = rows_plan(R);
+    unsigned n_items = 0;
+    if (int rc = rows_items(plan, who, n_items)) return rc;
+    std::vector<int32_t> perm((size_t)n_radii);  // sorted place s holds the caller's radius perm[s]
+    for (int32_t k = 0; k < n_radii; ++k) perm[(size_t)k] = k;
+    std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return thr[(size_t)a] < thr[(size_t)b]; });
+    std::vector<double> sorted((size_t)n_radii);
+    for (int32_t s = 0; s < n_radii; ++s) sorted[(size_t)s] = thr[(size_t)perm[(size_t)s]];
+    Packed up;
+    const size_t o_work = up.add(plan.work), o_cen = up.add(centers, K * 2), o_thr = up.add(sorted), o_perm = up.add(perm);
+    const size_t hist_bytes = K * (size_t)(n_radii + 1) * 8, out_bytes = K * (size_t)n_radii * 8;
+    DevBuf d_hist, d_inside;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_hist.alloc(hist_bytes)) || (rc = d_inside.alloc(out_bytes))) return rc;
+    EventTimer timer;
+    if ((rc = timer.start(st))) return rc;
+    HIP_TRY(hipMemsetAsync(d_hist.p, 0, hist_bytes, st));
+    if (n_items > 0)
+        hipLaunchKernelGGL(spot_ee_kernel, dim3(n_items), dim3(256), 0, st, rows, cols, up.at<SplitWork>(o_work), up.at<double2>(o_cen), shape, up.at<double>(o_thr), n_radii,
+                           (unsigned long long*)d_hist.p);
+    hipLaunchKernelGGL(spot_ee_cumulate_kernel, dim3((unsigned)K), dim3(256), 0, st, (const unsigned long long*)d_hist.p, up.at<int32_t>(o_perm), n_radii,
+                       (long long*)d_inside.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(inside, d_inside.p, out_bytes, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_spot_ee(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, const double center[2], int32_t shape, const double* radii,
+                           int32_t n_radii, int32_t device, int64_t* inside, double* kernel_ms) {
+    if (!center || !radii || !inside || n_radii <= 0 || n_rows < 0 || (n_rows > 0 && !rows) || row_cols < 2 || row_cols > 9)
+        return fail(BMO_ERR_INVALID, "bmo_spot_ee: bad argument (null pointer, n_radii <= 0, n_rows < 0, row_cols outside 2..9)");
+    std::vector<double> thr;
+    if (!ee_args_ok(shape, radii, n_radii, center, 1, thr))
+        return fail(BMO_ERR_INVALID, "bmo_spot_ee: shape must be 0 or 1, every radius finite and >= 0, the centre finite");
+    if (n_radii > SPOT_EE_MAX_RADII) return fail(BMO_ERR_LIMIT, "bmo_spot_ee: more than 4096 radii; ask for them in several calls");
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_rows;
+    if (int rc = single_rows("bmo_spot_ee", rows, n_rows, row_cols, rows_on_device, device, d_rows)) return rc;
+    return spot_ee_read(rows, row_cols, Ranges{{0}, {n_rows}}, center, shape, thr, inside, kernel_ms, "bmo_spot_ee");
+}
+
+extern "C" int bmo_spot_ee_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* centers, int32_t shape, const double* radii, int32_t n_radii,
+                                 int64_t* inside, int64_t* n_rows, double* kernel_ms) {
+    if (!res || !centers || !radii || !inside || !n_rows || n_radii <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_spot_ee_sweep: bad argument (null pointer, n_radii <= 0)");
+    if (int rc = slot_check("bmo_spot_ee_sweep", res, detector, BMO_OBJ_SPOTDETECTOR, true, n_configs)) return rc;
+    std::vector<double> thr;
+    if (!ee_args_ok(shape, radii, n_radii, centers, n_configs, thr))
+        return fail(BMO_ERR_INVALID, "bmo_spot_ee_sweep: shape must be 0 or 1, every radius finite and >= 0, every centre finite");
+    if (n_radii > SPOT_EE_MAX_RADII) return fail(BMO_ERR_LIMIT, "bmo_spot_ee_sweep: more than 4096 radii; ask for them in several calls");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_rows = 0
+        std::fill(inside, inside + (size_t)n_configs * (size_t)n_radii, (int64_t)0);
+        std::fill(n_rows, n_rows + n_configs, (int64_t)0);
+        return BMO_OK;
+    }
+    Ranges R;
+    const double* rows;
+    if (int rc = resident_rows("bmo_spot_ee_sweep", res, detector, H, n_configs, R, rows)) return rc;
+    std::copy(R.count.begin(), R.count.end(), n_rows);
+    return spot_ee_read(rows, 9, R, centers, shape, thr, inside, kernel_ms, "bmo_spot_ee_sweep");
+}

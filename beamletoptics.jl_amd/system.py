@@ -547,6 +547,46 @@ class EngineSolution:
         self.readout_ms = float(sum(ms))
         return out
 
+    def psf_encircled_energy(self, slot, position, orientation, radii, offsets=(0.0,), kind="geometric", shape="circle", n=None, half_width=None, axis=None,
+                             follow="centroid"):
+        """The encircled or ensquared energy of the resident rows of PSFDetector slot `slot` (bmo_psf_focus_stats, then bmo_psf_geo_ee or
+        bmo_psf_ee on the device pointer: no row and no image leaves the device): (ee [M, nr], energy [M, nr], sums [M], centers [M, 2],
+        stats [M, 12]) as PSFDetector.encircled_energy gives them from host rows."""
+        o = np.asarray(orientation, dtype=np.float64)
+        e1, e2 = o[:, 0], o[:, 2]
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        rows = dict(device=dev, hits_device_ptr=ptr, n_hits=cnt)
+        ms = []
+
+        def timed(out):
+            ms.append(out[-1])
+            return out
+
+        def window_fn():
+            st, info = self.psf_stats(slot, position, o), self.psf_zernike(slot, position, o, order=0)[1]
+            return st[abi.PSF_K_MAX], info[abi.ZERN_RHO], int(st[abi.PSF_N])
+
+        def geo_fn(ax, off, r, cen, sh):
+            ee, energy, _, sums, _ = timed(abi.psf_geo_ee(None, position, e1, e2, ax, off, r, centers=cen, shape=sh, want_count=False, **rows))
+            return ee, energy, sums
+
+        out = cp.psf_encircled_energy(lambda ax, off: timed(abi.psf_focus_stats(None, position, e1, e2, ax, off, **rows))[0], geo_fn,
+                                      lambda d, xs, zs, r, sh: timed(abi.psf_ee(None, position, e1, e2, d, xs, zs, r, shape=sh, **rows))[:4],
+                                      window_fn, o, radii, offsets=offsets, kind=kind, shape=shape, n=n, half_width=half_width, axis=axis, follow=follow)
+        self.readout_ms = float(sum(ms))
+        return out
+
+    def spot_encircled_energy(self, slot, radii, center=None, shape="circle"):
+        """bmo_spot_ee_sweep on the resident rows of Spotdetector slot `slot`: (fraction [nr], inside int64 [nr], n_rows) as
+        Spotdetector.encircled_energy gives them from host rows; center None: the centroid of spot_stats(slot)."""
+        ms = 0.0
+        if center is None:
+            center = cp.spot_ee_centers(self.spot_stats(slot))
+            ms = self.readout_ms
+        inside, n_rows, ms2 = abi.spot_ee_sweep(self.handle, slot, 1, center, radii, shape=shape)
+        self.readout_ms = ms + ms2
+        return cp.spot_ee_fraction(inside[0], int(n_rows[0])), inside[0], int(n_rows[0])
+
     def psf_intensity(self, slot, position, orientation, n=100, **window_kw):
         """intensity(psf; ...) of the resident rows of PSFDetector slot `slot`: (xs, zs, I[n, n]).  The window comes from psf_stats
         (components.psf_axes_from_stats takes window_kw), the image from bmo_psf_intensity_sweep: only the image leaves the device."""
@@ -993,6 +1033,24 @@ class SweepSolution:
             w = np.tile(w, (K, 1)) if w.ndim == 1 else w.reshape(K, 4)
         img, outside, self.readout_ms = abi.spot_image_sweep(self._handle, slot, K, w, nx, nz)
         return w, img, outside
+
+    def spot_encircled_energy(self, det, radii, center=None, shape="circle"):
+        """The share of the rows of Spotdetector `det` inside a circle or a square of every half-size of `radii`, in every configuration, in
+        one batched read-out (bmo_spot_ee_sweep): (fraction [n_cfg, nr], inside int64 [n_cfg, nr], n_rows int64 [n_cfg], centers [n_cfg, 2]).
+        center: one (x, z) for all configurations, an array [n_cfg, 2], or None for each configuration's centroid (one spot_stats call).
+        Row c equals abi.spot_ee on spot_hits(det, c) about its centre; a configuration without rows reads 0 and a NaN fraction."""
+        slot = self._slot(det)
+        K = self.n
+        ms = 0.0
+        if center is None:
+            c = cp.spot_ee_centers(self.spot_stats(det))
+            ms = self.readout_ms
+        else:
+            c = np.asarray(center, dtype=np.float64)
+            c = np.tile(c, (K, 1)) if c.ndim == 1 else c.reshape(K, 2)
+        inside, n_rows, ms2 = abi.spot_ee_sweep(self._handle, slot, K, c, radii, shape=shape)
+        self.readout_ms = ms + ms2
+        return cp.spot_ee_fraction(inside, n_rows), inside, n_rows, c
 
     def optical_power(self, pd, field=None):
         """optical_power(pd) of every configuration, [n]: the trapezoid rule of Photodetector.optical_power on each configuration's field."""

@@ -777,6 +777,64 @@ int bmo_psf_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, cons
                 const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* freqs,
                 int32_t n_freqs, int32_t device, double* otf, double* mtf, double* sums, double* out_intensity, double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Encircled-energy read-out: the share of the light inside a circle (encircled energy) or a square (ensquared energy) of half-size R about
+ * a centre, for a list of R, computed on the device from the rows where they lie.  Shared by the four entries:
+ *   shape: 0 = circle, 1 = square.   radii: [n_radii], host, in any order, each finite and >= 0.
+ *   (ax, az): a point's local coordinates less the centre.
+ *   circle:  r2 = ax * ax + az * az,   inside iff r2 <= R * R       (R * R computed once in FP64; there is no square root)
+ *   square:  inside iff fabs(ax) <= R && fabs(az) <= R
+ * Everything is FP64, each expression evaluated left to right as written, without contraction.  The compares are plain: a NaN is outside
+ * every radius, and the edge is closed.
+ *
+ * bmo_spot_ee: rows, n_rows, row_cols, rows_on_device, device, kernel_ms as for bmo_spot_image (x in column 0, z in column 1).
+ *   ax = x - center[0],   az = z - center[1];   inside[k]: the number of rows inside radii[k]
+ * Counts are integers: exact, whatever the order of the adds.  n_radii <= 4096, BMO_ERR_LIMIT beyond.
+ *
+ * bmo_spot_ee_sweep: the resident rows of Spotdetector slot `detector` of `res`, one curve per configuration (n_configs = 1 for an ordinary
+ * result; it works on record_segments = 0 results).  centers: [n_configs][2]; inside: [n_configs][n_radii]; n_rows: [n_configs], the rows
+ * of each configuration.  Configuration c equals bmo_spot_ee on its rows exactly.  It refuses what bmo_spot_stats_sweep refuses.
+ *
+ * bmo_psf_geo_ee: hits .. n_planes and centers as for bmo_psf_geo_otf (centers NULL: (0, 0)).  Per row and plane m:
+ *   den, o_m, s, q, x, z: exactly the expressions of bmo_psf_focus_stats
+ *   ax = x - cx_m,   az = z - cz_m
+ *   energy[m][k] = sum of proj over the rows inside radii[k],   count[m][k] their number (count: optional, NULL skips it)
+ *   sums[m] = S = sum proj (equal to BMO_FOCUS_STAT_S bit for bit),   ee[m][k] = energy[m][k] / S
+ * The sum of a (plane, radius) pair runs over the rows of a split in row order, starts at +0.0, and a row outside adds nothing; the splits
+ * (those of bmo_spot_stats) are folded in split order.  So a pair's value does not depend on the planes and radii asked for along with it,
+ * and resident rows equal host rows, both bit for bit.  No rows: zeros, and NaN in ee.  A row with den = 0 (or a NaN proj): NaN in ee,
+ * energy and sums; count is still the plain count.  BMO_ERR_LIMIT if the partial sums (16 bytes per split, plane and radius; at most 2 048
+ * splits) would pass 4 GiB: ask for the planes or radii in several calls.
+ *
+ * bmo_psf_ee: hits .. displacements, n_planes, xs, zs, n, device as for bmo_psf_through_focus.  The images I_m are those of
+ * bmo_psf_through_focus for the same arguments bit for bit (the same kernels and plan) and stay on the device; out_intensity: optional,
+ * host, [n_planes][n*n].  centers: NULL or [n_planes][2].  Per plane, i ascending inside and j ascending outside:
+ *   sums[m] = sum_j (sum_i I(i,j))
+ *   centers NULL:  cx = (sum_j (sum_i I(i,j) * xs[i])) / sums[m],   cz = (sum_j ((sum_i I(i,j)) * zs[j])) / sums[m]     (the centroid)
+ *   otherwise:     (cx, cz) = centers[m];     centers_out[m] = (cx, cz), always the centre used
+ *   ax = xs[i] - cx,   az = zs[j] - cz
+ *   energy[m][k] = sum_j (sum_i (inside ? I(i,j) : nothing)),   ee[m][k] = energy[m][k] / sums[m]
+ * The curve is a ratio of pixel sums: it is normalised by the energy inside the sampled window, not by the energy of the whole PSF, so
+ * the window must hold the PSF (components.mtf_window), and a radius whose circle or square leaves the window only reads 1 (the Python
+ * layer refuses it).  n_hits = 0: zeros, NaN in ee, and NaN in centers_out where centers is NULL.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than centers (PSF entries), count, out_intensity,
+ * kernel_ms; n_radii <= 0, n_planes <= 0, n <= 0, n_hits or n_rows < 0; shape outside 0..1; a radius that is negative or not finite; a
+ * centre that is not finite; row_cols outside 2..9; a wrong slot or n_configs.  BMO_ERR_UNSUPPORTED: a GaussianBeamlet result.  The two PSF
+ * entries have no _sweep form and no GaussianBeamlet form: resident rows come through bmo_result_psf_rows.                              */
+int bmo_spot_ee(const double* rows, int64_t n_rows, int32_t row_cols, int32_t rows_on_device, const double center[2], int32_t shape,
+                const double* radii, int32_t n_radii, int32_t device, int64_t* inside, double* kernel_ms);
+int bmo_spot_ee_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* centers, int32_t shape, const double* radii,
+                      int32_t n_radii, int64_t* inside, int64_t* n_rows, double* kernel_ms);
+int bmo_psf_geo_ee(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                   const double e2[3], const double axis[3], const double* offsets, const double* centers, int32_t n_planes, int32_t shape,
+                   const double* radii, int32_t n_radii, int32_t device, double* ee, double* energy, int64_t* count, double* sums,
+                   double* kernel_ms);
+int bmo_psf_ee(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+               const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* centers,
+               int32_t shape, const double* radii, int32_t n_radii, int32_t device, double* ee, double* energy, double* sums,
+               double* centers_out, double* out_intensity, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
