@@ -31,6 +31,12 @@ ZERN_MAX_ORDER = 6
 (ZERN_N, ZERN_STATUS, ZERN_S, ZERN_X_REF, ZERN_Z_REF, ZERN_U0, ZERN_V0, ZERN_RHO, ZERN_W_MEAN, ZERN_FIT_RMS, ZERN_E_LO, ZERN_E_HI,
  ZERN_N_OUT) = range(ZERN_INFO_N)
 
+# BMO_OPD_*: columns of the info row of the OPD map read-out (bmo_psf_opd_map); the first thirteen are the Zernike read-out's
+OPD_INFO_N = 20
+OPD_MAX_N = 4096
+(OPD_N, OPD_STATUS, OPD_S, OPD_X_REF, OPD_Z_REF, OPD_U0, OPD_V0, OPD_RHO, OPD_W_MEAN, OPD_E_RMS, OPD_E_LO, OPD_E_HI, OPD_N_OUT, OPD_N_OUTSIDE, OPD_N_BAD,
+ OPD_N_FILLED, OPD_SH_Q, OPD_SH_P, OPD_MAP_LO, OPD_MAP_HI) = range(OPD_INFO_N)
+
 # BMO_FOCUS_STAT_*: columns of the focus statistics (bmo_psf_focus_stats)
 FOCUS_STAT_N = 12
 (FOCUS_N, FOCUS_S, FOCUS_CX, FOCUS_CZ, FOCUS_X_MIN, FOCUS_X_MAX, FOCUS_Z_MIN, FOCUS_Z_MAX, FOCUS_HWX, FOCUS_HWZ, FOCUS_RMS_R, FOCUS_MAX_R) = range(FOCUS_STAT_N)
@@ -260,6 +266,8 @@ def load_engine():
     lib.bmo_psf_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
     lib.bmo_psf_zernike.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
     lib.bmo_psf_zernike_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_opd_map.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, ip, ip, dp, dp]
+    lib.bmo_psf_opd_map_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, dp, dp, ip, ip, dp, dp]
     lib.bmo_psf_through_focus.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, C.c_int32, dp, dp, dp]
     lib.bmo_psf_focus_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, dp]
     lib.bmo_result_psf_rows.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
@@ -665,3 +673,57 @@ def psf_zernike_sweep(res_handle, detector, n_configs, origins, e1s, e2s, order=
                                          coef.ctypes.data_as(dp), info.ctypes.data_as(dp), gram.ctypes.data_as(dp) if want_gram else None, C.byref(ms)),
           "bmo_psf_zernike_sweep")
     return coef[:K], info[:K], None if gram is None else gram[:K], ms.value
+
+
+def _opd_maps(a, K, n):
+    """[K, n * n] with bin (i, j) at i + n * j -> [K, n, n] indexed [c, i, j]"""
+    return np.ascontiguousarray(a.reshape(K, n, n, *a.shape[2:]).swapaxes(1, 2))
+
+
+def psf_opd_map(hits, origin, e1, e2, n=64, order=0, coef=None, ref=None, pupil=None, device=0, hits_device_ptr=None, n_hits=None, want_raw=False):
+    """bmo_psf_opd_map: the wavefront of PSF rows at the detector pose (origin, e1, e2) less the Zernike surface `coef` ([J] at `order`,
+    metres; None with order 0: nothing removed), as the proj-weighted mean per bin of an n x n grid over the pupil square, binned on the
+    device with integer sums.  ref, pupil, `hits` / `hits_device_ptr`: as psf_zernike.  Returns (opd [n, n] indexed [i, j], weight [n, n],
+    count int64 [n, n], info [20] at the OPD_* columns, raw int64 [n, n, 2] of (Q, P) or None, kernel_ms)."""
+    lib = load_engine()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
+    q = None if pupil is None else np.ascontiguousarray(pupil, dtype=np.float64).reshape(3)
+    cf = None if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+    if cf is not None and len(cf) != zernike_sizes(order)[0]:
+        raise ValueError("psf_opd_map: coef must have the (order + 1)(order + 2) / 2 terms of `order`")
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    nb = min(max(int(n), 1), OPD_MAX_N)
+    opd, weight, count, info = np.zeros((1, nb * nb)), np.zeros((1, nb * nb)), np.zeros((1, nb * nb), dtype=np.int64), np.zeros(OPD_INFO_N)
+    raw = np.zeros((1, nb * nb, 2), dtype=np.int64) if want_raw else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_opd_map(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
+                                   None if q is None else q.ctypes.data_as(dp), int(order), None if cf is None else cf.ctypes.data_as(dp), int(n), int(device),
+                                   opd.ctypes.data_as(dp), weight.ctypes.data_as(dp), count.ctypes.data_as(ip), raw.ctypes.data_as(ip) if want_raw else None,
+                                   info.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_opd_map")
+    return _opd_maps(opd, 1, nb)[0], _opd_maps(weight, 1, nb)[0], _opd_maps(count, 1, nb)[0], info, _opd_maps(raw, 1, nb)[0] if want_raw else None, ms.value
+
+
+def psf_opd_map_sweep(res_handle, detector, n_configs, origins, e1s, e2s, n=64, order=0, coef=None, ref=None, pupil=None, want_raw=False):
+    """bmo_psf_opd_map_sweep on the result handle `res_handle`: origins / e1s / e2s [K, 3]; ref, pupil as psf_zernike_sweep; coef None
+    (order 0), one [J] for all or [K, J].  Returns (opd [K, n, n] indexed [c, i, j], weight, count int64, info [K, 20], raw [K, n, n, 2] or
+    None, kernel_ms); configuration c equals psf_opd_map on its rows bit for bit."""
+    lib = load_engine()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
+    r, q = _per_config(ref, K1, 2), _per_config(pupil, K1, 3)
+    cf = _per_config(coef, K1, zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))[0])
+    nb = min(max(int(n), 1), OPD_MAX_N)
+    opd, weight, count, info = np.zeros((K1, nb * nb)), np.zeros((K1, nb * nb)), np.zeros((K1, nb * nb), dtype=np.int64), np.zeros((K1, OPD_INFO_N))
+    raw = np.zeros((K1, nb * nb, 2), dtype=np.int64) if want_raw else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_opd_map_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
+                                         None if r is None else r.ctypes.data_as(dp), None if q is None else q.ctypes.data_as(dp), int(order),
+                                         None if cf is None else cf.ctypes.data_as(dp), int(n), opd.ctypes.data_as(dp), weight.ctypes.data_as(dp),
+                                         count.ctypes.data_as(ip), raw.ctypes.data_as(ip) if want_raw else None, info.ctypes.data_as(dp), C.byref(ms)),
+          "bmo_psf_opd_map_sweep")
+    return (_opd_maps(opd, K1, nb)[:K], _opd_maps(weight, K1, nb)[:K], _opd_maps(count, K1, nb)[:K], info[:K], _opd_maps(raw, K1, nb)[:K] if want_raw else None,
+            ms.value)

@@ -796,6 +796,66 @@ def zernike_surface(coef, n, order):
     return np.where(x * x + y * y <= 1.0, np.tensordot(c, Z, axes=1), np.nan)
 
 
+def opd_remove_terms(remove, order):
+    """The (n, m) of the Zernike terms up to `order` that an OPD map removes: "none", "tilt" (n <= 1: piston and tilt), "defocus" (those
+    and (2, 0)), "fit" (every term: the residual map), or an iterable of (n, m)."""
+    terms = zernike_terms(order)
+    if isinstance(remove, str):
+        if remove not in ("none", "tilt", "defocus", "fit"):
+            raise ValueError('opd_map: remove must be "none", "tilt", "defocus", "fit" or an iterable of (n, m)')
+        if remove == "none":
+            return []
+        if remove == "fit":
+            return terms
+        return [t for t in terms if t[0] <= 1 or (remove == "defocus" and t == (2, 0))]
+    want = [(int(n), int(m)) for n, m in remove]
+    missing = [t for t in want if t not in terms]
+    if missing:
+        raise ValueError("opd_map: no term %s at order %d" % (missing[0], order))
+    return [t for t in terms if t in want]
+
+
+def psf_opd_map(zernike_fn, map_fn, n=64, order=4, remove="tilt", ref=None, pupil=None, coef=None):
+    """The binned wavefront (OPD) map shared by PSFDetector.opd_map, EngineSolution.psf_opd_map and SweepSolution.psf_opd_map.
+    zernike_fn(order, ref, pupil) -> (coef [.., J], info [.., 13]) is the Zernike read-out, map_fn(order, coef, ref, pupil) ->
+    (opd, weight, count, info) the map read-out (both of one configuration, or of every configuration of a sweep with a leading axis).
+    With `remove` other than "none" (and no `coef` given) the wavefront is fitted at `order`, the coefficients of the terms to keep are
+    zeroed, and the map is read about that fit's reference point (X_REF, Z_REF) and pupil (U0, V0, RHO) with the rest removed; a given
+    `coef` is removed as it stands.  Returns (opd [.., n, n] indexed [i, j] in metres, NaN in bins without rows; weight; count; info [.., 20]
+    at the abi.OPD_* columns; coef_removed [.., J])."""
+    from . import abi
+
+    if coef is not None:
+        cf = np.asarray(coef, dtype=np.float64)
+        return (*map_fn(order, cf, ref, pupil), cf)
+    removed = opd_remove_terms(remove, order)
+    if not removed:
+        out = map_fn(0, None, ref, pupil)
+        return (*out, np.zeros(np.shape(out[3])[:-1] + (1,)))
+    cf, zi = zernike_fn(order, ref, pupil)
+    keep = [j for j, t in enumerate(zernike_terms(order)) if t not in removed]
+    cf = np.array(cf, dtype=np.float64)
+    cf[..., keep] = 0.0
+    cf = np.where(np.isfinite(cf), cf, 0.0)  # a fit that was not solved removes nothing
+    r, q = zi[..., [abi.ZERN_X_REF, abi.ZERN_Z_REF]], zi[..., [abi.ZERN_U0, abi.ZERN_V0, abi.ZERN_RHO]]
+    usable = np.isfinite(r).all(axis=-1) & np.isfinite(q).all(axis=-1) & (q[..., 2] > 0)
+    if zi.ndim == 1:
+        if not usable:  # no rows, or a single direction: the map computes (and reports) what the fit did
+            r, q = ref, pupil
+    elif not usable.all():  # a batched call takes a pupil for every configuration: those without one are read on the unit pupil
+        r, q = np.where(usable[:, None], r, 0.0), np.where(usable[:, None], q, np.array([0.0, 0.0, 1.0]))
+    return (*map_fn(order, cf, r, q), cf)
+
+
+def opd_axes(info, n):
+    """(us, vs): the centres of the n bins per axis of an OPD map in direction cosines, from its info row: U0 + RHO x_i with
+    x_i = -1 + (2 i + 1) / n."""
+    from . import abi
+
+    x = -1.0 + (2.0 * np.arange(int(n)) + 1.0) / int(n)
+    return info[abi.OPD_U0] + info[abi.OPD_RHO] * x, info[abi.OPD_V0] + info[abi.OPD_RHO] * x
+
+
 class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
     kind = O_PSF
 
@@ -838,6 +898,17 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
         o = self.orientation()
         coef, info, _, _ = abi.psf_zernike(self.data, self.position(), o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil, device=device)
         return coef, info
+
+    def opd_map(self, n=64, order=4, remove="tilt", ref=None, pupil=None, device=0):
+        """The binned wavefront (OPD) map of all rows accumulated so far (bmo_psf_opd_map): (opd [n, n] indexed [i, j] in metres, weight,
+        count, info [20] at the abi.OPD_* columns, coef_removed [J]) as psf_opd_map describes them; opd_axes(info, n) gives the bin centres.
+        remove: "none", "tilt", "defocus", "fit" or an iterable of (n, m), the terms of a fit at `order` taken out of the map."""
+        from . import abi
+
+        o, pos = self.orientation(), self.position()
+        return psf_opd_map(lambda od, r, q: abi.psf_zernike(self.data, pos, o[:, 0], o[:, 2], order=od, ref=r, pupil=q, device=device)[:2],
+                           lambda od, cf, r, q: abi.psf_opd_map(self.data, pos, o[:, 0], o[:, 2], n=n, order=od, coef=cf, ref=r, pupil=q, device=device)[:4],
+                           n=n, order=order, remove=remove, ref=ref, pupil=pupil)
 
     def focus_stats(self, offsets, axis=None, device=0):
         """The twelve spot statistics (abi.FOCUS_* columns) of all rows accumulated so far, propagated along their directions to the detector

@@ -1886,6 +1886,28 @@ __global__ __launch_bounds__(256) void psf_zernike_gram_reduce_kernel(const Spli
     for (int q = 0; q < J; ++q) cf[q] = yv[q];
 }
 
+// The residual of one row of the scratch column about the surface cf [J], one definition for the Zernike read-out's pass D and the OPD map's
+// passes E and M: the pupil coordinates (x, y) of the row and E_h = (W_h - W_MEAN) - F_h.
+template <int ORDER>
+__device__ __forceinline__ double zern_residual(const double4& q, const ZernMid& M, const double* cf, double& x, double& y) {
+    x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
+    double f = 0.0;
+    zern_terms<ORDER>(x, y, [&](int j, double Z) { f = j == 0 ? cf[0] * Z : f + cf[j] * Z; });
+    return (q.y - M.w_mean) - f;
+}
+// the residual sums of that row added to a record with the fields of ZERN_SUM_D; returns E_h
+template <int ORDER, class R>
+__device__ __forceinline__ double zern_residual_add(R& s, const double4& q, const ZernMid& M, const double* cf) {
+    double x, y;
+    const double e = zern_residual<ORDER>(q, M, cf, x, y);
+    const double t = x * x + y * y;
+    s.var += q.x * (e * e);
+    s.lo = e < s.lo ? e : s.lo;
+    s.hi = e > s.hi ? e : s.hi;
+    s.n_out += t > 1.0 ? 1.0 : 0.0;
+    return e;
+}
+
 // pass D of work item blockIdx.x, on the scratch column: the residual of the fit
 template <int ORDER>
 __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
@@ -1896,18 +1918,7 @@ __global__ __launch_bounds__(256) void psf_zernike_residual_kernel(const double4
     double cf[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
-    sum_pass_strided(W, partial, [&](ZernSumD& s, int64_t h) {
-        const double4 q = col[h];
-        const double x = (q.z - M.u0) / M.rho, y = (q.w - M.v0) / M.rho;
-        const double t = x * x + y * y;
-        double f = 0.0;
-        zern_terms<ORDER>(x, y, [&](int j, double Z) { f = j == 0 ? cf[0] * Z : f + cf[j] * Z; });
-        const double e = (q.y - M.w_mean) - f;
-        s.var += q.x * (e * e);
-        s.lo = e < s.lo ? e : s.lo;
-        s.hi = e > s.hi ? e : s.hi;
-        s.n_out += t > 1.0 ? 1.0 : 0.0;
-    });
+    sum_pass_strided(W, partial, [&](ZernSumD& s, int64_t h) { zern_residual_add<ORDER>(s, col[h], M, cf); });
 }
 
 struct ZernResidualFinish {
@@ -2017,6 +2028,407 @@ extern "C" int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, in
     const double* hits;
     if (int rc = resident_rows("bmo_psf_zernike_sweep", res, detector, H, n_configs, R, hits)) return rc;
     return psf_zernike_read(hits, H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, info, gram, kernel_ms, "bmo_psf_zernike_sweep");
+}
+
+// ====================================================================================================================
+// OPD map read-out: the wavefront of a PSFDetector's rows less a given Zernike surface, binned over the pupil square (include/bmo.h "OPD map
+// read-out").  Passes A and B are the Zernike read-out's kernels and finish functors, unchanged, writing a Zernike info row that stays on
+// the device; then
+//   E  psf_zernike_residual_kernel's row body (zern_residual_add) with MQ, MP and N_BAD added to the record; its reduce writes the info
+//      columns up to N_BAD and leaves the two scales and STATUS on the device
+//   M  the binning: one workgroup per work item, every lane evaluates E_h of its row again, its bin and the integers q_h, p_h, and adds
+//      them to the bin's (Q, P, count).  A map of at most OPD_LDS_BINS bins is privatised in LDS (zeroed, filled with LDS integer atomics,
+//      its non-zero bins flushed with 64-bit global atomic adds); a larger one is added to global memory directly.  opd_add can aggregate
+//      the adds of a wave whose lanes share a bin (BMO_OPD_AGG_ITERS); measured, plain per-lane atomics won and are the default.  Integer
+//      adds only: the sums do not depend on their order, which is what makes sweep = single = resident rows bit for bit without a sort.
+//   finish  a thread per bin writes opd, weight and raw; the blocks' filled-bin counts, row counts and extrema are folded per configuration
+//      (integers, min and max: order-free).
+// LDS budget: 20 bytes a bin (int64 Q, int64 P, uint32 count).  OPD_LDS_BINS = 4 096 bins (n <= 64, the Python layer's default) is 80 KiB, two
+// workgroups on a CU's 160 KiB: two waves per SIMD, which a pass that spends its time on FP64 arithmetic (the terms and two divisions per row)
+// still runs several times faster than the same adds sent to global memory one by one (the flush never sends more global adds
+// than the rows would have).  The LDS a launch asks for is its own map's: n = 32 takes 20 KiB and runs at the CU's full 32 waves, n = 45 40 KiB.
+#ifndef BMO_OPD_AGG_ITERS
+#define BMO_OPD_AGG_ITERS 0  // distinct bins a wave adds by ballot and reduction before the remaining lanes add singly; 0: plain per-lane atomics,
+#endif                       // which measured faster on ordered and on shuffled rows (profiles/psf_opd_bench.txt); the tests hold for either
+namespace {
+
+constexpr int OPD_LDS_BINS = 4096;
+constexpr int OPD_AGG_ITERS = BMO_OPD_AGG_ITERS;
+static_assert(OPD_AGG_ITERS >= 0 && OPD_AGG_ITERS <= 8, "OPD_AGG_ITERS: 0 .. 8");
+
+#define OPD_SUM_E(F) ZERN_SUM_D(F) F(mq, SumMax0) F(mp, SumMax0) F(n_bad, SumAdd)
+SUM_RECORD(OpdSumE, OPD_SUM_E);
+// what pass M and the finish need of configuration c
+struct OpdMid {
+    double scale_q, scale_p, inv_q, inv_p;  // ldexp(1.0, SH_Q), ldexp(1.0, SH_P), ldexp(1.0, -SH_Q), ldexp(1.0, -SH_P)
+    int32_t status, pad;
+};
+
+// pass E of work item blockIdx.x
+template <int ORDER>
+__global__ __launch_bounds__(256) void psf_opd_residual_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
+                                                               const double* __restrict__ coef, OpdSumE* __restrict__ partial) {
+    constexpr int J = zern_terms_of(ORDER);
+    const SplitWork W = work[blockIdx.x];
+    const ZernMid M = mid[W.cfg];
+    double cf[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
+    sum_pass_strided(W, partial, [&](OpdSumE& s, int64_t h) {
+        const double4 q = col[h];
+        const double e = zern_residual_add<ORDER>(s, q, M, cf);
+        const double pe = q.x * e;
+        const double aq = fabs(pe), ap = fabs(q.x);
+        s.mq = aq > s.mq ? aq : s.mq;
+        s.mp = ap > s.mp ? ap : s.mp;
+        s.n_bad += (isfinite(q.x) && isfinite(pe)) ? 0.0 : 1.0;
+    });
+}
+
+// sh(M) of include/bmo.h for N <= 2^b rows
+__device__ __forceinline__ int opd_shift(double m, int b) {
+    if (m == 0.0) return 0;
+    const int sh = 60 - b - ilogb(m);
+    return sh < -1000 ? -1000 : sh > 1000 ? 1000 : sh;
+}
+
+// The info columns of passes A and B come from the Zernike info row zinfo[c] those passes wrote; this writes the rest up to N_BAD, the shifts,
+// and mid[c] for pass M and the finish.
+struct OpdResidualFinish {
+    const int64_t* count;
+    const double* zinfo;
+    double* info;
+    OpdMid* mid;
+    __device__ void empty(int32_t c) const {
+        double* out = info + (int64_t)c * BMO_OPD_INFO_N;
+        for (int q = 0; q < BMO_OPD_INFO_N; ++q) out[q] = knan();
+        out[BMO_OPD_N_ROWS] = 0.0;
+        out[BMO_OPD_STATUS] = 1.0;
+        mid[c] = OpdMid{0.0, 0.0, 0.0, 0.0, 1, 0};
+    }
+    __device__ void operator()(int32_t c, const OpdSumE& s) const {
+        double* out = info + (int64_t)c * BMO_OPD_INFO_N;
+        const double* z = zinfo + (int64_t)c * BMO_ZERNIKE_INFO_N;
+        for (int q = 0; q <= BMO_ZERNIKE_W_MEAN; ++q) out[q] = z[q];  // the two enums agree up to N_OUT (static_assert below)
+        const double rho = z[BMO_ZERNIKE_RHO];
+        const int status = (rho == 0.0 || !isfinite(rho)) ? 1 : s.n_bad > 0.0 ? 2 : 0;
+        const bool usable = status != 1;
+        out[BMO_OPD_STATUS] = (double)status;
+        out[BMO_OPD_E_RMS] = usable ? sqrt(s.var / z[BMO_ZERNIKE_S]) : knan();
+        out[BMO_OPD_E_LO] = usable ? s.lo : knan();
+        out[BMO_OPD_E_HI] = usable ? s.hi : knan();
+        out[BMO_OPD_N_OUT] = s.n_out;
+        out[BMO_OPD_N_BAD] = s.n_bad;
+        const int64_t n = count[c];
+        int b = 0;
+        while (((int64_t)1 << b) < n) ++b;
+        const int sh_q = status == 0 ? opd_shift(s.mq, b) : 0, sh_p = status == 0 ? opd_shift(s.mp, b) : 0;
+        out[BMO_OPD_SH_Q] = status == 0 ? (double)sh_q : knan();
+        out[BMO_OPD_SH_P] = status == 0 ? (double)sh_p : knan();
+        mid[c] = OpdMid{ldexp(1.0, sh_q), ldexp(1.0, sh_p), ldexp(1.0, -sh_q), ldexp(1.0, -sh_p), status, 0};
+    }
+};
+static_assert(BMO_OPD_N_ROWS == (int)BMO_ZERNIKE_N_ROWS && BMO_OPD_STATUS == (int)BMO_ZERNIKE_STATUS && BMO_OPD_S == (int)BMO_ZERNIKE_S &&
+                  BMO_OPD_X_REF == (int)BMO_ZERNIKE_X_REF && BMO_OPD_Z_REF == (int)BMO_ZERNIKE_Z_REF && BMO_OPD_U0 == (int)BMO_ZERNIKE_U0 &&
+                  BMO_OPD_V0 == (int)BMO_ZERNIKE_V0 && BMO_OPD_RHO == (int)BMO_ZERNIKE_RHO && BMO_OPD_W_MEAN == (int)BMO_ZERNIKE_W_MEAN,
+              "the OPD info row begins like the Zernike info row");
+
+// (Q, P, count)[key] += (q, p, 1) for every lane with `live`, called by whole waves in uniform control flow (a lane without a row passes
+// live = false).  The first live lane's bin is taken, the lanes that share it are found by ballot, their q and p are summed over the wave
+// (integer adds: any tree is exact) and that lane adds the three sums; after OPD_AGG_ITERS such bins the lanes left add singly.
+template <class Cnt>
+__device__ __forceinline__ void opd_add(unsigned long long* Q, unsigned long long* P, Cnt* N, int32_t key, long long q, long long p, bool live) {
+    const int lane = (int)(threadIdx.x & 63);
+#pragma unroll
+    for (int it = 0; it < OPD_AGG_ITERS; ++it) {
+        const unsigned long long lm = __ballot(live);
+        if (lm == 0) break;  // wave-uniform
+        const int first = __ffsll((long long)lm) - 1;
+        const int32_t k = __builtin_amdgcn_readlane(key, first);
+        const bool match = live && key == k;
+        const unsigned long long mm = __ballot(match);
+        long long sq = match ? q : 0, sp = match ? p : 0;
+        for (int off = 32; off > 0; off >>= 1) {
+            sq += __shfl_xor(sq, off);
+            sp += __shfl_xor(sp, off);
+        }
+        if (lane == first) {
+            atomicAdd(&Q[k], (unsigned long long)sq);
+            atomicAdd(&P[k], (unsigned long long)sp);
+            atomicAdd(&N[k], (Cnt)__popcll(mm));
+        }
+        live = live && !match;
+    }
+    if (live) {
+        atomicAdd(&Q[key], (unsigned long long)q);
+        atomicAdd(&P[key], (unsigned long long)p);
+        atomicAdd(&N[key], (Cnt)1);
+    }
+}
+
+// pass M of work item blockIdx.x: its rows binned into (gq, gp, gc)[cfg][n * n].  A configuration of STATUS 1 bins nothing; one of STATUS 2
+// counts its rows and adds q = p = 0.
+template <int ORDER, bool LDS>
+__global__ __launch_bounds__(256) void psf_opd_bin_kernel(const double4* __restrict__ col, const SplitWork* __restrict__ work, const ZernMid* __restrict__ mid,
+                                                          const double* __restrict__ coef, const OpdMid* __restrict__ omid, int32_t n,
+                                                          unsigned long long* __restrict__ gq, unsigned long long* __restrict__ gp,
+                                                          unsigned long long* __restrict__ gc) {
+    extern __shared__ unsigned long long opd_lds[];  // LDS: Q [n * n], P [n * n], then the uint32 counts [n * n]
+    constexpr int J = zern_terms_of(ORDER);
+    const SplitWork W = work[blockIdx.x];
+    const OpdMid O = omid[W.cfg];
+    if (O.status == 1) return;  // the whole workgroup
+    const ZernMid M = mid[W.cfg];
+    const int32_t n_bins = n * n;
+    unsigned long long *lq = opd_lds, *lp = opd_lds + n_bins;
+    uint32_t* lc = (uint32_t*)(opd_lds + 2 * (size_t)n_bins);
+    gq += (int64_t)W.cfg * n_bins, gp += (int64_t)W.cfg * n_bins, gc += (int64_t)W.cfg * n_bins;
+    if (LDS) {
+        for (int32_t b = threadIdx.x; b < n_bins; b += 256) lq[b] = 0, lp[b] = 0, lc[b] = 0;
+        __syncthreads();
+    }
+    double cf[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) cf[j] = coef[(int64_t)W.cfg * J + j];
+    const double sx = (double)n / 2.0;
+    const SpotWindow B{-1.0, 1.0, -1.0, 1.0, sx, sx};
+    for (int64_t base = W.h0; base < W.h1; base += 256) {  // workgroup-uniform trips: opd_add needs whole waves
+        const int64_t h = base + threadIdx.x;
+        int32_t key = -1;
+        long long q = 0, p = 0;
+        if (h < W.h1) {
+            const double4 r = col[h];
+            double x, y;
+            const double e = zern_residual<ORDER>(r, M, cf, x, y);
+            key = spot_bin(x, y, B, n, n);
+            if (key >= 0 && O.status == 0) {
+                q = (long long)rint((r.x * e) * O.scale_q);
+                p = (long long)rint(r.x * O.scale_p);
+            }
+        }
+        if (LDS) opd_add(lq, lp, lc, key, q, p, key >= 0);
+        else opd_add(gq, gp, gc, key, q, p, key >= 0);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int32_t b = threadIdx.x; b < n_bins; b += 256) {
+            const uint32_t v = lc[b];
+            if (v) {
+                atomicAdd(&gc[b], (unsigned long long)v);
+                if (lq[b]) atomicAdd(&gq[b], lq[b]);
+                if (lp[b]) atomicAdd(&gp[b], lp[b]);
+            }
+        }
+    }
+}
+
+// what a block of the finish knows of its 256 bins
+struct OpdBlockSum {
+    unsigned long long filled, rows;
+    double lo, hi;  // extrema of the opd that are not NaN (inf, -inf: none)
+};
+
+// Bin blockIdx.x * 256 + threadIdx.x of configuration blockIdx.y: opd, weight and raw from the integer sums; the block's sums go to
+// part[blockIdx.y][blockIdx.x].
+__global__ __launch_bounds__(256) void psf_opd_finish_kernel(const OpdMid* __restrict__ omid, int32_t n_bins, const unsigned long long* __restrict__ gq,
+                                                             const unsigned long long* __restrict__ gp, const unsigned long long* __restrict__ gc,
+                                                             double* __restrict__ opd, double* __restrict__ weight, long long* __restrict__ raw,
+                                                             OpdBlockSum* __restrict__ part) {
+    __shared__ OpdBlockSum sh[4];
+    const int32_t c = (int32_t)blockIdx.y;
+    const OpdMid O = omid[c];
+    const int32_t b = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    OpdBlockSum s{0, 0, kinf(), -kinf()};
+    if (b < n_bins) {
+        const int64_t at = (int64_t)c * n_bins + b;
+        const long long Q = (long long)gq[at], P = (long long)gp[at];
+        const unsigned long long cnt = gc[at];
+        double w = knan(), v = knan();
+        if (O.status == 0) {
+            w = (double)P * O.inv_p;
+            if (cnt != 0 && P != 0) v = ((double)Q * O.inv_q) / w;
+        }
+        opd[at] = v;
+        weight[at] = w;
+        if (raw) raw[2 * at] = Q, raw[2 * at + 1] = P;
+        s.filled = cnt != 0;
+        s.rows = cnt;
+        if (v == v) s.lo = v, s.hi = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s.filled += __shfl_down(s.filled, off);
+        s.rows += __shfl_down(s.rows, off);
+        const double lo = __shfl_down(s.lo, off), hi = __shfl_down(s.hi, off);
+        s.lo = lo < s.lo ? lo : s.lo;
+        s.hi = hi > s.hi ? hi : s.hi;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            s.filled += sh[w].filled, s.rows += sh[w].rows;
+            s.lo = sh[w].lo < s.lo ? sh[w].lo : s.lo;
+            s.hi = sh[w].hi > s.hi ? sh[w].hi : s.hi;
+        }
+        part[(int64_t)c * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+// configuration blockIdx.x: the n_blocks block sums folded into N_OUTSIDE, N_FILLED, MAP_LO and MAP_HI (integers, min and max: any order)
+__global__ __launch_bounds__(256) void psf_opd_info_kernel(const int64_t* __restrict__ count, const OpdMid* __restrict__ omid, const OpdBlockSum* __restrict__ part,
+                                                           int32_t n_blocks, double* __restrict__ info) {
+    __shared__ OpdBlockSum sh[4];
+    const int32_t c = (int32_t)blockIdx.x;
+    OpdBlockSum s{0, 0, kinf(), -kinf()};
+    for (int32_t i = threadIdx.x; i < n_blocks; i += 256) {
+        const OpdBlockSum v = part[(int64_t)c * n_blocks + i];
+        s.filled += v.filled, s.rows += v.rows;
+        s.lo = v.lo < s.lo ? v.lo : s.lo;
+        s.hi = v.hi > s.hi ? v.hi : s.hi;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        s.filled += __shfl_down(s.filled, off);
+        s.rows += __shfl_down(s.rows, off);
+        const double lo = __shfl_down(s.lo, off), hi = __shfl_down(s.hi, off);
+        s.lo = lo < s.lo ? lo : s.lo;
+        s.hi = hi > s.hi ? hi : s.hi;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x != 0 || count[c] == 0) return;  // no rows: answered already
+    for (int w = 1; w < 4; ++w) {
+        s.filled += sh[w].filled, s.rows += sh[w].rows;
+        s.lo = sh[w].lo < s.lo ? sh[w].lo : s.lo;
+        s.hi = sh[w].hi > s.hi ? sh[w].hi : s.hi;
+    }
+    double* out = info + (int64_t)c * BMO_OPD_INFO_N;
+    const bool any = omid[c].status == 0 && s.lo <= s.hi;
+    out[BMO_OPD_N_OUTSIDE] = (double)(count[c] - (int64_t)s.rows);
+    out[BMO_OPD_N_FILLED] = (double)s.filled;
+    out[BMO_OPD_MAP_LO] = any ? s.lo + 0.0 : knan();
+    out[BMO_OPD_MAP_HI] = any ? s.hi + 0.0 : knan();
+}
+
+}  // namespace
+
+// what a slot without rows reads: every configuration like a call with n_hits = 0
+static void psf_opd_empty(int32_t n_configs, int64_t n_bins, double* opd, double* weight, int64_t* count, int64_t* raw, double* info) {
+    const size_t cells = (size_t)n_configs * (size_t)n_bins;
+    std::fill(opd, opd + cells, std::nan(""));
+    std::fill(weight, weight + cells, std::nan(""));
+    std::fill(count, count + cells, (int64_t)0);
+    if (raw) std::fill(raw, raw + 2 * cells, (int64_t)0);
+    fill_empty_stats(info, (size_t)n_configs, BMO_OPD_INFO_N);
+    for (int32_t c = 0; c < n_configs; ++c) info[(size_t)c * BMO_OPD_INFO_N + BMO_OPD_STATUS] = 1.0;
+}
+
+// the arguments both entries check before a device is looked for
+static int psf_opd_args(const double* pupil, int32_t n_configs, int32_t order, const double* coef, int32_t n, const char* who) {
+    if (n < 1 || n > BMO_OPD_MAX_N) return fail(BMO_ERR_INVALID, std::string(who) + ": n must be 1 .. 4096 bins per axis");
+    if (!psf_zernike_args_ok(pupil, n_configs, order))
+        return fail(BMO_ERR_INVALID, std::string(who) + ": order must be 0 .. 6, every given pupil (U0, V0, RHO) finite with RHO > 0");
+    if (!coef && order != 0) return fail(BMO_ERR_INVALID, std::string(who) + ": coef may be NULL only with order = 0");
+    for (int64_t q = 0; coef && q < (int64_t)n_configs * zern_terms_of(order); ++q)
+        if (!std::isfinite(coef[q])) return fail(BMO_ERR_INVALID, std::string(who) + ": a given coefficient is not finite");
+    if ((double)n_configs * (double)n * (double)n * 24.0 > 4294967296.0)
+        return fail(BMO_ERR_LIMIT, std::string(who) + ": the bin arrays of the call would pass 4 GiB");
+    return BMO_OK;
+}
+
+// The maps of the K configurations from the n_rows device rows `hits` [..][9]: the arguments of psf_zernike_read, coef nullptr (order 0:
+// nothing removed) or [K][J]; opd, weight, count [K][n * n], raw nullptr or [K][n * n][2], info [K][BMO_OPD_INFO_N].
+static int psf_opd_read(const double* hits, int64_t n_rows, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* ref_xz,
+                        const double* pupil, int32_t order, const double* coef, int32_t n, double* opd, double* weight, int64_t* count, int64_t* raw, double* info,
+                        double* kernel_ms, const char* who) {
+    const size_t K = R.count.size();
+    const int32_t J = zern_terms_of(order);
+    const int32_t n_bins = n * n;
+    const size_t cells = K * (size_t)n_bins;
+    const unsigned n_blocks = (unsigned)((n_bins + 255) / 256);
+    if (K > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more configurations than the finish launch holds");
+    RowPasses P(R);
+    if (int rc = P.items(who)) return rc;
+    const std::vector<double> none(K * (size_t)J, 0.0);
+    const size_t o_count = P.up.add(R.count), o_pose = P.up.add(psf_poses(K, origins, e1s, e2s)), o_coef = P.up.add(coef ? coef : none.data(), K * (size_t)J);
+    const size_t o_ref = ref_xz ? P.up.add(ref_xz, 2 * K) : 0, o_pupil = pupil ? P.up.add(pupil, 3 * K) : 0;
+    DevBuf d_zinfo, d_info, d_mid, d_omid, d_col, d_sums, d_maps, d_raw, d_part;
+    int rc;
+    if ((rc = d_zinfo.alloc(K * BMO_ZERNIKE_INFO_N * 8)) || (rc = d_info.alloc(K * BMO_OPD_INFO_N * 8)) || (rc = d_mid.alloc(K * sizeof(ZernMid))) ||
+        (rc = d_omid.alloc(K * sizeof(OpdMid))) || (rc = d_col.alloc((size_t)n_rows * sizeof(double4))) || (rc = d_sums.alloc(3 * cells * 8)) ||
+        (rc = d_maps.alloc(2 * cells * 8)) || (raw && (rc = d_raw.alloc(2 * cells * 8))) || (rc = d_part.alloc(K * (size_t)n_blocks * sizeof(OpdBlockSum))) ||
+        (rc = P.begin<ZernSumA, ZernSumB, OpdSumE>()))
+        return rc;
+    const int64_t* d_count = P.up.at<int64_t>(o_count);
+    const PsfPose* d_pose = P.up.at<PsfPose>(o_pose);
+    const double* d_coef = P.up.at<double>(o_coef);
+    const double* d_pupil = pupil ? P.up.at<double>(o_pupil) : (const double*)nullptr;
+    double *const g_zinfo = (double*)d_zinfo.p, *const g_info = (double*)d_info.p;
+    ZernMid* const g_mid = (ZernMid*)d_mid.p;
+    OpdMid* const g_omid = (OpdMid*)d_omid.p;
+    double4* const g_col = (double4*)d_col.p;
+    unsigned long long *const g_q = (unsigned long long*)d_sums.p, *const g_p = g_q + cells, *const g_c = g_p + cells;
+    double *const g_opd = (double*)d_maps.p, *const g_weight = g_opd + cells;
+    HIP_TRY(hipMemsetAsync(d_sums.p, 0, 3 * cells * 8, P.st));
+    P.pass<ZernSumA>(psf_zernike_sums_kernel, ZernSumsFinish{d_count, d_pose, ref_xz ? P.up.at<double>(o_ref) : (const double*)nullptr, d_pupil, g_zinfo, g_mid}, hits,
+                     P.work(), d_pose);
+    P.pass<ZernSumB>(psf_zernike_wave_kernel, ZernWaveFinish{d_pupil, g_zinfo, g_mid}, hits, P.work(), d_pose, g_mid, g_col);
+    void (*const residual[])(const double4*, const SplitWork*, const ZernMid*, const double*, OpdSumE*) = {
+        psf_opd_residual_kernel<0>, psf_opd_residual_kernel<1>, psf_opd_residual_kernel<2>, psf_opd_residual_kernel<3>,
+        psf_opd_residual_kernel<4>, psf_opd_residual_kernel<5>, psf_opd_residual_kernel<6>};
+    P.pass<OpdSumE>(residual[order], OpdResidualFinish{d_count, g_zinfo, g_info, g_omid}, g_col, P.work(), g_mid, d_coef);
+    using BinKernel = void (*)(const double4*, const SplitWork*, const ZernMid*, const double*, const OpdMid*, int32_t, unsigned long long*, unsigned long long*,
+                               unsigned long long*);
+    static const BinKernel bin_lds[] = {psf_opd_bin_kernel<0, true>, psf_opd_bin_kernel<1, true>, psf_opd_bin_kernel<2, true>, psf_opd_bin_kernel<3, true>,
+                                        psf_opd_bin_kernel<4, true>, psf_opd_bin_kernel<5, true>, psf_opd_bin_kernel<6, true>};
+    static const BinKernel bin_global[] = {psf_opd_bin_kernel<0, false>, psf_opd_bin_kernel<1, false>, psf_opd_bin_kernel<2, false>, psf_opd_bin_kernel<3, false>,
+                                           psf_opd_bin_kernel<4, false>, psf_opd_bin_kernel<5, false>, psf_opd_bin_kernel<6, false>};
+    if (P.n_items > 0) {
+        const bool lds = n_bins <= OPD_LDS_BINS;
+        // more dynamic LDS than a launch gets by default (64 KiB) has to be asked for, once per kernel
+        if (lds) HIP_TRY(hipFuncSetAttribute((const void*)bin_lds[order], hipFuncAttributeMaxDynamicSharedMemorySize, OPD_LDS_BINS * 20));
+        hipLaunchKernelGGL(lds ? bin_lds[order] : bin_global[order], P.grid, dim3(256), lds ? (size_t)n_bins * 20 : 0, P.st, g_col, P.work(), g_mid, d_coef, g_omid, n, g_q,
+                           g_p, g_c);
+    }
+    hipLaunchKernelGGL(psf_opd_finish_kernel, dim3(n_blocks, (unsigned)K), dim3(256), 0, P.st, g_omid, n_bins, g_q, g_p, g_c, g_opd, g_weight,
+                       raw ? (long long*)d_raw.p : (long long*)nullptr, (OpdBlockSum*)d_part.p);
+    hipLaunchKernelGGL(psf_opd_info_kernel, dim3((unsigned)K), dim3(256), 0, P.st, d_count, g_omid, (const OpdBlockSum*)d_part.p, (int32_t)n_blocks, g_info);
+    if ((rc = P.end(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(info, d_info.p, K * BMO_OPD_INFO_N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(opd, g_opd, cells * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(weight, g_weight, cells * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(count, g_c, cells * 8, hipMemcpyDeviceToHost));
+    if (raw) HIP_TRY(hipMemcpy(raw, d_raw.p, 2 * cells * 8, hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_opd_map(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3], const double e2[3],
+                               const double* ref_xz, const double* pupil, int32_t order, const double* coef, int32_t n, int32_t device, double* opd, double* weight,
+                               int64_t* count, int64_t* raw, double* info, double* kernel_ms) {
+    if (!origin || !e1 || !e2 || !opd || !weight || !count || !info || n_hits < 0 || (n_hits > 0 && !hits))
+        return fail(BMO_ERR_INVALID, "bmo_psf_opd_map: bad argument (null pointer, n_hits < 0)");
+    if (int rc = psf_opd_args(pupil, 1, order, coef, n, "bmo_psf_opd_map")) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_opd_map", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    return psf_opd_read(hits, n_hits, Ranges{{0}, {n_hits}}, origin, e1, e2, ref_xz, pupil, order, coef, n, opd, weight, count, raw, info, kernel_ms, "bmo_psf_opd_map");
+}
+
+extern "C" int bmo_psf_opd_map_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                     const double* ref_xz, const double* pupil, int32_t order, const double* coef, int32_t n, double* opd, double* weight,
+                                     int64_t* count, int64_t* raw, double* info, double* kernel_ms) {
+    if (!res || !origins || !e1s || !e2s || !opd || !weight || !count || !info) return fail(BMO_ERR_INVALID, "bmo_psf_opd_map_sweep: bad argument");
+    if (int rc = slot_check("bmo_psf_opd_map_sweep", res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
+    if (int rc = psf_opd_args(pupil, n_configs, order, coef, n, "bmo_psf_opd_map_sweep")) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    const int64_t H = res->det_count[detector];
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        psf_opd_empty(n_configs, (int64_t)n * n, opd, weight, count, raw, info);
+        return BMO_OK;
+    }
+    Ranges R;
+    const double* hits;
+    if (int rc = resident_rows("bmo_psf_opd_map_sweep", res, detector, H, n_configs, R, hits)) return rc;
+    return psf_opd_read(hits, H, R, origins, e1s, e2s, ref_xz, pupil, order, coef, n, opd, weight, count, raw, info, kernel_ms, "bmo_psf_opd_map_sweep");
 }
 
 // ====================================================================================================================

@@ -487,6 +487,27 @@ class EngineSolution:
         coef, info, _, self.readout_ms = abi.psf_zernike_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], order=order, ref=ref, pupil=pupil)
         return coef[0], info[0]
 
+    def psf_opd_map(self, slot, position, orientation, n=64, order=4, remove="tilt", ref=None, pupil=None):
+        """The binned wavefront (OPD) map of the resident rows of PSFDetector slot `slot` at the pose (position, orientation)
+        (bmo_psf_zernike_sweep, then bmo_psf_opd_map_sweep: no row leaves the device): (opd [n, n], weight, count, info [20], coef_removed)
+        as PSFDetector.opd_map gives them from host rows."""
+        o = np.asarray(orientation, dtype=np.float64)
+        ms = []
+
+        def zernike_fn(od, r, q):
+            coef, info, _, t = abi.psf_zernike_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], order=od, ref=r, pupil=q)
+            ms.append(t)
+            return coef[0], info[0]
+
+        def map_fn(od, cf, r, q):
+            opd, weight, count, info, _, t = abi.psf_opd_map_sweep(self.handle, slot, 1, position, o[:, 0], o[:, 2], n=n, order=od, coef=cf, ref=r, pupil=q)
+            ms.append(t)
+            return opd[0], weight[0], count[0], info[0]
+
+        out = cp.psf_opd_map(zernike_fn, map_fn, n=n, order=order, remove=remove, ref=ref, pupil=pupil)
+        self.readout_ms = float(sum(ms))
+        return out
+
     def _psf_resident_rows(self, slot):
         """(device pointer, count, device) of the resident rows of PSFDetector slot `slot` (bmo_result_psf_rows: the library refuses a slot that
         is not a PSFDetector's and a GaussianBeamlet solution), for the single-call read-outs."""
@@ -1007,6 +1028,34 @@ class SweepSolution:
         coef, info, gram, self.readout_ms = abi.psf_zernike_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], order=order, ref=ref, pupil=pupil,
                                                                   want_gram=want_gram)
         return (coef, info, gram) if want_gram else (coef, info)
+
+    def psf_opd_map(self, det, n=64, order=4, remove="tilt", ref=None, pupil=None, coef=None):
+        """The binned wavefront (OPD) map of PSFDetector `det` in every configuration, in one batched read-out (bmo_psf_opd_map_sweep, after
+        one bmo_psf_zernike_sweep where `remove` asks for a fit) at each configuration's detector pose: (opd [n_cfg, n, n] indexed
+        [c, i, j], weight, count, info [n_cfg, 20] at the abi.OPD_* columns, coef_removed [n_cfg, J]) as components.psf_opd_map describes
+        them.  ref, pupil and coef (a surface to remove as it stands, instead of `remove`): None, one value or one per configuration.
+        Configuration c equals abi.psf_opd_map on detector_hits(det, c) bit for bit."""
+        slot = self._slot(det)
+        K = self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
+        ms = []
+
+        def zernike_fn(od, r, q):
+            cf, info, _, t = abi.psf_zernike_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], order=od, ref=r, pupil=q)
+            ms.append(t)
+            return cf, info
+
+        def map_fn(od, cf, r, q):
+            out = abi.psf_opd_map_sweep(self._handle, slot, K, pos, ori[:, :, 0], ori[:, :, 2], n=n, order=od, coef=cf, ref=r, pupil=q)
+            ms.append(out[5])
+            return out[:4]
+
+        if coef is not None:
+            coef = abi._per_config(coef, K, abi.zernike_sizes(order)[0])
+        out = cp.psf_opd_map(zernike_fn, map_fn, n=n, order=order, remove=remove, ref=ref, pupil=pupil, coef=coef)
+        self.readout_ms = float(sum(ms))
+        return out
 
     def spot_stats(self, det):
         """The spot statistics [n_cfg, 12] (abi.SPOT_* columns) of Spotdetector `det` in every configuration, in one batched read-out

@@ -671,6 +671,78 @@ int bmo_psf_zernike_sweep(bmo_trace_result* res, int32_t detector, int32_t n_con
                           double* gram, double* kernel_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * OPD map read-out: the wavefront of a PSFDetector's rows as a picture over the pupil, binned on the device from the rows where they lie:
+ * the proj-weighted mean, per bin of an n x n grid over the pupil square, of the wavefront less a Zernike surface the caller chooses.
+ *
+ * hits, origin, e1, e2, ref_xz, pupil, the _sweep form and its conventions: exactly those of bmo_psf_zernike.
+ * order : 0 .. BMO_ZERNIKE_MAX_ORDER, the order of the surface to remove; J = (order + 1)(order + 2) / 2.
+ * coef  : [n_configs][J], metres: the Zernike surface that is REMOVED before binning (zero the terms to keep).  NULL only with order = 0,
+ *         and then c_0 = 0: nothing is removed.
+ * n     : bins per axis, 1 .. BMO_OPD_MAX_N.
+ * opd, weight : [n_configs][n * n] doubles;  count : [n_configs][n * n] int64.  Bin (i, j) lies at i + n * j, i along u (x_h), j along v.
+ * raw   : NULL or [n_configs][n * n][2] int64, the integer sums (Q_b, P_b) below.   info : [n_configs][BMO_OPD_INFO_N] at BMO_OPD_*.
+ * Everything is FP64, each expression evaluated left to right as written, without contraction, h running over the N rows:
+ *   X_REF, Z_REF, p, W_h, S, W_MEAN, u_h, v_h, (U0, V0, RHO), x_h, y_h, t_h, Z_j, F_h (with c = coef): as "Zernike read-out" defines them,
+ *   the same expressions in the same blocked order of the sums: equal bit for bit.
+ *   E_h = (W_h - W_MEAN) - F_h.   E_RMS, E_LO, E_HI, N_OUT: FIT_RMS, E_LO, E_HI and N_OUT of the Zernike read-out, the same expressions,
+ *   record and fold: with coef, ref_xz = (X_REF, Z_REF) and pupil = (U0, V0, RHO) of a bmo_psf_zernike call on the same rows these four
+ *   columns equal that call's bit for bit.
+ *   Bins: the rule of bmo_spot_image on the window (-1, 1, -1, 1) of (x_h, y_h) with sx = n / 2.0: a row is inside iff
+ *     x >= -1 && x <= 1 && y >= -1 && y <= 1 (plain compares: a NaN is outside, the upper edge is closed);
+ *     i = min((int64)floor((x + 1.0) * sx), n - 1), j likewise with y.  N_OUTSIDE = the rows not inside; sum(count) + N_OUTSIDE = N.
+ *     A row with t_h > 1 inside the square is binned, and counted in N_OUT.
+ *   Fixed-point sums.  MQ = max_h |proj_h * E_h|, MP = max_h |proj_h| (each starts at 0; a row that compares false leaves it), N_BAD = the
+ *     rows whose proj_h or proj_h * E_h is not finite.  b = the smallest integer with N <= 2^b.  For M in {MQ, MP}:
+ *     sh(M) = 0 if M = 0, otherwise clamp(60 - b - ilogb(M), -1000, 1000);  SH_Q = sh(MQ), SH_P = sh(MP);  scale = ldexp(1.0, sh).
+ *     q_h = (int64)rint((proj_h * E_h) * scale_q),  p_h = (int64)rint(proj_h * scale_p)  (ties to even);  |q_h| <= 2^(61 - b): the sum
+ *     of a bin cannot leave int64.  Per bin b: count_b, Q_b = sum q_h, P_b = sum p_h over its rows, integer adds.
+ *     weight_b = (double)P_b * ldexp(1.0, -SH_P);   opd_b = ((double)Q_b * ldexp(1.0, -SH_Q)) / weight_b, NaN where count_b = 0 or P_b = 0.
+ *   The sums are integers: the maps do not depend on the order of the adds.  Configuration c of the _sweep form equals the single call on
+ *   its rows and resident rows equal host rows, bit for bit, in every output.
+ *   N_FILLED = the bins with count > 0;  MAP_LO, MAP_HI = the extrema of the opd_b that are not NaN, + 0.0 (a zero reads +0), NaN if none.
+ * STATUS 0: read.
+ * STATUS 1: no rows (N_ROWS = 0, NaN elsewhere in info), or RHO zero or not finite: no row is binned (count 0, opd and weight NaN, raw 0,
+ *   N_OUTSIDE = N, N_FILLED = 0), E_RMS, E_LO, E_HI, SH_Q, SH_P, MAP_LO and MAP_HI are NaN, the rest of info is filled.
+ * STATUS 2: N_BAD > 0: opd and weight are NaN, raw is 0, SH_Q, SH_P, MAP_LO and MAP_HI are NaN; count, N_OUTSIDE and N_FILLED are still
+ *   exact, and E_RMS, E_LO, E_HI are what the Zernike read-out's expressions give on such rows.  Never a wrong answer.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than ref_xz, pupil, raw, kernel_ms and coef with order = 0;
+ * n_hits < 0; n outside 1 .. BMO_OPD_MAX_N; order outside 0 .. BMO_ZERNIKE_MAX_ORDER; a NULL coef with order != 0; a given coef that is not
+ * finite; the pupil, slot and n_configs refusals of bmo_psf_zernike.  BMO_ERR_LIMIT: the call's bin arrays ([n_configs][n * n] of Q, P and
+ * count, 24 bytes a bin) would pass 4 GiB.  BMO_ERR_UNSUPPORTED: a GaussianBeamlet result.  A refused call writes nothing to the caller's
+ * buffers.  kernel_ms: optional, HIP-event time of the launches.                                                                     */
+enum bmo_opd_info {
+    BMO_OPD_N_ROWS = 0,
+    BMO_OPD_STATUS = 1, /* 0: read, 1: no rows or no usable RHO, 2: a row that is not finite */
+    BMO_OPD_S = 2,
+    BMO_OPD_X_REF = 3,
+    BMO_OPD_Z_REF = 4,
+    BMO_OPD_U0 = 5,
+    BMO_OPD_V0 = 6,
+    BMO_OPD_RHO = 7,
+    BMO_OPD_W_MEAN = 8,
+    BMO_OPD_E_RMS = 9,
+    BMO_OPD_E_LO = 10,
+    BMO_OPD_E_HI = 11,
+    BMO_OPD_N_OUT = 12,
+    BMO_OPD_N_OUTSIDE = 13,
+    BMO_OPD_N_BAD = 14,
+    BMO_OPD_N_FILLED = 15,
+    BMO_OPD_SH_Q = 16,
+    BMO_OPD_SH_P = 17,
+    BMO_OPD_MAP_LO = 18,
+    BMO_OPD_MAP_HI = 19
+};
+#define BMO_OPD_INFO_N 20
+#define BMO_OPD_MAX_N 4096
+int bmo_psf_opd_map(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
+                    const double e2[3], const double* ref_xz, const double* pupil, int32_t order, const double* coef, int32_t n,
+                    int32_t device, double* opd, double* weight, int64_t* count, int64_t* raw, double* info, double* kernel_ms);
+int bmo_psf_opd_map_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s,
+                          const double* e2s, const double* ref_xz, const double* pupil, int32_t order, const double* coef, int32_t n,
+                          double* opd, double* weight, int64_t* count, int64_t* raw, double* info, double* kernel_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Through-focus read-out: the PSF of the same rows on a stack of displaced sample grids, and the spot statistics of the rows propagated to
  * a stack of planes, in one pass each over the rows where they lie.
  *
