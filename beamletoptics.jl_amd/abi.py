@@ -41,6 +41,8 @@ OPD_MAX_N = 4096
 FOCUS_STAT_N = 12
 (FOCUS_N, FOCUS_S, FOCUS_CX, FOCUS_CZ, FOCUS_X_MIN, FOCUS_X_MAX, FOCUS_Z_MIN, FOCUS_Z_MAX, FOCUS_HWX, FOCUS_HWZ, FOCUS_RMS_R, FOCUS_MAX_R) = range(FOCUS_STAT_N)
 
+PSF_MAX_BANDS = 64  # BMO_PSF_MAX_BANDS: the wavelength bands of one bmo_psf_bands handle
+
 NODE_MISS, NODE_STOPPED, NODE_RMAX, NODE_SPLIT, NODE_DETECTED, NODE_ERR_UNIT, NODE_GAUSS_DIVERGED, NODE_BLOCKED, NODE_ERR_ORTHO = (
     1, 2, 4, 8, 16, 32, 64, 128, 256)
 
@@ -277,6 +279,12 @@ def load_engine():
     lib.bmo_spot_ee_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, dp]
     lib.bmo_psf_geo_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, ip, dp, dp]
     lib.bmo_psf_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp]
+    lib.bmo_psf_bands_create.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, C.c_int32, C.POINTER(vp), dp]
+    lib.bmo_psf_bands_info.argtypes = [vp, C.POINTER(C.c_int32), ip, ip, C.POINTER(C.c_int32)]
+    lib.bmo_psf_bands_get.argtypes = [vp, C.c_int32, dp, C.POINTER(C.POINTER(C.c_double)), ip]
+    lib.bmo_psf_bands_free.argtypes = [vp]
+    lib.bmo_psf_poly_through_focus.argtypes = [vp, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_poly_otf.argtypes = [vp, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, dp, dp, dp, dp]
     _engine = lib
     return lib
 
@@ -526,6 +534,117 @@ def psf_otf(hits, origin, e1, e2, displacements, xs, zs, freqs, device=0, hits_d
     check(lib, lib.bmo_psf_otf(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
                                z.ctypes.data_as(dp), n, fq.ctypes.data_as(dp), nf, int(device), otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp),
                                sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_otf")
+    I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
+    return mtf, otf[..., 0] + 1j * otf[..., 1], sums, I, ms.value
+
+
+class PsfBands:
+    """A bmo_psf_bands handle: the PSF rows of one buffer split by wave number into band-contiguous ranges on the device.  `ks` [B] the
+    bands' wave numbers, `counts` int64 [B] their rows, `unmatched` the rows of no band, `device` the ordinal the rows lie on;
+    rows(b) -> (device pointer, count) to hand to any read-out as hits_device_ptr / n_hits with device=self.device.  A context manager;
+    close() frees the device rows."""
+
+    def __init__(self, lib, handle):
+        self.lib, self.handle = lib, handle
+        nb, n_rows, unmatched, device = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
+        check(lib, lib.bmo_psf_bands_info(handle, C.byref(nb), C.byref(n_rows), C.byref(unmatched), C.byref(device)), "bmo_psf_bands_info")
+        self.n_rows, self.unmatched, self.device = n_rows.value, unmatched.value, device.value
+        self.ks, self.counts, self._ptrs = np.zeros(nb.value), np.zeros(nb.value, dtype=np.int64), []
+        for b in range(nb.value):
+            k, p, cnt = C.c_double(), C.POINTER(C.c_double)(), C.c_int64()
+            check(lib, lib.bmo_psf_bands_get(handle, b, C.byref(k), C.byref(p), C.byref(cnt)), "bmo_psf_bands_get")
+            self.ks[b], self.counts[b] = k.value, cnt.value
+            self._ptrs.append(C.cast(p, C.c_void_p).value or 0)
+
+    def __len__(self):
+        return len(self.ks)
+
+    def rows(self, b):
+        if self.handle is None:
+            raise ValueError("PsfBands: the handle is closed")
+        if not 0 <= int(b) < len(self.ks):
+            raise IndexError("PsfBands.rows: band index out of range")
+        return self._ptrs[int(b)], int(self.counts[int(b)])
+
+    def close(self):
+        if self.handle is not None:
+            self.lib.bmo_psf_bands_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def psf_bands(hits, ks=None, device=0, hits_device_ptr=None, n_hits=None, want_ms=False):
+    """bmo_psf_bands_create: the rows split by wave number (column 8, a plain == compare), stably, on the device.  ks None: the bands are the
+    distinct wave numbers of the rows, ascending; otherwise exactly the bands `ks`, in that order.  `hits` is a host [H, 9] array, or pass
+    `hits_device_ptr` + `n_hits` for rows resident on `device`.  Returns a PsfBands (with want_ms: (PsfBands, kernel_ms))."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
+    kk = None if ks is None else np.ascontiguousarray(np.asarray(ks, dtype=np.float64).reshape(-1))
+    h = C.c_void_p()
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_bands_create(hp, nh, on_dev, int(device), None if kk is None else kk.ctypes.data_as(dp), 0 if kk is None else len(kk), C.byref(h),
+                                        C.byref(ms)), "bmo_psf_bands_create")
+    bands = PsfBands(lib, h)
+    return (bands, ms.value) if want_ms else bands
+
+
+def _poly_args(bands, origin, e1, e2, displacements, xs, zs, coeffs):
+    if not isinstance(bands, PsfBands) or bands.handle is None:
+        raise ValueError("bands must be an open PsfBands")
+    o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
+    d = np.ascontiguousarray(np.asarray(displacements, dtype=np.float64).reshape(-1, 3))
+    x, z = np.ascontiguousarray(xs, dtype=np.float64), np.ascontiguousarray(zs, dtype=np.float64)
+    if len(z) != len(x):
+        raise ValueError("xs and zs must have the same length")
+    c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float64).reshape(-1))
+    if len(c) != len(bands):
+        raise ValueError("coeffs must hold one coefficient per band (%d), got %d" % (len(bands), len(c)))
+    return o, a1, a2, d, x, z, c
+
+
+def psf_poly_through_focus(bands, origin, e1, e2, displacements, xs, zs, coeffs, want_bands=False):
+    """bmo_psf_poly_through_focus: the incoherent sum ((c_0 I_0 + c_1 I_1) + ...) of the bands' through-focus stacks, I_b what
+    psf_through_focus returns for band b's rows.  Returns (I[M, n, n] indexed [m, i, j], I_b [B, M, n, n] or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2, d, x, z, c = _poly_args(bands, origin, e1, e2, displacements, xs, zs, coeffs)
+    n, M, B = len(x), len(d), len(bands)
+    out = np.zeros(M * n * n)
+    per = np.zeros(B * M * n * n) if want_bands else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_poly_through_focus(bands.handle, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M,
+                                              x.ctypes.data_as(dp), z.ctypes.data_as(dp), n, c.ctypes.data_as(dp), out.ctypes.data_as(dp),
+                                              per.ctypes.data_as(dp) if want_bands else None, C.byref(ms)), "bmo_psf_poly_through_focus")
+    I_b = np.ascontiguousarray(per.reshape(B, M, n, n).transpose(0, 1, 3, 2)) if want_bands else None
+    return np.ascontiguousarray(out.reshape(M, n, n).transpose(0, 2, 1)), I_b, ms.value
+
+
+def psf_poly_otf(bands, origin, e1, e2, displacements, xs, zs, coeffs, freqs, want_intensity=False):
+    """bmo_psf_poly_otf: the transform of the combined stack of psf_poly_through_focus (kept on the device) at the frequencies `freqs`
+    [nf, 2] (cycles per metre).  Returns (mtf [M, nf], otf [M, nf] complex, sums [M], I[M, n, n] indexed [m, i, j] or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    o, a1, a2, d, x, z, c = _poly_args(bands, origin, e1, e2, displacements, xs, zs, coeffs)
+    fq = _freqs(freqs)
+    n, M, nf = len(x), len(d), len(fq)
+    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
+    img = np.zeros(M * n * n) if want_intensity else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_poly_otf(bands.handle, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
+                                    z.ctypes.data_as(dp), n, c.ctypes.data_as(dp), fq.ctypes.data_as(dp), nf, otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp),
+                                    sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_poly_otf")
     I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
     return mtf, otf[..., 0] + 1j * otf[..., 1], sums, I, ms.value
 

@@ -644,6 +644,162 @@ def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.
     return out["r"] + (st,)
 
 
+# The polychromatic read-out (include/bmo.h "Polychromatic read-out"): a slot's rows split by wave number (abi.PsfBands), every band read by
+# the single-call read-outs through its device pointer, and the incoherent sum of the bands' images.
+def poly_coefficients(weights, S, normalize="energy"):
+    """The coefficients c_b of the incoherent sum of the bands' PSFs from the spectral weights w_b (None: all 1) and the bands' sums of proj
+    S_b (abi.FOCUS_S of each band's focus statistics).  normalize "energy": c_b = w_b / (S_b * S_b), which scales every band's PSF to the peak
+    of its own in-phase sum before the weights apply (a band without rows, S_b zero or NaN, gets 0); None: c_b = w_b."""
+    S = np.asarray(S, dtype=np.float64).reshape(-1)
+    w = np.ones(len(S)) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != len(S):
+        raise ValueError("poly_coefficients: %d weights for %d bands" % (len(w), len(S)))
+    if not np.isfinite(w).all():
+        raise ValueError("poly_coefficients: every weight must be finite")
+    if normalize is None:
+        return w.copy()
+    if normalize != "energy":
+        raise ValueError('poly_coefficients: normalize must be "energy" or None')
+    c = np.zeros(len(S))
+    ok = np.isfinite(S) & (S != 0)
+    c[ok] = w[ok] / (S[ok] * S[ok])
+    return c
+
+
+def poly_combine(coeffs, images):
+    """((c_0 I_0 + c_1 I_1) + c_2 I_2) + ...: the combination rule of bmo_psf_poly_through_focus, a multiply and an add per band in band
+    order, restated in numpy (equal to the device's bit for bit).  images: [B, ...]; no band: ValueError."""
+    c, I = np.asarray(coeffs, dtype=np.float64).reshape(-1), np.asarray(images, dtype=np.float64)
+    if len(c) != len(I) or len(c) == 0:
+        raise ValueError("poly_combine: needs one coefficient per image and at least one band")
+    acc = c[0] * I[0]
+    for b in range(1, len(c)):
+        acc = acc + c[b] * I[b]
+    return acc
+
+
+def psf_chromatic_focus(stats_fn_per_band, ks, offsets, axis, plane=None):
+    """Where each colour focuses and where it lands, from the focus statistics of every band: stats_fn_per_band(b, axis, offsets) -> [M, 12]
+    (abi.FOCUS_* columns) of band b's rows on the detector plane moved by each of `offsets` along `axis`.  Returns
+    (stats [B, M, 12], focus [B], rms [B], centroids [B, 2], plane):
+      focus, rms : best_focus of each band's RMS_R curve, the offset of its least spot and the radius there: the spread of `focus` over the
+                   bands is the longitudinal colour;
+      centroids  : (CX, CZ) of each band on one common plane, `plane` (an index into offsets; None: the sample nearest the mean of the bands'
+                   foci): their spread is the lateral colour.
+    A band without rows (or with a row parallel to the planes) has NaN in its entries."""
+    from . import abi
+
+    off = np.asarray(offsets, dtype=np.float64).reshape(-1)
+    B = len(np.asarray(ks).reshape(-1))
+    if len(off) == 0:
+        raise ValueError("chromatic_focus: no offsets")
+    st = np.full((B, len(off), abi.FOCUS_STAT_N), np.nan)
+    focus, rms = np.full(B, np.nan), np.full(B, np.nan)
+    for b in range(B):
+        st[b] = np.asarray(stats_fn_per_band(b, axis, off), dtype=np.float64).reshape(len(off), abi.FOCUS_STAT_N)
+        if not np.isnan(st[b, :, abi.FOCUS_RMS_R]).all():
+            focus[b], rms[b] = best_focus(off, st[b, :, abi.FOCUS_RMS_R])
+    if plane is None:
+        plane = 0 if np.isnan(focus).all() else int(np.argmin(np.abs(off - np.nanmean(focus))))
+    plane = int(plane)
+    if not 0 <= plane < len(off):
+        raise ValueError("chromatic_focus: plane must be an index into offsets")
+    return st, focus, rms, st[:, plane, [abi.FOCUS_CX, abi.FOCUS_CZ]].copy(), plane
+
+
+def _band_rows(bands, b):
+    """The keyword arguments that hand band b of an abi.PsfBands to a single-call read-out."""
+    ptr, cnt = bands.rows(b)
+    return dict(device=bands.device, hits_device_ptr=ptr, n_hits=cnt)
+
+
+def chromatic_focus_of(bands, position, orientation, offsets, axis=None, plane=None):
+    """psf_chromatic_focus of the bands of an abi.PsfBands at the pose (position, orientation), every band read by bmo_psf_focus_stats through
+    its device pointer.  Returns (psf_chromatic_focus's tuple, kernel ms)."""
+    from . import abi
+
+    o = np.asarray(orientation, dtype=np.float64)
+    ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
+    ms = []
+
+    def per_band(b, a, off):
+        st, t = abi.psf_focus_stats(None, position, o[:, 0], o[:, 2], a, off, **_band_rows(bands, b))
+        ms.append(t)
+        return st
+
+    return psf_chromatic_focus(per_band, bands.ks, offsets, ax, plane=plane), float(sum(ms))
+
+
+def _band_sums(bands, position, o):
+    """S_b, the sum of proj of every band (abi.FOCUS_S of its focus statistics at offset 0; it does not depend on the plane), and the ms."""
+    from . import abi
+
+    out = [abi.psf_focus_stats(None, position, o[:, 0], o[:, 2], o[:, 1], [0.0], **_band_rows(bands, b)) for b in range(len(bands))]
+    return np.array([st[0, abi.FOCUS_S] for st, _ in out]), float(sum(t for _, t in out))
+
+
+def poly_through_focus_of(all_rows, bands, position, orientation, offsets, weights=None, n=100, normalize="energy", axis=None, follow="centroid",
+                          window_plane=None, crop_factor=1.0, half_width=None, want_bands=False):
+    """The polychromatic through-focus stack of an abi.PsfBands.  The window and the centres are psf_through_focus's from the focus statistics of
+    ALL rows (`all_rows`: the keyword arguments that hand them to abi.psf_focus_stats): they are geometric and shared by the bands, because
+    intensities add only at the same physical point.  Returns ((xs, zs, displacements, I[M, n, n], stats, coeffs, I_b or None), kernel ms)."""
+    from . import abi
+
+    o = np.asarray(orientation, dtype=np.float64)
+    if len(bands) == 0:
+        raise ValueError("poly_through_focus: no wavelength band (the PSFDetector recorded no hit)")
+    S, ms = _band_sums(bands, position, o)
+    coeffs = poly_coefficients(weights, S, normalize)
+    hits, kw = all_rows.get("hits"), {k: v for k, v in all_rows.items() if k != "hits"}
+    t, keep = [ms], {}
+
+    def stats_fn(ax, off):
+        st, ms_ = abi.psf_focus_stats(hits, position, o[:, 0], o[:, 2], ax, off, **kw)
+        t.append(ms_)
+        return st
+
+    def stack_fn(d, xs, zs):
+        I, keep["bands"], ms_ = abi.psf_poly_through_focus(bands, position, o[:, 0], o[:, 2], d, xs, zs, coeffs, want_bands=want_bands)
+        t.append(ms_)
+        return I
+
+    xs, zs, d, I, st = psf_through_focus(stats_fn, stack_fn, o, offsets, n=n, axis=axis, follow=follow, window_plane=window_plane, crop_factor=crop_factor,
+                                         half_width=half_width)
+    return (xs, zs, d, I, st, coeffs, keep.get("bands")), float(sum(t))
+
+
+def poly_mtf_of(all_rows, bands, position, orientation, freqs, offsets=(0.0,), weights=None, normalize="energy", n=None, half_width=None, axis=None,
+                follow="centroid"):
+    """The white-light diffraction MTF of an abi.PsfBands: psf_mtf's grid with bmo_psf_poly_otf as the transform.  half_width None takes
+    mtf_window's at the SMALLEST wave number of the rows (the longest wavelength has the widest PSF and the nearest replicas); the cutoff of
+    the sum is that of the largest, mtf_cutoff(bands.ks.max(), rho), and the pitch follows the largest |f| asked for as in psf_mtf.
+    Returns ((mtf [M, nf], otf [M, nf] complex, sums [M], stats [M, 12], coeffs), kernel ms)."""
+    from . import abi
+
+    o = np.asarray(orientation, dtype=np.float64)
+    e1, e2 = o[:, 0], o[:, 2]
+    if len(bands) == 0:
+        raise ValueError("poly_mtf: no wavelength band (the PSFDetector recorded no hit)")
+    S, ms = _band_sums(bands, position, o)
+    coeffs = poly_coefficients(weights, S, normalize)
+    hits, kw = all_rows.get("hits"), {k: v for k, v in all_rows.items() if k != "hits"}
+    t = [ms]
+
+    def timed(out):
+        t.append(out[-1])
+        return out
+
+    def window_fn():
+        st = timed(abi.psf_stats(hits, position, e1, e2, **kw))[0]
+        info = timed(abi.psf_zernike(hits, position, e1, e2, order=0, **kw))[1]
+        return st[abi.PSF_K_MIN], info[abi.ZERN_RHO], int(st[abi.PSF_N])
+
+    out = psf_mtf(lambda ax, off: timed(abi.psf_focus_stats(hits, position, e1, e2, ax, off, **kw))[0], None,
+                  lambda d, xs, zs, fq: timed(abi.psf_poly_otf(bands, position, e1, e2, d, xs, zs, coeffs, fq))[:3],
+                  window_fn, o, freqs, offsets=offsets, kind="diffraction", n=n, half_width=half_width, axis=axis, follow=follow)
+    return out + (coeffs,), float(sum(t))
+
+
 # The encircled-energy read-out (include/bmo.h "Encircled-energy read-out").  Radii are half-sizes in metres in the detector's local frame.
 def ee_radii(r_max, n):
     """[n]: n radii from 0 to r_max in equal steps (the first is 0: only the points at the centre itself)."""
@@ -969,6 +1125,38 @@ class PSFDetector(AbstractObject):  # Detectors/PSFDetector.jl:44-68
         return psf_encircled_energy(lambda ax, off: abi.psf_focus_stats(self.data, pos, e1, e2, ax, off, device=device)[0], geo_fn,
                                     lambda d, xs, zs, r, sh_: abi.psf_ee(self.data, pos, e1, e2, d, xs, zs, r, shape=sh_, device=device)[:4],
                                     window_fn, o, radii, offsets=offsets, kind=kind, shape=shape, n=n, half_width=half_width, axis=axis, follow=follow)
+
+    def bands(self, ks=None, device=0):
+        """All rows accumulated so far split by wave number on the device (bmo_psf_bands_create): an abi.PsfBands, to be closed by the caller
+        (a context manager).  ks None: one band per distinct wave number, ascending; otherwise exactly the bands `ks`."""
+        from . import abi
+
+        return abi.psf_bands(self.data, ks=ks, device=device)
+
+    def chromatic_focus(self, offsets, axis=None, ks=None, plane=None, device=0):
+        """Where each colour of the rows accumulated so far focuses and lands: (ks [B], stats [B, M, 12], focus [B], rms [B], centroids [B, 2],
+        plane) as psf_chromatic_focus describes them (longitudinal colour: the spread of `focus`; lateral colour: that of `centroids`)."""
+        with self.bands(ks=ks, device=device) as b:
+            out, _ = chromatic_focus_of(b, self.position(), self.orientation(), offsets, axis=axis, plane=plane)
+            return (b.ks.copy(),) + out
+
+    def poly_through_focus(self, offsets, weights=None, n=100, normalize="energy", axis=None, follow="centroid", window_plane=None, crop_factor=1.0,
+                           half_width=None, ks=None, want_bands=False, device=0):
+        """The incoherent, spectrally weighted through-focus stack of the rows accumulated so far (bmo_psf_poly_through_focus): (xs, zs,
+        displacements, I[M, n, n], stats, ks, coeffs, I_b or None).  weights: one per band (None: 1); normalize: poly_coefficients's."""
+        with self.bands(ks=ks, device=device) as b:
+            out, _ = poly_through_focus_of(dict(hits=self.data, device=device), b, self.position(), self.orientation(), offsets, weights=weights, n=n,
+                                           normalize=normalize, axis=axis, follow=follow, window_plane=window_plane, crop_factor=crop_factor,
+                                           half_width=half_width, want_bands=want_bands)
+            return out[:5] + (b.ks.copy(),) + out[5:]
+
+    def poly_mtf(self, freqs, offsets=(0.0,), weights=None, normalize="energy", n=None, half_width=None, axis=None, follow="centroid", ks=None, device=0):
+        """The white-light diffraction MTF of the rows accumulated so far (bmo_psf_poly_otf): (mtf [M, nf], otf [M, nf] complex, sums [M],
+        stats [M, 12], ks, coeffs) as poly_mtf_of describes them."""
+        with self.bands(ks=ks, device=device) as b:
+            out, _ = poly_mtf_of(dict(hits=self.data, device=device), b, self.position(), self.orientation(), freqs, offsets=offsets, weights=weights,
+                                 normalize=normalize, n=n, half_width=half_width, axis=axis, follow=follow)
+            return out[:4] + (b.ks.copy(),) + out[4:]
 
     def intensity(self, n=100, device=0, _intensity_fn=None, **kw):
         """intensity(psf; n, crop_factor, center, x_min, ...) -> (xs, zs, I) with I[i, j] (PSFDetector.jl:190-237)."""

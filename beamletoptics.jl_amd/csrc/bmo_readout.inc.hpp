@@ -3509,3 +3509,423 @@ extern "C" int bmo_spot_ee_sweep(bmo_trace_result* res, int32_t detector, int32_
     std::copy(R.count.begin(), R.count.end(), n_rows);
     return spot_ee_read(rows, 9, R, centers, shape, thr, inside, kernel_ms, "bmo_spot_ee_sweep");
 }
+
+// ====================================================================================================================
+// Polychromatic read-out (include/bmo.h "Polychromatic read-out"): the rows of a slot split by wave number into band-contiguous ranges,
+// which every single-call read-out above then reads through its hits_on_device pointer, and the weighted sum of the bands' stacks.
+//
+// Discovery (ks == NULL): one pass over column 8.  A wave usually agrees on one key: every lane compares its key with the first pending
+// lane's, the ballot's popcount is that key's count, one lane adds it to a table in LDS, and the loop goes on with the lanes that
+// disagreed.  The workgroup's table is merged into a global open-addressed table of 64-bit patterns (atomicCAS on the key, an integer
+// atomic add on the count); a table that is full raises a flag.  The host sorts.  Integer counts of a set: no order shows in the result.
+//
+// Stable partition, three launches over tiles of PSF_TILE rows:
+//   (a) psf_band_count_kernel: every row is classified against the <= 64 keys in LDS; the rows of each (band, tile) are counted by ballot
+//       and popcount per wave, the four waves folded through LDS;
+//   (b) psf_band_scan_kernel: one workgroup per band, the exclusive scan of the band's tile counts and the band's total;
+//   (c) psf_band_scatter_kernel: classifies again; a row's place is base[band] + scan[band][tile] + the count of the earlier waves of the
+//       tile + the lanes of the wave below it in the same band.  No atomic decides a position: the order is fixed by construction.
+// The scatter writes every row straight to its place (nine stores of 8 bytes per lane).
+struct bmo_psf_bands {
+    int32_t device = 0;
+    int64_t n_rows = 0, unmatched = 0;  // matched (the sum of `count`) and dropped rows
+    std::vector<double> ks;
+    std::vector<int64_t> base, count;  // band b: rows base[b] .. base[b] + count[b] - 1 of `rows`
+    DevBuf rows;                       // [n_rows][9], band-major
+};
+
+namespace {
+
+constexpr int BAND_LDS_SLOTS = 128, BAND_TABLE_SLOTS = 256;  // powers of two, at least twice BMO_PSF_MAX_BANDS
+constexpr unsigned long long BAND_EMPTY = ~0ull;              // a NaN's pattern: never a key
+static_assert(BAND_LDS_SLOTS >= 2 * BMO_PSF_MAX_BANDS && BAND_TABLE_SLOTS >= 2 * BMO_PSF_MAX_BANDS && BMO_PSF_MAX_BANDS <= 64, "band tables");
+
+struct BandTable {
+    unsigned long long keys[BAND_TABLE_SLOTS], counts[BAND_TABLE_SLOTS];
+    unsigned long long n_nan, overflow;
+};
+
+// `cnt` more rows of `key` in the open-addressed table (keys, counts) of `slots` entries; false: the table holds `slots` other keys
+__device__ __forceinline__ bool band_table_add(unsigned long long* keys, unsigned long long* counts, int slots, unsigned long long key, unsigned long long cnt) {
+    unsigned s = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 40) & (unsigned)(slots - 1);
+    for (int probe = 0; probe < slots; ++probe, s = (s + 1) & (unsigned)(slots - 1)) {
+        const unsigned long long prev = atomicCAS(&keys[s], BAND_EMPTY, key);
+        if (prev == BAND_EMPTY || prev == key) {
+            atomicAdd(&counts[s], cnt);
+            return true;
+        }
+    }
+    return false;
+}
+
+// workgroup blockIdx.x reads tiles blockIdx.x, blockIdx.x + gridDim.x, ... of column 8
+__global__ __launch_bounds__(256) void psf_band_discover_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t n_tiles, BandTable* __restrict__ table) {
+    __shared__ unsigned long long l_keys[BAND_LDS_SLOTS], l_counts[BAND_LDS_SLOTS], l_nan, l_over;
+    for (int q = threadIdx.x; q < BAND_LDS_SLOTS; q += 256) l_keys[q] = BAND_EMPTY, l_counts[q] = 0;
+    if (threadIdx.x == 0) l_nan = 0, l_over = 0;
+    __syncthreads();
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t h = tile * PSF_TILE + threadIdx.x;
+        const bool in = h < n_hits;
+        double k = in ? hits[h * 9 + 8] : 0.0;
+        if (k == 0.0) k = 0.0;  // -0 == +0: one key
+        const bool nan = in && k != k;
+        const unsigned long long m_nan = __ballot(nan);
+        if (m_nan && lane_id() == 0) atomicAdd(&l_nan, (unsigned long long)__popcll(m_nan));
+        bool pending = in && !nan;
+        for (unsigned long long todo = __ballot(pending); todo; todo = __ballot(pending)) {  // one trip per distinct key of the wave
+            const int leader = __ffsll(todo) - 1;
+            const double k0 = __shfl(k, leader);
+            const bool same = pending && k == k0;
+            const unsigned long long m = __ballot(same);
+            if (lane_id() == leader && !band_table_add(l_keys, l_counts, BAND_LDS_SLOTS, (unsigned long long)__double_as_longlong(k0), (unsigned long long)__popcll(m)))
+                atomicAdd(&l_over, 1ull);
+            pending = pending && !same;
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < BAND_LDS_SLOTS; q += 256)
+        if (l_keys[q] != BAND_EMPTY && !band_table_add(table->keys, table->counts, BAND_TABLE_SLOTS, l_keys[q], l_counts[q])) atomicAdd(&table->overflow, 1ull);
+    if (threadIdx.x == 0) {
+        if (l_nan) atomicAdd(&table->n_nan, l_nan);
+        if (l_over) atomicAdd(&table->overflow, l_over);
+    }
+}
+
+constexpr int BAND_SLOTS = BMO_PSF_MAX_BANDS + 1;  // the bands and, at index n_bands, the rows of none
+
+// Row tile * PSF_TILE + threadIdx.x classified against the n_bands keys: its band, n_bands for a row of none (a NaN compares false), -1 for
+// a lane past the rows.  wcount[wave][band] (zeroed by the caller) receives the wave's rows of every band it holds, `rank` the lanes of the
+// wave below this one in the same band.  Every lane of the workgroup calls it.
+__device__ __forceinline__ int band_classify_tile(const double* __restrict__ hits, int64_t n_hits, int64_t tile, const double* keys, int n_bands,
+                                                  int (*wcount)[BAND_SLOTS], int& rank) {
+    const int64_t h = tile * PSF_TILE + threadIdx.x;
+    int band = -1;
+    if (h < n_hits) {
+        const double k = hits[h * 9 + 8];
+        band = n_bands;
+        for (int b = 0; b < n_bands; ++b)
+            if (k == keys[b]) band = b;  // the keys are distinct: at most one compares equal
+    }
+    rank = 0;
+    bool pending = band >= 0;
+    for (unsigned long long todo = __ballot(pending); todo; todo = __ballot(pending)) {  // one trip per distinct band of the wave
+        const int leader = __ffsll(todo) - 1;
+        const int b0 = __shfl(band, leader);
+        const bool same = pending && band == b0;
+        const unsigned long long m = __ballot(same);
+        if (same) rank = prefix_rank(m);
+        if (lane_id() == leader) wcount[threadIdx.x >> 6][b0] = __popcll(m);
+        pending = pending && !same;
+    }
+    return band;
+}
+
+// the keys into LDS and the wave counts zeroed; the caller syncs
+__device__ __forceinline__ void band_tile_begin(const double* __restrict__ keys_g, int n_bands, double* keys, int (*wcount)[BAND_SLOTS]) {
+    if ((int)threadIdx.x < n_bands) keys[threadIdx.x] = keys_g[threadIdx.x];
+    for (int q = threadIdx.x; q < 4 * BAND_SLOTS; q += 256) wcount[q / BAND_SLOTS][q % BAND_SLOTS] = 0;
+}
+
+// (a) tile blockIdx.x: tile_count[band][tile], band = 0 .. n_bands (the last: the rows of no band)
+__global__ __launch_bounds__(256) void psf_band_count_kernel(const double* __restrict__ hits, int64_t n_hits, const double* __restrict__ keys_g, int n_bands,
+                                                             int64_t n_tiles, int32_t* __restrict__ tile_count) {
+    __shared__ double keys[BMO_PSF_MAX_BANDS];
+    __shared__ int wcount[4][BAND_SLOTS];
+    band_tile_begin(keys_g, n_bands, keys, wcount);
+    __syncthreads();
+    int rank;
+    (void)band_classify_tile(hits, n_hits, blockIdx.x, keys, n_bands, wcount, rank);
+    __syncthreads();
+    const int b = threadIdx.x;
+    if (b <= n_bands) tile_count[(int64_t)b * n_tiles + blockIdx.x] = (wcount[0][b] + wcount[1][b]) + (wcount[2][b] + wcount[3][b]);
+}
+
+// (b) band blockIdx.x: tile_start[band][tile] = the rows of the band in the tiles before, totals[band] = its rows.  Lane l owns a run of
+// consecutive tiles.
+__global__ __launch_bounds__(256) void psf_band_scan_kernel(const int32_t* __restrict__ tile_count, int64_t n_tiles, int64_t* __restrict__ tile_start,
+                                                            int64_t* __restrict__ totals) {
+    __shared__ int64_t run_start[256];
+    const int32_t* c = tile_count + (int64_t)blockIdx.x * n_tiles;
+    int64_t* s = tile_start + (int64_t)blockIdx.x * n_tiles;
+    const int64_t per = (n_tiles + 255) / 256;
+    const int64_t t0 = std::min<int64_t>((int64_t)threadIdx.x * per, n_tiles), t1 = std::min<int64_t>(t0 + per, n_tiles);
+    int64_t sum = 0;
+    for (int64_t t = t0; t < t1; ++t) sum += c[t];
+    run_start[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int q = 0; q < 256; ++q) {
+            const int64_t v = run_start[q];
+            run_start[q] = acc;
+            acc += v;
+        }
+        totals[blockIdx.x] = acc;
+    }
+    __syncthreads();
+    int64_t at = run_start[threadIdx.x];
+    for (int64_t t = t0; t < t1; ++t) {
+        s[t] = at;
+        at += c[t];
+    }
+}
+
+// (c) tile blockIdx.x: every matched row copied to its place in `out` [n_out][9]
+__global__ __launch_bounds__(256) void psf_band_scatter_kernel(const double* __restrict__ hits, int64_t n_hits, const double* __restrict__ keys_g, int n_bands,
+                                                               int64_t n_tiles, const int64_t* __restrict__ tile_start, const int64_t* __restrict__ totals,
+                                                               int64_t n_out, double* __restrict__ out) {
+    __shared__ double keys[BMO_PSF_MAX_BANDS];
+    __shared__ int wcount[4][BAND_SLOTS];
+    __shared__ int64_t base[BMO_PSF_MAX_BANDS];
+    band_tile_begin(keys_g, n_bands, keys, wcount);
+    if (threadIdx.x == 0) {
+        int64_t acc = 0;
+        for (int b = 0; b < n_bands; ++b) {
+            base[b] = acc;
+            acc += totals[b];
+        }
+    }
+    __syncthreads();
+    int rank;
+    const int band = band_classify_tile(hits, n_hits, blockIdx.x, keys, n_bands, wcount, rank);
+    __syncthreads();
+    if (band < 0 || band >= n_bands) return;
+    int before = 0;
+    for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) before += wcount[w][band];
+    const int64_t dst = base[band] + tile_start[(int64_t)band * n_tiles + blockIdx.x] + before + rank;
+    if (dst >= n_out) return;  // (cannot happen: the totals are the counts of the same classification)
+    const double* r = hits + ((int64_t)blockIdx.x * PSF_TILE + threadIdx.x) * 9;
+    double* o = out + dst * 9;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) o[q] = r[q];
+}
+
+// acc = c * I (first) or acc + c * I per sample, a multiply and an add; src nullptr: a band without rows, I = 0
+__global__ void psf_poly_combine_kernel(double* __restrict__ acc, const double* __restrict__ src, double c, int first, int64_t n_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    const double v = c * (src ? src[i] : 0.0);
+    acc[i] = first ? v : acc[i] + v;
+}
+
+}  // namespace
+
+// The distinct keys of column 8 of the n_hits > 0 device rows, ascending, with their counts; n_nan: the rows whose key is a NaN.
+static int psf_bands_discover(const double* hits, int64_t n_hits, hipStream_t st, std::vector<double>& ks, std::vector<int64_t>& counts, int64_t& n_nan) {
+    std::unique_ptr<BandTable> host(new BandTable);
+    std::fill(host->keys, host->keys + BAND_TABLE_SLOTS, BAND_EMPTY);
+    std::fill(host->counts, host->counts + BAND_TABLE_SLOTS, 0ull);
+    host->n_nan = host->overflow = 0;
+    DevBuf d_table;
+    if (int rc = d_table.alloc(sizeof(BandTable))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_table.p, host.get(), sizeof(BandTable), hipMemcpyHostToDevice, st));
+    const int64_t n_tiles = (n_hits + PSF_TILE - 1) / PSF_TILE;
+    hipLaunchKernelGGL(psf_band_discover_kernel, dim3((unsigned)std::min<int64_t>(n_tiles, 1024)), dim3(256), 0, st, hits, n_hits, n_tiles, (BandTable*)d_table.p);
+    HIP_TRY(hipMemcpyAsync(host.get(), d_table.p, sizeof(BandTable), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    std::vector<std::pair<double, int64_t>> found;
+    for (int q = 0; q < BAND_TABLE_SLOTS; ++q)
+        if (host->keys[q] != BAND_EMPTY) {
+            double k;
+            memcpy(&k, &host->keys[q], 8);
+            found.push_back({k, (int64_t)host->counts[q]});
+        }
+    if (host->overflow != 0 || found.size() > (size_t)BMO_PSF_MAX_BANDS)
+        return fail(BMO_ERR_LIMIT, "bmo_psf_bands_create: the rows hold more than BMO_PSF_MAX_BANDS (64) distinct wave numbers");
+    std::sort(found.begin(), found.end());
+    for (const auto& f : found) ks.push_back(f.first), counts.push_back(f.second);
+    n_nan = (int64_t)host->n_nan;
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_bands_create(const double* hits, int64_t n_hits, int32_t hits_on_device, int32_t device, const double* ks, int32_t n_ks, bmo_psf_bands** out,
+                                    double* kernel_ms) {
+    if (!out || n_hits < 0 || (n_hits > 0 && !hits)) return fail(BMO_ERR_INVALID, "bmo_psf_bands_create: bad argument (null pointer, n_hits < 0)");
+    if (ks) {
+        if (n_ks <= 0) return fail(BMO_ERR_INVALID, "bmo_psf_bands_create: ks given with n_ks <= 0");
+        for (int32_t a = 0; a < n_ks; ++a) {
+            if (!std::isfinite(ks[a])) return fail(BMO_ERR_INVALID, "bmo_psf_bands_create: a wave number of ks is not finite");
+            for (int32_t b = 0; b < a && b < BMO_PSF_MAX_BANDS; ++b)
+                if (ks[a] == ks[b]) return fail(BMO_ERR_INVALID, "bmo_psf_bands_create: two wave numbers of ks are equal");
+        }
+        if (n_ks > BMO_PSF_MAX_BANDS) return fail(BMO_ERR_LIMIT, "bmo_psf_bands_create: more than BMO_PSF_MAX_BANDS (64) bands");
+    }
+    if (kernel_ms) *kernel_ms = 0.0;
+    DevBuf d_hits;
+    if (int rc = single_rows("bmo_psf_bands_create", hits, n_hits, 9, hits_on_device, device, d_hits)) return rc;
+    const int64_t n_tiles = (n_hits + PSF_TILE - 1) / PSF_TILE;
+    if (n_tiles > (int64_t)0x7fffffff) return fail(BMO_ERR_LIMIT, "bmo_psf_bands_create: more tiles of rows than one launch holds");
+    std::unique_ptr<bmo_psf_bands> B(new bmo_psf_bands);
+    B->device = device;
+    if (ks) B->ks.assign(ks, ks + n_ks);
+    hipStream_t st = 0;
+    EventTimer timer;
+    std::vector<int64_t> found;  // the counts the discovery pass saw
+    int64_t n_nan = 0;
+    if (n_hits > 0)
+        if (int rc = timer.start(st)) return rc;
+    if (!ks && n_hits > 0)
+        if (int rc = psf_bands_discover(hits, n_hits, st, B->ks, found, n_nan)) return rc;
+    const int nb = (int)B->ks.size();
+    B->base.assign((size_t)nb, 0);
+    B->count.assign((size_t)nb, 0);
+    if (n_hits == 0 || nb == 0) {  // nothing to place: every row, if any, has a NaN key
+        B->unmatched = n_nan;
+        if (int rc = B->rows.alloc(0)) return rc;
+        if (n_hits > 0)
+            if (int rc = timer.stop(kernel_ms)) return rc;
+        *out = B.release();
+        return BMO_OK;
+    }
+    Packed up;
+    const size_t o_keys = up.add(B->ks);
+    DevBuf d_count, d_start, d_totals;
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_count.alloc((size_t)(nb + 1) * (size_t)n_tiles * 4)) || (rc = d_start.alloc((size_t)(nb + 1) * (size_t)n_tiles * 8)) ||
+        (rc = d_totals.alloc((size_t)(nb + 1) * 8)))
+        return rc;
+    hipLaunchKernelGGL(psf_band_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, hits, n_hits, up.at<double>(o_keys), nb, n_tiles, (int32_t*)d_count.p);
+    hipLaunchKernelGGL(psf_band_scan_kernel, dim3((unsigned)(nb + 1)), dim3(256), 0, st, (const int32_t*)d_count.p, n_tiles, (int64_t*)d_start.p, (int64_t*)d_totals.p);
+    std::vector<int64_t> totals((size_t)nb + 1);
+    HIP_TRY(hipMemcpyAsync(totals.data(), d_totals.p, totals.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    int64_t matched = 0;
+    for (int b = 0; b < nb; ++b) {
+        B->base[(size_t)b] = matched;
+        B->count[(size_t)b] = totals[(size_t)b];
+        matched += totals[(size_t)b];
+    }
+    B->n_rows = matched;
+    B->unmatched = totals[(size_t)nb];
+    if (matched + B->unmatched != n_hits || (!ks && (B->count != found || B->unmatched != n_nan)))
+        return fail(BMO_ERR_INTERNAL, "bmo_psf_bands_create: the band counts do not add up to the rows");
+    if ((rc = B->rows.alloc((size_t)matched * 9 * sizeof(double)))) return rc;
+    if (matched > 0)
+        hipLaunchKernelGGL(psf_band_scatter_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, hits, n_hits, up.at<double>(o_keys), nb, n_tiles, (const int64_t*)d_start.p,
+                           (const int64_t*)d_totals.p, matched, (double*)B->rows.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    *out = B.release();
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_bands_info(const bmo_psf_bands* b, int32_t* n_bands, int64_t* n_rows, int64_t* unmatched, int32_t* device) {
+    if (!b) return fail(BMO_ERR_INVALID, "bmo_psf_bands_info: null handle");
+    if (n_bands) *n_bands = (int32_t)b->ks.size();
+    if (n_rows) *n_rows = b->n_rows;
+    if (unmatched) *unmatched = b->unmatched;
+    if (device) *device = b->device;
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_bands_get(const bmo_psf_bands* b, int32_t band, double* k, const double** rows, int64_t* count) {
+    if (!b) return fail(BMO_ERR_INVALID, "bmo_psf_bands_get: null handle");
+    if (band < 0 || (size_t)band >= b->ks.size()) return fail(BMO_ERR_INVALID, "bmo_psf_bands_get: band index out of range");
+    if (k) *k = b->ks[(size_t)band];
+    if (rows) *rows = (const double*)b->rows.p + 9 * b->base[(size_t)band];
+    if (count) *count = b->count[(size_t)band];
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_bands_free(bmo_psf_bands* b) {
+    delete b;
+    return BMO_OK;
+}
+
+// what the two polychromatic entries refuse of their coefficients
+static bool poly_coeffs_ok(const bmo_psf_bands* b, const double* coeffs) {
+    for (size_t q = 0; q < b->ks.size(); ++q)
+        if (!std::isfinite(coeffs[q])) return false;
+    return true;
+}
+
+// The weighted sum of the bands' stacks, left on the device: d_acc [n_planes][n * n] (at least one band).  Band after band: psf_focus_stack
+// on the band's range, then the combine launch, so one band's stack and the accumulator are held; out_band (host, [n_bands][n_out]) takes
+// each band's stack as it is made.  `timer` runs from the first launch; the caller may queue more on stream 0 and stop it again.
+static int psf_poly_stack(const bmo_psf_bands* B, const double* origin, const double* e1, const double* e2, const double* disp, int32_t n_planes, const double* xs,
+                          const double* zs, int32_t n, const double* coeffs, DevBuf& d_acc, double* out_band, EventTimer& timer, double* kernel_ms) {
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    hipStream_t st = 0;
+    if (int rc = d_acc.alloc(n_out * sizeof(double))) return rc;
+    for (size_t b = 0; b < B->ks.size(); ++b) {
+        DevBuf d_int, d_field;
+        const double* src = nullptr;
+        if (B->count[b] > 0) {
+            if (int rc = psf_focus_stack((const double*)B->rows.p + 9 * B->base[b], B->count[b], origin, e1, e2, disp, n_planes, xs, zs, n, false, d_int, d_field, timer, kernel_ms))
+                return rc;
+            src = (const double*)d_int.p;
+        }
+        if (!timer.e0)
+            if (int rc = timer.start(st)) return rc;
+        hipLaunchKernelGGL(psf_poly_combine_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, (double*)d_acc.p, src, coeffs[b], b == 0 ? 1 : 0, (int64_t)n_out);
+        if (out_band) {
+            if (src) HIP_TRY(hipMemcpy(out_band + b * n_out, src, n_out * sizeof(double), hipMemcpyDeviceToHost));
+            else std::fill(out_band + b * n_out, out_band + (b + 1) * n_out, 0.0);
+        }
+    }
+    return timer.stop(kernel_ms);
+}
+
+extern "C" int bmo_psf_poly_through_focus(const bmo_psf_bands* b, const double origin[3], const double e1[3], const double e2[3], const double* displacements,
+                                          int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* coeffs, double* out_intensity,
+                                          double* out_band_intensity, double* kernel_ms) {
+    if (!b || !origin || !e1 || !e2 || !displacements || !xs || !zs || !coeffs || !out_intensity || n <= 0 || n_planes <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_poly_through_focus: bad argument (null pointer, n <= 0, n_planes <= 0)");
+    if (!poly_coeffs_ok(b, coeffs)) return fail(BMO_ERR_INVALID, "bmo_psf_poly_through_focus: a coefficient is not finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    if (b->ks.empty()) {
+        std::fill(out_intensity, out_intensity + n_out, 0.0);
+        return BMO_OK;
+    }
+    if ((n_out + 255) / 256 > (size_t)0x7fffffff) return fail(BMO_ERR_LIMIT, "bmo_psf_poly_through_focus: more samples than one launch holds");
+    HIP_TRY(hipSetDevice(b->device));
+    DevBuf d_acc;
+    EventTimer timer;
+    if (int rc = psf_poly_stack(b, origin, e1, e2, displacements, n_planes, xs, zs, n, coeffs, d_acc, out_band_intensity, timer, kernel_ms)) return rc;
+    HIP_TRY(hipMemcpy(out_intensity, d_acc.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_poly_otf(const bmo_psf_bands* b, const double origin[3], const double e1[3], const double e2[3], const double* displacements, int32_t n_planes,
+                                const double* xs, const double* zs, int32_t n, const double* coeffs, const double* freqs, int32_t n_freqs, double* otf, double* mtf,
+                                double* sums, double* out_intensity, double* kernel_ms) {
+    if (!b || !origin || !e1 || !e2 || !displacements || !xs || !zs || !coeffs || !freqs || !otf || !mtf || !sums || n <= 0 || n_planes <= 0 || n_freqs <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_poly_otf: bad argument (null pointer, n <= 0, n_planes <= 0, n_freqs <= 0)");
+    if (!poly_coeffs_ok(b, coeffs)) return fail(BMO_ERR_INVALID, "bmo_psf_poly_otf: a coefficient is not finite");
+    if (!otf_freqs_ok(freqs, n_freqs)) return fail(BMO_ERR_INVALID, "bmo_psf_poly_otf: a frequency is not finite");
+    if (kernel_ms) *kernel_ms = 0.0;
+    const size_t n_out = (size_t)n_planes * (size_t)n * (size_t)n;
+    const int64_t n_pairs = (int64_t)n_planes * n_freqs;
+    if (b->ks.empty() || b->n_rows == 0) {
+        otf_fill_empty((size_t)n_pairs, (size_t)n_planes, otf, mtf, sums);
+        if (out_intensity) std::fill(out_intensity, out_intensity + n_out, 0.0);
+        return BMO_OK;
+    }
+    const int64_t n_rowsums = (int64_t)n_planes * (n_freqs + 1) * n;
+    if ((n_rowsums + 255) / 256 > (int64_t)0x7fffffff || (n_out + 255) / 256 > (size_t)0x7fffffff)
+        return fail(BMO_ERR_LIMIT, "bmo_psf_poly_otf: more row sums or samples than one launch holds");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = 0;
+    DevBuf d_acc, d_rowsum, d_otf, d_mtf, d_sums;
+    Packed up;
+    const size_t o_xs = up.add(xs, (size_t)n), o_zs = up.add(zs, (size_t)n), o_freq = up.add(freqs, (size_t)n_freqs * 2);
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_rowsum.alloc((size_t)n_rowsums * sizeof(double2))) || (rc = d_otf.alloc((size_t)n_pairs * sizeof(double2))) ||
+        (rc = d_mtf.alloc((size_t)n_pairs * 8)) || (rc = d_sums.alloc((size_t)n_planes * 8)))
+        return rc;
+    EventTimer timer;
+    if ((rc = psf_poly_stack(b, origin, e1, e2, displacements, n_planes, xs, zs, n, coeffs, d_acc, nullptr, timer, kernel_ms))) return rc;
+    hipLaunchKernelGGL(psf_otf_rows_kernel, dim3((unsigned)((n_rowsums + 255) / 256)), dim3(256), 0, st, (const double*)d_acc.p, up.at<double>(o_xs), n,
+                       up.at<double2>(o_freq), n_freqs, n_rowsums, (double2*)d_rowsum.p);
+    hipLaunchKernelGGL(psf_otf_cols_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, (const double2*)d_rowsum.p, up.at<double>(o_zs), n,
+                       up.at<double2>(o_freq), n_freqs, n_pairs, (double2*)d_otf.p, (double*)d_mtf.p, (double*)d_sums.p);
+    if ((rc = timer.stop(kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(otf, d_otf.p, (size_t)n_pairs * sizeof(double2), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mtf, d_mtf.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    if (out_intensity) HIP_TRY(hipMemcpy(out_intensity, d_acc.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}

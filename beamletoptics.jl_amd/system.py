@@ -597,6 +597,51 @@ class EngineSolution:
         self.readout_ms = float(sum(ms))
         return out
 
+    def psf_bands(self, slot, ks=None):
+        """The resident rows of PSFDetector slot `slot` split by wave number on the device (bmo_psf_bands_create on the pointer of
+        bmo_result_psf_rows: no row leaves the device): an abi.PsfBands, to be closed by the caller.  It owns a copy of the rows and outlives
+        this solution."""
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        bands, self.readout_ms = abi.psf_bands(None, ks=ks, device=dev, hits_device_ptr=ptr, n_hits=cnt, want_ms=True)
+        return bands
+
+    def _psf_all_rows(self, slot):
+        ptr, cnt, dev = self._psf_resident_rows(slot)
+        return dict(hits=None, device=dev, hits_device_ptr=ptr, n_hits=cnt)
+
+    def psf_chromatic_focus(self, slot, position, orientation, offsets, axis=None, ks=None, plane=None):
+        """Where each colour of the resident rows of PSFDetector slot `slot` focuses and lands: (ks, stats [B, M, 12], focus [B], rms [B],
+        centroids [B, 2], plane) as PSFDetector.chromatic_focus gives them from host rows."""
+        with self.psf_bands(slot, ks=ks) as b:
+            ms = self.readout_ms
+            out, t = cp.chromatic_focus_of(b, position, orientation, offsets, axis=axis, plane=plane)
+            self.readout_ms = ms + t
+            return (b.ks.copy(),) + out
+
+    def psf_poly_through_focus(self, slot, position, orientation, offsets, weights=None, n=100, normalize="energy", axis=None, follow="centroid",
+                               window_plane=None, crop_factor=1.0, half_width=None, ks=None, want_bands=False):
+        """The incoherent, spectrally weighted through-focus stack of the resident rows of PSFDetector slot `slot`: (xs, zs, displacements,
+        I[M, n, n], stats, ks, coeffs, I_b or None) as PSFDetector.poly_through_focus gives them from host rows."""
+        all_rows = self._psf_all_rows(slot)
+        with self.psf_bands(slot, ks=ks) as b:
+            ms = self.readout_ms
+            out, t = cp.poly_through_focus_of(all_rows, b, position, orientation, offsets, weights=weights, n=n, normalize=normalize, axis=axis, follow=follow,
+                                              window_plane=window_plane, crop_factor=crop_factor, half_width=half_width, want_bands=want_bands)
+            self.readout_ms = ms + t
+            return out[:5] + (b.ks.copy(),) + out[5:]
+
+    def psf_poly_mtf(self, slot, position, orientation, freqs, offsets=(0.0,), weights=None, normalize="energy", n=None, half_width=None, axis=None,
+                     follow="centroid", ks=None):
+        """The white-light diffraction MTF of the resident rows of PSFDetector slot `slot`: (mtf [M, nf], otf [M, nf] complex, sums [M],
+        stats [M, 12], ks, coeffs) as PSFDetector.poly_mtf gives them from host rows."""
+        all_rows = self._psf_all_rows(slot)
+        with self.psf_bands(slot, ks=ks) as b:
+            ms = self.readout_ms
+            out, t = cp.poly_mtf_of(all_rows, b, position, orientation, freqs, offsets=offsets, weights=weights, normalize=normalize, n=n,
+                                    half_width=half_width, axis=axis, follow=follow)
+            self.readout_ms = ms + t
+            return out[:4] + (b.ks.copy(),) + out[4:]
+
     def spot_encircled_energy(self, slot, radii, center=None, shape="circle"):
         """bmo_spot_ee_sweep on the resident rows of Spotdetector slot `slot`: (fraction [nr], inside int64 [nr], n_rows) as
         Spotdetector.encircled_energy gives them from host rows; center None: the centroid of spot_stats(slot)."""

@@ -907,6 +907,60 @@ int bmo_psf_ee(const double* hits, int64_t n_hits, int32_t hits_on_device, const
                int32_t shape, const double* radii, int32_t n_radii, int32_t device, double* ee, double* energy, double* sums,
                double* centers_out, double* out_intensity, double* kernel_ms);
 
+/* ------------------------------------------------------------------------------------------------
+ * Polychromatic read-out: the rows of a PSFDetector split by wavelength band on the device, and the incoherent, spectrally weighted sum of
+ * the bands' through-focus stacks with its transform.  A PSF row carries its wave number k in column 8; every read-out above sums the rows
+ * it is given coherently, as intensity(psf) does.  Light of different wavelengths does not interfere: the image of a solve that mixes
+ * wavelengths is the weighted sum of the per-wavelength images.  No reference counterpart.
+ *
+ * Bands.  A row belongs to band b iff row[8] == k_b, a plain FP64 compare (-0 == +0; a NaN belongs to no band).  The engine writes
+ * k = 2 * 3.141592653589793 / lambda per ray (bmo_lane.hpp), so rows of one wavelength share their k bit for bit.
+ * bmo_psf_bands_create: hits, n_hits, hits_on_device, device as for bmo_psf_intensity.
+ *   ks == NULL, the discovery form: the bands are the distinct k of the rows, ascending; n_ks is ignored.  Only rows with a NaN k are
+ *     unmatched.  Counts are integers and the bands a set: the result does not depend on the order in which the device finds them.
+ *   ks != NULL: exactly those n_ks bands in the caller's order.  A band without rows is legal and has count 0.  A row whose k is none of them,
+ *     or is NaN, is dropped and counted in `unmatched`.
+ *   The handle owns a device copy of the matched rows, [sum of counts][9], band-major; within a band the rows keep their original order
+ *   (the partition is stable: no atomic decides a position).  It does not depend on the lifetime of the result or buffer it was built from.
+ *   The defining property: band b equals, bit for bit and in order, the rows hits[hits[:, 8] == k_b].
+ * bmo_psf_bands_info: the band count, the matched rows (sum of counts), the unmatched rows and the device ordinal; each pointer may be NULL.
+ * bmo_psf_bands_get: the band's k, the device pointer to its first row and its count (each pointer may be NULL).  The pointer is made to be
+ *   handed to every read-out above that takes hits_on_device != 0, on the handle's device: such a call reads the band exactly as it reads
+ *   host rows hits[hits[:, 8] == k_b].
+ * bmo_psf_bands_free: frees the rows and the handle (NULL: nothing).
+ *
+ * bmo_psf_poly_through_focus: origin .. n as for bmo_psf_through_focus; all bands share the pose, the displacements and the grid
+ * (intensities add only at the same physical point).  coeffs: [n_bands], host.  FP64, no contraction, left to right as written:
+ *   I_b = the stack bmo_psf_through_focus returns for band b's rows and the same arguments, bit for bit (the same kernels and plan, run on
+ *         the band's range); a band without rows gives zeros
+ *   acc = coeffs[0] * I_0;   acc = acc + coeffs[b] * I_b  for b = 1 .. n_bands - 1 in band order   (a multiply and an add, never fused)
+ *   out_intensity[m][i + n*j] = acc:  host, [n_planes][n*n].   out_band_intensity: optional, host, [n_bands][n_planes][n*n], the I_b.
+ * No bands: zeros.
+ *
+ * bmo_psf_poly_otf: the combined stack stays on the device and is transformed by the row and column passes of bmo_psf_otf (the same
+ * kernels, expressions and order, `acc` in the place of I): freqs, otf, mtf, sums as there.  By linearity T(f) = sum_b coeffs[b] T_b(f) and
+ * sums = sum_b coeffs[b] T_b(0).  out_intensity: optional, equal to bmo_psf_poly_through_focus's bit for bit.  No bands or no matched rows:
+ * zeros, and NaN in mtf.
+ *
+ * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than ks, the optional outputs and kernel_ms; n_hits < 0;
+ * ks given with n_ks <= 0, with a k that is not finite, or with two equal k; n, n_planes or n_freqs <= 0; a coefficient or a frequency that
+ * is not finite; a band index out of range.  BMO_ERR_LIMIT: n_ks > BMO_PSF_MAX_BANDS, or the discovery form finds more distinct k than that.
+ * There is no _sweep form and no GaussianBeamlet form: resident rows come through bmo_result_psf_rows and inherit its refusals.
+ * kernel_ms: optional, HIP-event time of the launches.                                                                                  */
+#define BMO_PSF_MAX_BANDS 64
+typedef struct bmo_psf_bands bmo_psf_bands;
+int bmo_psf_bands_create(const double* hits, int64_t n_hits, int32_t hits_on_device, int32_t device, const double* ks, int32_t n_ks,
+                         bmo_psf_bands** out, double* kernel_ms);
+int bmo_psf_bands_info(const bmo_psf_bands* b, int32_t* n_bands, int64_t* n_rows, int64_t* unmatched, int32_t* device);
+int bmo_psf_bands_get(const bmo_psf_bands* b, int32_t band, double* k, const double** rows, int64_t* count);
+int bmo_psf_bands_free(bmo_psf_bands* b);
+int bmo_psf_poly_through_focus(const bmo_psf_bands* b, const double origin[3], const double e1[3], const double e2[3],
+                               const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n,
+                               const double* coeffs, double* out_intensity, double* out_band_intensity, double* kernel_ms);
+int bmo_psf_poly_otf(const bmo_psf_bands* b, const double origin[3], const double e1[3], const double e2[3], const double* displacements,
+                     int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* coeffs, const double* freqs,
+                     int32_t n_freqs, double* otf, double* mtf, double* sums, double* out_intensity, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
