@@ -97,6 +97,12 @@ class ResultView(C.Structure):
     ]
 
 
+def _out(shape, dtype=float):
+    """Every buffer a C entry writes is allocated here, and nowhere else in this module.  Zeros in production; tests/test_state_independence_gpu.py
+    swaps this for a filler of 0x7FF8DEAD words, as a caller that hands the entries uninitialised memory (julia/GPUSystem.jl) would."""
+    return np.zeros(shape, dtype=dtype)
+
+
 def _np(ptr, n, dtype):
     if n == 0:
         return np.zeros(0, dtype=dtype)
@@ -236,6 +242,8 @@ def load_engine():
     lib.bmo_scene_mesh_bvh.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.bmo_mesh_nearest_host.argtypes = [vp, C.c_int32, C.c_int64] + [C.POINTER(C.c_double)] * 3 + [C.POINTER(C.c_int32)]
     lib.bmo_scene_destroy.argtypes = [vp]
+    lib.bmo_pool_release.argtypes = []
+    lib.bmo_pool_release.restype = C.c_int
     lib.bmo_trace.argtypes = [vp, C.POINTER(RayBatch), C.POINTER(TraceOpts), C.POINTER(vp)]
     lib.bmo_batch_upload.argtypes = [vp, C.POINTER(RayBatch), C.c_int32, C.POINTER(vp)]
     lib.bmo_batch_free.argtypes = [vp]
@@ -295,6 +303,12 @@ def check(lib, rc, what):
         raise RuntimeError(f"{what} failed ({rc}): {msg.decode() if msg else ''}")
 
 
+def pool_release():
+    """bmo_pool_release: gives every block the device pool keeps back to the driver (the next allocations are fresh ones)."""
+    lib = load_engine()
+    check(lib, lib.bmo_pool_release(), "bmo_pool_release")
+
+
 def _psf_rows(hits, hits_device_ptr, n_hits):
     """(pointer, row count, on_device, keep-alive) of the PSF rows of a single read-out."""
     if hits_device_ptr is not None:
@@ -326,8 +340,8 @@ def psf_intensity(hits, origin, e1, e2, xs, zs, device=0, hits_device_ptr=None, 
     if len(z) != n:
         raise ValueError("xs and zs must have the same length")
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    out = np.zeros(n * n)
-    fld = np.zeros(2 * n * n) if want_field else None
+    out = _out(n * n)
+    fld = _out(2 * n * n) if want_field else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_intensity(hp, nh, on_dev, op, e1p, e2p, xp, zp, n, int(device), out.ctypes.data_as(dp),
                                      fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_intensity")
@@ -349,8 +363,8 @@ def psf_intensity_sweep(res_handle, detector, n_configs, origins, e1s, e2s, xs, 
     xs = np.asarray(xs, dtype=np.float64)
     n = xs.shape[-1]
     (o, op), (a1, e1p), (a2, e2p), (x, xp), (z, zp) = arr(origins, 3), arr(e1s, 3), arr(e2s, 3), arr(xs, n), arr(zs, n)
-    out = np.zeros(K * n * n)
-    fld = np.zeros(2 * K * n * n) if want_field else None
+    out = _out(K * n * n)
+    fld = _out(2 * K * n * n) if want_field else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_intensity_sweep(res_handle, int(detector), K, op, e1p, e2p, xp, zp, n, out.ctypes.data_as(dp),
                                            fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_intensity_sweep")
@@ -375,7 +389,7 @@ def spot_image(rows, window, nx, nz=None, device=0, rows_device_ptr=None, n_rows
     nz = nx if nz is None else nz
     rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
     w = np.ascontiguousarray(window, dtype=np.float64).reshape(4)
-    img = np.zeros(max(int(nx) * int(nz), 0), dtype=np.int64)
+    img = _out(max(int(nx) * int(nz), 0), dtype=np.int64)
     out = C.c_int64()
     ms = C.c_double()
     check(lib, lib.bmo_spot_image(rp, n, cols, on_dev, w.ctypes.data_as(C.POINTER(C.c_double)), int(nx), int(nz), int(device),
@@ -390,8 +404,8 @@ def spot_image_sweep(res_handle, detector, n_configs, windows, nx, nz=None):
     K = int(n_configs)
     nz = nx if nz is None else nz
     w = _per_config(windows, max(K, 1), 4)
-    img = np.zeros(max(K, 1) * max(int(nx) * int(nz), 0), dtype=np.int64)
-    out = np.zeros(max(K, 1), dtype=np.int64)
+    img = _out(max(K, 1) * max(int(nx) * int(nz), 0), dtype=np.int64)
+    out = _out(max(K, 1), dtype=np.int64)
     ms = C.c_double()
     ip = C.POINTER(C.c_int64)
     check(lib, lib.bmo_spot_image_sweep(res_handle, int(detector), K, w.ctypes.data_as(C.POINTER(C.c_double)), int(nx), int(nz), img.ctypes.data_as(ip),
@@ -403,7 +417,7 @@ def spot_stats(rows, device=0, rows_device_ptr=None, n_rows=None, row_cols=9):
     """bmo_spot_stats: the twelve statistics (SPOT_* columns) of the rows, two passes on the device.  Returns (stats [12], kernel_ms)."""
     lib = load_engine()
     rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
-    st = np.zeros(SPOT_STAT_N)
+    st = _out(SPOT_STAT_N)
     ms = C.c_double()
     check(lib, lib.bmo_spot_stats(rp, n, cols, on_dev, int(device), st.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ms)), "bmo_spot_stats")
     return st, ms.value
@@ -414,7 +428,7 @@ def spot_stats_sweep(res_handle, detector, n_configs):
     configuration c bit for bit."""
     lib = load_engine()
     K = int(n_configs)
-    st = np.zeros((max(K, 1), SPOT_STAT_N))
+    st = _out((max(K, 1), SPOT_STAT_N))
     ms = C.c_double()
     check(lib, lib.bmo_spot_stats_sweep(res_handle, int(detector), K, st.ctypes.data_as(C.POINTER(C.c_double)), C.byref(ms)), "bmo_spot_stats_sweep")
     return st[:K], ms.value
@@ -429,7 +443,7 @@ def psf_stats(hits, origin, e1, e2, ref=None, device=0, hits_device_ptr=None, n_
     o, a1, a2 = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2))
     r = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(2)
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    st = np.zeros(PSF_STAT_N)
+    st = _out(PSF_STAT_N)
     ms = C.c_double()
     check(lib, lib.bmo_psf_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
                                  int(device), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats")
@@ -445,7 +459,7 @@ def psf_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, ref=None
     K1 = max(K, 1)
     o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
     r = _per_config(ref, K1, 2)
-    st = np.zeros((K1, PSF_STAT_N))
+    st = _out((K1, PSF_STAT_N))
     ms = C.c_double()
     check(lib, lib.bmo_psf_stats_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                        None if r is None else r.ctypes.data_as(dp), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_stats_sweep")
@@ -465,8 +479,8 @@ def psf_through_focus(hits, origin, e1, e2, displacements, xs, zs, device=0, hit
     if len(z) != n:
         raise ValueError("xs and zs must have the same length")
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    out = np.zeros(M * n * n)
-    fld = np.zeros(2 * M * n * n) if want_field else None
+    out = _out(M * n * n)
+    fld = _out(2 * M * n * n) if want_field else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_through_focus(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M,
                                          x.ctypes.data_as(dp), z.ctypes.data_as(dp), n, int(device), out.ctypes.data_as(dp),
@@ -483,7 +497,7 @@ def psf_focus_stats(hits, origin, e1, e2, axis, offsets, device=0, hits_device_p
     o, a1, a2, ax = (np.ascontiguousarray(v, dtype=np.float64).reshape(3) for v in (origin, e1, e2, axis))
     off = np.ascontiguousarray(np.asarray(offsets, dtype=np.float64).reshape(-1))
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    st = np.zeros((len(off), FOCUS_STAT_N))
+    st = _out((len(off), FOCUS_STAT_N))
     ms = C.c_double()
     check(lib, lib.bmo_psf_focus_stats(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp),
                                        off.ctypes.data_as(dp), len(off), int(device), st.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_focus_stats")
@@ -507,7 +521,7 @@ def psf_geo_otf(hits, origin, e1, e2, axis, offsets, freqs, centers=None, device
     M, nf = len(off), len(fq)
     cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
+    otf, mtf, sums = _out((M, nf, 2)), _out((M, nf)), _out(M)
     ms = C.c_double()
     check(lib, lib.bmo_psf_geo_otf(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp), off.ctypes.data_as(dp),
                                    None if cen is None else cen.ctypes.data_as(dp), M, fq.ctypes.data_as(dp), nf, int(device), otf.ctypes.data_as(dp),
@@ -528,8 +542,8 @@ def psf_otf(hits, origin, e1, e2, displacements, xs, zs, freqs, device=0, hits_d
     if len(z) != n:
         raise ValueError("xs and zs must have the same length")
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
-    img = np.zeros(M * n * n) if want_intensity else None
+    otf, mtf, sums = _out((M, nf, 2)), _out((M, nf)), _out(M)
+    img = _out(M * n * n) if want_intensity else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_otf(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
                                z.ctypes.data_as(dp), n, fq.ctypes.data_as(dp), nf, int(device), otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp),
@@ -549,7 +563,7 @@ class PsfBands:
         nb, n_rows, unmatched, device = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32()
         check(lib, lib.bmo_psf_bands_info(handle, C.byref(nb), C.byref(n_rows), C.byref(unmatched), C.byref(device)), "bmo_psf_bands_info")
         self.n_rows, self.unmatched, self.device = n_rows.value, unmatched.value, device.value
-        self.ks, self.counts, self._ptrs = np.zeros(nb.value), np.zeros(nb.value, dtype=np.int64), []
+        self.ks, self.counts, self._ptrs = _out(nb.value), _out(nb.value, dtype=np.int64), []  # (filled band by band below)
         for b in range(nb.value):
             k, p, cnt = C.c_double(), C.POINTER(C.c_double)(), C.c_int64()
             check(lib, lib.bmo_psf_bands_get(handle, b, C.byref(k), C.byref(p), C.byref(cnt)), "bmo_psf_bands_get")
@@ -621,8 +635,8 @@ def psf_poly_through_focus(bands, origin, e1, e2, displacements, xs, zs, coeffs,
     dp = C.POINTER(C.c_double)
     o, a1, a2, d, x, z, c = _poly_args(bands, origin, e1, e2, displacements, xs, zs, coeffs)
     n, M, B = len(x), len(d), len(bands)
-    out = np.zeros(M * n * n)
-    per = np.zeros(B * M * n * n) if want_bands else None
+    out = _out(M * n * n)
+    per = _out(B * M * n * n) if want_bands else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_poly_through_focus(bands.handle, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M,
                                               x.ctypes.data_as(dp), z.ctypes.data_as(dp), n, c.ctypes.data_as(dp), out.ctypes.data_as(dp),
@@ -639,8 +653,8 @@ def psf_poly_otf(bands, origin, e1, e2, displacements, xs, zs, coeffs, freqs, wa
     o, a1, a2, d, x, z, c = _poly_args(bands, origin, e1, e2, displacements, xs, zs, coeffs)
     fq = _freqs(freqs)
     n, M, nf = len(x), len(d), len(fq)
-    otf, mtf, sums = np.zeros((M, nf, 2)), np.zeros((M, nf)), np.zeros(M)
-    img = np.zeros(M * n * n) if want_intensity else None
+    otf, mtf, sums = _out((M, nf, 2)), _out((M, nf)), _out(M)
+    img = _out(M * n * n) if want_intensity else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_poly_otf(bands.handle, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
                                     z.ctypes.data_as(dp), n, c.ctypes.data_as(dp), fq.ctypes.data_as(dp), nf, otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp),
@@ -674,7 +688,7 @@ def spot_ee(rows, center, radii, shape="circle", device=0, rows_device_ptr=None,
     rp, n, cols, on_dev, keep = _spot_rows(rows, rows_device_ptr, n_rows, row_cols)
     c = np.ascontiguousarray(center, dtype=np.float64).reshape(2)
     r = _radii(radii)
-    inside = np.zeros(len(r), dtype=np.int64)
+    inside = _out(len(r), dtype=np.int64)
     ms = C.c_double()
     check(lib, lib.bmo_spot_ee(rp, n, cols, on_dev, c.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), len(r), int(device), inside.ctypes.data_as(ip),
                                C.byref(ms)), "bmo_spot_ee")
@@ -690,7 +704,7 @@ def spot_ee_sweep(res_handle, detector, n_configs, centers, radii, shape="circle
     K1 = max(K, 1)
     c = _per_config(centers, K1, 2)
     r = _radii(radii)
-    inside, n_rows = np.zeros((K1, len(r)), dtype=np.int64), np.zeros(K1, dtype=np.int64)
+    inside, n_rows = _out((K1, len(r)), dtype=np.int64), _out(K1, dtype=np.int64)
     ms = C.c_double()
     check(lib, lib.bmo_spot_ee_sweep(res_handle, int(detector), K, c.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), len(r), inside.ctypes.data_as(ip),
                                      n_rows.ctypes.data_as(ip), C.byref(ms)), "bmo_spot_ee_sweep")
@@ -709,8 +723,8 @@ def psf_geo_ee(hits, origin, e1, e2, axis, offsets, radii, centers=None, shape="
     M, nr = len(off), len(r)
     cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    ee, energy, sums = np.zeros((M, nr)), np.zeros((M, nr)), np.zeros(M)
-    count = np.zeros((M, nr), dtype=np.int64) if want_count else None
+    ee, energy, sums = _out((M, nr)), _out((M, nr)), _out(M)
+    count = _out((M, nr), dtype=np.int64) if want_count else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_geo_ee(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), ax.ctypes.data_as(dp), off.ctypes.data_as(dp),
                                   None if cen is None else cen.ctypes.data_as(dp), M, _ee_shape(shape), r.ctypes.data_as(dp), nr, int(device), ee.ctypes.data_as(dp),
@@ -735,8 +749,8 @@ def psf_ee(hits, origin, e1, e2, displacements, xs, zs, radii, centers=None, sha
         raise ValueError("xs and zs must have the same length")
     cen = None if centers is None else np.ascontiguousarray(np.asarray(centers, dtype=np.float64).reshape(M, 2))
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
-    ee, energy, sums, cout = np.zeros((M, nr)), np.zeros((M, nr)), np.zeros(M), np.zeros((M, 2))
-    img = np.zeros(M * n * n) if want_intensity else None
+    ee, energy, sums, cout = _out((M, nr)), _out((M, nr)), _out(M), _out((M, 2))
+    img = _out(M * n * n) if want_intensity else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_ee(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), d.ctypes.data_as(dp), M, x.ctypes.data_as(dp),
                               z.ctypes.data_as(dp), n, None if cen is None else cen.ctypes.data_as(dp), _ee_shape(shape), r.ctypes.data_as(dp), nr, int(device),
@@ -764,8 +778,8 @@ def psf_zernike(hits, origin, e1, e2, order=4, ref=None, pupil=None, device=0, h
     q = None if pupil is None else np.ascontiguousarray(pupil, dtype=np.float64).reshape(3)
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
     J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
-    coef, info = np.zeros(J), np.zeros(ZERN_INFO_N)
-    gram = np.zeros(E) if want_gram else None
+    coef, info = _out(J), _out(ZERN_INFO_N)
+    gram = _out(E) if want_gram else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_zernike(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
                                    None if q is None else q.ctypes.data_as(dp), int(order), int(device), coef.ctypes.data_as(dp), info.ctypes.data_as(dp),
@@ -784,8 +798,8 @@ def psf_zernike_sweep(res_handle, detector, n_configs, origins, e1s, e2s, order=
     o, a1, a2 = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(K1, 3)) for v in (origins, e1s, e2s))
     r, q = _per_config(ref, K1, 2), _per_config(pupil, K1, 3)
     J, E = zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))
-    coef, info = np.zeros((K1, J)), np.zeros((K1, ZERN_INFO_N))
-    gram = np.zeros((K1, E)) if want_gram else None
+    coef, info = _out((K1, J)), _out((K1, ZERN_INFO_N))
+    gram = _out((K1, E)) if want_gram else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_zernike_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                          None if r is None else r.ctypes.data_as(dp), None if q is None else q.ctypes.data_as(dp), int(order),
@@ -814,8 +828,8 @@ def psf_opd_map(hits, origin, e1, e2, n=64, order=0, coef=None, ref=None, pupil=
         raise ValueError("psf_opd_map: coef must have the (order + 1)(order + 2) / 2 terms of `order`")
     hp, nh, on_dev, keep = _psf_rows(hits, hits_device_ptr, n_hits)
     nb = min(max(int(n), 1), OPD_MAX_N)
-    opd, weight, count, info = np.zeros((1, nb * nb)), np.zeros((1, nb * nb)), np.zeros((1, nb * nb), dtype=np.int64), np.zeros(OPD_INFO_N)
-    raw = np.zeros((1, nb * nb, 2), dtype=np.int64) if want_raw else None
+    opd, weight, count, info = _out((1, nb * nb)), _out((1, nb * nb)), _out((1, nb * nb), dtype=np.int64), _out(OPD_INFO_N)
+    raw = _out((1, nb * nb, 2), dtype=np.int64) if want_raw else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_opd_map(hp, nh, on_dev, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp), None if r is None else r.ctypes.data_as(dp),
                                    None if q is None else q.ctypes.data_as(dp), int(order), None if cf is None else cf.ctypes.data_as(dp), int(n), int(device),
@@ -836,8 +850,8 @@ def psf_opd_map_sweep(res_handle, detector, n_configs, origins, e1s, e2s, n=64, 
     r, q = _per_config(ref, K1, 2), _per_config(pupil, K1, 3)
     cf = _per_config(coef, K1, zernike_sizes(min(max(int(order), 0), ZERN_MAX_ORDER))[0])
     nb = min(max(int(n), 1), OPD_MAX_N)
-    opd, weight, count, info = np.zeros((K1, nb * nb)), np.zeros((K1, nb * nb)), np.zeros((K1, nb * nb), dtype=np.int64), np.zeros((K1, OPD_INFO_N))
-    raw = np.zeros((K1, nb * nb, 2), dtype=np.int64) if want_raw else None
+    opd, weight, count, info = _out((K1, nb * nb)), _out((K1, nb * nb)), _out((K1, nb * nb), dtype=np.int64), _out((K1, OPD_INFO_N))
+    raw = _out((K1, nb * nb, 2), dtype=np.int64) if want_raw else None
     ms = C.c_double()
     check(lib, lib.bmo_psf_opd_map_sweep(res_handle, int(detector), K, o.ctypes.data_as(dp), a1.ctypes.data_as(dp), a2.ctypes.data_as(dp),
                                          None if r is None else r.ctypes.data_as(dp), None if q is None else q.ctypes.data_as(dp), int(order),

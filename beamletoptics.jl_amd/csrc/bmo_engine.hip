@@ -56,6 +56,7 @@ struct Knobs {  // once per process (knobs())
     int64_t thin_waves;  // BMO_THIN_WAVES=<n>: a launch of fewer than n waves spreads its records over more waves (plan_launch)
     bool lpt;            // BMO_LPT=0: no tile-order feedback (tile_order_feedback)
     int reverse;         // BMO_REVERSE=<0|1|2>: StepParams::reverse (-1: the default)
+    bool pool_poison;    // BMO_POOL_POISON: every block DevBuf / HostBuf hand out is filled with POOL_POISON_WORD first (bmo_pool.inc.hpp)
 };
 struct SolveSwitches {  // at the start of every solve (run_trace): the tests change these between solves
     int fuse, fuse_gauss;     // BMO_FUSE / BMO_FUSE_GAUSS=<n>: at most n bounce levels per launch (unset: INT_MAX, what the kernels take)
@@ -74,7 +75,8 @@ Switches read_switches() {
     auto set = [](const char* name) { return getenv(name) != nullptr; };
     auto num = [](const char* name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; };
     auto small = [](const char* name, int unset) { return getenv(name) ? atoi(getenv(name)) : unset; };
-    static const Knobs process{set("BMO_DEBUG"), num("BMO_KEEP_KIDS", 1) != 0, num("BMO_THIN_WAVES", 0), num("BMO_LPT", 1) != 0, (int)num("BMO_REVERSE", -1)};
+    static const Knobs process{set("BMO_DEBUG"), num("BMO_KEEP_KIDS", 1) != 0, num("BMO_THIN_WAVES", 0), num("BMO_LPT", 1) != 0, (int)num("BMO_REVERSE", -1),
+                                set("BMO_POOL_POISON")};
     Switches s;
     s.process = process;  // (the first call's values: a solve does not pay for them again)
     s.solve = SolveSwitches{small("BMO_FUSE", INT_MAX), small("BMO_FUSE_GAUSS", INT_MAX), num("BMO_WIDE_MIN_WAVES", 4096), set("BMO_FORCE_SORT_ORDER"),

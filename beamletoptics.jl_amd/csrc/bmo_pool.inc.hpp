@@ -83,6 +83,24 @@ struct PoolHold {
     };
 };
 
+// BMO_POOL_POISON (a test hook, DESIGN.md §2 "State independence"): every block handed out, recycled or fresh, is filled over its whole
+// `bytes` with a word that cannot pass for data: a NaN as FP64 and as FP32, 2 147 016 365 as int32, and neither 0 nor -1 in any width,
+// the two markers the engine sets itself with hipMemsetAsync.  The device is synchronised before and after the fill: the mode is
+// deterministic and orders nothing that was not ordered already.
+constexpr uint32_t POOL_POISON_WORD = 0x7FF8DEADu;
+int poison_device_block(void* p, size_t bytes) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemsetD32((hipDeviceptr_t)p, (int)POOL_POISON_WORD, bytes / 4));
+    for (size_t i = bytes & ~(size_t)3; i < bytes; ++i)  // the tail's bytes continue the word (little endian)
+        HIP_TRY(hipMemsetD8((hipDeviceptr_t)((char*)p + i), (unsigned char)(POOL_POISON_WORD >> (8 * (i & 3))), 1));
+    HIP_TRY(hipDeviceSynchronize());
+    return BMO_OK;
+}
+void poison_host_block(void* p, size_t bytes) {
+    for (size_t i = 0; i < bytes / 4; ++i) static_cast<uint32_t*>(p)[i] = POOL_POISON_WORD;
+    for (size_t i = bytes & ~(size_t)3; i < bytes; ++i) static_cast<unsigned char*>(p)[i] = (unsigned char)(POOL_POISON_WORD >> (8 * (i & 3)));
+}
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -95,7 +113,7 @@ struct DevBuf {
         if (void* q = pool_take(b, device, got)) {
             p = q;
             bytes = got;
-            return BMO_OK;
+            return knobs().pool_poison ? poison_device_block(p, bytes) : BMO_OK;
         }
         hipError_t e = hipMalloc(&p, b);
         if (e != hipSuccess) {
@@ -107,7 +125,7 @@ struct DevBuf {
             return fail(BMO_ERR_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
         }
         bytes = b;
-        return BMO_OK;
+        return knobs().pool_poison ? poison_device_block(p, bytes) : BMO_OK;
     }
     void release() {
         if (p) {
@@ -150,13 +168,16 @@ struct HostBuf {
         if (b == 0) b = 16;
         {
             std::lock_guard<std::mutex> lk(g_hpool_mu);
-            if ((p = take_best_fit(g_hpool, g_hpool_bytes, b, 0, bytes))) return BMO_OK;  // (host blocks are kept as device 0)
+            p = take_best_fit(g_hpool, g_hpool_bytes, b, 0, bytes);  // (host blocks are kept as device 0)
         }
-        if (hipHostMalloc(&p, b, hipHostMallocDefault) != hipSuccess) {
-            p = nullptr;
-            return fail(BMO_ERR_OOM, "hipHostMalloc failed");
+        if (!p) {
+            if (hipHostMalloc(&p, b, hipHostMallocDefault) != hipSuccess) {
+                p = nullptr;
+                return fail(BMO_ERR_OOM, "hipHostMalloc failed");
+            }
+            bytes = b;
         }
-        bytes = b;
+        if (knobs().pool_poison) poison_host_block(p, bytes);
         return BMO_OK;
     }
     void release() {

@@ -434,7 +434,7 @@ class EngineSolution:
         """bmo_gauss_parameters: rows (w, R, psi, w0) of beamlet `node` (result order) at the distances `zs` along the beam."""
         dp = C.POINTER(C.c_double)
         z = np.ascontiguousarray(zs, dtype=np.float64)
-        out = np.zeros((len(z), 4))
+        out = abi._out((len(z), 4))
         abi.check(self.lib, self.lib.bmo_gauss_parameters(self.handle, int(node), z.ctypes.data_as(dp), len(z), out.ctypes.data_as(dp)), "bmo_gauss_parameters")
         return out
 
