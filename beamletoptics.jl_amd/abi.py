@@ -283,6 +283,11 @@ def load_engine():
     lib.bmo_result_psf_rows.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     lib.bmo_psf_geo_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp]
     lib.bmo_psf_otf.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp]
+    # include/bmo_sweep_readout.h
+    lib.bmo_psf_focus_stats_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, C.c_int32, dp, dp]
+    lib.bmo_psf_through_focus_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, dp, dp]
+    lib.bmo_psf_geo_otf_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, dp]
+    lib.bmo_psf_otf_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, dp, dp, dp, C.c_int32, dp, dp, C.c_int32, dp, C.c_int32, dp, dp, dp, dp, dp]
     lib.bmo_spot_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, dp, C.c_int32, dp, C.c_int32, C.c_int32, ip, dp]
     lib.bmo_spot_ee_sweep.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, C.c_int32, ip, ip, dp]
     lib.bmo_psf_geo_ee.argtypes = [C.c_void_p, C.c_int64, C.c_int32, dp, dp, dp, dp, dp, dp, C.c_int32, C.c_int32, dp, C.c_int32, C.c_int32, dp, dp, ip, dp, dp]
@@ -550,6 +555,98 @@ def psf_otf(hits, origin, e1, e2, displacements, xs, zs, freqs, device=0, hits_d
                                sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)), "bmo_psf_otf")
     I = np.ascontiguousarray(img.reshape(M, n, n).transpose(0, 2, 1)) if want_intensity else None
     return mtf, otf[..., 0] + 1j * otf[..., 1], sums, I, ms.value
+
+
+# The through-focus and MTF read-outs of a sweep (include/bmo_sweep_readout.h): `res_handle` a result handle, K = n_configs, poses [K, 3].
+# Block c of every output equals the single wrapper above on the rows of configuration c with configuration c's arguments, bit for bit.
+def _sweep_args(K, *arrays):
+    """[(contiguous FP64 array of shape (K,) + tail, its pointer), ...] for (array, tail) pairs; a pointer of None for an array of None."""
+    dp = C.POINTER(C.c_double)
+    out = []
+    for a, tail in arrays:
+        a = None if a is None else np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape((max(K, 1),) + tuple(tail)))
+        out.append((a, None if a is None else a.ctypes.data_as(dp)))
+    return out
+
+
+def _sweep_planes(K, v):
+    """offsets of a sweep as [K, M]: one list counts for every configuration."""
+    v = np.asarray(v, dtype=np.float64)
+    return np.ascontiguousarray(np.tile(v.reshape(1, -1), (max(K, 1), 1)) if v.ndim <= 1 else v.reshape(max(K, 1), -1))
+
+
+def psf_focus_stats_sweep(res_handle, detector, n_configs, origins, e1s, e2s, axes, offsets):
+    """bmo_psf_focus_stats_sweep: axes [K, 3], offsets [K, M] (or one list [M] for all).  Returns (stats [K, M, 12], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    off = _sweep_planes(K, offsets)
+    M = off.shape[1]
+    (o, op), (a1, e1p), (a2, e2p), (ax, axp) = _sweep_args(K, (origins, (3,)), (e1s, (3,)), (e2s, (3,)), (axes, (3,)))
+    st = _out((max(K, 1), M, FOCUS_STAT_N))
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_focus_stats_sweep(res_handle, int(detector), K, op, e1p, e2p, axp, off.ctypes.data_as(dp), M, st.ctypes.data_as(dp), C.byref(ms)),
+          "bmo_psf_focus_stats_sweep")
+    return st[:K], ms.value
+
+
+def psf_through_focus_sweep(res_handle, detector, n_configs, origins, e1s, e2s, displacements, xs, zs, want_field=False):
+    """bmo_psf_through_focus_sweep: displacements [K, M, 3], xs / zs [K, n].  Returns (I[K, M, n, n] indexed [c, m, i, j], field [K, M, n, n]
+    or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    n = np.asarray(xs).shape[-1]
+    M = np.asarray(displacements).size // (3 * K1)
+    (o, op), (a1, e1p), (a2, e2p), (d, d_p), (x, xp), (z, zp) = _sweep_args(K, (origins, (3,)), (e1s, (3,)), (e2s, (3,)), (displacements, (M, 3)), (xs, (n,)), (zs, (n,)))
+    out = _out(K1 * M * n * n)
+    fld = _out(2 * K1 * M * n * n) if want_field else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_through_focus_sweep(res_handle, int(detector), K, op, e1p, e2p, d_p, M, xp, zp, n, out.ctypes.data_as(dp),
+                                               fld.ctypes.data_as(dp) if want_field else None, C.byref(ms)), "bmo_psf_through_focus_sweep")
+    field = np.ascontiguousarray((fld[0::2] + 1j * fld[1::2]).reshape(K1, M, n, n).transpose(0, 1, 3, 2))[:K] if want_field else None
+    return np.ascontiguousarray(out.reshape(K1, M, n, n).transpose(0, 1, 3, 2))[:K], field, ms.value
+
+
+def psf_geo_otf_sweep(res_handle, detector, n_configs, origins, e1s, e2s, axes, offsets, freqs, centers=None):
+    """bmo_psf_geo_otf_sweep: axes [K, 3], offsets [K, M] (or one list for all), freqs [nf, 2] for all configurations, centers None or
+    [K, M, 2].  Returns (mtf [K, M, nf], otf [K, M, nf] complex, sums [K, M], kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    off = _sweep_planes(K, offsets)
+    fq = _freqs(freqs)
+    M, nf = off.shape[1], len(fq)
+    (o, op), (a1, e1p), (a2, e2p), (ax, axp), (cen, cenp) = _sweep_args(K, (origins, (3,)), (e1s, (3,)), (e2s, (3,)), (axes, (3,)), (centers, (M, 2)))
+    otf, mtf, sums = _out((K1, M, nf, 2)), _out((K1, M, nf)), _out((K1, M))
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_geo_otf_sweep(res_handle, int(detector), K, op, e1p, e2p, axp, off.ctypes.data_as(dp), cenp, M, fq.ctypes.data_as(dp), nf,
+                                         otf.ctypes.data_as(dp), mtf.ctypes.data_as(dp), sums.ctypes.data_as(dp), C.byref(ms)), "bmo_psf_geo_otf_sweep")
+    return mtf[:K], (otf[..., 0] + 1j * otf[..., 1])[:K], sums[:K], ms.value
+
+
+def psf_otf_sweep(res_handle, detector, n_configs, origins, e1s, e2s, displacements, xs, zs, freqs, want_intensity=False):
+    """bmo_psf_otf_sweep: the arguments of psf_through_focus_sweep and freqs [nf, 2] for all configurations.  Returns (mtf [K, M, nf],
+    otf [K, M, nf] complex, sums [K, M], I[K, M, n, n] indexed [c, m, i, j] or None, kernel_ms)."""
+    lib = load_engine()
+    dp = C.POINTER(C.c_double)
+    K = int(n_configs)
+    K1 = max(K, 1)
+    n = np.asarray(xs).shape[-1]
+    M = np.asarray(displacements).size // (3 * K1)
+    fq = _freqs(freqs)
+    nf = len(fq)
+    (o, op), (a1, e1p), (a2, e2p), (d, d_p), (x, xp), (z, zp) = _sweep_args(K, (origins, (3,)), (e1s, (3,)), (e2s, (3,)), (displacements, (M, 3)), (xs, (n,)), (zs, (n,)))
+    otf, mtf, sums = _out((K1, M, nf, 2)), _out((K1, M, nf)), _out((K1, M))
+    img = _out(K1 * M * n * n) if want_intensity else None
+    ms = C.c_double()
+    check(lib, lib.bmo_psf_otf_sweep(res_handle, int(detector), K, op, e1p, e2p, d_p, M, xp, zp, n, fq.ctypes.data_as(dp), nf, otf.ctypes.data_as(dp),
+                                     mtf.ctypes.data_as(dp), sums.ctypes.data_as(dp), img.ctypes.data_as(dp) if want_intensity else None, C.byref(ms)),
+          "bmo_psf_otf_sweep")
+    I = np.ascontiguousarray(img.reshape(K1, M, n, n).transpose(0, 1, 3, 2))[:K] if want_intensity else None
+    return mtf[:K], (otf[..., 0] + 1j * otf[..., 1])[:K], sums[:K], I, ms.value
 
 
 class PsfBands:

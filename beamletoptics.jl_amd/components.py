@@ -520,17 +520,33 @@ def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None
     over -hw .. +hw about each plane's centre.  The centre of plane m is its own centroid (follow="centroid": the grid follows the chief
     ray) or the centroid of the window plane (follow=None).
     Returns (xs, zs, displacements [M, 3], I[M, n, n], stats): the point (i, j) of plane m lies at origin + xs[i] e1 + zs[j] e2 + d_m."""
-    from . import abi
+    ax, off = focus_planes(orientation, offsets, axis, follow, "through_focus")
+    st = stats_fn(ax, off)
+    xs, zs, d = through_focus_plan(st, orientation, ax, off, n=n, follow=follow, window_plane=window_plane, crop_factor=crop_factor, half_width=half_width)
+    return xs, zs, d, stack_fn(d, xs, zs), st
 
+
+def focus_planes(orientation, offsets, axis, follow, who):
+    """(axis [3], offsets [M]) of a stack of planes as the focus statistics take them (axis None: the detector's local y), after the
+    checks the through-focus read-outs share.  The single path and the sweep path (one call per configuration) both plan through here."""
     if follow not in ("centroid", None):
-        raise ValueError('through_focus: follow must be "centroid" or None')
+        raise ValueError('%s: follow must be "centroid" or None' % who)
     o = np.asarray(orientation, dtype=np.float64)
-    e1, e2 = o[:, 0], o[:, 2]
     ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
     off = np.asarray(offsets, dtype=np.float64).reshape(-1)
     if len(off) == 0:
-        raise ValueError("through_focus: no offsets")
-    st = stats_fn(ax, off)
+        raise ValueError("%s: no offsets" % who)
+    return ax, off
+
+
+def through_focus_plan(stats, orientation, axis, offsets, n=100, follow="centroid", window_plane=None, crop_factor=1.0, half_width=None):
+    """What psf_through_focus hands its stack_fn, from the focus statistics [M, 12] of the planes (axis, offsets) of focus_planes:
+    (xs [n], zs [n], displacements [M, 3]).  ValueError for statistics without rows or without a plane that has any."""
+    from . import abi
+
+    st, ax, off = np.asarray(stats, dtype=np.float64), np.asarray(axis, dtype=np.float64), np.asarray(offsets, dtype=np.float64)
+    o = np.asarray(orientation, dtype=np.float64)
+    e1, e2 = o[:, 0], o[:, 2]
     if st[0, abi.FOCUS_N] == 0:
         raise ValueError("through_focus: the PSFDetector recorded no hit")
     if np.isnan(st[:, abi.FOCUS_RMS_R]).all():
@@ -542,7 +558,7 @@ def psf_through_focus(stats_fn, stack_fn, orientation, offsets, n=100, axis=None
     xs, zs = la.linrange(-hwx, hwx, n), la.linrange(-hwz, hwz, n)
     centre = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]] if follow == "centroid" else np.tile(st[w, [abi.FOCUS_CX, abi.FOCUS_CZ]], (len(off), 1))
     d = off[:, None] * ax[None, :] + centre[:, 0:1] * e1[None, :] + centre[:, 1:2] * e2[None, :]
-    return xs, zs, d, stack_fn(d, xs, zs), st
+    return xs, zs, d
 
 
 # The MTF read-out (include/bmo.h "MTF read-out").  Frequencies are (fx, fz) in cycles per metre in the detector's local frame.
@@ -598,6 +614,29 @@ def mtf_check_pitch(xs, zs, freqs):
                                  % (name, pitch, name, 1 / (2 * f)))
 
 
+def mtf_geo_centers(stats, follow):
+    """[M, 2]: the point of each plane the geometric MTF counts its phase from, from the planes' focus statistics [M, 12]: each plane's
+    centroid (follow="centroid"), or the centroid of the plane of least RMS radius for all (follow=None)."""
+    from . import abi
+
+    st = np.asarray(stats, dtype=np.float64)
+    centers = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]]
+    if follow is None and not np.isnan(st[:, abi.FOCUS_RMS_R]).all():
+        centers = np.tile(centers[int(np.nanargmin(st[:, abi.FOCUS_RMS_R]))], (len(st), 1))
+    return np.ascontiguousarray(centers)
+
+
+def mtf_image_grid(window, freqs, n=None, half_width=None):
+    """(half_width, n) of the image grid of the diffraction MTF at `freqs`: half_width None takes mtf_window's for window = (k_max, rho,
+    n_rows), n None the least n that the pitch rule allows for the half-width."""
+    f_max = float(np.abs(np.asarray(freqs, dtype=np.float64)).max())
+    if half_width is None:
+        half_width, n_rule = mtf_window(*window, f_max)
+    else:
+        n_rule = mtf_grid_points(half_width, f_max)
+    return half_width, (n_rule if n is None else int(n))
+
+
 def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.0,), kind="diffraction", n=None, half_width=None, axis=None,
             follow="centroid"):
     """The MTF of PSF rows on the detector plane moved by each of `offsets` along `axis` (None: local y), at `freqs` [nf, 2] in cycles per
@@ -607,8 +646,6 @@ def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.
     centroid of the plane of least RMS radius (follow=None).  kind "diffraction": the transform of the through-focus stack on the grid of
     psf_through_focus with the same `follow`; half_width None takes mtf_window's, n None the least n that mtf_window's pitch rule allows.
     Returns (mtf [M, nf], otf [M, nf] complex, sums [M], stats [M, 12])."""
-    from . import abi
-
     if kind not in ("diffraction", "geometric"):
         raise ValueError('mtf: kind must be "diffraction" or "geometric"')
     if follow not in ("centroid", None):
@@ -617,23 +654,11 @@ def psf_mtf(stats_fn, geo_fn, otf_fn, window_fn, orientation, freqs, offsets=(0.
     if len(fq) == 0 or not np.isfinite(fq).all():
         raise ValueError("mtf: needs at least one frequency, all finite")
     if kind == "geometric":
-        o = np.asarray(orientation, dtype=np.float64)
-        ax = o[:, 1] if axis is None else np.asarray(axis, dtype=np.float64).reshape(3)
-        off = np.asarray(offsets, dtype=np.float64).reshape(-1)
-        if len(off) == 0:
-            raise ValueError("mtf: no offsets")
+        ax, off = focus_planes(orientation, offsets, axis, follow, "mtf")
         st = stats_fn(ax, off)
-        centers = st[:, [abi.FOCUS_CX, abi.FOCUS_CZ]]
-        if follow is None and not np.isnan(st[:, abi.FOCUS_RMS_R]).all():
-            centers = np.tile(centers[int(np.nanargmin(st[:, abi.FOCUS_RMS_R]))], (len(off), 1))
-        mtf, otf, sums = geo_fn(ax, off, fq, np.ascontiguousarray(centers))
+        mtf, otf, sums = geo_fn(ax, off, fq, mtf_geo_centers(st, follow))
         return mtf, otf, sums, st
-    f_max = float(np.abs(fq).max())
-    if half_width is None:
-        half_width, n_rule = mtf_window(*window_fn(), f_max)
-    else:
-        n_rule = mtf_grid_points(half_width, f_max)
-    n = n_rule if n is None else int(n)
+    half_width, n = mtf_image_grid(window_fn() if half_width is None else None, fq, n=n, half_width=half_width)
     out = {}
 
     def stack_fn(d, xs, zs):

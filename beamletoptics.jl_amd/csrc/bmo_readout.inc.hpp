@@ -1140,9 +1140,10 @@ static void spot_splits(int64_t n_rows, int64_t& n_splits, int64_t& rows_per_spl
 
 // the plan of a read-out that walks rows without a grid of points (the spot image and every statistics pass): splits by spot_splits
 // (which knows no point blocks), no launch batching
-static SplitPlan rows_plan(const Ranges& R) {
-    return SplitPlan(R, 1, [](int64_t n_rows, unsigned, int64_t& n_splits, int64_t& rows_per_split) { spot_splits(n_rows, n_splits, rows_per_split); });
-}
+static void rows_splits(int64_t n_rows, unsigned, int64_t& n_splits, int64_t& rows_per_split) { spot_splits(n_rows, n_splits, rows_per_split); }
+static SplitPlan rows_plan(const Ranges& R) { return SplitPlan(R, 1, rows_splits); }
+// the same splits with the launches of a read-out that writes n_pts partial sums per work item
+static SplitPlan rows_plan(const Ranges& R, int64_t n_pts) { return SplitPlan(R, 1, n_pts, rows_splits); }
 
 // the work items of such a read-out on the grid's x dimension
 static int rows_items(const SplitPlan& plan, const char* who, unsigned& n_items) {
@@ -2456,13 +2457,14 @@ static_assert(PSF_FOCUS_MP == 8 || PSF_FOCUS_MP == 16, "PSF_FOCUS_MP: 8 or 16");
 // rows whose factors are in LDS together for chunks of mp planes: 1 024 factors, at most the tile
 constexpr int psf_focus_rows(int mp) { return 1024 / mp < PSF_TILE ? 1024 / mp : PSF_TILE; }
 
-// split blockIdx.y of the rows, planes m_first + blockIdx.z * MP .. of the n_planes displacements `disp` [n_planes][3]; the partial
-// plane of a pass that starts at plane m_pass and holds pass_planes planes: [split][m - m_pass][pt]
+// Rows h0 .. h1 - 1 on planes m_first + blockIdx.z * MP .. of the n_planes displacements `disp` [n_planes][3], summed in row order into row
+// blockIdx.y of the partial plane of a pass that starts at plane m_pass and holds pass_planes planes: [item][m - m_pass][pt].  Every lane of
+// the workgroup calls it (it syncs).
 template <int MP>
-__global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split,
-                                                                   const double* __restrict__ xs, const double* __restrict__ zs, int32_t n, d3 origin, d3 e1,
-                                                                   d3 e2, const double* __restrict__ disp, int32_t n_planes, int32_t m_first,
-                                                                   int32_t m_pass, int32_t pass_planes, double2* __restrict__ partial) {
+__device__ __forceinline__ void psf_focus_sum_chunk(const double* __restrict__ hits, int64_t h0, int64_t h1, const double* __restrict__ xs,
+                                                    const double* __restrict__ zs, int32_t n, const d3& origin, const d3& e1, const d3& e2,
+                                                    const double* __restrict__ disp, int32_t n_planes, int32_t m_first, int32_t m_pass, int32_t pass_planes,
+                                                    double2* __restrict__ partial) {
     constexpr int FR = psf_focus_rows(MP);
     static_assert(PSF_TILE % FR == 0 && (MP * FR) % 256 == 0, "whole factor sub-tiles, every lane computes as many factors");
     __shared__ double tile[PSF_TILE * 9];
@@ -2471,8 +2473,6 @@ __global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double*
     const int64_t n_pts = (int64_t)n * n;
     const int64_t pt = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool live = pt < n_pts;
-    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
-    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
     const int32_t m0 = m_first + (int32_t)blockIdx.z * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;  // planes of this chunk; the slots past them run on d = 0 and are not stored
     if ((int)threadIdx.x < MP * 3) dsp[threadIdx.x] = (int)threadIdx.x < mcnt * 3 ? disp[(int64_t)m0 * 3 + threadIdx.x] : 0.0;
@@ -2521,6 +2521,43 @@ __global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double*
     for (int m = 0; m < MP; ++m)
         if (m < mcnt) out[(int64_t)m * n_pts] = make_double2(re[m], im[m]);
 }
+
+// A launch of one configuration, which every single call is: split blockIdx.y of its n_hits rows, the pose in the kernel arguments
+template <int MP>
+__global__ __launch_bounds__(256) void psf_focus_accumulate_kernel(const double* __restrict__ hits, int64_t n_hits, int64_t hits_per_split,
+                                                                   const double* __restrict__ xs, const double* __restrict__ zs, int32_t n, d3 origin, d3 e1,
+                                                                   d3 e2, const double* __restrict__ disp, int32_t n_planes, int32_t m_first,
+                                                                   int32_t m_pass, int32_t pass_planes, double2* __restrict__ partial) {
+    const int64_t h0 = (int64_t)blockIdx.y * hits_per_split;
+    const int64_t h1 = h0 + hits_per_split < n_hits ? h0 + hits_per_split : n_hits;
+    psf_focus_sum_chunk<MP>(hits, h0, h1, xs, zs, n, origin, e1, e2, disp, n_planes, m_first, m_pass, pass_planes, partial);
+}
+
+// work item w0 + blockIdx.y, on its configuration's axes (xs, zs: [K][n]), pose and displacements (disp: [K][n_planes][3])
+template <int MP>
+__global__ __launch_bounds__(256) void psf_focus_accumulate_list_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, int64_t w0,
+                                                                        const PsfPose* __restrict__ pose, const double* __restrict__ xs,
+                                                                        const double* __restrict__ zs, int32_t n, const double* __restrict__ disp,
+                                                                        int32_t n_planes, int32_t m_first, int32_t m_pass, int32_t pass_planes,
+                                                                        double2* __restrict__ partial) {
+    const SplitWork W = work[w0 + blockIdx.y];
+    const PsfPose& C = pose[W.cfg];
+    psf_focus_sum_chunk<MP>(hits, W.h0, W.h1, xs + (int64_t)W.cfg * n, zs + (int64_t)W.cfg * n, n, C.origin, C.e1, C.e2, disp + (int64_t)W.cfg * n_planes * 3,
+                            n_planes, m_first, m_pass, pass_planes, partial);
+}
+
+// what becomes of the sum of point i = c * pass_pts + q of a pass over the planes m_pass .. of a sweep's stacks: it goes to
+// [c][m_pass + m][pt], q = m * n_pts + pt (`intensity` and `field` start at plane m_pass of configuration 0; cfg_pts = n_planes * n_pts)
+struct PsfStackFinish {
+    double* intensity;
+    double2* field;  // nullptr: not asked for
+    int64_t pass_pts, cfg_pts;
+    __device__ void operator()(int64_t i, double re, double im) const {
+        const int64_t o = i / pass_pts * cfg_pts + i % pass_pts;
+        intensity[o] = re * re + im * im;  // abs2
+        if (field) field[o] = make_double2(re, im);
+    }
+};
 
 }  // namespace
 
@@ -2620,11 +2657,10 @@ __device__ __forceinline__ void focus_local(const double* r, const FocusFrame& F
 __device__ __forceinline__ d3 focus_origin(const FocusFrame& F, double off) { return d3{F.origin.x + off * F.axis.x, F.origin.y + off * F.axis.y, F.origin.z + off * F.axis.z}; }
 __device__ __forceinline__ double focus_den(const double* r, const FocusFrame& F) { return (r[3] * F.nrm.x + r[4] * F.nrm.y) + r[5] * F.nrm.z; }
 
-// pass A of work item blockIdx.x on planes blockIdx.y * FOCUS_STAT_MP ..
-__global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
-                                                             const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
+// pass A of work item W on planes blockIdx.y * FOCUS_STAT_MP .. of the frame F: the record of plane m goes to out[m * stride + index]
+__device__ __forceinline__ void focus_sums_item(const double* __restrict__ hits, const SplitWork& W, const FocusFrame& F, const double* __restrict__ offsets,
+                                                int32_t n_planes, FocusSumA* __restrict__ out, int64_t stride, int64_t index) {
     constexpr int MP = FOCUS_STAT_MP;
-    const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
     d3 o[MP];
@@ -2654,8 +2690,24 @@ __global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __res
     for (int m = 0; m < MP; ++m) {
         a[m].s = a[0].s, a[m].bad = a[0].bad;
         const FocusSumA v = sum_wg_reduce(a[m]);
-        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = v;
+        if (threadIdx.x == 0 && m < mcnt) out[(int64_t)(m0 + m) * stride + index] = v;
     }
+}
+// a call of one configuration: work item blockIdx.x, the frame in the kernel arguments, the records [plane][item]
+__global__ __launch_bounds__(256) void psf_focus_sums_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                             const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
+    const SplitWork W = work[blockIdx.x];
+    focus_sums_item(hits, W, F, offsets, n_planes, partial, gridDim.x, blockIdx.x);
+}
+// Work item blockIdx.x of a sweep at its configuration's frame (frames [K]) and offsets ([K][n_planes]); the frame's address is uniform over
+// the workgroup (scalar loads).  The records are [configuration][plane][split]: those of (c, m) start at n_planes * first_work + m * n_splits.
+__global__ __launch_bounds__(256) void psf_focus_sums_list_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work,
+                                                                  const SplitCfg* __restrict__ cfg, const FocusFrame* __restrict__ frames,
+                                                                  const double* __restrict__ offsets, int32_t n_planes, FocusSumA* __restrict__ partial) {
+    const SplitWork W = work[blockIdx.x];
+    const SplitCfg C = cfg[W.cfg];
+    focus_sums_item(hits, W, frames[W.cfg], offsets + (int64_t)W.cfg * n_planes, n_planes, partial + (int64_t)n_planes * C.first_work, C.n_splits,
+                    (int64_t)blockIdx.x - C.first_work);
 }
 
 // the sums, the centroid and the extrema go to stats[m], the centroid to mid[m]
@@ -2683,13 +2735,22 @@ struct FocusSumsFinish {
         mid[m] = make_double2(cx, cz);
     }
 };
+// the same for range r = c * n_planes + m of a sweep: stats [K][n_planes][..], mid [K][n_planes], count [K] the rows of every configuration
+struct FocusSumsListFinish {
+    const int64_t* count;
+    int32_t n_planes;
+    double* stats;
+    double2* mid;
+    __device__ void empty(int32_t) const {}  // a configuration without rows: the host fills its statistics as the single call does
+    __device__ void operator()(int32_t r, const FocusSumA& a) const { FocusSumsFinish{count[r / n_planes], stats, mid}(r, a); }
+};
 
-// pass C of work item blockIdx.x on planes blockIdx.y * FOCUS_STAT_MP ..
-__global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
-                                                               const double* __restrict__ offsets, int32_t n_planes, const double2* __restrict__ mid,
-                                                               FocusSumC* __restrict__ partial) {
+// pass C of work item W on planes blockIdx.y * FOCUS_STAT_MP .. of the frame F, about the centroids mid[m]: the record of plane m goes to
+// out[m * stride + index]
+__device__ __forceinline__ void focus_spread_item(const double* __restrict__ hits, const SplitWork& W, const FocusFrame& F, const double* __restrict__ offsets,
+                                                  int32_t n_planes, const double2* __restrict__ mid, FocusSumC* __restrict__ out, int64_t stride,
+                                                  int64_t index) {
     constexpr int MP = FOCUS_STAT_MP;
-    const SplitWork W = work[blockIdx.x];
     const int32_t m0 = (int32_t)blockIdx.y * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;
     d3 o[MP];
@@ -2720,8 +2781,24 @@ __global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __r
 #pragma unroll
     for (int m = 0; m < MP; ++m) {
         const FocusSumC s = sum_wg_reduce(v[m]);
-        if (threadIdx.x == 0 && m < mcnt) partial[(int64_t)(m0 + m) * gridDim.x + blockIdx.x] = s;
+        if (threadIdx.x == 0 && m < mcnt) out[(int64_t)(m0 + m) * stride + index] = s;
     }
+}
+__global__ __launch_bounds__(256) void psf_focus_spread_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                               const double* __restrict__ offsets, int32_t n_planes, const double2* __restrict__ mid,
+                                                               FocusSumC* __restrict__ partial) {
+    const SplitWork W = work[blockIdx.x];
+    focus_spread_item(hits, W, F, offsets, n_planes, mid, partial, gridDim.x, blockIdx.x);
+}
+// the list form, laid out as psf_focus_sums_list_kernel's records; mid [K][n_planes]
+__global__ __launch_bounds__(256) void psf_focus_spread_list_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work,
+                                                                    const SplitCfg* __restrict__ cfg, const FocusFrame* __restrict__ frames,
+                                                                    const double* __restrict__ offsets, int32_t n_planes, const double2* __restrict__ mid,
+                                                                    FocusSumC* __restrict__ partial) {
+    const SplitWork W = work[blockIdx.x];
+    const SplitCfg C = cfg[W.cfg];
+    focus_spread_item(hits, W, frames[W.cfg], offsets + (int64_t)W.cfg * n_planes, n_planes, mid + (int64_t)W.cfg * n_planes,
+                      partial + (int64_t)n_planes * C.first_work, C.n_splits, (int64_t)blockIdx.x - C.first_work);
 }
 
 struct FocusSpreadFinish {
@@ -2743,13 +2820,19 @@ struct FocusSpreadFinish {
 
 }  // namespace
 
+// the frame of the planes of a detector pose moved along `axis`: nrm = e1 x e2
+static FocusFrame focus_frame(const double* origin, const double* e1, const double* e2, const double* axis) {
+    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
+    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    return F;
+}
+
 // The statistics [n_planes][BMO_FOCUS_STAT_N] of the n_hits > 0 device rows `hits` [..][9] on the planes at offsets[m] * axis.
 static int psf_focus_stats_read(const double* hits, int64_t n_hits, const double* origin, const double* e1, const double* e2, const double* axis, const double* offsets,
                                 int32_t n_planes, double* stats, double* kernel_ms, const char* who) {
     RowPasses P(Ranges{{0}, {n_hits}});
     if (int rc = P.items(who)) return rc;
-    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
-    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    const FocusFrame F = focus_frame(origin, e1, e2, axis);
     const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
     if (chunks > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
     // the partial sums are [plane][item]: to the reduces a plane is a range of n_items records like a configuration's
@@ -2804,17 +2887,17 @@ constexpr int GEO_OTF_MP = 8;  // planes per chunk of a stack; a stack of fewer 
 #define GEO_OTF_SUM(F) F(s, SumAdd) F(bad, SumAdd)
 SUM_RECORD(GeoOtfSum, GEO_OTF_SUM);
 
-// split blockIdx.y (work item) of the rows, planes blockIdx.z * MP .., frequencies blockIdx.x * (256 / MP) ..; partial: [item][plane][freq]
+// Work item W of the rows on planes blockIdx.z * MP .. of the frame F, frequencies blockIdx.x * (256 / MP) ..: the item's sums go to row
+// blockIdx.y of `partial` [item][plane][freq], its record (from the workgroups of the first frequency block and chunk) to sums[item].
+// Every lane calls it (it syncs).
 template <int MP>
-__global__ __launch_bounds__(256) void psf_geo_otf_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
-                                                          const double* __restrict__ offsets, const double2* __restrict__ centers, int32_t n_planes,
-                                                          const double2* __restrict__ freqs, int32_t n_freqs, double2* __restrict__ partial,
-                                                          GeoOtfSum* __restrict__ sums) {
+__device__ __forceinline__ void geo_otf_item(const double* __restrict__ hits, const SplitWork& W, const FocusFrame& F, const double* __restrict__ offsets,
+                                             const double2* __restrict__ centers, int32_t n_planes, const double2* __restrict__ freqs, int32_t n_freqs,
+                                             double2* __restrict__ partial, GeoOtfSum* __restrict__ sums, int64_t item) {
     constexpr int FB = 256 / MP;
     static_assert(MP >= 1 && MP <= 8 && 256 % MP == 0, "a chunk of planes divides the workgroup");
     __shared__ double tile[PSF_TILE * 9];
     __shared__ double2 xz[MP * PSF_TILE];
-    const SplitWork W = work[blockIdx.y];
     const int32_t m0 = (int32_t)blockIdx.z * MP;
     const int mcnt = n_planes - m0 < MP ? n_planes - m0 : MP;  // planes of this chunk; the slots past them repeat its first and are not stored
     d3 o[MP];
@@ -2862,8 +2945,28 @@ __global__ __launch_bounds__(256) void psf_geo_otf_kernel(const double* __restri
     if (live) partial[((int64_t)blockIdx.y * n_planes + (m0 + ml)) * n_freqs + f] = make_double2(re, im);
     if (blockIdx.x == 0 && blockIdx.z == 0) {  // uniform over the workgroup: one record per work item
         a = sum_wg_reduce(a);
-        if (threadIdx.x == 0) sums[blockIdx.y] = a;
+        if (threadIdx.x == 0) sums[item] = a;
     }
+}
+// split blockIdx.y (work item) of the rows of one configuration, the frame in the kernel arguments; partial: [item][plane][freq]
+template <int MP>
+__global__ __launch_bounds__(256) void psf_geo_otf_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, FocusFrame F,
+                                                          const double* __restrict__ offsets, const double2* __restrict__ centers, int32_t n_planes,
+                                                          const double2* __restrict__ freqs, int32_t n_freqs, double2* __restrict__ partial,
+                                                          GeoOtfSum* __restrict__ sums) {
+    const SplitWork W = work[blockIdx.y];
+    geo_otf_item<MP>(hits, W, F, offsets, centers, n_planes, freqs, n_freqs, partial, sums, blockIdx.y);
+}
+// Work item w0 + blockIdx.y of a sweep at its configuration's frame (frames [K]), offsets ([K][n_planes]) and centres (nullptr or
+// [K][n_planes]); all configurations share the frequencies.  partial: [item - w0][plane][freq]; sums: one record per item of the sweep.
+template <int MP>
+__global__ __launch_bounds__(256) void psf_geo_otf_list_kernel(const double* __restrict__ hits, const SplitWork* __restrict__ work, int64_t w0,
+                                                               const FocusFrame* __restrict__ frames, const double* __restrict__ offsets,
+                                                               const double2* __restrict__ centers, int32_t n_planes, const double2* __restrict__ freqs,
+                                                               int32_t n_freqs, double2* __restrict__ partial, GeoOtfSum* __restrict__ sums) {
+    const SplitWork W = work[w0 + blockIdx.y];
+    geo_otf_item<MP>(hits, W, frames[W.cfg], offsets + (int64_t)W.cfg * n_planes, centers ? centers + (int64_t)W.cfg * n_planes : nullptr, n_planes, freqs,
+                     n_freqs, partial, sums, w0 + blockIdx.y);
 }
 
 // S of the call, NaN when a row runs parallel to the planes
@@ -2872,9 +2975,23 @@ struct GeoOtfSumFinish {
     __device__ void empty(int32_t) const {}  // a call with rows has work items
     __device__ void operator()(int32_t, const GeoOtfSum& a) const { *s = a.bad != 0.0 ? knan() : a.s; }
 };
+// S of every configuration of a sweep: s [K]; 0 for a configuration without rows
+struct GeoOtfSumListFinish {
+    double* s;
+    __device__ void empty(int32_t c) const { s[c] = 0.0; }
+    __device__ void operator()(int32_t c, const GeoOtfSum& a) const { GeoOtfSumFinish{s + c}(c, a); }
+};
 
-// pair (plane, frequency) = blockIdx.x * 256 + threadIdx.x: its partial sums folded in split order; otf, mtf and, from the pairs of
-// frequency 0, sums
+// what becomes of the folded sum (re, im) of pair q = plane * n_freqs + frequency of a call whose rows sum to S: otf, mtf and, from the
+// pairs of frequency 0, sums
+__device__ __forceinline__ void geo_otf_finish(int64_t q, double re, double im, double S, int32_t n_freqs, double2* __restrict__ otf, double* __restrict__ mtf,
+                                               double* __restrict__ sums) {
+    if (S != S) re = im = knan();  // a row parallel to the planes (or a NaN proj): no transfer function
+    otf[q] = make_double2(re, im);
+    mtf[q] = sqrt(re * re + im * im) / S;
+    if (q % n_freqs == 0) sums[q / n_freqs] = S;
+}
+// pair (plane, frequency) = blockIdx.x * 256 + threadIdx.x: its partial sums folded in split order
 __global__ void psf_geo_otf_reduce_kernel(const double2* __restrict__ partial, int32_t n_splits, int64_t n_pairs, int32_t n_freqs, const double* __restrict__ s_all,
                                           double2* __restrict__ otf, double* __restrict__ mtf, double* __restrict__ sums) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2885,22 +3002,38 @@ __global__ void psf_geo_otf_reduce_kernel(const double2* __restrict__ partial, i
         re += v.x;
         im += v.y;
     }
-    const double S = *s_all;
-    if (S != S) re = im = knan();  // a row parallel to the planes (or a NaN proj): no transfer function
-    otf[q] = make_double2(re, im);
-    mtf[q] = sqrt(re * re + im * im) / S;
-    if (q % n_freqs == 0) sums[q / n_freqs] = S;
+    geo_otf_finish(q, re, im, *s_all, n_freqs, otf, mtf, sums);
+}
+// the same pair of configuration c0 + blockIdx.y of a sweep: its own splits (partial rows first_work - w0 ...) folded in split order;
+// otf, mtf [K][n_pairs], sums [K][n_planes], s_all [K]
+__global__ void psf_geo_otf_reduce_list_kernel(const SplitCfg* __restrict__ cfg, int32_t c0, int64_t w0, const double2* __restrict__ partial, int64_t n_pairs,
+                                               int32_t n_freqs, const double* __restrict__ s_all, double2* __restrict__ otf, double* __restrict__ mtf,
+                                               double* __restrict__ sums) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pairs) return;
+    const int32_t c = c0 + (int32_t)blockIdx.y;
+    const SplitCfg C = cfg[c];
+    double re = 0.0, im = 0.0;
+    for (int32_t s = 0; s < C.n_splits; ++s) {
+        const double2 v = partial[(C.first_work - w0 + s) * n_pairs + q];
+        re += v.x;
+        im += v.y;
+    }
+    geo_otf_finish(q, re, im, s_all[c], n_freqs, otf + (int64_t)c * n_pairs, mtf + (int64_t)c * n_pairs, sums + (int64_t)c * (n_pairs / n_freqs));
 }
 
 // Diffraction: the transform of the stack's images where they lie, separable.  Thread (plane m, slot f, row j) sums image row j against the
 // x factors of frequency f; slot n_freqs has the factor (1, 0), whose transform is the plane's sum.
-__global__ void psf_otf_rows_kernel(const double* __restrict__ img, const double* __restrict__ xs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
-                                    int64_t n_threads, double2* __restrict__ rowsum) {
+// planes_per_axes > 0: that many consecutive images share the axis at xs + (m / planes_per_axes) * n (the stack of one configuration of a
+// sweep); 0: every image is on xs
+__device__ __forceinline__ void otf_rows_thread(const double* __restrict__ img, const double* __restrict__ xs, int32_t planes_per_axes, int32_t n,
+                                                const double2* __restrict__ freqs, int32_t n_freqs, int64_t n_threads, double2* __restrict__ rowsum) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_threads) return;  // n_planes * (n_freqs + 1) * n
     const int32_t j = (int32_t)(t % n), f = (int32_t)(t / n % (n_freqs + 1));
     const int64_t m = t / n / (n_freqs + 1);
     const double* row = img + (m * n + j) * n;
+    if (planes_per_axes > 0) xs += m / planes_per_axes * n;
     double re = 0.0, im = 0.0;
     if (f == n_freqs) {
         for (int32_t i = 0; i < n; ++i) {
@@ -2918,14 +3051,26 @@ __global__ void psf_otf_rows_kernel(const double* __restrict__ img, const double
     }
     rowsum[t] = make_double2(re, im);  // [m][f][j]
 }
+__global__ void psf_otf_rows_kernel(const double* __restrict__ img, const double* __restrict__ xs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
+                                    int64_t n_threads, double2* __restrict__ rowsum) {
+    otf_rows_thread(img, xs, 0, n, freqs, n_freqs, n_threads, rowsum);
+}
+// the K * n_planes images of a sweep's stacks, each against its configuration's axis (xs: [K][n])
+__global__ void psf_otf_rows_list_kernel(const double* __restrict__ img, const double* __restrict__ xs, int32_t n_planes, int32_t n,
+                                         const double2* __restrict__ freqs, int32_t n_freqs, int64_t n_threads, double2* __restrict__ rowsum) {
+    otf_rows_thread(img, xs, n_planes, n, freqs, n_freqs, n_threads, rowsum);
+}
 
 // thread (plane m, frequency f): the row sums against the z factors, j ascending; the plane's sum the same way from slot n_freqs
-__global__ void psf_otf_cols_kernel(const double2* __restrict__ rowsum, const double* __restrict__ zs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
-                                    int64_t n_pairs, double2* __restrict__ otf, double* __restrict__ mtf, double* __restrict__ sums) {
+// (planes_per_axes: as in otf_rows_thread, for zs)
+__device__ __forceinline__ void otf_cols_thread(const double2* __restrict__ rowsum, const double* __restrict__ zs, int32_t planes_per_axes, int32_t n,
+                                                const double2* __restrict__ freqs, int32_t n_freqs, int64_t n_pairs, double2* __restrict__ otf,
+                                                double* __restrict__ mtf, double* __restrict__ sums) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_pairs) return;
     const int64_t m = q / n_freqs;
     const int32_t f = (int32_t)(q % n_freqs);
+    if (planes_per_axes > 0) zs += m / planes_per_axes * n;
     const double2* r = rowsum + (m * (n_freqs + 1) + f) * n;
     const double2* r1 = rowsum + (m * (n_freqs + 1) + n_freqs) * n;
     const double fz = freqs[f].y;
@@ -2940,6 +3085,15 @@ __global__ void psf_otf_cols_kernel(const double2* __restrict__ rowsum, const do
     otf[q] = make_double2(re, im);
     mtf[q] = sqrt(re * re + im * im) / S;
     if (f == 0) sums[m] = S;
+}
+__global__ void psf_otf_cols_kernel(const double2* __restrict__ rowsum, const double* __restrict__ zs, int32_t n, const double2* __restrict__ freqs, int32_t n_freqs,
+                                    int64_t n_pairs, double2* __restrict__ otf, double* __restrict__ mtf, double* __restrict__ sums) {
+    otf_cols_thread(rowsum, zs, 0, n, freqs, n_freqs, n_pairs, otf, mtf, sums);
+}
+__global__ void psf_otf_cols_list_kernel(const double2* __restrict__ rowsum, const double* __restrict__ zs, int32_t n_planes, int32_t n,
+                                         const double2* __restrict__ freqs, int32_t n_freqs, int64_t n_pairs, double2* __restrict__ otf, double* __restrict__ mtf,
+                                         double* __restrict__ sums) {
+    otf_cols_thread(rowsum, zs, n_planes, n, freqs, n_freqs, n_pairs, otf, mtf, sums);
 }
 
 }  // namespace
@@ -2963,8 +3117,7 @@ static int psf_geo_otf_read(const double* hits, int64_t n_hits, const double* or
                             const char* who) {
     RowPasses P(Ranges{{0}, {n_hits}});  // the plan, the upload and the reduce of the statistics passes: S is one
     if (int rc = P.items(who)) return rc;
-    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
-    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    const FocusFrame F = focus_frame(origin, e1, e2, axis);
     int mp = 1;
     while (mp < GEO_OTF_MP && mp < n_planes) mp *= 2;
     const unsigned chunks = (unsigned)((n_planes + mp - 1) / mp), f_blocks = (unsigned)(((int64_t)n_freqs + 256 / mp - 1) / (256 / mp));
@@ -3065,6 +3218,274 @@ extern "C" int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, cons
     *count = res->det_count[detector];
     *data = res->det_data.p ? (const double*)res->det_data.p + 9 * res->det_offset[detector] : nullptr;
     if (device) *device = res->device;
+    return BMO_OK;
+}
+
+// ====================================================================================================================
+// Through-focus and MTF read-out of sweeps (include/bmo_sweep_readout.h): the four read-outs above for every configuration of a sweep, from
+// the rows resident in the result, in list-form launches that run all configurations' work items in one grid.  Configuration c is split
+// as a single call with its row count splits it (SplitPlan, rows_plan), its rows are summed in row order and its splits folded in split
+// order by the code the single kernels run (psf_focus_sum_chunk, focus_sums_item, focus_spread_item, geo_otf_item, otf_rows_thread,
+// otf_cols_thread), and a plane's value does not depend on the chunk that ran it: block c equals the single call on configuration c's rows
+// bit for bit.  A configuration without rows has no work item; what it reads is filled on the host as the single call fills it.
+
+// What the four entries end their checks on: the ranges of the slot's rows over the configurations (H = 0: every count is 0, no device is
+// touched) and the rows themselves.
+static int sweep_focus_rows(const char* who, bmo_trace_result* res, int32_t detector, int32_t n_configs, Ranges& R, const double*& hits, int64_t& H) {
+    H = res->det_count[detector];
+    hits = nullptr;
+    if (H > 0) return resident_rows(who, res, detector, H, n_configs, R, hits);
+    R.begin.assign((size_t)n_configs, 0);
+    R.count.assign((size_t)n_configs, 0);
+    return BMO_OK;
+}
+
+// frames [K] from poses and axes [K][3]
+static std::vector<FocusFrame> focus_frames(size_t K, const double* origins, const double* e1s, const double* e2s, const double* axes) {
+    std::vector<FocusFrame> F(K);
+    for (size_t c = 0; c < K; ++c) F[c] = focus_frame(origins + 3 * c, e1s + 3 * c, e2s + 3 * c, axes + 3 * c);
+    return F;
+}
+
+extern "C" int bmo_psf_focus_stats_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                         const double* axes, const double* offsets, int32_t n_planes, double* stats, double* kernel_ms) {
+    const char* who = "bmo_psf_focus_stats_sweep";
+    if (!res || !origins || !e1s || !e2s || !axes || !offsets || !stats || n_planes <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_focus_stats_sweep: bad argument (null pointer, n_planes <= 0)");
+    if (int rc = slot_check(who, res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
+    const unsigned chunks = (unsigned)((n_planes + FOCUS_STAT_MP - 1) / FOCUS_STAT_MP);
+    if (chunks > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
+    if (kernel_ms) *kernel_ms = 0.0;
+    Ranges R;
+    const double* hits;
+    int64_t H;
+    if (int rc = sweep_focus_rows(who, res, detector, n_configs, R, hits, H)) return rc;
+    const size_t K = (size_t)n_configs, M = (size_t)n_planes;
+    if (H > 0) {
+        RowPasses P(R);
+        if (int rc = P.items(who)) return rc;
+        // the records are [configuration][plane][split]: to the reduces a (configuration, plane) pair is a range of the configuration's splits
+        P.ranges.resize(K * M);
+        for (size_t c = 0; c < K; ++c)
+            for (size_t m = 0; m < M; ++m) {
+                const SplitCfg& C = P.plan.cfg[c];
+                P.ranges[c * M + m] = SplitCfg{(int64_t)M * C.first_work + (int64_t)m * C.n_splits, C.n_splits, 0};
+            }
+        const size_t o_cfg = P.up.add(P.plan.cfg), o_frames = P.up.add(focus_frames(K, origins, e1s, e2s, axes)), o_off = P.up.add(offsets, K * M),
+                     o_count = P.up.add(R.count);
+        DevBuf d_stats, d_mid;
+        int rc;
+        if ((rc = d_stats.alloc(K * M * BMO_FOCUS_STAT_N * 8)) || (rc = d_mid.alloc(K * M * sizeof(double2))) || (rc = P.begin<FocusSumA, FocusSumC>())) return rc;
+        P.grid.y = chunks;  // a workgroup per work item and chunk of planes
+        const SplitCfg* d_cfg = P.up.at<SplitCfg>(o_cfg);
+        const FocusFrame* d_frames = P.up.at<FocusFrame>(o_frames);
+        const double* d_off = P.up.at<double>(o_off);
+        double* const g_stats = (double*)d_stats.p;
+        double2* const g_mid = (double2*)d_mid.p;
+        P.pass<FocusSumA>(psf_focus_sums_list_kernel, FocusSumsListFinish{P.up.at<int64_t>(o_count), n_planes, g_stats, g_mid}, hits, P.work(), d_cfg, d_frames, d_off,
+                          n_planes);
+        P.pass<FocusSumC>(psf_focus_spread_list_kernel, FocusSpreadFinish{g_stats}, hits, P.work(), d_cfg, d_frames, d_off, n_planes, (const double2*)g_mid);
+        if ((rc = P.end(kernel_ms))) return rc;
+        HIP_TRY(hipMemcpy(stats, g_stats, K * M * BMO_FOCUS_STAT_N * 8, hipMemcpyDeviceToHost));
+    }
+    for (size_t c = 0; c < K; ++c)
+        if (R.count[c] == 0) fill_empty_stats(stats + c * M * BMO_FOCUS_STAT_N, M, BMO_FOCUS_STAT_N);
+    return BMO_OK;
+}
+
+// The stacks of the K = R.count.size() configurations from the device rows `hits` (some configuration has rows), left on the device: d_int
+// [K][n_planes][n * n], and d_field likewise when want_field; a configuration without rows reads zeros.  poses [K][3], disp
+// [K][n_planes][3], axes [K][n].  `timer` runs from the first launch; the caller may queue more behind the stacks on stream 0 and stop it again.
+static int psf_focus_stack_sweep(const double* hits, const Ranges& R, const double* origins, const double* e1s, const double* e2s, const double* disp, int32_t n_planes,
+                                 const double* xs, const double* zs, int32_t n, bool want_field, DevBuf& d_int, DevBuf& d_field, EventTimer& timer, double* kernel_ms) {
+    const size_t K = R.count.size();
+    const int64_t n_pts = (int64_t)n * n;
+    const unsigned pt_blocks = (unsigned)((n_pts + 255) / 256);
+    const size_t n_out = K * (size_t)n_planes * (size_t)n_pts;
+    hipStream_t st = 0;
+    // planes per pass: whole chunks, partial sums of at most 1 GiB for the configuration of most splits (one chunk if a single one needs
+    // more); the launches: SplitPlan's rule on the pass_planes * n_pts partial sums an item writes
+    int64_t most = 1;
+    for (int64_t n_hits : R.count) {
+        int64_t n_splits, hits_per_split;
+        psf_splits(n_hits, pt_blocks, n_splits, hits_per_split);
+        most = std::max(most, n_splits);
+    }
+    const int64_t fit = ((int64_t)1 << 30) / (most * n_pts * (int64_t)sizeof(double2)) / PSF_FOCUS_MP * PSF_FOCUS_MP;
+    const int32_t per_pass = (int32_t)std::min<int64_t>({std::max<int64_t>(fit, PSF_FOCUS_MP), (int64_t)65535 * PSF_FOCUS_MP, (int64_t)n_planes});
+    const SplitPlan plan(R, pt_blocks, (int64_t)per_pass * n_pts, psf_splits);  // bmo_psf_intensity's splits of every configuration's rows on this grid
+    Packed up;
+    const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_pose = up.add(psf_poses(K, origins, e1s, e2s)), o_xs = up.add(xs, K * (size_t)n),
+                 o_zs = up.add(zs, K * (size_t)n), o_d = up.add(disp, K * (size_t)n_planes * 3);
+    int rc;
+    if ((rc = up.upload(st)) || (rc = d_int.alloc(n_out * sizeof(double))) || (want_field && (rc = d_field.alloc(n_out * sizeof(double2))))) return rc;
+    for (int32_t m_pass = 0; m_pass < n_planes; m_pass += per_pass) {
+        const int32_t pass_planes = std::min(per_pass, n_planes - m_pass);
+        auto accumulate = [&](dim3, const SplitPlan::Launch& L, double2* partial) {
+            auto launch = [&](auto mp, int32_t m_first, int32_t chunks) {
+                hipLaunchKernelGGL(psf_focus_accumulate_list_kernel<decltype(mp)::value>, dim3(pt_blocks, (unsigned)L.nw, (unsigned)chunks), dim3(256), 0, st, hits,
+                                   up.at<SplitWork>(o_work), L.w0, up.at<PsfPose>(o_pose), up.at<double>(o_xs), up.at<double>(o_zs), n, up.at<double>(o_d), n_planes,
+                                   m_first, m_pass, pass_planes, partial);
+            };
+            const int32_t full = pass_planes / PSF_FOCUS_MP, rest = pass_planes % PSF_FOCUS_MP, m_rest = m_pass + full * PSF_FOCUS_MP;
+            if (full > 0) launch(std::integral_constant<int, PSF_FOCUS_MP>{}, m_pass, full);
+            if (rest > 8) launch(std::integral_constant<int, 16>{}, m_rest, 1);  // the slots past the last plane run idle
+            else if (rest > 4) launch(std::integral_constant<int, 8>{}, m_rest, 1);
+            else if (rest > 2) launch(std::integral_constant<int, 4>{}, m_rest, 1);
+            else if (rest > 1) launch(std::integral_constant<int, 2>{}, m_rest, 1);
+            else if (rest > 0) launch(std::integral_constant<int, 1>{}, m_rest, 1);
+        };
+        const int64_t pass_pts = (int64_t)pass_planes * n_pts;
+        const PsfStackFinish finish{(double*)d_int.p + (int64_t)m_pass * n_pts, want_field ? (double2*)d_field.p + (int64_t)m_pass * n_pts : nullptr, pass_pts,
+                                    (int64_t)n_planes * n_pts};
+        if ((rc = split_reduce(plan, up.at<SplitCfg>(o_cfg), pass_pts, st, timer, kernel_ms, accumulate, finish))) return rc;
+    }
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_through_focus_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                           const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, double* out_intensity,
+                                           double* out_field, double* kernel_ms) {
+    const char* who = "bmo_psf_through_focus_sweep";
+    if (!res || !origins || !e1s || !e2s || !displacements || !xs || !zs || !out_intensity || n <= 0 || n_planes <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_through_focus_sweep: bad argument (null pointer, n <= 0, n_planes <= 0)");
+    if (int rc = slot_check(who, res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
+    if (kernel_ms) *kernel_ms = 0.0;
+    Ranges R;
+    const double* hits;
+    int64_t H;
+    if (int rc = sweep_focus_rows(who, res, detector, n_configs, R, hits, H)) return rc;
+    const size_t n_out = (size_t)n_configs * (size_t)n_planes * (size_t)n * (size_t)n;
+    if (H == 0) {  // every configuration reads like a call with n_hits = 0
+        std::fill(out_intensity, out_intensity + n_out, 0.0);
+        if (out_field) std::fill(out_field, out_field + 2 * n_out, 0.0);
+        return BMO_OK;
+    }
+    DevBuf d_int, d_field;
+    EventTimer timer;
+    if (int rc = psf_focus_stack_sweep(hits, R, origins, e1s, e2s, displacements, n_planes, xs, zs, n, out_field != nullptr, d_int, d_field, timer, kernel_ms)) return rc;
+    HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    if (out_field) HIP_TRY(hipMemcpy(out_field, d_field.p, n_out * sizeof(double2), hipMemcpyDeviceToHost));
+    return BMO_OK;
+}
+
+// block c of the transfer functions of a sweep as a configuration without rows reads it
+static void otf_fill_empty_configs(const Ranges& R, size_t n_planes, size_t n_freqs, double* otf, double* mtf, double* sums) {
+    const size_t n_pairs = n_planes * n_freqs;
+    for (size_t c = 0; c < R.count.size(); ++c)
+        if (R.count[c] == 0) otf_fill_empty(n_pairs, n_planes, otf + 2 * c * n_pairs, mtf + c * n_pairs, sums + c * n_planes);
+}
+
+extern "C" int bmo_psf_geo_otf_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                     const double* axes, const double* offsets, const double* centers, int32_t n_planes, const double* freqs, int32_t n_freqs,
+                                     double* otf, double* mtf, double* sums, double* kernel_ms) {
+    const char* who = "bmo_psf_geo_otf_sweep";
+    if (!res || !origins || !e1s || !e2s || !axes || !offsets || !freqs || !otf || !mtf || !sums || n_planes <= 0 || n_freqs <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_geo_otf_sweep: bad argument (null pointer, n_planes <= 0, n_freqs <= 0)");
+    if (!otf_freqs_ok(freqs, n_freqs)) return fail(BMO_ERR_INVALID, "bmo_psf_geo_otf_sweep: a frequency is not finite");
+    if (int rc = slot_check(who, res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
+    int mp = 1;
+    while (mp < GEO_OTF_MP && mp < n_planes) mp *= 2;
+    const unsigned chunks = (unsigned)((n_planes + mp - 1) / mp), f_blocks = (unsigned)(((int64_t)n_freqs + 256 / mp - 1) / (256 / mp));
+    if (chunks > 65535) return fail(BMO_ERR_LIMIT, std::string(who) + ": more planes than one launch holds");
+    if (kernel_ms) *kernel_ms = 0.0;
+    Ranges R;
+    const double* hits;
+    int64_t H;
+    if (int rc = sweep_focus_rows(who, res, detector, n_configs, R, hits, H)) return rc;
+    const size_t K = (size_t)n_configs;
+    const int64_t n_pairs = (int64_t)n_planes * n_freqs;
+    if (H > 0) {
+        // the splits of the statistics passes (S is one of their sums), in launches of consecutive configurations by SplitPlan's rule
+        const SplitPlan plan = rows_plan(R, n_pairs);
+        unsigned n_items = 0;
+        if (int rc = rows_items(plan, who, n_items)) return rc;
+        // a pair's value does not depend on the pairs asked for along with it: a caller with more of them splits the call
+        if (plan.max_nw * n_pairs > ((int64_t)1 << 32) / (int64_t)sizeof(double2))
+            return fail(BMO_ERR_LIMIT, std::string(who) + ": the partial sums of n_planes * n_freqs pairs pass 4 GiB; ask for them in several calls");
+        hipStream_t st = 0;
+        Packed up;
+        const size_t o_cfg = up.add(plan.cfg), o_work = up.add(plan.work), o_frames = up.add(focus_frames(K, origins, e1s, e2s, axes)),
+                     o_off = up.add(offsets, K * (size_t)n_planes), o_freq = up.add(freqs, (size_t)n_freqs * 2);
+        const size_t o_cen = centers ? up.add(centers, K * (size_t)n_planes * 2) : 0;
+        DevBuf d_partial, d_records, d_s, d_otf, d_mtf, d_sums;
+        int rc;
+        if ((rc = up.upload(st)) || (rc = d_partial.alloc((size_t)plan.max_nw * (size_t)n_pairs * sizeof(double2))) ||
+            (rc = d_records.alloc((size_t)n_items * sizeof(GeoOtfSum))) || (rc = d_s.alloc(K * 8)) || (rc = d_otf.alloc(K * (size_t)n_pairs * sizeof(double2))) ||
+            (rc = d_mtf.alloc(K * (size_t)n_pairs * 8)) || (rc = d_sums.alloc(K * (size_t)n_planes * 8)))
+            return rc;
+        const SplitCfg* d_cfg = up.at<SplitCfg>(o_cfg);
+        const double2* d_cen = centers ? up.at<double2>(o_cen) : nullptr;
+        EventTimer timer;
+        if ((rc = timer.start(st))) return rc;
+        for (const SplitPlan::Launch& L : plan.launches) {
+            auto launch = [&](auto MP) {
+                hipLaunchKernelGGL(psf_geo_otf_list_kernel<decltype(MP)::value>, dim3(f_blocks, (unsigned)L.nw, chunks), dim3(256), 0, st, hits, up.at<SplitWork>(o_work),
+                                   L.w0, up.at<FocusFrame>(o_frames), up.at<double>(o_off), d_cen, n_planes, up.at<double2>(o_freq), n_freqs, (double2*)d_partial.p,
+                                   (GeoOtfSum*)d_records.p);
+            };
+            if (L.nw > 0) {
+                if (mp == 1) launch(std::integral_constant<int, 1>{});
+                else if (mp == 2) launch(std::integral_constant<int, 2>{});
+                else if (mp == 4) launch(std::integral_constant<int, 4>{});
+                else launch(std::integral_constant<int, GEO_OTF_MP>{});
+            }
+            sum_reduce<GeoOtfSum>((unsigned)L.nc, st, d_cfg + L.c0, d_records, GeoOtfSumListFinish{(double*)d_s.p + L.c0});
+            hipLaunchKernelGGL(psf_geo_otf_reduce_list_kernel, dim3((unsigned)((n_pairs + 255) / 256), (unsigned)L.nc), dim3(256), 0, st, d_cfg, L.c0, L.w0,
+                               (const double2*)d_partial.p, n_pairs, n_freqs, (const double*)d_s.p, (double2*)d_otf.p, (double*)d_mtf.p, (double*)d_sums.p);
+        }
+        if ((rc = timer.stop(kernel_ms))) return rc;
+        HIP_TRY(hipMemcpy(otf, d_otf.p, K * (size_t)n_pairs * sizeof(double2), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(mtf, d_mtf.p, K * (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sums, d_sums.p, K * (size_t)n_planes * 8, hipMemcpyDeviceToHost));
+    }
+    otf_fill_empty_configs(R, (size_t)n_planes, (size_t)n_freqs, otf, mtf, sums);
+    return BMO_OK;
+}
+
+extern "C" int bmo_psf_otf_sweep(bmo_trace_result* res, int32_t detector, int32_t n_configs, const double* origins, const double* e1s, const double* e2s,
+                                 const double* displacements, int32_t n_planes, const double* xs, const double* zs, int32_t n, const double* freqs, int32_t n_freqs,
+                                 double* otf, double* mtf, double* sums, double* out_intensity, double* kernel_ms) {
+    const char* who = "bmo_psf_otf_sweep";
+    if (!res || !origins || !e1s || !e2s || !displacements || !xs || !zs || !freqs || !otf || !mtf || !sums || n <= 0 || n_planes <= 0 || n_freqs <= 0)
+        return fail(BMO_ERR_INVALID, "bmo_psf_otf_sweep: bad argument (null pointer, n <= 0, n_planes <= 0, n_freqs <= 0)");
+    if (!otf_freqs_ok(freqs, n_freqs)) return fail(BMO_ERR_INVALID, "bmo_psf_otf_sweep: a frequency is not finite");
+    if (int rc = slot_check(who, res, detector, BMO_OBJ_PSFDETECTOR, true, n_configs)) return rc;
+    const size_t K = (size_t)n_configs;
+    const int64_t n_images = (int64_t)n_configs * n_planes, n_pairs = n_images * n_freqs, n_rowsums = n_images * (n_freqs + 1) * n;
+    if ((n_rowsums + 255) / 256 > (int64_t)0x7fffffff) return fail(BMO_ERR_LIMIT, std::string(who) + ": more row sums than one launch holds");
+    if (kernel_ms) *kernel_ms = 0.0;
+    Ranges R;
+    const double* hits;
+    int64_t H;
+    if (int rc = sweep_focus_rows(who, res, detector, n_configs, R, hits, H)) return rc;
+    const size_t n_out = (size_t)n_images * (size_t)n * (size_t)n;
+    if (H > 0) {
+        hipStream_t st = 0;
+        DevBuf d_int, d_field, d_rowsum, d_otf, d_mtf, d_sums;
+        Packed up;
+        const size_t o_xs = up.add(xs, K * (size_t)n), o_zs = up.add(zs, K * (size_t)n), o_freq = up.add(freqs, (size_t)n_freqs * 2);
+        int rc;
+        if ((rc = up.upload(st)) || (rc = d_rowsum.alloc((size_t)n_rowsums * sizeof(double2))) || (rc = d_otf.alloc((size_t)n_pairs * sizeof(double2))) ||
+            (rc = d_mtf.alloc((size_t)n_pairs * 8)) || (rc = d_sums.alloc((size_t)n_images * 8)))
+            return rc;
+        EventTimer timer;
+        if ((rc = psf_focus_stack_sweep(hits, R, origins, e1s, e2s, displacements, n_planes, xs, zs, n, false, d_int, d_field, timer, kernel_ms))) return rc;
+        hipLaunchKernelGGL(psf_otf_rows_list_kernel, dim3((unsigned)((n_rowsums + 255) / 256)), dim3(256), 0, st, (const double*)d_int.p, up.at<double>(o_xs), n_planes, n,
+                           up.at<double2>(o_freq), n_freqs, n_rowsums, (double2*)d_rowsum.p);
+        hipLaunchKernelGGL(psf_otf_cols_list_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, (const double2*)d_rowsum.p, up.at<double>(o_zs), n_planes, n,
+                           up.at<double2>(o_freq), n_freqs, n_pairs, (double2*)d_otf.p, (double*)d_mtf.p, (double*)d_sums.p);
+        if ((rc = timer.stop(kernel_ms))) return rc;
+        HIP_TRY(hipMemcpy(otf, d_otf.p, (size_t)n_pairs * sizeof(double2), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(mtf, d_mtf.p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sums, d_sums.p, (size_t)n_images * 8, hipMemcpyDeviceToHost));
+        if (out_intensity) HIP_TRY(hipMemcpy(out_intensity, d_int.p, n_out * sizeof(double), hipMemcpyDeviceToHost));
+    } else if (out_intensity) {
+        std::fill(out_intensity, out_intensity + n_out, 0.0);
+    }
+    // a configuration without rows: its images are zeros already; its transfer function must not depend on its axes (NaN where the caller
+    // has no window for it)
+    otf_fill_empty_configs(R, (size_t)n_planes, (size_t)n_freqs, otf, mtf, sums);
     return BMO_OK;
 }
 
@@ -3326,8 +3747,7 @@ static int psf_geo_ee_read(const double* hits, int64_t n_hits, const double* ori
     const int32_t n_radii = (int32_t)thr.size();
     RowPasses P(Ranges{{0}, {n_hits}});  // the plan, the upload and the reduce of the statistics passes: S is one
     if (int rc = P.items(who)) return rc;
-    FocusFrame F{d3{origin[0], origin[1], origin[2]}, d3{e1[0], e1[1], e1[2]}, d3{e2[0], e2[1], e2[2]}, d3{axis[0], axis[1], axis[2]}, d3{0, 0, 0}};
-    F.nrm = d3{F.e1.y * F.e2.z - F.e1.z * F.e2.y, F.e1.z * F.e2.x - F.e1.x * F.e2.z, F.e1.x * F.e2.y - F.e1.y * F.e2.x};
+    const FocusFrame F = focus_frame(origin, e1, e2, axis);
     int mp = 1;
     while (mp < GEO_EE_MP && mp < n_planes) mp *= 2;
     const unsigned chunks = (unsigned)((n_planes + mp - 1) / mp), r_blocks = (unsigned)(((int64_t)n_radii + 256 / mp - 1) / (256 / mp));

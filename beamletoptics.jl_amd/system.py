@@ -1102,6 +1102,112 @@ class SweepSolution:
         self.readout_ms = float(sum(ms))
         return out
 
+    def _focus_planes(self, det, offsets, axis, follow, who):
+        """(slot, pos [K, 3], ori [K, 3, 3], axes [K, 3], offsets [K, M]) of a through-focus read-out of every configuration: `offsets` one
+        list for all or [K, M], `axis` None (each configuration's local y), one vector for all or [K, 3]."""
+        slot = self._slot(det)
+        K = self.n
+        pos = np.ascontiguousarray([self._poses[c][slot][0] for c in range(K)], dtype=np.float64)
+        ori = np.ascontiguousarray([self._poses[c][slot][1] for c in range(K)], dtype=np.float64)
+        off = abi._sweep_planes(K, offsets)
+        ax = None if axis is None else abi._per_config(axis, K, 3)
+        planes = [cp.focus_planes(ori[c], off[c], None if ax is None else ax[c], follow, who) for c in range(K)]
+        return slot, pos, ori, np.ascontiguousarray([p[0] for p in planes]), np.ascontiguousarray([p[1] for p in planes])
+
+    def psf_focus_stats(self, det, offsets, axis=None):
+        """The focus statistics [n_cfg, M, 12] (abi.FOCUS_* columns) of PSFDetector `det` in every configuration, in one batched read-out
+        (bmo_psf_focus_stats_sweep): the rows of configuration c propagated to its detector plane moved by offsets[m] (one list for all
+        configurations, or [n_cfg, M]) along `axis` (None: its local y).  Block c equals abi.psf_focus_stats on detector_hits(det, c) bit for
+        bit; a configuration without rows reads N = 0 and NaN."""
+        slot, pos, ori, ax, off = self._focus_planes(det, offsets, axis, "centroid", "psf_focus_stats")
+        st, self.readout_ms = abi.psf_focus_stats_sweep(self._handle, slot, self.n, pos, ori[:, :, 0], ori[:, :, 2], ax, off)
+        return st
+
+    def psf_best_focus(self, det, offsets, column=abi.FOCUS_RMS_R, kind="min"):
+        """(offset [n_cfg], value [n_cfg]) of the extremum of the focus curve of every configuration: components.best_focus on column
+        `column` of psf_focus_stats(det, offsets); NaN for a configuration without statistics."""
+        st = self.psf_focus_stats(det, offsets)
+        off = abi._sweep_planes(self.n, offsets)
+        best = np.full((self.n, 2), np.nan)
+        for c in range(self.n):
+            if not np.isnan(st[c, :, column]).all():
+                best[c] = cp.best_focus(off[c], st[c, :, column], kind=kind)
+        return best[:, 0].copy(), best[:, 1].copy()
+
+    def _through_focus_plans(self, st, ori, ax, off, n, plan_kw):
+        """components.through_focus_plan for every configuration with rows, from the focus statistics st [K, M, 12]: (xs [K, n], zs [K, n],
+        displacements [K, M, 3]), NaN for a configuration without rows (its stack reads zeros whatever they hold)."""
+        K, M = off.shape
+        xs, zs, d = np.full((K, int(n)), np.nan), np.full((K, int(n)), np.nan), np.full((K, M, 3), np.nan)
+        for c in range(K):
+            if st[c, 0, abi.FOCUS_N] > 0:
+                kw = {k: (v[c] if k == "half_width" and v is not None and np.ndim(v) == 2 else v) for k, v in plan_kw.items()}
+                try:
+                    xs[c], zs[c], d[c] = cp.through_focus_plan(st[c], ori[c], ax[c], off[c], n=n, **kw)
+                except ValueError as e:
+                    raise ValueError("configuration %d: %s" % (c, e)) from None
+        return xs, zs, d
+
+    def psf_through_focus(self, det, offsets, n=100, axis=None, follow="centroid", window_plane=None, crop_factor=1.0, half_width=None):
+        """The through-focus PSF stack of PSFDetector `det` in every configuration, in two batched read-outs (bmo_psf_focus_stats_sweep, then
+        bmo_psf_through_focus_sweep: no row leaves the device): (xs [n_cfg, n], zs [n_cfg, n], displacements [n_cfg, M, 3],
+        I[n_cfg, M, n, n], stats [n_cfg, M, 12]).  Block c is what components.psf_through_focus gives on detector_hits(det, c) at
+        configuration c's pose, bit for bit.  half_width: None, one number, (hwx, hwz), or [n_cfg, 2].  A configuration without rows does not
+        raise: its axes and displacements are NaN, its images 0, its statistics N = 0 and NaN."""
+        slot, pos, ori, ax, off = self._focus_planes(det, offsets, axis, follow, "through_focus")
+        st, ms0 = abi.psf_focus_stats_sweep(self._handle, slot, self.n, pos, ori[:, :, 0], ori[:, :, 2], ax, off)
+        xs, zs, d = self._through_focus_plans(st, ori, ax, off, n, dict(follow=follow, window_plane=window_plane, crop_factor=crop_factor, half_width=half_width))
+        I, _, ms1 = abi.psf_through_focus_sweep(self._handle, slot, self.n, pos, ori[:, :, 0], ori[:, :, 2], d, xs, zs)
+        self.readout_ms = ms0 + ms1
+        return xs, zs, d, I, st
+
+    def psf_mtf(self, det, freqs, offsets=(0.0,), kind="diffraction", n=None, half_width=None, axis=None, follow="centroid"):
+        """The MTF of PSFDetector `det` in every configuration at `freqs` [nf, 2] (cycles per metre, shared by all), in batched read-outs
+        (bmo_psf_focus_stats_sweep, then bmo_psf_geo_otf_sweep or bmo_psf_otf_sweep: no row and no image leaves the device):
+        (mtf [n_cfg, M, nf], otf [n_cfg, M, nf] complex, sums [n_cfg, M], stats [n_cfg, M, 12]) as components.psf_mtf describes them.
+        kind "diffraction": half_width None takes components.mtf_window's for every configuration (from one psf_stats_sweep and one
+        psf_zernike_sweep of order 0), n None the largest n any configuration's window asks for; block c equals components.psf_mtf on
+        detector_hits(det, c) given that n and configuration c's half-width, bit for bit.  A configuration without rows does not raise: its
+        mtf is NaN, its otf and sums 0."""
+        if kind not in ("diffraction", "geometric"):
+            raise ValueError('mtf: kind must be "diffraction" or "geometric"')
+        fq = np.asarray(freqs, dtype=np.float64).reshape(-1, 2)
+        if len(fq) == 0 or not np.isfinite(fq).all():
+            raise ValueError("mtf: needs at least one frequency, all finite")
+        slot, pos, ori, ax, off = self._focus_planes(det, offsets, axis, follow, "mtf")
+        K = self.n
+        e1s, e2s = ori[:, :, 0], ori[:, :, 2]
+        st, ms = abi.psf_focus_stats_sweep(self._handle, slot, K, pos, e1s, e2s, ax, off)
+        full = [c for c in range(K) if st[c, 0, abi.FOCUS_N] > 0]
+        if kind == "geometric":
+            centers = np.full((K, off.shape[1], 2), np.nan)
+            for c in full:
+                centers[c] = cp.mtf_geo_centers(st[c], follow)
+            mtf, otf, sums, ms1 = abi.psf_geo_otf_sweep(self._handle, slot, K, pos, e1s, e2s, ax, off, fq, centers=centers)
+            self.readout_ms = ms + ms1
+            return mtf, otf, sums, st
+        hw = None if half_width is None else np.broadcast_to(np.asarray(half_width, dtype=np.float64), (K, 2)).copy()
+        if hw is None:
+            wst, ms1 = abi.psf_stats_sweep(self._handle, slot, K, pos, e1s, e2s)
+            _, info, _, ms2 = abi.psf_zernike_sweep(self._handle, slot, K, pos, e1s, e2s, order=0)
+            ms += ms1 + ms2
+            hw, n_rule = np.full((K, 2), np.nan), 2
+            for c in full:
+                try:
+                    hw[c], n_c = cp.mtf_image_grid((wst[c, abi.PSF_K_MAX], info[c, abi.ZERN_RHO], int(wst[c, abi.PSF_N])), fq)
+                except ValueError as e:
+                    raise ValueError("configuration %d: %s" % (c, e)) from None
+                n_rule = max(n_rule, n_c)
+        else:
+            n_rule = max([2] + [cp.mtf_image_grid(None, fq, half_width=hw[c])[1] for c in full])
+        n = n_rule if n is None else int(n)
+        xs, zs, d = self._through_focus_plans(st, ori, ax, off, n, dict(follow=follow, half_width=hw))
+        for c in full:
+            cp.mtf_check_pitch(xs[c], zs[c], fq)
+        mtf, otf, sums, _, ms3 = abi.psf_otf_sweep(self._handle, slot, K, pos, e1s, e2s, d, xs, zs, fq)
+        self.readout_ms = ms + ms3
+        return mtf, otf, sums, st
+
     def spot_stats(self, det):
         """The spot statistics [n_cfg, 12] (abi.SPOT_* columns) of Spotdetector `det` in every configuration, in one batched read-out
         (bmo_spot_stats_sweep); row c equals abi.spot_stats on spot_hits(det, c) bit for bit, a configuration without rows reads N = 0 and NaN."""

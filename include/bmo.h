@@ -776,7 +776,7 @@ int bmo_psf_opd_map_sweep(bmo_trace_result* res, int32_t detector, int32_t n_con
  * in the other columns of every plane.
  *
  * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than out_field / kernel_ms, n <= 0, n_planes <= 0,
- * n_hits < 0.  There is no _sweep form and no GaussianBeamlet form.
+ * n_hits < 0.  The _sweep forms are in bmo_sweep_readout.h; there is no GaussianBeamlet form.
  *
  * bmo_result_psf_rows: the device pointer, the row count and (optional) the device ordinal of the rows of PSFDetector slot `detector` still
  * resident in `res`, to hand to the two calls above (hits_on_device != 0).  It is bmo_result_device_hits with the refusals of the _sweep
@@ -840,8 +840,8 @@ int bmo_result_psf_rows(bmo_trace_result* res, int32_t detector, const double** 
  * Python layer refuses it), and the window must hold the PSF without its replicas (components.mtf_window).
  *
  * BMO_ERR_INVALID (checked before a device is looked for): a null pointer other than centers, out_intensity, kernel_ms; n_planes <= 0,
- * n_freqs <= 0, n <= 0, n_hits < 0; a frequency that is not finite.  There is no _sweep form and no GaussianBeamlet form: resident rows come
- * through bmo_result_psf_rows.                                                                                                          */
+ * n_freqs <= 0, n <= 0, n_hits < 0; a frequency that is not finite.  The _sweep forms are in bmo_sweep_readout.h; there is no
+ * GaussianBeamlet form.  Resident rows of an ordinary result come through bmo_result_psf_rows.                                          */
 int bmo_psf_geo_otf(const double* hits, int64_t n_hits, int32_t hits_on_device, const double origin[3], const double e1[3],
                     const double e2[3], const double axis[3], const double* offsets, const double* centers, int32_t n_planes,
                     const double* freqs, int32_t n_freqs, int32_t device, double* otf, double* mtf, double* sums, double* kernel_ms);
@@ -964,4 +964,6 @@ int bmo_psf_poly_otf(const bmo_psf_bands* b, const double origin[3], const doubl
 #ifdef __cplusplus
 }
 #endif
+/* the _sweep forms of bmo_psf_focus_stats, bmo_psf_through_focus, bmo_psf_geo_otf and bmo_psf_otf */
+#include "bmo_sweep_readout.h"
 #endif /* BMO_H */
